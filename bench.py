@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - image+text tokens/s of the AKI-4B forward pass on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one forward pass of the whole AKI-4B model (SigLIP tower -> Perceiver connector -> splice ->
@@ -32,6 +32,7 @@ sys.path.insert(0, ROOT)
 PEAK_BF16_TFLOPS = 2500.0   # dense MFMA peak, MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0
 N_TXT, NV, IMG_PX, BATCH = 512, 144, 336, 8
+DUMP_ROWS = 256     # --dump-outputs: logits rows kept (x 32013 vocabulary columns x 4 B = 33 MB, under the 64 MB cap)
 
 
 def synth_batch(B, device, dtype, media_id, seed):
@@ -225,6 +226,19 @@ def rank_spread(elapsed, device):
     return float(hi.item()), float(lo.item())
 
 
+def dump_outputs(d, out):
+    """--dump-outputs: the last timed step's logits at DUMP_ROWS (sample, position) rows -> d/logits_sample.npy, float32.  The rows
+    depend on the logits' shape alone, so two builds run with the same arguments write the same rows."""
+    import numpy as np
+    import torch
+    logits = out.logits
+    B, L, _ = logits.shape
+    rows = torch.randperm(B * L, generator=torch.Generator().manual_seed(0))[:DUMP_ROWS].sort().values.to(logits.device)
+    sample = logits[rows // L, rows % L].float().cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "logits_sample.npy"), sample)
+
+
 def spawn_ranks(n, argv, script=None):
     """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a
     CHILD process (nothing in this process has touched the GPU) and return its exit code.  Refuses when fewer than N GPUs are
@@ -259,7 +273,13 @@ def main():
                     help="image side of the synthetic batch: 336 = BASELINE's metric resolution (default), 384 = the tower's native size, what the "
                          "reference's SFT collate and demo feed (train/sft_data_utils/loader_utils.py:8, local_demo.py:20): 729 patches, M = 5832 rows in the tower at batch 8")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary legs (the other BASELINE configs, decode, first token, 384 px) that run after the headline at N = 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) to DIR/*.npy: "
+                         f"logits_sample.npy = float32 logits of {DUMP_ROWS} (sample, position) rows drawn once from a seed-0 generator "
+                         "and sorted, all vocabulary columns (about 33 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     IMG_PX = args.px
 
     # --gpus N outside a launcher: start the N ranks ourselves (one process per GPU) BEFORE anything touches the GPU, as a child
@@ -315,7 +335,6 @@ def main():
 
     for _ in range(args.warmup):
         out = step()
-    assert out.logits.shape[:2] == (B, L)
     torch.cuda.synchronize()
     # HIP events on the launch stream around the kernels that are reported: the dominant GEMM (gate_up + SwiGLU, known
     # from profiles/) and the MMA op.  --kernel-table brackets every GEMM instead (costs ~4 % of the step).
@@ -339,7 +358,10 @@ def main():
     if world > 1:
         dist.barrier()
         elapsed, elapsed_min = rank_spread(elapsed, dev if backend == "nccl" else "cpu")
+    assert out.logits.shape[:2] == (B, L)
     assert torch.isfinite(out.logits.float()).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     # the same loop once more WITHOUT the event probes (reported next to ms_per_step: what the probes cost)
     n_un = min(args.steps, 10)
     torch.cuda.synchronize()

@@ -42,3 +42,28 @@ def test_gpus_n_spawns_ranks_and_relays_their_exit_code():
 def test_world_size_mismatch_is_an_error():
     r = _run(["--gpus", "4", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
+
+
+def test_zero_timed_steps_is_an_error():
+    r = _run(["--steps", "0", "--no-cpu-baseline"])
+    assert r.returncode != 0 and not _json_lines(r)
+    assert "--steps must be >= 1" in r.stderr
+
+
+def test_dump_outputs_writes_a_fixed_float32_sample_of_the_logits(tmp_path):
+    """--dump-outputs: the same rows of the logits on every run (so two builds compare output for output), float32, under 64 MB."""
+    import types
+
+    import numpy as np
+    import torch
+    import bench
+    B, L, V = 2, 655, 32064
+    logits = torch.randn(B, L, V, generator=torch.Generator().manual_seed(3)).to(torch.bfloat16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), types.SimpleNamespace(logits=logits))
+    a, b = (np.load(tmp_path / d / "logits_sample.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_ROWS, V) and a.nbytes <= 64 << 20
+    assert np.array_equal(a, b)
+    flat = logits.float().reshape(B * L, V).numpy()
+    hits = [int(np.flatnonzero((flat == row).all(1))[0]) for row in a[:8]]
+    assert hits == sorted(set(hits))          # rows of the logits, distinct, in increasing (sample, position) order

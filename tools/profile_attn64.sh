@@ -5,7 +5,7 @@
 # PMC counters are collected in their own runs (no trace domains alongside), as the MI355X guide prescribes.
 set -u
 TAG=${1:-r06}
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 for B in 1 4; do
   OUT=gpurun_out/prof_${TAG}_b$B
   mkdir -p $OUT

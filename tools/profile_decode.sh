@@ -7,7 +7,7 @@ TAG=${1:-r04}
 shift || true
 OUT=gpurun_out/prof_decode_$TAG
 mkdir -p $OUT
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 tools/decode_bench.py --steps 32 "$@" > $OUT/bench.log 2>&1
 tail -1 $OUT/bench.log | cut -c1-600
 python3 tools/decode_trace_summary.py $OUT/trace gpurun_out/${TAG}_decode

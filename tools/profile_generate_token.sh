@@ -6,7 +6,7 @@ set -u
 TAG=${1:-r05}
 OUT=gpurun_out/prof_generate_$TAG
 mkdir -p $OUT
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 tools/generate_bench.py --new 48 --rounds 1 > $OUT/bench.log 2>&1
 tail -1 $OUT/bench.log | cut -c1-400
 python3 tools/decode_trace_summary.py $OUT/trace gpurun_out/${TAG}_decode

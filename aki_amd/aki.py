@@ -30,6 +30,27 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 0, 
     return torch.multinomial(x.softmax(dim=-1), 1, generator=generator).squeeze(-1)
 
 
+# HF generation keywords that select a logits processor (transformers GenerationMixin._get_logits_processor), with their neutral values
+PROCESSOR_KWARGS = {"repetition_penalty": 1.0, "no_repeat_ngram_size": 0, "bad_words_ids": None, "min_length": 0, "min_new_tokens": 0,
+                    "suppress_tokens": None, "begin_suppress_tokens": None}
+
+
+def _pop_processor_kwargs(kwargs: dict) -> dict:
+    """The logits-processor keywords of `generate` (popped), with None read as the neutral value, as HF's GenerationConfig does."""
+    out = {}
+    for k, neutral in PROCESSOR_KWARGS.items():
+        v = kwargs.pop(k, None)
+        out[k] = neutral if v is None else v
+    return out
+
+
+def _reject_unused_kwargs(kwargs: dict) -> None:
+    """What HF's `_validate_model_kwargs` does with keywords generate() does not use: a ValueError naming them, never a silent drop."""
+    if kwargs:
+        raise ValueError(f"generate() cannot honour the keyword argument(s) {sorted(kwargs)}: the supported ones are the greedy / sampling / "
+                         f"beam-search controls and the logits processors {sorted(PROCESSOR_KWARGS)}")
+
+
 def _embedding_tables(emb: nn.Module, logits: torch.Tensor):
     """(weight, additional weight or None, max_original_id) when ops.greedy_pick can gather the picked token's embedding row itself
     (bf16 tables that hold a row for every logit column), else None: the module's own forward is used."""
@@ -100,7 +121,8 @@ class AKI(VLMWithLanguageStream):
         self._post_forward_hook()
         return output
 
-    def _beam_search(self, cache, logits, K: int, max_new_tokens: int, eos_ids, pad_id: int, length_penalty: float, early_stopping):
+    def _beam_search(self, cache, logits, K: int, max_new_tokens: int, eos_ids, pad_id: int, length_penalty: float, early_stopping,
+                     proc=None):
         """Beam search over the decode path (the algorithm of HF `GenerationMixin` beam search with a `BeamSearchScorer`:
         2K candidates per step, hypotheses normalised by generated_length ** length_penalty, one sequence returned per sample).
         The prompt's cache rows are expanded to K beams and re-ordered in place every step (AkiKVCache.select_rows)."""
@@ -129,6 +151,8 @@ class AKI(VLMWithLanguageStream):
                     hyps[b].remove(min(hyps[b], key=lambda h: h[0]))
 
         for t in range(max_new_tokens):
+            if proc is not None:                       # HF: the processors see each beam's log-softmax scores and its own tokens
+                proc.apply(logp, out=logp, tokens=seqs, step=seqs.shape[1])
             cand = (logp.view(B, K, V) + scores[:, :, None]).view(B, K * V)
             top_s, top_i = cand.topk(2 * K, dim=-1)
             top_s_h, top_i_h = top_s.tolist(), top_i.tolist()
@@ -187,6 +211,11 @@ class AKI(VLMWithLanguageStream):
         with pad_token_id.  Decoding modes, selected by the HF keyword arguments the reference forwards (`**kwargs`,
         src/aki.py:160-207): greedy (default), sampling (`do_sample=True` with `temperature`, `top_k`, `top_p`, optional
         `generator`), beam search (`num_beams=K`, `length_penalty`, `early_stopping`; one returned sequence per sample).
+        Logits processors, applied on the device in every mode and in HF's order (ops.LogitsProcessors): `repetition_penalty`,
+        `no_repeat_ngram_size`, `bad_words_ids`, `min_length` / `min_new_tokens` (eos ids banned until that many tokens are
+        generated), `suppress_tokens`, `begin_suppress_tokens`.  As in HF `generate` with inputs_embeds only, they see the generated
+        tokens, never the prompt; beam search applies them to each beam's log-softmax scores.  Any other keyword (`logits_processor`,
+        `stopping_criteria`, `output_scores`, `generation_config`, ...) raises ValueError instead of being ignored.
         Differences from the reference, both only visible for B > 1 (where the reference is inconsistent): the
         prompt batch is right-padded and every sample continues from its own length."""
         num_beams = int(kwargs.pop("num_beams", 1))
@@ -216,6 +245,8 @@ class AKI(VLMWithLanguageStream):
         use_graph = kwargs.pop("use_graph", None)
         if use_graph is None:
             use_graph = max_new_tokens >= 8          # capture costs about two eager steps
+        pk = _pop_processor_kwargs(kwargs)
+        _reject_unused_kwargs(kwargs)
         if vision_x is None:
             raise NotImplementedError("text-only generation is outside the AKI hot path")
         plan = self._start_splice_plan(lang_x)
@@ -229,8 +260,13 @@ class AKI(VLMWithLanguageStream):
         cache = out.past_key_values
         B = lang_x.shape[0]
         logits = out.logits[:, 0]                                                  # logits of each sample's last real token
+        from . import ops
+        proc = ops.LogitsProcessors(logits.shape[-1], logits.device, pk["repetition_penalty"], pk["no_repeat_ngram_size"],
+                                    max(int(pk["min_length"]), int(pk["min_new_tokens"])), sorted(eos_ids), pk["suppress_tokens"],
+                                    pk["begin_suppress_tokens"], pk["bad_words_ids"])
+        proc = proc if proc.active else None       # no processor: exactly the launches of a plain generate
         if num_beams > 1:
-            tokens = self._beam_search(cache, logits, num_beams, max_new_tokens, eos_ids, pad_id, length_penalty, early_stopping)
+            tokens = self._beam_search(cache, logits, num_beams, max_new_tokens, eos_ids, pad_id, length_penalty, early_stopping, proc)
             self._post_forward_hook()
             return tokens
         tokens = torch.full((B, max_new_tokens), pad_id, dtype=torch.long, device=lang_x.device)
@@ -253,6 +289,8 @@ class AKI(VLMWithLanguageStream):
             done_at = torch.full((B,), -1, dtype=torch.int32, device=lang_x.device)
             start_len, host_len0 = cache.cache_len.clone(), cache.host_len
             pick = dict(pad_token_id=pad_id, eos_ids=eos_t, done=done8, tokens=tokens, start_len=start_len, done_at=done_at)
+            if proc is not None:                    # the processors read tokens[:, :t] and t from cache_len: replays and rewinds stay right
+                pick["processors"] = proc
             ids = torch.zeros(B, dtype=torch.long, device=lang_x.device)
             emb_mod = lm.get_input_embeddings()
             embed = _embedding_tables(emb_mod, logits)
@@ -325,7 +363,8 @@ class AKI(VLMWithLanguageStream):
                         ok = False
                         break
                     ck = (t, logits.clone(), done.clone(), cache.cache_len.clone(), cache.host_len)
-                nxt = sample_next(logits, temperature, top_k, top_p, rng) if do_sample else logits.float().argmax(dim=-1)
+                x = logits if proc is None else proc.apply(logits, tokens=tokens, step=t)
+                nxt = sample_next(x, temperature, top_k, top_p, rng) if do_sample else x.float().argmax(dim=-1)
                 nxt = torch.where(done, torch.full_like(nxt, pad_id), nxt)
                 tokens[:, t] = nxt
                 t += 1

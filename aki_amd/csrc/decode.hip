@@ -1132,7 +1132,9 @@ __device__ __forceinline__ bool pick_better(float a, int ia, float b, int ib) {
 // One workgroup of 16 waves per row: the scan of 32 064 logits is a latency chain (load, eight compares, next load); 1024 threads walk it in 4 trips of two
 // loads each instead of 16 trips of one (19.4 -> measured in profiles/r05_decode_token_trace.txt).
 constexpr int PICK_THREADS = 1024;
-__global__ __launch_bounds__(PICK_THREADS) void greedy_pick_kernel(const PickParams p) {
+// F32: the row to scan is `rowf` (an f32 row of processed scores, see logits processors below), not p.logits
+template <bool F32>
+__device__ __forceinline__ void greedy_pick_row(const PickParams& p, const float* rowf) {
   __shared__ float s_v[PICK_THREADS / 64];
   __shared__ int s_i[PICK_THREADS / 64];
   __shared__ int64_t s_next;
@@ -1152,9 +1154,30 @@ __global__ __launch_bounds__(PICK_THREADS) void greedy_pick_kernel(const PickPar
     for (int i = 0; i < 4; ++i)
       if (i < p.n_eos) eos4[i] = p.eos[i];
   }
-  const bf16_t* row = p.logits + (size_t)b * p.ld;
   float best = -INFINITY;
   int bi = 0x7fffffff;
+  if constexpr (F32) {
+    // rowf is 16-byte aligned (checked on the host); two float4 loads per trip, as the bf16 scan below
+    const int nvec = p.V / 4;
+    for (int c0 = tid; c0 < nvec; c0 += 2 * PICK_THREADS) {
+      const int c1 = c0 + PICK_THREADS;
+      const float4 v0 = *(const float4*)(rowf + (size_t)c0 * 4);
+      const float4 v1 = c1 < nvec ? *(const float4*)(rowf + (size_t)c1 * 4) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float4 v = h ? v1 : v0;
+        const int c = (h ? c1 : c0) * 4;
+        if (h && c1 >= nvec) break;
+        if (pick_better(v.x, c, best, bi)) { best = v.x; bi = c; }
+        if (pick_better(v.y, c + 1, best, bi)) { best = v.y; bi = c + 1; }
+        if (pick_better(v.z, c + 2, best, bi)) { best = v.z; bi = c + 2; }
+        if (pick_better(v.w, c + 3, best, bi)) { best = v.w; bi = c + 3; }
+      }
+    }
+    for (int i = nvec * 4 + tid; i < p.V; i += PICK_THREADS)
+      if (pick_better(rowf[i], i, best, bi)) { best = rowf[i]; bi = i; }
+  } else {
+  const bf16_t* row = p.logits + (size_t)b * p.ld;
   const bool vec = ((p.ld & 7) == 0) && ((((uintptr_t)p.logits) & 15) == 0);
   const int nvec = vec ? p.V / 8 : 0;
   for (int c0 = tid; c0 < nvec; c0 += 2 * PICK_THREADS) {
@@ -1177,6 +1200,7 @@ __global__ __launch_bounds__(PICK_THREADS) void greedy_pick_kernel(const PickPar
   for (int i = nvec * 8 + tid; i < p.V; i += PICK_THREADS) {
     const float x = bf16_bits_to_f32(row[i]);
     if (pick_better(x, i, best, bi)) { best = x; bi = i; }
+  }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -1218,6 +1242,8 @@ __global__ __launch_bounds__(PICK_THREADS) void greedy_pick_kernel(const PickPar
   }
 }
 
+__global__ __launch_bounds__(PICK_THREADS) void greedy_pick_kernel(const PickParams p) { greedy_pick_row<false>(p, nullptr); }
+
 int greedy_pick_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done, int64_t* ids,
                        int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at, const void* emb_main,
                        const void* emb_extra, int64_t max_original_id, int d, void* emb_out, hipStream_t s) {
@@ -1225,6 +1251,155 @@ int greedy_pick_launch(const void* logits, int B, int V, int ld, const int64_t* 
                   (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out};
   AKI_CLEAR_ERR();
   hipLaunchKernelGGL(greedy_pick_kernel, dim3(B), dim3(PICK_THREADS), 0, s, p);
+  AKI_LAUNCH_CHECK();
+  return AKI_OK;
+}
+
+
+// ---- logits processors: what HF `generate` applies to a step's f32 scores before it picks (GenerationMixin._get_logits_processor, in its
+// order), for the case the reference runs - a decoder-only model called with inputs_embeds only, so the processors' input_ids are the row's
+// GENERATED tokens h[0, n) and never the prompt:
+//   1 repetition penalty  s = s < 0 ? s * penalty : s / penalty for every distinct token of h (RepetitionPenaltyLogitsProcessor)
+//   2 no-repeat n-gram    -inf for every token that would complete an n-gram already in h (NoRepeatNGramLogitsProcessor)
+//   3 bad words           -inf for a one-token word; for a longer word, -inf for its last token when h ends with the rest of it and h holds
+//                         at least the whole word's length (SequenceBiasLogitsProcessor's rule)
+//   4 minimum length      -inf for every eos id while n < min_length (MinLength / MinNewTokensLength: the prompt length is 0 here)
+//   5 suppress tokens     -inf always; begin-suppress tokens -inf at n == 0
+// n = step + (cache_len ? cache_len[b] - start_len[b] : 0), so that one captured graph serves every replay.  Rows with done[b] set get the
+// plain f32 copy.  One workgroup per row, O(V + n * ngram + bad-word ids); ids outside [0, V) are skipped.
+struct ProcParams {
+  const void* in; int in_f32, ld_in;
+  float* out; int ld_out;
+  int V;
+  const int64_t* tokens; int tokens_ld;
+  const int* cache_len; const int* start_len; int step;
+  const unsigned char* done;
+  float penalty; int ngram, min_len;
+  const int64_t* eos; int n_eos;
+  const int64_t* suppress; int n_suppress;
+  const int64_t* begin_suppress; int n_begin;
+  const int64_t* bad_ids; const int* bad_off; int n_bad, n_bad_ids;
+};
+
+constexpr int PROC_MAX_V = 131072;   // the repetition penalty's LDS bitmap: 16 KB
+
+__device__ __forceinline__ void ban(float* out, int V, int64_t g) {
+  if (g >= 0 && g < V) out[g] = -INFINITY;
+}
+
+__device__ void process_row(const ProcParams& q, int b, float* out, unsigned* s_bits) {
+  const int tid = threadIdx.x, nt = blockDim.x, V = q.V;
+  int n = q.step;
+  if (q.cache_len != nullptr) n += q.cache_len[b] - (q.start_len != nullptr ? q.start_len[b] : 0);
+  n = q.tokens == nullptr ? 0 : min(max(n, 0), q.tokens_ld);
+  const bool skip = q.done != nullptr && q.done[b] != 0;
+  // 0: the row in f32
+  if (q.in_f32) {
+    const float* in = (const float*)q.in + (size_t)b * q.ld_in;
+    for (int i = tid; i < V; i += nt) out[i] = in[i];
+  } else {
+    const bf16_t* in = (const bf16_t*)q.in + (size_t)b * q.ld_in;
+    const bool vec = ((q.ld_in & 7) == 0) && ((((uintptr_t)q.in) & 15) == 0) && ((q.ld_out & 3) == 0) && ((((uintptr_t)q.out) & 15) == 0);
+    const int nvec = vec ? V / 8 : 0;
+    for (int c = tid; c < nvec; c += nt) {
+      const u32x4 v = *(const u32x4*)(in + (size_t)c * 8);
+      *(float4*)(out + (size_t)c * 8) = make_float4(bf16_lo(v[0]), bf16_hi(v[0]), bf16_lo(v[1]), bf16_hi(v[1]));
+      *(float4*)(out + (size_t)c * 8 + 4) = make_float4(bf16_lo(v[2]), bf16_hi(v[2]), bf16_lo(v[3]), bf16_hi(v[3]));
+    }
+    for (int i = nvec * 8 + tid; i < V; i += nt) out[i] = bf16_bits_to_f32(in[i]);
+  }
+  if (skip) {
+    __syncthreads();
+    return;
+  }
+  const int64_t* h = q.tokens + (size_t)b * q.tokens_ld;
+  const bool pen = q.penalty != 1.f && n > 0;
+  if (pen)
+    for (int i = tid; i < (V + 31) / 32; i += nt) s_bits[i] = 0u;
+  __syncthreads();                                           // the copy (and the bitmap) before any scattered write
+  if (pen) {
+    // every distinct token once: the occurrence that sets its bit owns it, reads the copied score and writes the penalised one
+    for (int i = tid; i < n; i += nt) {
+      const int64_t g = h[i];
+      if (g < 0 || g >= V) continue;
+      const unsigned m = 1u << (g & 31);
+      if (atomicOr(&s_bits[g >> 5], m) & m) continue;
+      const float x = out[g];
+      out[g] = x < 0.f ? x * q.penalty : x / q.penalty;
+    }
+    __syncthreads();                                         // penalties before the bans: a banned token ends at -inf
+  }
+  const int ng = q.ngram;
+  if (ng > 0 && n + 1 >= ng) {
+    for (int i = tid; i <= n - ng; i += nt) {
+      bool match = true;
+      for (int j = 0; j < ng - 1 && match; ++j) match = h[i + j] == h[n - ng + 1 + j];
+      if (match) ban(out, V, h[i + ng - 1]);
+    }
+  }
+  for (int s = tid; s < q.n_bad; s += nt) {
+    const int o0 = min(max(q.bad_off[s], 0), q.n_bad_ids), o1 = min(max(q.bad_off[s + 1], o0), q.n_bad_ids), L = o1 - o0;
+    if (L <= 0) continue;
+    bool hit = L == 1 || L <= n;
+    for (int j = 0; j < L - 1 && hit; ++j) hit = h[n - (L - 1) + j] == q.bad_ids[o0 + j];
+    if (hit) ban(out, V, q.bad_ids[o1 - 1]);
+  }
+  if (n < q.min_len)
+    for (int i = tid; i < q.n_eos; i += nt) ban(out, V, q.eos[i]);
+  for (int i = tid; i < q.n_suppress; i += nt) ban(out, V, q.suppress[i]);
+  if (n == 0)
+    for (int i = tid; i < q.n_begin; i += nt) ban(out, V, q.begin_suppress[i]);
+  __syncthreads();
+}
+
+constexpr int PROC_THREADS = 1024;
+__global__ __launch_bounds__(PROC_THREADS) void logits_process_kernel(const ProcParams q) {
+  __shared__ unsigned s_bits[PROC_MAX_V / 32];
+  process_row(q, blockIdx.x, q.out + (size_t)blockIdx.x * q.ld_out, s_bits);
+}
+
+// the greedy pick over the processed row: one launch, the processed scores land in q.out (a [B, ld_out] f32 scratch) and are scanned from there
+__global__ __launch_bounds__(PICK_THREADS) void greedy_pick_processed_kernel(const PickParams p, const ProcParams q) {
+  __shared__ unsigned s_bits[PROC_MAX_V / 32];
+  float* rowf = q.out + (size_t)blockIdx.x * q.ld_out;
+  process_row(q, blockIdx.x, rowf, s_bits);
+  greedy_pick_row<true>(p, rowf);
+}
+
+static ProcParams proc_params(const void* in, int in_f32, int ld_in, float* out, int ld_out, int V, const int64_t* tokens, int tokens_ld,
+                              const int* cache_len, const int* start_len, int step, const unsigned char* done, float penalty, int ngram,
+                              int min_len, const int64_t* eos, int n_eos, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress,
+                              int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad, int n_bad_ids) {
+  return ProcParams{in, in_f32, ld_in, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, penalty, ngram, min_len,
+                    eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off, n_bad, n_bad_ids};
+}
+
+int logits_process_launch(const void* logits, int in_f32, int B, int V, int ld, float* out, int ld_out, const int64_t* tokens, int tokens_ld,
+                          const int* cache_len, const int* start_len, int step, const unsigned char* done, float penalty, int ngram,
+                          int min_len, const int64_t* eos, int n_eos, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress,
+                          int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad, int n_bad_ids, hipStream_t s) {
+  const ProcParams q = proc_params(logits, in_f32, ld, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, penalty, ngram,
+                                   min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off, n_bad, n_bad_ids);
+  AKI_CLEAR_ERR();
+  hipLaunchKernelGGL(logits_process_kernel, dim3(B), dim3(PROC_THREADS), 0, s, q);
+  AKI_LAUNCH_CHECK();
+  return AKI_OK;
+}
+
+int greedy_pick_processed_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done,
+                                 int64_t* ids, int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at,
+                                 const void* emb_main, const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores,
+                                 int ld_scores, float penalty, int ngram, int min_len, const int64_t* suppress, int n_suppress,
+                                 const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad,
+                                 int n_bad_ids, hipStream_t s) {
+  PickParams p = {(const bf16_t*)logits, B, V, ld, eos, n_eos, pad, done, ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
+                  (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out};
+  // the processors see the tokens generated BEFORE this pick: n = cache_len + advance - start_len, the index the pick writes
+  const ProcParams q = proc_params(logits, 0, ld, scores, ld_scores, V, tokens, tokens_ld, cache_len, start_len, cache_len ? advance : 0, done,
+                                   penalty, ngram, min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off, n_bad,
+                                   n_bad_ids);
+  AKI_CLEAR_ERR();
+  hipLaunchKernelGGL(greedy_pick_processed_kernel, dim3(B), dim3(PICK_THREADS), 0, s, p, q);
   AKI_LAUNCH_CHECK();
   return AKI_OK;
 }

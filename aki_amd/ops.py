@@ -572,17 +572,108 @@ def chain_replay_on_current_stream() -> None:
         _CHAIN_LAST[cur.device_index] = cur
 
 
+class LogitsProcessors:
+    """HF `generate`'s logits processors for a decoder-only model called with inputs_embeds only (what src/aki.py:192-207 runs), on the
+    device (aki_logits_process / aki_greedy_pick_processed; include/aki_mi355x.h): the processors' input_ids are the GENERATED tokens,
+    never the prompt.  In HF's order: repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length (eos ids banned while fewer
+    tokens have been generated; min_new_tokens is the same number here), suppress_tokens, begin_suppress_tokens.  The arguments are
+    checked here, on the host, and held as device tensors, so one object serves a whole generation (and a captured graph).
+    eos_ids: the ids min_length bans; a one-token bad word equal to one of them is dropped, as HF's NoBadWordsLogitsProcessor does."""
+
+    def __init__(self, V: int, device, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_length: int = 0, eos_ids=(),
+                 suppress_tokens=None, begin_suppress_tokens=None, bad_words_ids=None):
+        V = int(V)
+        if V <= 0:
+            raise ValueError(f"logits processors: a vocabulary of {V} columns")
+        pen = float(repetition_penalty)
+        if not (pen > 0.0 and pen < float("inf")):
+            raise ValueError(f"repetition_penalty has to be a strictly positive float, got {repetition_penalty}")
+        if int(no_repeat_ngram_size) < 0 or int(min_length) < 0:
+            raise ValueError("no_repeat_ngram_size and min_length / min_new_tokens are non-negative integers")
+        eos = [int(e) for e in eos_ids]
+
+        def ids(name, x):
+            out = [int(i) for i in (x or [])]
+            if any(not 0 <= i < V for i in out):
+                raise ValueError(f"{name}: every id has to be in [0, {V})")
+            return out
+
+        words = []
+        for w in (bad_words_ids or []):
+            if isinstance(w, int) or len(w) == 0:
+                raise ValueError(f"bad_words_ids has to be a list of non-empty lists of token ids, got {bad_words_ids}")
+            w = ids("bad_words_ids", w)
+            if not (len(w) == 1 and w[0] in eos):
+                words.append(w)
+        self.V, self.penalty, self.ngram, self.min_length = V, pen, int(no_repeat_ngram_size), int(min_length)
+        self.suppress, self.begin_suppress = ids("suppress_tokens", suppress_tokens), ids("begin_suppress_tokens", begin_suppress_tokens)
+        self.words = words
+        self.active = bool(pen != 1.0 or self.ngram > 0 or words or (self.min_length > 0 and eos) or self.suppress or self.begin_suppress)
+        if self.active and V > L.AKI_LOGITS_PROCESS_MAX_V:
+            raise ValueError(f"logits processors: a vocabulary of {V} is above {L.AKI_LOGITS_PROCESS_MAX_V}")
+        dev = torch.device(device)
+        i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev) if v else None
+        self._eos, self._sup, self._bsup = i64(eos), i64(self.suppress), i64(self.begin_suppress)
+        self._bad = i64([t for w in words for t in w])
+        offs = [0]
+        for w in words:
+            offs.append(offs[-1] + len(w))
+        self._off = torch.tensor(offs, dtype=torch.int32, device=dev) if words else None
+        self._scores = None
+
+    def _tail(self):
+        n = lambda t: 0 if t is None else t.numel()
+        return (self.penalty, self.ngram, self.min_length), (_ptr(self._sup), n(self._sup), _ptr(self._bsup), n(self._bsup), _ptr(self._bad),
+                                                            _ptr(self._off), len(self.words), n(self._bad))
+
+    def scores(self, B: int, device) -> torch.Tensor:
+        """The f32 [B, >= V] scratch the processed greedy pick writes its scores to (kept: a captured graph holds its address)."""
+        if self._scores is None or self._scores.shape[0] != B or self._scores.device != torch.device(device):
+            self._scores = torch.empty((B, (self.V + 3) // 4 * 4), dtype=torch.float32, device=device)
+        return self._scores
+
+    def apply(self, logits: torch.Tensor, out: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, step: int = 0,
+              cache_len: Optional[torch.Tensor] = None, start_len: Optional[torch.Tensor] = None,
+              done: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Processed f32 scores [B, V] of bf16 / f32 logits [B, V] (one launch).  The history of row b is tokens[b, :n] (int64 [B, *]) with
+        n = step + (cache_len[b] - start_len[b] when cache_len is given); rows with done[b] (uint8) are copied unprocessed.  out may be
+        logits itself when they are f32."""
+        if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[1] != self.V:
+            raise AkiError(f"logits processors: logits [B, {self.V}] with unit column stride are expected, got {tuple(logits.shape)}")
+        B = logits.shape[0]
+        dev = _dev(logits, out, tokens, cache_len, start_len, done)
+        if out is None:
+            out = torch.empty((B, self.V), dtype=torch.float32, device=dev)
+        if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.stride(1) != 1 or out.shape[1] != self.V:
+            raise AkiError("logits processors: out is f32 [B, V] with unit column stride")
+        for t_, dt in ((tokens, torch.int64), (cache_len, torch.int32), (start_len, torch.int32), (done, torch.uint8)):
+            if t_ is not None and (t_.dtype != dt or not t_.is_contiguous()):
+                raise AkiError(f"logits processors: a contiguous {dt} tensor is expected, got {t_.dtype}")
+        if tokens is not None and (tokens.dim() != 2 or tokens.shape[0] != B):
+            raise AkiError("logits processors: tokens is [B, *]")
+        if tokens is not None and tokens.shape[1] == 0:
+            tokens = None
+        head, tail = self._tail()
+        L.check(L.load().aki_logits_process(_ptr(logits), _dt(logits), B, self.V, logits.stride(0), _ptr(out), out.stride(0), _ptr(tokens),
+                                            0 if tokens is None else tokens.shape[1], _ptr(cache_len), _ptr(start_len), int(step), _ptr(done),
+                                            *head, _ptr(self._eos), 0 if self._eos is None else self._eos.numel(), *tail, _stream()),
+                "aki_logits_process")
+        return out
+
+
 def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int = 0, eos_ids: Optional[torch.Tensor] = None,
                 done: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, cache_len: Optional[torch.Tensor] = None,
                 start_len: Optional[torch.Tensor] = None, advance: bool = False, done_at: Optional[torch.Tensor] = None,
-                embed=None, next_embeds: Optional[torch.Tensor] = None) -> torch.Tensor:
+                embed=None, next_embeds: Optional[torch.Tensor] = None, processors: Optional[LogitsProcessors] = None) -> torch.Tensor:
     """The step between two decode steps of a greedy `generate` as one launch (aki_greedy_pick; HF GenerationMixin's greedy branch):
     next_ids[b] = pad if done[b] else argmax(logits[b]); tokens[b, t] = next with t = cache_len[b] + advance - start_len[b]; rows whose
     next is an eos id become done (done_at[b] = t); advance: cache_len += 1.  logits: bf16 [B, V] (row stride >= V); next_ids / tokens /
     eos_ids int64; done uint8; cache_len / start_len / done_at int32.  Capturable: no host value is read.
     embed = (weight [rows, d], additional_weight [extra, d] or None, max_original_id) with next_embeds bf16 [B, d]: the picked token's
     embedding row (DecoupledEmbedding's two tables, src/helpers.py:440-492) is written to next_embeds in the same launch - the input of the next
-    decode step."""
+    decode step.
+    processors (an active LogitsProcessors): the pick scans the processed scores of the row instead, in the same launch
+    (aki_greedy_pick_processed); the history is tokens[b, :t] and the minimum length bans eos_ids."""
     if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
         raise AkiError("greedy_pick takes bf16 logits [B, V] with unit column stride")
     B, V = logits.shape
@@ -595,18 +686,28 @@ def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
     common = (_ptr(logits), B, V, logits.stride(0), _ptr(eos_ids), 0 if eos_ids is None else eos_ids.numel(), int(pad_token_id), _ptr(done),
               _ptr(next_ids), _ptr(tokens), 0 if tokens is None else tokens.shape[1], _ptr(cache_len), _ptr(start_len), 1 if advance else 0,
               _ptr(done_at))
+    if embed is not None:
+        w, extra, max_orig = embed
+        d = w.shape[1]
+        for t_ in (w, extra, next_embeds):
+            if t_ is not None and (t_.dtype != torch.bfloat16 or not t_.is_contiguous() or t_.device != logits.device or t_.shape[-1] != d):
+                raise AkiError("greedy_pick: embedding tables and next_embeds are contiguous bf16 [*, d] on the logits' device")
+        if next_embeds is None or next_embeds.numel() != B * d:
+            raise AkiError("greedy_pick: next_embeds is [B, d]")
+        if w.shape[0] <= max_orig:
+            raise AkiError("greedy_pick: the embedding table has fewer than max_original_id + 1 rows")
+    if processors is not None and processors.active:
+        if processors.V != V:
+            raise AkiError(f"greedy_pick: the processors were built for V = {processors.V}, the logits have {V} columns")
+        sc = processors.scores(B, logits.device)
+        head, tail = processors._tail()
+        emb = (None, None, 0, 0, 0, None) if embed is None else \
+            (_ptr(w), _ptr(extra), int(max_orig), 0 if extra is None else extra.shape[0], d, _ptr(next_embeds))
+        L.check(L.load().aki_greedy_pick_processed(*common, *emb, _ptr(sc), sc.stride(0), *head, *tail, _stream()), "aki_greedy_pick_processed")
+        return next_ids
     if embed is None:
         L.check(L.load().aki_greedy_pick(*common, _stream()), "aki_greedy_pick")
         return next_ids
-    w, extra, max_orig = embed
-    d = w.shape[1]
-    for t_ in (w, extra, next_embeds):
-        if t_ is not None and (t_.dtype != torch.bfloat16 or not t_.is_contiguous() or t_.device != logits.device or t_.shape[-1] != d):
-            raise AkiError("greedy_pick: embedding tables and next_embeds are contiguous bf16 [*, d] on the logits' device")
-    if next_embeds is None or next_embeds.numel() != B * d:
-        raise AkiError("greedy_pick: next_embeds is [B, d]")
-    if w.shape[0] <= max_orig:
-        raise AkiError("greedy_pick: the embedding table has fewer than max_original_id + 1 rows")
     L.check(L.load().aki_greedy_pick_embed(*common, _ptr(w), _ptr(extra), int(max_orig), 0 if extra is None else extra.shape[0], d,
                                            _ptr(next_embeds), _stream()), "aki_greedy_pick_embed")
     return next_ids

@@ -710,6 +710,38 @@ int aki_greedy_pick_embed(const void* logits, int32_t B, int32_t V, int64_t ld, 
                           int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
                           int64_t num_additional, int32_t d, void* next_embeds, void* stream);
 
+/* aki_logits_process - HF `generate`'s logits processors on one decode step's scores, in the order of
+ * GenerationMixin._get_logits_processor, for a decoder-only model called with inputs_embeds only (src/aki.py:192-207): the processors'
+ * input_ids are the row's GENERATED tokens h = tokens[b, 0:n), never the prompt.  logits [B, ld] (AKI_DT_BF16 or AKI_DT_F32, V columns
+ * used) -> out f32 [B, ld_out] (out == logits is allowed for f32):
+ *   repetition_penalty   every distinct token g of h: s = s < 0 ? s * penalty : s / penalty      (1.0 = off)
+ *   no_repeat_ngram_size every token that completes an n-gram of h: -inf                            (0 = off)
+ *   bad words            word w = bad_ids[bad_offsets[i] : bad_offsets[i + 1]], i < n_bad: its last token -inf when |w| == 1, or when
+ *                        n >= |w| and h ends with w's first |w| - 1 tokens (bad_offsets: n_bad + 1 ascending entries in [0, n_bad_ids])
+ *   min_length           every eos id -inf while n < min_length                                      (0 = off)
+ *   suppress ids         -inf; begin-suppress ids -inf at n == 0
+ *   n = step + (cache_len ? cache_len[b] - start_len[b] : 0), clamped to [0, tokens_ld] (0 when tokens is NULL): the greedy loop's device
+ *   counters, so the launch can sit inside a replayed hipGraph.  Rows with done[b] != 0 are copied unprocessed.  Ids outside [0, V)
+ *   are skipped.  V <= AKI_LOGITS_PROCESS_MAX_V.  One launch, no host value read. */
+#define AKI_LOGITS_PROCESS_MAX_V 131072
+int aki_logits_process(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out, const int64_t* tokens,
+                       int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step, const uint8_t* done,
+                       float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* eos_ids, int32_t n_eos,
+                       const int64_t* suppress_ids, int32_t n_suppress, const int64_t* begin_suppress_ids, int32_t n_begin_suppress,
+                       const int64_t* bad_ids, const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, void* stream);
+
+/* aki_greedy_pick_processed - aki_greedy_pick_embed over the processed scores, in ONE launch: the row is processed as aki_logits_process
+ * does (with n = cache_len[b] + advance - start_len[b], the index the pick writes, and eos_ids as the minimum length's eos ids) into the
+ * f32 scratch scores [B, ld_scores] (16-byte aligned, ld_scores % 4 == 0), and the pick scans it.  embed_weight NULL: no embedding row
+ * (as aki_greedy_pick; additional_weight and next_embeds NULL too).  A greedy token with processors stays chain + head + this launch. */
+int aki_greedy_pick_processed(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                              uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                              int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                              int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                              int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                              const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                              int32_t n_bad, int32_t n_bad_ids, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,9 @@
 `generate(max_new_tokens=256)`, greedy): full AKI-4B (random-init), one 336 px image + 512-token prompt, batch 1.  Reports the time to the
 first token (vision tower + connector + splice + MMA prefill into the KV cache) and the time per generated token (one hipGraph replay
 each, the greedy pick inside it), with bf16 and with e4m3 weights.  No EOS (random weights never emit one on cue): all 256 tokens.
-    python tools/generate_bench.py [--new 256] [--fp8] [--txt 64]"""
+--repetition-penalty / --no-repeat-ngram: every round also runs with those logits processors on (the processed greedy pick) and reports the
+per-token cost they add, measured on the same box in the same process.
+    python tools/generate_bench.py [--new 256] [--fp8] [--txt 64] [--repetition-penalty 1.2] [--no-repeat-ngram 3]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -15,7 +17,14 @@ def main():
     ap.add_argument("--fp8", action="store_true")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--txt", type=int, default=512, help="prompt tokens: 512 = the headline prompt (L = 655), 64 = BASELINE configs[0] (L = 207)")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0)
+    ap.add_argument("--no-repeat-ngram", type=int, default=0)
     a = ap.parse_args()
+    proc_kw = {}
+    if a.repetition_penalty != 1.0:
+        proc_kw["repetition_penalty"] = a.repetition_penalty
+    if a.no_repeat_ngram > 0:
+        proc_kw["no_repeat_ngram_size"] = a.no_repeat_ngram
     import bench
     bench.N_TXT = a.txt
     from aki_amd.factory import build_aki
@@ -27,17 +36,21 @@ def main():
 
     host = [0.0]
 
-    def run(n_new):
+    def run(n_new, **kw):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        toks = model.generate(vx, ids, attention_mask=am, max_new_tokens=n_new, do_sample=False, eos_token_id=[])
+        toks = model.generate(vx, ids, attention_mask=am, max_new_tokens=n_new, do_sample=False, eos_token_id=[], **kw)
         host[0] = time.perf_counter() - t0          # the call has returned; with one new token and no EOS set nothing in it synchronises
         torch.cuda.synchronize()
         return time.perf_counter() - t0, toks
 
     run(16)                                   # warm-up: allocator, lazily-built folds, the graph capture path
+    if proc_kw:
+        run(16, **proc_kw)
     res = {"prompt_tokens_lm_stream": bench.N_TXT - 1 + bench.NV, "new_tokens": a.new, "fp8": bool(a.fp8), "rounds": []}
-    ref = None
+    if proc_kw:
+        res["processors"] = proc_kw
+    ref = ref_p = None
     for _ in range(a.rounds):
         t1, _ = run(1)                        # prefill + first token
         h1 = host[0]
@@ -49,6 +62,20 @@ def main():
         res["rounds"].append({"first_token_ms": round(t1 * 1e3, 2), "first_token_host_issue_ms": round(h1 * 1e3, 2), "total_ms": round(tn * 1e3, 2),
                               "ms_per_new_token_after_the_first": round((tn - t1) * 1e3 / (a.new - 1), 4),
                               "new_tokens_per_s_end_to_end": round(a.new / tn, 1)})
+        if proc_kw:
+            t1p, _ = run(1, **proc_kw)
+            tnp, toks_p = run(a.new, **proc_kw)
+            assert toks_p.shape == (1, a.new)
+            if ref_p is None:
+                ref_p = toks_p.clone()
+            assert torch.equal(ref_p, toks_p), "generate with processors is not reproducible from call to call"
+            per_p = (tnp - t1p) * 1e3 / (a.new - 1)
+            r = res["rounds"][-1]
+            r["processed_ms_per_new_token_after_the_first"] = round(per_p, 4)
+            r["processors_added_us_per_token"] = round((per_p - r["ms_per_new_token_after_the_first"]) * 1e3, 2)
+    if proc_kw:
+        add = sorted(r["processors_added_us_per_token"] for r in res["rounds"])
+        res["processors_added_us_per_token_median"] = add[len(add) // 2]
     print(json.dumps(res))
 
 

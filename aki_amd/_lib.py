@@ -269,8 +269,6 @@ def load_lab() -> C.CDLL:
     lib.aki_lab_set_chain_lds.argtypes = [C.c_int]
     lib.aki_lab_set_slice_major.restype = None
     lib.aki_lab_set_slice_major.argtypes = [C.c_int]
-    lib.aki_lab_set_small_m.restype = None
-    lib.aki_lab_set_small_m.argtypes = [C.c_int, C.c_int]
     lib.aki_lab_set_chain_fault.restype = None
     lib.aki_lab_set_chain_fault.argtypes = [C.c_int, C.c_int]
     return lib
@@ -298,8 +296,8 @@ class use_lab:
 
 class use_lab_attn:
     """Context manager for tests / tools: the lab library with an attention-core variant forced (mma_attn_bf16.hip, g_attn_variant:
-    1 = the 32-row kernel at every length, 9 = the 64-row kernel at every length, 10 = the 64-row kernel with the exact running
-    maximum, 164 = the 64-row kernel with every tile sent through its exact redo path)."""
+    0 = the product rule, 1 / 2 = the 32-row kernel at every length, 9 = the 64-row kernel at every length, 10 = the 64-row kernel with
+    the exact running maximum, 100 + m = timing ablation m of the 64-row kernel, e.g. 164 = every tile sent through its exact redo path)."""
 
     def __init__(self, variant: int):
         self.variant = variant

@@ -61,12 +61,10 @@ int mask_to_table_launch(const int64_t* mask, int B, int L, int max_rects, aki_m
                          int* status, void* ws, hipStream_t s);
 size_t linear_splitk_plan_ws_bytes(int M, int N, int K);
 #ifdef AKI_LAB_HOOKS
-extern int g_sm_variant;
 extern int g_sk_slice_major;
-extern int g_sm_ksplit;
 extern int g_force_tile;
 extern int g_deep_ring;
-extern int g_pipe;
+extern int g_res_prefetch;
 extern int g_deepx;
 extern int g_attn_variant;
 extern long long* g_clock_probe;
@@ -121,21 +119,20 @@ int aki_abi_version(void) { return AKI_ABI_VERSION; }
 
 #ifdef AKI_LAB_HOOKS
 // Lab build only (libaki_mi355x_lab.so, `python -m aki_amd.build --lab`): force the bf16 GEMM tile configuration
-// (0 = heuristic, 1 = 256x256, 2 = 128x128, 3 = 128 features x 96 tokens where that tile exists, else 128x128); +256 switches
-// off the 4-stage / 64-feature variant of single-row launches, +512 the mid-step pipeline of the 256x256 tile.  Process-global,
-// not thread safe - which is why the product library does not carry it.
+// (0 = heuristic, 1 = 256x256, 2 = 128x128, 3 = 128 features x 96 tokens where that tile exists, else 128x128, 5 = 64x64 on a
+// four-stage ring where that tile exists, else 128x128); +256 switches off the 4-stage / 64-feature variant of single-row launches,
+// +1024 the residual prefetch of the 256x256 tile, +4096 / +8192 force / forbid the three-deep ring on the tokens of residual GEMMs.
+// Process-global, not thread safe - which is why the product library does not carry it.
 void aki_lab_set_gemm_tile(int mode) {
   aki::g_deep_ring = (mode & 256) ? 0 : 1;
-  aki::g_deepx = (mode & 4096) ? 1 : ((mode & 8192) ? 2 : 0);   // residual GEMMs: three-deep ring on the tokens (forced / forbidden)
-  aki::g_pipe = (mode & 512) ? 0 : ((mode & 1024) ? 2 : ((mode & 2048) ? 3 : 1));     // +1024: pipeline without the residual prefetch, +2048: with the two-deep weight ring
+  aki::g_deepx = (mode & 4096) ? 1 : ((mode & 8192) ? 2 : 0);
+  aki::g_res_prefetch = (mode & 1024) ? 0 : 1;
   mode &= 255;
-  aki::g_force_tile = (mode >= 1 && mode <= 5) ? mode : 0;
+  aki::g_force_tile = (mode >= 1 && mode <= 5 && mode != 4) ? mode : 0;
 }
 // split-K workgroup order: 0 = tile-major (product), 1 = slice-major
 void aki_lab_set_slice_major(int on) { aki::g_sk_slice_major = on ? 1 : 0; }
-// small-M tile variant (gemm_bf16.hip: launch_variant; -1 = the planner) and its K split, for every bf16 GEMM launch
-void aki_lab_set_small_m(int variant, int ksplit) { aki::g_sm_variant = variant; aki::g_sm_ksplit = ksplit < 1 ? 1 : ksplit; }
-// 0 = product choice, 1 = 32-row attention core (two waves per SIMD), 2 = 64-row core (one wave per SIMD)
+// attention core (mma_attn_bf16.hip, g_attn_variant): 0 = product choice, 1 / 2 = the 32-row core at every length, 9 / 10 = the 64-row core
 void aki_lab_set_attn_variant(int v) { aki::g_attn_variant = v; }
 // device pointer to two int64: every bf16 GEMM launch then leaves {shader cycles, 100 MHz wall ticks} of its workgroup 0 there
 void aki_lab_set_probe_block(int b) { aki::g_probe_block = b; }   // which workgroup of a GEMM launch stamps

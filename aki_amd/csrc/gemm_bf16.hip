@@ -28,13 +28,13 @@
 //
 // K-loop variants (template parameter PIPE; which one a launch gets is decided in launch_big / run_planned):
 //   0  two stages, one vmcnt(0) + barrier per K-step (small tiles, fp8); NST 3-4: a ring for one-row weight-streaming launches
-//   1  256 x 256: the barrier in the MIDDLE of the step, fragment reads and DMA issue spread between the MFMAs (lab: the form before the three-deep rings)
-//   2  = 1 + the residual tile prefetched under the last two K-steps into the two stage buffers (lab, as above)
-//   3  lab: four waves, one per SIMD, hand-placed stream (asm MFMAs on AGPR accumulators), per-phase stamps
-//   4  = 1 with the WEIGHT tiles on a three-deep ring (160 KiB of LDS): a weight tile is asked for two K-steps ahead - operands come out of HBM
+//   4  256 x 256 (bf16): the barrier in the MIDDLE of the step, fragment reads and DMA issue spread between the MFMAs, and the WEIGHT
+//      tiles on a three-deep ring (160 KiB of LDS): a weight tile is asked for two K-steps ahead - operands come out of HBM
 //   5  = 4 + the residual tile's four 32 KiB blocks prefetched into ring slots as they fall free (o_proj)
-//   6  = 5 with the TOKEN tiles three deep instead (down_proj: the activation is the larger cold operand);  7 = 4 likewise (not dispatched)
+//   6  = 5 with the TOKEN tiles three deep instead (down_proj: the activation is the larger cold operand)
 //   8  128 x 96 tile, unpipelined loop, token tiles three deep (SigLIP fc2 reads a 40 MB activation out of HBM)
+// (PIPE 1-3 and 7 - the two-deep mid-step pipeline, its residual prefetch, a hand-placed four-wave loop, 7 = 4 with deep tokens - and
+// the K groups of the small-M variants were measured and left the tree; EXPERIMENTS.md keeps their numbers.)
 #include <type_traits>
 
 #include "aki_device.h"
@@ -42,21 +42,6 @@
 namespace aki {
 
 enum { EPI_PLAIN = 0, EPI_SWIGLU = 1, EPI_QKV_ROPE8 = 3 };
-
-// compile-time loops (the hand-placed K-loop below needs immediates for the fragment index and the ds_read offset)
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for_impl(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for_impl<I + 1, N>(f);
-  }
-}
-// chunk swizzle of a 64-byte-row LDS image read with ds_read_b128 by MFMA 16x16x32 fragment lanes (row = lane & 15, chunk = lane >> 4):
-// the instruction's four lane groups are {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32 (MI355X_MICROARCH.md, LDS), so the
-// four lanes of a group that share row & 3 are rows q = 0, 3 of one chunk and q = 1, 2 of the next (q = row >> 2); 0, 3, 2, 1 keeps them apart
-__device__ __forceinline__ int swz4(int q) { return (q & 3) ^ ((q & 1) << 1); }
-template <class F> __device__ __forceinline__ void static_for16(F&& f) { static_for_impl<0, 16>(f); }
-template <class F> __device__ __forceinline__ void static_for64(F&& f) { static_for_impl<0, 64>(f); }
 
 // EPI_QKV_ROPE8: QKV + RoPE on the generic 256x256 / 128x128 tiles.  RoPE only needs d and d + 48 of a head in the same lane
 // and register slot, not a whole head per wave, so the 3*H*96 output features are re-ordered into 32-feature UNITS - for q
@@ -120,7 +105,7 @@ struct GemmParams {
   unsigned* sk_cnt;    // [tiles] arrival tickets, zero between launches
 #ifdef AKI_LAB_HOOKS
   int probe_block;          // lab: which workgroup stamps (default 0)
-  long long* clock_probe;   // lab: 32 int64: {shader cycles, 100 MHz ticks} of workgroup 0, [2..17] phase sums of the PIPE 3 loop, [18] prologue, [19] epilogue cycles
+  long long* clock_probe;   // lab: 32 int64: {shader cycles, 100 MHz ticks} of workgroup 0, [18] prologue, [19] epilogue cycles
 #endif
   float st_eps;
 };
@@ -141,14 +126,9 @@ typedef int v8i_t __attribute__((ext_vector_type(8)));
 // FP8: e4m3 operands through v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales (2x the bf16 MFMA rate).  A 128-byte
 // LDS row then holds BK = 128 k-values instead of 64, so staging, swizzle and the epilogues are byte-for-byte the same; the
 // per-row dequantisation scales (one per token, one per weight row) multiply the f32 accumulators before the epilogue.
-// KG (K groups, small-M launches with at most one tile per CU): the workgroup is KG x (WN x WM) waves; group g has its own stage buffers and walks
-// K-steps g, g + KG, ... of the tile, so a CU holds KG waves per SIMD whose DMA waits, fragment reads and MFMAs overlap (one 4-wave workgroup alone
-// serialises them: 1200-1450 cycles per K-step for 384-512 of MFMA work).  After the loop the groups' accumulators meet in LDS and are added in
-// group order by group 0, which runs the epilogue alone: an on-chip, fixed-order fold - no partial tiles in memory, no tickets, bit-reproducible.
-template <int NF, int NT, int WN, int WM, int EPI, int ACT, bool FP8 = false, int NST = 2, int PIPE = 0, int SK = 0, int KG = 1>
-__global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2)) void gemm_bf16_kernel(const GemmParams p) {
-  static_assert(!SK || (!FP8 && PIPE <= 1), "split-K: bf16, the plain K loops and the mid-step-barrier pipeline");
-  static_assert(KG == 1 || (!FP8 && PIPE == 0 && NST == 2 && !SK), "K groups: bf16, the two-stage loop");
+template <int NF, int NT, int WN, int WM, int EPI, int ACT, bool FP8 = false, int NST = 2, int PIPE = 0, int SK = 0>
+__global__ __launch_bounds__(WN* WM * 64, (NF * NT > 32 ? 1 : 2)) void gemm_bf16_kernel(const GemmParams p) {
+  static_assert(!SK || (!FP8 && PIPE == 0), "split-K: bf16, the plain K loops");
   constexpr int BK = FP8 ? 128 : 64, ES = FP8 ? 1 : 2, NWAVES = WN * WM;
   constexpr int WROWS = NF * 16;      // features per wave
   constexpr int BN = WN * WROWS;      // features per block tile
@@ -161,11 +141,11 @@ __global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2
   extern __shared__ __attribute__((aligned(16))) char smem_all[];
 
   const int lane = threadIdx.x & 63;
-  const int wave_all = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int kgrp = KG > 1 ? wave_all / NWAVES : 0;                 // this wave's K group
-  const int wave = KG > 1 ? wave_all % NWAVES : wave_all;          // ... and its place in the group's WN x WM arrangement
-  const int tid = KG > 1 ? (int)threadIdx.x - kgrp * (NWAVES * 64) : (int)threadIdx.x;   // thread index inside the group (group 0 runs the epilogue)
-  char* const smem = smem_all + (KG > 1 ? kgrp * (NST * STAGE_BYTES) : 0);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int tid = threadIdx.x;
+  // LDS through a pointer rather than the array itself: hipcc then emits the stage-address arithmetic as inbounds offsets and keeps the
+  // DMA issue schedule of the deep rings it has always had (naming the array directly changes that schedule, not the results)
+  char* const smem = smem_all;
   const int wn = wave % WN, wm = wave / WN;
   const int l15 = lane & 15, kg = lane >> 4;
 #ifdef AKI_LAB_HOOKS
@@ -174,7 +154,7 @@ __global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2
   long long probe_c0 = 0, probe_w0 = 0;
   if ((int)blockIdx.x == p.probe_block && tid == 0 && p.clock_probe) { probe_c0 = clock64(); probe_w0 = wall_clock64(); }
   // probe_block == -2: EVERY workgroup stamps the 100 MHz wall clock (one time base for the whole chip) at its start, K-loop begin, K-loop end and
-  // exit into clock_probe[4 * blockIdx.x + 0..3] - the launch's timeline (dispatch ramp, stragglers, fold tails): tools/small_m_timeline.py
+  // exit into clock_probe[4 * blockIdx.x + 0..3] - the launch's timeline (dispatch ramp, stragglers, fold tails): tools/attic/small_m_timeline.py
 #define AKI_WG_STAMP(k) do { if (p.probe_block == -2 && tid == 0 && p.clock_probe) p.clock_probe[4 * (size_t)blockIdx.x + (k)] = wall_clock64(); } while (0)
   AKI_WG_STAMP(0);
 #else
@@ -230,12 +210,8 @@ __global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2
   const char* src[NLD];
 #pragma unroll
   for (int j = 0; j < NLD; ++j) {
-    // PIPE == 3 keeps the two k32 halves of a tile in separate 32 KiB regions (64-byte rows; a 1-KiB piece = 16 rows of one half,
-    // 16-byte chunk c of row r at position c ^ swz4(r >> 2)): a half is re-filled as soon as ITS fragments have been read
-    const int rowgroup = j * NWAVES + wave;
-    const int row = PIPE == 3 ? rowgroup * 16 + (lane >> 2) : rowgroup * 8 + (lane >> 3);
-    const int chunk = PIPE == 3 ? (lane & 3) ^ swz4(row >> 2) : (lane & 7) ^ ((row >> 1) & 7);
-    if (PIPE == 3 && j >= NLD / 2) { src[j] = nullptr; continue; }
+    const int row = (j * NWAVES + wave) * 8 + (lane >> 3);
+    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
     if (row < BN) {
       const int wr = weight_row(row);
       const char* wp = (const char*)p.w + (size_t)wr * p.ldw * ES;
@@ -248,16 +224,13 @@ __global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2
       src[j] = (const char*)p.x + (size_t)xrow * p.ldx * ES + chunk * 16;
     }
     if constexpr (SK) src[j] += (size_t)kt0 * 128;
-    if constexpr (KG > 1) src[j] += (size_t)kgrp * 128;               // group g starts at K-step g ...
   }
-  constexpr int KSTRIDE = KG * 128;                                   // ... and advances KG steps at a time (bytes per K-step of the group)
-  if constexpr (KG > 1) nk /= KG;                                     // host: the K-step count is a multiple of KG
 
   auto stage = [&](int s, int kt) {
 #pragma unroll
     for (int j = 0; j < NLD; ++j) {
       char* dst = smem + s * STAGE_BYTES + (j * NWAVES + wave) * 1024;
-      __builtin_amdgcn_global_load_lds(AKI_GLOBAL_PTR(src[j] + (size_t)kt * (KG > 1 ? KSTRIDE : 128)), AKI_LDS_PTR(dst), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(AKI_GLOBAL_PTR(src[j] + (size_t)kt * 128), AKI_LDS_PTR(dst), 16, 0, 0);
     }
   };
 
@@ -279,9 +252,9 @@ __global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2
   // staging, whose own round trip then covers it.
   constexpr int NOUT = (EPI == EPI_SWIGLU) ? NF / 2 : NF;     // output feature blocks per wave
   const int fwave = n0 + wn * (EPI == EPI_SWIGLU ? WROWS / 2 : WROWS);
-  // folded LayerNorm (consumer), kernel-uniform.  Not on the PIPELINED 256^2 tile: its epilogue has no registers left for the
-  // column sums (they spilled); the host sends row_shift launches that want the big tile to its unpipelined twin.
-  const bool shifted = (PIPE <= 1 || PIPE == 4 || PIPE == 7 || PIPE == 8) && (EPI == EPI_PLAIN) && p.row_shift != nullptr;
+  // folded LayerNorm (consumer), kernel-uniform.  Not with the residual prefetch (PIPE 5 / 6): the host sends row_shift launches that want the
+  // big tile to PIPE 4, whose straight-line interior epilogue has registers for the column sums.
+  const bool shifted = (PIPE == 0 || PIPE == 4 || PIPE == 8) && (EPI == EPI_PLAIN) && p.row_shift != nullptr;
   u32x2 biasp[NOUT];
   f32x4 colc4[NOUT];
   float rsv[NT], muv[NT];
@@ -310,10 +283,10 @@ __global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2
   constexpr bool RES_PF_OK = EPI == EPI_PLAIN && ACT == 0 && !FP8 && (!PIPE || PIPE == 8) && NST == 2 && RCH <= 64 && (64 % RCH == 0) && BM * RCH * 16 <= STAGE_BYTES &&
                              (PIPE != 8 || BM * RCH * 16 <= 2 * BM * 128) &&
                              (BM * RCH * 16) % (NWAVES * 1024) == 0;
-  const bool res_pf = RES_PF_OK && KG == 1 && p.residual != nullptr && p.res_wide && p.res_row_mod <= 0 && n_out >= 8;   // workgroup-uniform
+  const bool res_pf = RES_PF_OK && p.residual != nullptr && p.res_wide && p.res_row_mod <= 0 && n_out >= 8;   // workgroup-uniform
   int res_off = 0;                 // where the residual tile image sits in smem
   // QKV + RoPE on the pipelined 256 x 256 tile: cos / sin rows prefetched under the last half K-step (issue_cos_sin below); workgroup-uniform
-  const bool cs_pf = EPI == EPI_QKV_ROPE8 && (PIPE == 1 || PIPE == 4 || PIPE == 7) && BM == 256 && n0 / 32 < 6 * p.H && p.position_ids == nullptr && p.L >= BM;
+  const bool cs_pf = EPI == EPI_QKV_ROPE8 && PIPE == 4 && BM == 256 && n0 / 32 < 6 * p.H && p.position_ids == nullptr && p.L >= BM;
   if constexpr (EARLY_OPERANDS) fetch_epilogue_operands();
   auto compute = [&](const char* sb) {
     if constexpr (FP8) {   // one k128 step per BK: the lane's 32 bytes are chunks 2kg and 2kg+1 of its row
@@ -355,138 +328,17 @@ __global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2
   if ((int)blockIdx.x == p.probe_block && tid == 0 && p.clock_probe) probe_l0 = clock64();
 #endif
   AKI_WG_STAMP(1);
-  if constexpr (PIPE == 3) {
-    // One wave per SIMD with a hand-placed stream (lab).  Four waves, wave tile 128 features x 128 tokens: 256 accumulator registers
-    // in the AGPR half of the file, the fragments of both k32 halves (128 VGPRs) in the other - a third fewer LDS fragment bytes
-    // per FLOP than the 8-wave tile, and 95 instead of 134 other instructions per 128 MFMAs and SIMD.  This is the structure of the
-    // vendor library's kernel for these shapes (MT256x256x64, 256 threads; profiles/r03_hipblaslt_kernel_name.csv).  Left to hipcc's
-    // register allocation the same tile moved fragments through AGPRs (132 v_accvgpr_* per K-step) and ran 16-20 % slower; here every
-    // MFMA is an asm statement with the accumulator constrained to an AGPR and the fragment reads are asm too, in program order:
-    // one ds_read_b128 behind every 4th MFMA of the first half-step (the k32-half-1 fragments of tile kt), one read or one LDS-DMA
-    // piece behind every 2nd MFMA of the second (half-0 fragments of tile kt+1, the 16 pieces of tile kt+2); waits are explicit.
-    static_assert(PIPE != 3 || (NF == 8 && NT == 8 && WN == 2 && WM == 2 && NST == 2 && !FP8 && NLD == 16), "256 x 256 tile on four waves");
-    const unsigned lds0 = (unsigned)(unsigned long)((__attribute__((address_space(3))) char*)smem);
-    // stage buffer = [k32 half][512 rows: 256 features, 256 tokens][64 B]; stage 1 = address ^ STAGE_BYTES (64 KiB buffers, 64 KiB aligned)
-    constexpr int HALF_BYTES = STAGE_BYTES / 2;
-    const unsigned cpos = (unsigned)((kg ^ swz4(l15 >> 2)) << 4);
-    unsigned adrA0 = lds0 + (wn * WROWS + l15) * 64 + cpos, adrB0 = lds0 + (BN + wm * WTOK + l15) * 64 + cpos;
-    unsigned adrA1 = adrA0 + HALF_BYTES, adrB1 = adrB0 + HALF_BYTES;
-    bf16x8 a0[8], b0[8], a1[8], b1[8];
-#define AKI_DSR(dst, adr, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(adr), "n"(OFF))
-#define AKI_MFMA(n_, m_, A_, B_) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[n_][m_]) : "v"(A_[n_]), "v"(B_[m_]))
-    auto read_frag = [&](auto idx, bf16x8 (&fa)[8], bf16x8 (&fb)[8], unsigned adra, unsigned adrb) {   // fragment 0..7 = features, 8..15 = tokens
-      constexpr int I = decltype(idx)::value;
-      if constexpr (I < 8) AKI_DSR(fa[I], adra, I * 1024); else AKI_DSR(fb[I - 8], adrb, (I - 8) * 1024);
-    };
-    constexpr int NH = NLD / 2;                                  // DMA pieces per wave and half tile
-    auto dma_piece = [&](auto jj, int s, int h, int kt_) {
-      constexpr int J = decltype(jj)::value;
-      char* dst = smem + s * STAGE_BYTES + h * HALF_BYTES + (J * NWAVES + wave) * 1024;
-      __builtin_amdgcn_global_load_lds(AKI_GLOBAL_PTR(src[J] + (size_t)kt_ * 128 + h * 64), AKI_LDS_PTR(dst), 16, 0, 0);
-    };
-    // DMA order: (tile 0, half 0), (0, 1), (1, 0), (1, 1), then one half per half-step: (kt+2, h) during half-step (kt, h), into the region
-    // whose fragments every wave has finished reading at the barrier in front of that half-step.  A half then has a step and a half to land:
-    // it is awaited - counted, the two younger halves stay in flight - at the barrier in front of the half-step that READS it.
-    static_for_impl<0, NH>([&](auto j) { dma_piece(j, 0, 0, 0); });
-    static_for_impl<0, NH>([&](auto j) { dma_piece(j, 0, 1, 0); });
-    if (nk > 1) {
-      static_for_impl<0, NH>([&](auto j) { dma_piece(j, 1, 0, 1); });
-      static_for_impl<0, NH>([&](auto j) { dma_piece(j, 1, 1, 1); });
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * NH) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NH) : "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    static_for16([&](auto i) { read_frag(i, a0, b0, adrA0, adrB0); });
-#ifdef AKI_LAB_HOOKS
-    // phase stamps (lab): shader cycles per wave of workgroup 0 spent in {top wait + barrier, first half-step, mid wait + barrier,
-    // second half-step}, summed over the K loop -> clock_probe[2 + 4 * wave ..].  s_memtime returns through lgkmcnt: a stamp is only
-    // read behind one of the loop's own lgkmcnt(0) waits (SETTLE pins that for the compiler), so the stamps add no wait of their own.
-    unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, ph_a = 0, ph_b = 0, ph_c = 0, ph_d = 0;
-#define AKI_STAMP(t) asm volatile("s_memtime %0" : "=s"(t))
-#define AKI_SETTLE() asm volatile("" : "+s"(t0), "+s"(t1), "+s"(t2), "+s"(t3), "+s"(t4))
-#else
-#define AKI_STAMP(t)
-#define AKI_SETTLE()
-#endif
-    // one K-step; NEXT1 / NEXT2 (compile time): tiles kt+1 / kt+2 exist.  The 16 fragment reads of a half-step go out behind its FIRST
-    // 16 MFMAs (they are then 48 MFMAs = ~770 cycles old at the wait that needs them), the 8 DMA pieces behind every 4th MFMA after those
-    auto step3 = [&](int kt, auto n1, auto n2) {
-      constexpr bool NEXT1 = decltype(n1)::value, NEXT2 = decltype(n2)::value;
-      // half-0 fragments of tile kt are in a0 / b0; my pieces of (kt, half 1) have landed
-      AKI_STAMP(t0);
-      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NEXT1 ? 2 * NH : 0) : "memory");
-      __builtin_amdgcn_s_barrier();                              // ... everybody's have, and nobody reads (kt, half 0) from LDS any more
-#ifdef AKI_LAB_HOOKS
-      AKI_SETTLE();
-      ph_c += t3 - t2; ph_d += t4 - t3;                          // the previous step's second half
-#endif
-      AKI_STAMP(t1);
-      static_for64([&](auto ii) {                                // first half-step: MFMAs on a0 / b0, half-1 fragments of tile kt -> a1 / b1
-        constexpr int I = decltype(ii)::value, N_ = I >> 3, M_ = I & 7;
-        AKI_MFMA(N_, M_, a0, b0);
-        if constexpr (I < 16) read_frag(std::integral_constant<int, I>{}, a1, b1, adrA1, adrB1);
-        if constexpr (NEXT2 && I >= 17 && I < 65 && (I - 17) % 6 == 0) dma_piece(std::integral_constant<int, ((I - 17) / 6)>{}, kt & 1, 0, kt + 2);
-      });
-      AKI_STAMP(t2);
-      if constexpr (NEXT1) {
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NEXT2 ? 2 * NH : NH) : "memory");   // (kt+1, half 0) has landed; my reads of (kt, half 1) are done
-        __builtin_amdgcn_s_barrier();
-      } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-#ifdef AKI_LAB_HOOKS
-      AKI_SETTLE();
-      ph_a += t1 - t0; ph_b += t2 - t1;
-#endif
-      AKI_STAMP(t3);
-      adrA0 ^= STAGE_BYTES; adrA1 ^= STAGE_BYTES; adrB0 ^= STAGE_BYTES; adrB1 ^= STAGE_BYTES;       // tile kt+1's buffer
-      static_for64([&](auto ii) {                                // second half-step: MFMAs on a1 / b1; tile kt+1's half-0 fragments
-        constexpr int I = decltype(ii)::value, N_ = I >> 3, M_ = I & 7;
-        AKI_MFMA(N_, M_, a1, b1);
-        if constexpr (NEXT1 && I < 16) read_frag(std::integral_constant<int, I>{}, a0, b0, adrA0, adrB0);
-        if constexpr (NEXT2 && I >= 17 && I < 65 && (I - 17) % 6 == 0) dma_piece(std::integral_constant<int, ((I - 17) / 6)>{}, kt & 1, 1, kt + 2);
-      });
-      AKI_STAMP(t4);
-    };
-    {
-      int kt = 0;
-      for (; kt + 2 < nk; ++kt) step3(kt, std::true_type{}, std::true_type{});
-      if (kt + 1 < nk) { step3(kt, std::true_type{}, std::false_type{}); ++kt; }
-      step3(kt, std::false_type{}, std::false_type{});
-    }
-#ifdef AKI_LAB_HOOKS
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    AKI_SETTLE();
-    ph_c += t3 - t2; ph_d += t4 - t3;
-    if (blockIdx.x == 0 && lane == 0 && p.clock_probe) {
-      p.clock_probe[2 + 4 * wave + 0] = (long long)ph_a; p.clock_probe[2 + 4 * wave + 1] = (long long)ph_b;
-      p.clock_probe[2 + 4 * wave + 2] = (long long)ph_c; p.clock_probe[2 + 4 * wave + 3] = (long long)ph_d;
-    }
-#endif
-#undef AKI_STAMP
-#undef AKI_SETTLE
-    // hipcc does not see the asm MFMAs as matrix instructions: it pads no XDL-write -> VALU-read hazard in front of the epilogue's
-    // accumulator reads - the last MFMA (8 passes) has to have retired
-    asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-#undef AKI_DSR
-#undef AKI_MFMA
-  } else if constexpr (PIPE && PIPE != 8) {
-    // Mid-step barrier pipeline (bf16, 2 stages).  In the loop below every LDS fragment read of a K-step sits between
+  if constexpr (PIPE >= 4 && PIPE <= 6) {
+    // Mid-step barrier pipeline (bf16).  With the barrier at the top of a K-step every LDS fragment read of the step sits between
     // the barrier and the MFMAs that need it, and all eight waves do theirs at the same time: the LDS array (24
     // ds_read_b128 per wave and step, ~770 array cycles per CU) and then the matrix cores (2048 cycles per SIMD) take
-    // turns.  Here the barrier moves to the MIDDLE of the step: the k32-half-1 fragments of tile kt are read under the
+    // turns.  Here the barrier sits in the MIDDLE of the step: the k32-half-1 fragments of tile kt are read under the
     // half-0 MFMAs, and behind the barrier - which publishes tile kt+1 - its half-0 fragments are read under the half-1
-    // MFMAs of tile kt, into the registers the half-0 MFMAs have just released.  The DMA of tile kt+2 goes out right
-    // after the barrier (nobody reads that buffer any more) and has a full step to land, as before.
+    // MFMAs of tile kt, into the registers the half-0 MFMAs have just released.  One K-step is compiled per combination of
+    // NEXT1 / NEXT2 / NEXT3 (tiles kt+1 / kt+2 / kt+3 exist), so that the steady-state step is one basic block and the
+    // scheduling directives can spread the reads and the DMA issue between the MFMAs instead of leaving them in front: right
+    // after the barrier both waves of a SIMD would otherwise spend ~250 issue cycles on them with the matrix core idle.
     static_assert(NST == 2 && !FP8, "bf16, two stages");
-    auto load_frags = [&](const char* sb, int ks, bf16x8 (&a)[NF], bf16x8 (&b)[NT]) {
-      const int coff = ((4 * ks + kg) ^ swz) << 4;
-#pragma unroll
-      for (int n = 0; n < NF; ++n) a[n] = *(const bf16x8*)(sb + wbase + n * 2048 + coff);
-#pragma unroll
-      for (int m = 0; m < NT; ++m) b[m] = *(const bf16x8*)(sb + xbase + m * 2048 + coff);
-    };
     auto mma = [&](const bf16x8 (&a)[NF], const bf16x8 (&b)[NT]) {
 #pragma unroll
       for (int n = 0; n < NF; ++n)
@@ -498,13 +350,6 @@ __global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2
       for (int i = 0; i < NF + NT; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, (NF * NT) / (2 * (NF + NT)) > 0 ? (NF * NT) / (2 * (NF + NT)) : 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-    };
-    auto interleave_dma = [&]() {       // then NLD groups of (one MFMA, one global_load_lds)
-#pragma unroll
-      for (int i = 0; i < NLD; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
       }
     };
     // QKV + RoPE: the cos / sin rows of the tile's tokens (the epilogue's LDS image: token row r at r * 400, 12 chunks of cos[0:48], 12 of
@@ -529,172 +374,117 @@ __global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2
       }
     };
     bf16x8 a0[NF], b0[NT], a1[NF], b1[NT];
-    if constexpr (PIPE >= 4 && PIPE <= 7) {
-      // PIPE == 4: the same loop with the WEIGHT tiles on a three-deep ring (3 x 32 KiB) beside the two token-panel buffers (2 x 32 KiB; 160 KiB, all of
-      // the LDS): a weight tile is asked for TWO steps ahead instead of one.  Weights come out of HBM in every launch of the forward, and with the
-      // eight tiles that share a weight panel in lock-step every one of them waits for that first touch: workgroup 0's K-step is 2436 cycles with the
-      // weight on-die and 3032 with it in HBM (tools/gemm_cold_stamps.py), and the lab loop that asks 1.5 steps ahead loses a third of that.
-      // Issue order per step: token tile kt+2, then weight tile kt+3 - so the counted wait at the barrier leaves exactly the youngest weight tile in flight.
-      // PIPE == 5 = PIPE 4 + the residual tile prefetched under the last 1.5 K-steps (what PIPE 2 does on the two-stage layout): the tile's four
-      // blocks of 64 token rows (32 KiB each - the rows of one wave row wm) go wherever a 32 KiB slot has been read for the last time: block 0 into the
-      // slot of weight tile nk-3 after the barrier of step nk-3, blocks 1 and 2 into the slots of weight tile nk-2 and token tile nk-2 after the barrier
-      // of step nk-2, block 3 into the slot of weight tile nk-1 after the last barrier.  The epilogue finds a wave's block through res_off (set per wave below).
-      // PIPE == 7 / 6 = PIPE 4 / 5 with the roles swapped: the TOKEN tiles on the three-deep ring, the weight tiles on two buffers - for launches whose
-      // activation is the larger cold operand (down_proj: 86 MB of activations against 50 MB of weights).
-      constexpr bool DX = PIPE == 6 || PIPE == 7, RESPF = PIPE == 5 || PIPE == 6;
-      static_assert(PIPE < 4 || PIPE > 7 || (BN == BM && (BN / 8) % NWAVES == 0 && NLD % 2 == 0), "weight / token pieces split evenly");
-      static_assert(!RESPF || (WTOK == 64 && RCH == 32 && BM == 256 && NWAVES == 8), "one 32 KiB residual block per wave row");
-      constexpr int WB = BN * 128, XB = BM * 128, NLH = NLD / 2;
-      static_assert(WB == XB, "equal slots");
-      char* const sS = smem + 3 * WB;                   // the two-deep ring behind the three-deep one
-      constexpr int JD = DX ? NLH : 0, JS = DX ? 0 : NLH;   // src[] indices of the deep / shallow operand's pieces (weights are src[0 .. NLH))
-      auto stage_w = [&](int slot, int kt_) {            // the DEEP operand's tile kt_ (weights unless DX)
-#pragma unroll
-        for (int j = 0; j < NLH; ++j)
-          __builtin_amdgcn_global_load_lds(AKI_GLOBAL_PTR(src[JD + j] + (size_t)kt_ * 128), AKI_LDS_PTR(smem + slot * WB + (j * NWAVES + wave) * 1024), 16, 0, 0);
-      };
-      auto stage_x = [&](int slot, int kt_) {            // the SHALLOW operand's tile kt_
-#pragma unroll
-        for (int j = 0; j < NLH; ++j)
-          __builtin_amdgcn_global_load_lds(AKI_GLOBAL_PTR(src[JS + j] + (size_t)kt_ * 128), AKI_LDS_PTR(sS + slot * XB + (j * NWAVES + wave) * 1024), 16, 0, 0);
-      };
-      const int xb0 = (wm * WTOK + l15) * 128;
-      auto load_frags2 = [&](const char* sdeep, const char* sshal, int ks, bf16x8 (&a)[NF], bf16x8 (&b)[NT]) {
-        const char* const sw = DX ? sshal : sdeep;
-        const char* const sx = DX ? sdeep : sshal;
-        const int coff = ((4 * ks + kg) ^ swz) << 4;
-#pragma unroll
-        for (int n = 0; n < NF; ++n) a[n] = *(const bf16x8*)(sw + wbase + n * 2048 + coff);
-#pragma unroll
-        for (int m = 0; m < NT; ++m) b[m] = *(const bf16x8*)(sx + xb0 + m * 2048 + coff);
-      };
-      auto interleave_pieces = [&](int n_) {
-        for (int i = 0; i < n_; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-        }
-      };
-      int blkoff[4] = {0, 0, 0, 0};                     // PIPE 5: LDS byte offset of residual block b
-      auto issue_res_block = [&](int b_, int dst_off) {
-        if constexpr (RESPF) {
-          blkoff[b_] = dst_off;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int q = j * NWAVES + wave;                       // 1 KiB piece of the block = two token rows
-            const int tk = b_ * 64 + 2 * q + (lane >> 5);
-            const int ch = (lane & (RCH - 1)) ^ (tk & CMASK);
-            const int f = min(n0 + 8 * ch, n_out - 8);
-            const bf16_t* src_ = p.residual + (size_t)min(m0 + tk, p.M - 1) * p.ldr + f;
-            __builtin_amdgcn_global_load_lds(AKI_GLOBAL_PTR(src_), AKI_LDS_PTR(smem + dst_off + q * 1024), 16, 0, 0);
-          }
-        }
-      };
-      stage_w(0, 0); stage_x(0, 0);
-      if (nk > 1) { stage_w(1, 1); stage_x(1, 1); }
-      if (nk > 2) stage_w(2, 2);
-      if (nk > 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * NLH) : "memory");      // tile 0 landed; tile 1 and weight tile 2 may be in flight
-      else if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-#ifdef AKI_LAB_HOOKS
-      if ((int)blockIdx.x == p.probe_block && tid == 0 && p.clock_probe) p.clock_probe[21] = clock64() - probe_l0;   // first tile landed
-#endif
-      load_frags2(smem, sS, 0, a0, b0);
-      int ws = 0;                                      // ring slot of weight tile kt
-      auto step4 = [&](int kt, auto next1, auto next2, auto next3) {
-        constexpr bool NEXT1 = decltype(next1)::value, NEXT2 = decltype(next2)::value, NEXT3 = decltype(next3)::value;
-        const int ws1 = ws == 2 ? 0 : ws + 1;
-        load_frags2(smem + ws * WB, sS + (kt & 1) * XB, 1, a1, b1);
-        mma(a0, b0);
-        interleave_reads();
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (NEXT2) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NLH) : "memory");   // tile kt+1 landed (weight tile kt+2 stays in flight); my reads of tile kt are done
-        else if constexpr (NEXT1 || !RESPF) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // PIPE 5, last step: no tile is awaited, the residual blocks of step nk-2 stay in flight
-        __builtin_amdgcn_s_barrier();
-        if constexpr (NEXT1) load_frags2(smem + ws1 * WB, sS + ((kt + 1) & 1) * XB, 0, a0, b0);
-        if constexpr (NEXT2) stage_x(kt & 1, kt + 2);
-        if constexpr (NEXT3) stage_w(ws, kt + 3);
-        if constexpr (RESPF && NEXT2 && !NEXT3) issue_res_block(0, ws * WB);   // step nk-3: no weight tile nk will ask for this slot
-        if constexpr (RESPF && NEXT1 && !NEXT2) {             // step nk-2: two more slots have been read for the last time
-          if (nk == 2) issue_res_block(0, 2 * WB);                //   (no step nk-3: the third weight slot was never used)
-          issue_res_block(1, ws * WB);
-          issue_res_block(2, 3 * WB + (kt & 1) * XB);
-        }
-        if constexpr (RESPF && !NEXT1) {                     // last step
-          if (nk == 1) { issue_res_block(0, 1 * WB); issue_res_block(1, 2 * WB); issue_res_block(2, 3 * WB + XB); }
-          issue_res_block(3, ws * WB);
-        }
-        if constexpr (EPI == EPI_QKV_ROPE8 && !NEXT1) { if (cs_pf) issue_cos_sin(); }
-        mma(a1, b1);
-        if constexpr (NEXT1) interleave_reads();
-        if constexpr (NEXT2 || NEXT3) interleave_pieces((NEXT2 ? NLH : 0) + (NEXT3 ? NLH : 0));
-        if constexpr (RESPF && !NEXT3) interleave_pieces(NEXT2 ? 4 : (NEXT1 ? 8 : 4));
-        __builtin_amdgcn_sched_barrier(0);
-        ws = ws1;
-      };
-      int kt = 0;
-      for (; kt + 3 < nk; ++kt) step4(kt, std::true_type{}, std::true_type{}, std::true_type{});
-      if (kt + 2 < nk) { step4(kt, std::true_type{}, std::true_type{}, std::false_type{}); ++kt; }
-      if (kt + 1 < nk) { step4(kt, std::true_type{}, std::false_type{}, std::false_type{}); ++kt; }
-      step4(kt, std::false_type{}, std::false_type{}, std::false_type{});
-      if constexpr (RESPF) res_off = (wm == 0 ? blkoff[0] : wm == 1 ? blkoff[1] : wm == 2 ? blkoff[2] : blkoff[3]) - wm * (64 * RCH * 16);
-    } else {
-    stage(0, 0);
-    if (nk > 1) stage(1, 1);
-    if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");   // tile 0 landed (tile 1 may be in flight)
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    load_frags(smem, 0, a0, b0);
-    // one K-step; NEXT1 / NEXT2: tiles kt+1 / kt+2 exist (compile-time, so that the steady-state step is one basic
-    // block and the scheduling directives can spread the reads and the DMA issue between the MFMAs instead of leaving
-    // them in front: right after the barrier both waves of a SIMD would otherwise spend ~250 issue cycles on them with
-    // the matrix core idle)
-    // PIPE == 2 (plain GEMM + residual, 16-byte path, host-checked): the residual tile - BM rows x BN*2 bytes = exactly the two
-    // stage buffers - is brought in by LDS-DMA under the LAST TWO K-steps instead of after the loop, where its round trip
-    // (every workgroup of a one-round launch at the same moment: 32 MB chip-wide) was fully exposed: +8 us on o_proj / down.
-    // Half h (token rows [BM/2*h, +BM/2)) goes into stage buffer h as soon as nobody reads that buffer any more: buffer
-    // (nk-2)&1 after the mid-step barrier of step nk-2 (no tile nk to fetch), the other one after the barrier of step nk-1.
+    // PIPE == 4: the WEIGHT tiles on a three-deep ring (3 x 32 KiB) beside the two token-panel buffers (2 x 32 KiB; 160 KiB, all of the LDS):
+    // a weight tile is asked for TWO steps ahead.  Weights come out of HBM in every launch of the forward, and with the eight tiles that share a
+    // weight panel in lock-step every one of them waits for that first touch: workgroup 0's K-step is 2436 cycles with the weight on-die and 3032
+    // with it in HBM (tools/gemm_cold_stamps.py), and a two-deep ring that asks 1.5 steps ahead lost a third of that.
+    // Issue order per step: token tile kt+2, then weight tile kt+3 - so the counted wait at the barrier leaves exactly the youngest weight tile in flight.
+    // PIPE == 5 = PIPE 4 + the residual tile prefetched under the last 1.5 K-steps instead of fetched after the loop, where its round trip (every
+    // workgroup of a one-round launch at the same moment: 32 MB chip-wide) was fully exposed: +8 us on o_proj / down.  The tile's four
+    // blocks of 64 token rows (32 KiB each - the rows of one wave row wm) go wherever a 32 KiB slot has been read for the last time: block 0 into the
+    // slot of weight tile nk-3 after the barrier of step nk-3, blocks 1 and 2 into the slots of weight tile nk-2 and token tile nk-2 after the barrier
+    // of step nk-2, block 3 into the slot of weight tile nk-1 after the last barrier.  The epilogue finds a wave's block through res_off (set per wave below).
     // Image = the epilogue's: chunk c of token row t at chunk position c ^ (t & CMASK), swizzle on the SOURCE address.
-    auto issue_res_half = [&](int hb) {
-      static_assert(PIPE != 2 || (BM * RCH * 16 == 2 * STAGE_BYTES && NLD * NWAVES * 1024 == STAGE_BYTES), "residual tile = the two stage buffers");
+    // PIPE == 6 = PIPE 5 with the roles swapped: the TOKEN tiles on the three-deep ring, the weight tiles on two buffers - for launches whose
+    // activation is the larger cold operand (down_proj: 86 MB of activations against 50 MB of weights).
+    constexpr bool DX = PIPE == 6, RESPF = PIPE == 5 || PIPE == 6;
+    static_assert(BN == BM && (BN / 8) % NWAVES == 0 && NLD % 2 == 0, "weight / token pieces split evenly");
+    static_assert(!RESPF || (WTOK == 64 && RCH == 32 && BM == 256 && NWAVES == 8), "one 32 KiB residual block per wave row");
+    constexpr int WB = BN * 128, XB = BM * 128, NLH = NLD / 2;
+    static_assert(WB == XB, "equal slots");
+    char* const sS = smem + 3 * WB;                   // the two-deep ring behind the three-deep one
+    constexpr int JD = DX ? NLH : 0, JS = DX ? 0 : NLH;   // src[] indices of the deep / shallow operand's pieces (weights are src[0 .. NLH))
+    auto stage_w = [&](int slot, int kt_) {            // the DEEP operand's tile kt_ (weights unless DX)
 #pragma unroll
-      for (int j = 0; j < NLD; ++j) {
-        const int q = j * NWAVES + wave;                         // 1 KiB piece of the half = two token rows
-        const int tk = hb * (BM / 2) + 2 * q + (lane >> 5);
-        const int ch = (lane & (RCH - 1)) ^ (tk & CMASK);
-        const int f = min(n0 + 8 * ch, n_out - 8);
-        const bf16_t* src_ = p.residual + (size_t)min(m0 + tk, p.M - 1) * p.ldr + f;
-        __builtin_amdgcn_global_load_lds(AKI_GLOBAL_PTR(src_), AKI_LDS_PTR(smem + hb * STAGE_BYTES + q * 1024), 16, 0, 0);
+      for (int j = 0; j < NLH; ++j)
+        __builtin_amdgcn_global_load_lds(AKI_GLOBAL_PTR(src[JD + j] + (size_t)kt_ * 128), AKI_LDS_PTR(smem + slot * WB + (j * NWAVES + wave) * 1024), 16, 0, 0);
+    };
+    auto stage_x = [&](int slot, int kt_) {            // the SHALLOW operand's tile kt_
+#pragma unroll
+      for (int j = 0; j < NLH; ++j)
+        __builtin_amdgcn_global_load_lds(AKI_GLOBAL_PTR(src[JS + j] + (size_t)kt_ * 128), AKI_LDS_PTR(sS + slot * XB + (j * NWAVES + wave) * 1024), 16, 0, 0);
+    };
+    const int xb0 = (wm * WTOK + l15) * 128;
+    auto load_frags2 = [&](const char* sdeep, const char* sshal, int ks, bf16x8 (&a)[NF], bf16x8 (&b)[NT]) {
+      const char* const sw = DX ? sshal : sdeep;
+      const char* const sx = DX ? sdeep : sshal;
+      const int coff = ((4 * ks + kg) ^ swz) << 4;
+#pragma unroll
+      for (int n = 0; n < NF; ++n) a[n] = *(const bf16x8*)(sw + wbase + n * 2048 + coff);
+#pragma unroll
+      for (int m = 0; m < NT; ++m) b[m] = *(const bf16x8*)(sx + xb0 + m * 2048 + coff);
+    };
+    auto interleave_pieces = [&](int n_) {
+      for (int i = 0; i < n_; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
       }
     };
-    auto step = [&](int kt, auto next1, auto next2) {
-      constexpr bool NEXT1 = decltype(next1)::value, NEXT2 = decltype(next2)::value;
-      const char* sb = smem + (kt & 1) * STAGE_BYTES;
-      load_frags(sb, 1, a1, b1);
+    int blkoff[4] = {0, 0, 0, 0};                     // PIPE 5: LDS byte offset of residual block b
+    auto issue_res_block = [&](int b_, int dst_off) {
+      if constexpr (RESPF) {
+        blkoff[b_] = dst_off;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int q = j * NWAVES + wave;                       // 1 KiB piece of the block = two token rows
+          const int tk = b_ * 64 + 2 * q + (lane >> 5);
+          const int ch = (lane & (RCH - 1)) ^ (tk & CMASK);
+          const int f = min(n0 + 8 * ch, n_out - 8);
+          const bf16_t* src_ = p.residual + (size_t)min(m0 + tk, p.M - 1) * p.ldr + f;
+          __builtin_amdgcn_global_load_lds(AKI_GLOBAL_PTR(src_), AKI_LDS_PTR(smem + dst_off + q * 1024), 16, 0, 0);
+        }
+      }
+    };
+    stage_w(0, 0); stage_x(0, 0);
+    if (nk > 1) { stage_w(1, 1); stage_x(1, 1); }
+    if (nk > 2) stage_w(2, 2);
+    if (nk > 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * NLH) : "memory");      // tile 0 landed; tile 1 and weight tile 2 may be in flight
+    else if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+#ifdef AKI_LAB_HOOKS
+    if ((int)blockIdx.x == p.probe_block && tid == 0 && p.clock_probe) p.clock_probe[21] = clock64() - probe_l0;   // first tile landed
+#endif
+    load_frags2(smem, sS, 0, a0, b0);
+    int ws = 0;                                      // ring slot of weight tile kt
+    auto step4 = [&](int kt, auto next1, auto next2, auto next3) {
+      constexpr bool NEXT1 = decltype(next1)::value, NEXT2 = decltype(next2)::value, NEXT3 = decltype(next3)::value;
+      const int ws1 = ws == 2 ? 0 : ws + 1;
+      load_frags2(smem + ws * WB, sS + (kt & 1) * XB, 1, a1, b1);
       mma(a0, b0);
       interleave_reads();
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (NEXT1 || PIPE != 2) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // my pieces of tile kt+1 landed; my reads of tile kt are done
-      else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // last step: no tile is awaited, and the residual DMA of step nk-2 stays in flight
+      if constexpr (NEXT2) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NLH) : "memory");   // tile kt+1 landed (weight tile kt+2 stays in flight); my reads of tile kt are done
+      else if constexpr (NEXT1 || !RESPF) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // PIPE 5, last step: no tile is awaited, the residual blocks of step nk-2 stay in flight
       __builtin_amdgcn_s_barrier();
-      if constexpr (NEXT1) load_frags(smem + ((kt + 1) & 1) * STAGE_BYTES, 0, a0, b0);
-      if constexpr (NEXT2) stage(kt & 1, kt + 2);
-      if constexpr (PIPE == 2 && !NEXT2) {
-        issue_res_half(kt & 1);
-        if constexpr (!NEXT1) { if (nk == 1) issue_res_half((kt & 1) ^ 1); }
+      if constexpr (NEXT1) load_frags2(smem + ws1 * WB, sS + ((kt + 1) & 1) * XB, 0, a0, b0);
+      if constexpr (NEXT2) stage_x(kt & 1, kt + 2);
+      if constexpr (NEXT3) stage_w(ws, kt + 3);
+      if constexpr (RESPF && NEXT2 && !NEXT3) issue_res_block(0, ws * WB);   // step nk-3: no weight tile nk will ask for this slot
+      if constexpr (RESPF && NEXT1 && !NEXT2) {             // step nk-2: two more slots have been read for the last time
+        if (nk == 2) issue_res_block(0, 2 * WB);                //   (no step nk-3: the third weight slot was never used)
+        issue_res_block(1, ws * WB);
+        issue_res_block(2, 3 * WB + (kt & 1) * XB);
       }
-      if constexpr (EPI == EPI_QKV_ROPE8 && PIPE == 1 && !NEXT1) { if (cs_pf) issue_cos_sin(); }
+      if constexpr (RESPF && !NEXT1) {                     // last step
+        if (nk == 1) { issue_res_block(0, 1 * WB); issue_res_block(1, 2 * WB); issue_res_block(2, 3 * WB + XB); }
+        issue_res_block(3, ws * WB);
+      }
+      if constexpr (EPI == EPI_QKV_ROPE8 && !NEXT1) { if (cs_pf) issue_cos_sin(); }
       mma(a1, b1);
       if constexpr (NEXT1) interleave_reads();
-      if constexpr (NEXT2 || PIPE == 2) interleave_dma();
+      if constexpr (NEXT2 || NEXT3) interleave_pieces((NEXT2 ? NLH : 0) + (NEXT3 ? NLH : 0));
+      if constexpr (RESPF && !NEXT3) interleave_pieces(NEXT2 ? 4 : (NEXT1 ? 8 : 4));
       __builtin_amdgcn_sched_barrier(0);
+      ws = ws1;
     };
     int kt = 0;
-    for (; kt + 2 < nk; ++kt) step(kt, std::true_type{}, std::true_type{});
-    if (kt + 1 < nk) { step(kt, std::true_type{}, std::false_type{}); ++kt; }
-    step(kt, std::false_type{}, std::false_type{});
-    }
+    for (; kt + 3 < nk; ++kt) step4(kt, std::true_type{}, std::true_type{}, std::true_type{});
+    if (kt + 2 < nk) { step4(kt, std::true_type{}, std::true_type{}, std::false_type{}); ++kt; }
+    if (kt + 1 < nk) { step4(kt, std::true_type{}, std::false_type{}, std::false_type{}); ++kt; }
+    step4(kt, std::false_type{}, std::false_type{}, std::false_type{});
+    if constexpr (RESPF) res_off = (wm == 0 ? blkoff[0] : wm == 1 ? blkoff[1] : wm == 2 ? blkoff[2] : blkoff[3]) - wm * (64 * RCH * 16);
   } else if constexpr (PIPE == 8) {
     // Small tiles (two workgroups per CU), token tiles on a THREE-deep ring beside two weight buffers: a token tile is asked for two steps ahead.
     // For launches whose activation comes out of HBM - SigLIP fc2 reads the 40 MB fc1 has just written: 53.8 us with it on-die, 65.1 from HBM
@@ -804,28 +594,6 @@ __global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2
   if ((int)blockIdx.x == p.probe_block && tid == 0 && p.clock_probe) probe_l1 = clock64();
 #endif
   AKI_WG_STAMP(2);
-  if constexpr (KG > 1) {
-    // fold of the K groups through LDS, in group order (g0 + g1 + ...): the stage buffers are free once every wave has left the loop
-    static_assert(KG == 1 || BN * BM * 4 <= NST * STAGE_BYTES, "a group's accumulators fit its own stage buffers");
-    __syncthreads();
-    f32x4* const mine = (f32x4*)smem + (wave * NF * NT) * 64 + lane;             // fragment order: one 16-byte slot per lane and block
-    if (kgrp != 0) {
-#pragma unroll
-      for (int n = 0; n < NF; ++n)
-#pragma unroll
-        for (int m = 0; m < NT; ++m) mine[(n * NT + m) * 64] = acc[n][m];
-    }
-    __syncthreads();
-    if (kgrp != 0) { AKI_WG_STAMP(3); return; }                                   // (a finished wave leaves the workgroup's barriers)
-#pragma unroll
-    for (int g = 1; g < KG; ++g) {
-      const f32x4* const theirs = (const f32x4*)(smem_all + g * (NST * STAGE_BYTES)) + (wave * NF * NT) * 64 + lane;
-#pragma unroll
-      for (int n = 0; n < NF; ++n)
-#pragma unroll
-        for (int m = 0; m < NT; ++m) acc[n][m] += theirs[(n * NT + m) * 64];
-    }
-  }
   if constexpr (SK) {
     // Split-K fold, deterministic and without a second launch.  Every slice writes its f32 accumulators in fragment order (one 16-byte
     // store per lane and block: 1 KiB per wave-instruction, write-through), drains, and draws a ticket (cdna_hip_programming.md
@@ -860,7 +628,7 @@ __global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2
       if (sk_last == 0u) { AKI_WG_STAMP(3); return; }
       // The fold: sum over the slices IN SLICE ORDER, ((p0 + p1) + p2) ... - with this workgroup's own partial taken from its registers (the
       // same bits it stored) and, for the splits the planner hands out (2 and 3), every other slice's loads in flight at once: one memory
-      // round trip instead of one per pair of slices (the fold was ~6 us of a 30 us launch, tools/small_m_timeline.py).
+      // round trip instead of one per pair of slices (the fold was ~6 us of a 30 us launch, tools/attic/small_m_timeline.py).
       auto load_slice = [&](int i, f32x4 (&dst)[NF][NT]) {
 #pragma unroll
         for (int n = 0; n < NF; ++n)
@@ -1053,7 +821,7 @@ __global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2
   // rows, two to sixteen per thread.  Chunk c of token row t sits at chunk c ^ (t & CMASK): the 16 token rows of a
   // ds_read_b64 land in 16 different bank groups without padding (a padded 256 x 256 tile would not fit).
   const bool res_lds = (EPI == EPI_PLAIN) && p.residual != nullptr && p.res_wide;   // workgroup-uniform
-  if constexpr (PIPE == 2 || PIPE == 5 || PIPE == 6) {
+  if constexpr (PIPE == 5 || PIPE == 6) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // my pieces of the prefetched residual tile have landed ...
     __syncthreads();                                           // ... and so have everybody else's
   } else if (RES_PF_OK && res_pf) {
@@ -1252,7 +1020,7 @@ __global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2
         else if (key == 3) write_rows(c1{}, c1{}, c1{}, c0{}, c0{}, c0{});             // bias + residual
         else if (key == 6) write_rows(c1{}, c0{}, c1{}, c1{}, c0{}, c0{});             // residual + statistics (o_proj, down)
         else if (key == 7) write_rows(c1{}, c1{}, c1{}, c1{}, c0{}, c0{});             // + bias (SigLIP out / fc2)
-        else if constexpr (PIPE <= 1 || PIPE == 4 || PIPE == 7 || PIPE == 8) {
+        else if constexpr (PIPE == 0 || PIPE == 4 || PIPE == 8) {
           if (key == 25) write_rows(c1{}, c1{}, c0{}, c0{}, c1{}, c1{});               // folded LayerNorm + bias (SigLIP qkv / fc1)
           else done = false;
         } else done = false;
@@ -1346,23 +1114,22 @@ __global__ __launch_bounds__(WN* WM * 64 * KG, ((NF * NT > 32 || KG > 1) ? 1 : 2
 
 #ifdef AKI_LAB_HOOKS
 int g_sk_slice_major = 0;                            // set by aki_lab_set_slice_major (lab A/B of the split-K workgroup order)
-int g_sm_variant = -1, g_sm_ksplit = 1;              // set by aki_lab_set_small_m: force a small-M tile variant (launch_variant) and its K split
-int g_force_tile = 0, g_deep_ring = 1, g_pipe = 1, g_deepx = 0;   // set by aki_lab_set_gemm_tile (lab build only); g_pipe: 0 off, 1 on, 2 on without the residual prefetch
+int g_force_tile = 0, g_deep_ring = 1, g_res_prefetch = 1, g_deepx = 0;   // set by aki_lab_set_gemm_tile (lab build only)
 long long* g_clock_probe = nullptr;                  // set by aki_lab_set_clock_probe
 int g_probe_block = 0;                               // set by aki_lab_set_probe_block
 #else
-static constexpr int g_force_tile = 0, g_deep_ring = 1, g_pipe = 1, g_deepx = 0, g_sm_variant = -1, g_sm_ksplit = 1, g_sk_slice_major = 0;
+static constexpr int g_force_tile = 0, g_deep_ring = 1, g_res_prefetch = 1, g_deepx = 0, g_sk_slice_major = 0;
 #endif
 
-template <int NF, int NT, int WN, int WM, int EPI, int ACT = 0, bool FP8 = false, int NST = 2, int PIPE = 0, int SK = 0, int KG = 1>
+template <int NF, int NT, int WN, int WM, int EPI, int ACT = 0, bool FP8 = false, int NST = 2, int PIPE = 0, int SK = 0>
 static int launch_gemm(GemmParams& p, hipStream_t stream) {
   constexpr int BN = WN * NF * 16, BM = WM * NT * 16;
-  constexpr int SMEM = (PIPE >= 4 && PIPE <= 7) ? (BN > BM ? 3 * BN + 2 * BM : 3 * BM + 2 * BN) * 128   // PIPE 4-7: three + two tiles
-                       : (PIPE == 8 ? (2 * BN + 4 * BM) * 128 : KG * NST * (BN + BM) * 128);                 // PIPE 8: two weight, three token slots + a spare
+  constexpr int SMEM = (PIPE >= 4 && PIPE <= 6) ? (BN > BM ? 3 * BN + 2 * BM : 3 * BM + 2 * BN) * 128   // PIPE 4-6: three + two tiles
+                       : (PIPE == 8 ? (2 * BN + 4 * BM) * 128 : NST * (BN + BM) * 128);                      // PIPE 8: two weight, three token slots + a spare
   static_assert(SMEM <= 160 * 1024, "LDS");
   static bool attr_set = false;
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)gemm_bf16_kernel<NF, NT, WN, WM, EPI, ACT, FP8, NST, PIPE, SK, KG>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)gemm_bf16_kernel<NF, NT, WN, WM, EPI, ACT, FP8, NST, PIPE, SK>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
       return AKI_ERR_LAUNCH;
     attr_set = true;
   }
@@ -1377,13 +1144,12 @@ static int launch_gemm(GemmParams& p, hipStream_t stream) {
 #endif
   const int slices = SK ? (p.ksplit > 1 ? p.ksplit : (p.ksplit = 1)) : 1;
   p.sk_slice_major = g_sk_slice_major;
-  if (KG > 1 && (p.K / 64) % KG) return AKI_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((gemm_bf16_kernel<NF, NT, WN, WM, EPI, ACT, FP8, NST, PIPE, SK, KG>), dim3(p.tiles_m * p.tiles_n * slices), dim3(WN * WM * 64 * KG), SMEM, stream, p);
+  hipLaunchKernelGGL((gemm_bf16_kernel<NF, NT, WN, WM, EPI, ACT, FP8, NST, PIPE, SK>), dim3(p.tiles_m * p.tiles_n * slices), dim3(WN * WM * 64), SMEM, stream, p);
   AKI_LAUNCH_CHECK();
   return AKI_OK;
 }
 
-// g_force_tile: 0 = heuristic, 1 = 256^2, 2 = 128^2, 3 = 128 features x 96 tokens, 5 = 64 x 64 on a four-stage ring (plain bf16 only), 4 = lab loop
+// g_force_tile: 0 = heuristic, 1 = 256^2, 2 = 128^2, 3 = 128 features x 96 tokens, 5 = 64 x 64 on a four-stage ring (plain bf16 only)
 
 // Cost model in units of one 256x256 tile's run time.  256^2 tiles: one workgroup per CU.  128-token tiles do a
 // quarter of the work; up to 256 of them run one per CU at ~75 % of the big tile's efficiency, beyond that two share a CU
@@ -1452,27 +1218,22 @@ static int launch_small(GemmParams& p, hipStream_t stream) {
   return launch_gemm<4, 4, 2, 2, EPI, ACT, FP8>(p, stream);
 }
 
-// g_pipe (lab bit 9 clears it): mid-step barrier pipeline on the 256 x 256 tile
-
 // Which operand of a residual GEMM gets the three-deep ring: the tokens when the activation panel is the larger cold operand (lab bit 12 forces it, bit 13 forbids it)
 static bool deep_tokens(const GemmParams& p) { return g_deepx == 1 || (g_deepx == 0 && (long)p.M > 3L * p.N / 2 && p.K >= 4096); }
 
+// 256 x 256 tiles: the two-stage loop for fp8, the mid-step pipeline with a three-deep ring for bf16.  g_res_prefetch (lab bit 10 clears it):
+// residual tile prefetched under the last K-steps (o_proj, down_proj)
 template <int EPI, int ACT, bool FP8>
 static int launch_big(GemmParams& p, hipStream_t stream) {
-  if constexpr (!FP8) {
-#ifdef AKI_LAB_HOOKS
-    // lab: the same 256 x 256 tile on FOUR waves, one per SIMD (wave tile 128 features x 128 tokens, 256 accumulator registers)
-    if (g_force_tile == 4 && p.row_shift == nullptr) return launch_gemm<8, 8, 2, 2, EPI, ACT, FP8, 2, 3>(p, stream);
-#endif
-    if constexpr (EPI == EPI_PLAIN && ACT == 0) {   // residual tile prefetched under the last K-steps (o_proj, down_proj)
-      if ((g_pipe == 1 || g_pipe == 3) && p.row_shift == nullptr && p.residual != nullptr && p.res_wide && p.res_row_mod <= 0 && p.N % 8 == 0 && p.N >= 8)
-        return g_pipe == 3 ? launch_gemm<8, 4, 2, 4, EPI, ACT, FP8, 2, 2>(p, stream)
-               : (deep_tokens(p) ? launch_gemm<8, 4, 2, 4, EPI, ACT, FP8, 2, 6>(p, stream) : launch_gemm<8, 4, 2, 4, EPI, ACT, FP8, 2, 5>(p, stream));
+  if constexpr (FP8) {
+    return launch_gemm<8, 4, 2, 4, EPI, ACT, FP8>(p, stream);
+  } else {
+    if constexpr (EPI == EPI_PLAIN && ACT == 0) {
+      if (g_res_prefetch && p.row_shift == nullptr && p.residual != nullptr && p.res_wide && p.res_row_mod <= 0 && p.N % 8 == 0 && p.N >= 8)
+        return deep_tokens(p) ? launch_gemm<8, 4, 2, 4, EPI, ACT, FP8, 2, 6>(p, stream) : launch_gemm<8, 4, 2, 4, EPI, ACT, FP8, 2, 5>(p, stream);
     }
-    if (g_pipe == 3) return launch_gemm<8, 4, 2, 4, EPI, ACT, FP8, 2, 1>(p, stream);   // lab: two-deep weight ring
-    if (g_pipe) return launch_gemm<8, 4, 2, 4, EPI, ACT, FP8, 2, 4>(p, stream);
+    return launch_gemm<8, 4, 2, 4, EPI, ACT, FP8, 2, 4>(p, stream);
   }
-  return launch_gemm<8, 4, 2, 4, EPI, ACT, FP8>(p, stream);
 }
 
 // ---- small M (one-sample prefill: M = 655 / 207; one image through the SigLIP tower: M = 576) --------------------------------------
@@ -1480,35 +1241,36 @@ static int launch_big(GemmParams& p, hipStream_t stream) {
 // over `ksplit` workgroups (EPI_PLAIN without activation).  What these launches lack is not FLOPs but requests in flight: a 128 x 128 tile on
 // the two-stage loop has ONE 32 KiB tile outstanding per workgroup and pays the memory latency every K-step (o_proj at M = 655: 144
 // workgroups x 48 steps x ~2000 cycles = 46 us for 12 GFLOP).
+// The variants plan_small_m hands out (numbered as in the sweep of EXPERIMENTS.md, round 5):
 //   id  features x tokens  stages  LDS      per CU
-//   0   128 x 128          2       64 KiB   2          5   128 x 64   3   72 KiB   2
-//   1   128 x 128          3       96 KiB   1          6   64 x 128   3   72 KiB   2
-//   2   128 x 128          4       128 KiB  1          7   64 x 64    4   64 KiB   2
-//   3   128 x 96           2       56 KiB   2          8   128 x 64   2   48 KiB   3
-//   4   128 x 96           3       84 KiB   1          9   64 x 128   4   96 KiB   1
-constexpr int kSmallMVariants = 21;
-struct SmallMTile { int bn, bm, lds_kib; };
-static const SmallMTile kSmallMTiles[kSmallMVariants] = {{128, 128, 64}, {128, 128, 96}, {128, 128, 128}, {128, 96, 56}, {128, 96, 84},
-                                                        {128, 64, 72}, {64, 128, 72}, {64, 64, 64}, {128, 64, 48}, {64, 128, 96},
-                                                        // 10-15: the mid-step-barrier pipeline (PIPE 1: fragments double-buffered in registers, reads and DMA issue spread between the MFMAs)
-                                                        {128, 128, 64}, {128, 96, 56}, {256, 128, 96}, {128, 128, 64}, {256, 64, 80}, {128, 256, 96},
-                                                        // 16-20: K groups inside the workgroup (KG x 4 waves, fold through LDS): 128 x 96 x 2, 128 x 128 x 2, 128 x 64 x 2 / x 3, 64 x 64 x 4
-                                                        {128, 96, 112}, {128, 128, 128}, {128, 64, 96}, {128, 64, 144}, {64, 64, 128}};
+//   1   128 x 128          3       96 KiB   1
+//   3   128 x 96           2       56 KiB   2
+//   4   128 x 96           3       84 KiB   1
+//   5   128 x 64           3       72 KiB   2
+struct SmallMTile { int bn, bm; };
+static SmallMTile small_m_tile(int variant) {
+  switch (variant) {
+    case 1: return {128, 128};
+    case 3: case 4: return {128, 96};
+    case 5: return {128, 64};
+  }
+  return {0, 0};
+}
 size_t linear_splitk_cnt_bytes() { return size_t(64) << 10; }     // 16 384 tile tickets, at the front of the split-K workspace
-size_t linear_splitk_ws_bytes(int variant, int ksplit, int M, int n_out) {
-  if (ksplit <= 1 || variant < 0 || variant >= kSmallMVariants) return 0;
-  const SmallMTile& tl = kSmallMTiles[variant];
+static size_t linear_splitk_ws_bytes(int variant, int ksplit, int M, int n_out) {
+  const SmallMTile tl = small_m_tile(variant);
+  if (ksplit <= 1 || tl.bn == 0) return 0;
   const size_t tiles = (size_t)((M + tl.bm - 1) / tl.bm) * ((n_out + tl.bn - 1) / tl.bn);
   return linear_splitk_cnt_bytes() + tiles * ksplit * tl.bn * tl.bm * sizeof(float);
 }
 
 // The planner's choice for a bf16 GEMM with few rows (17 .. 1024: a one-sample prefill, one image through the tower): tile variant (-1: none, the
-// ordinary plans) and K split.  From tools/small_m_sweep.py on cold operands (profiles/r05_small_m_sweep.txt, us per launch, planner before -> now):
+// ordinary plans) and K split.  From tools/attic/small_m_sweep.py on cold operands (profiles/r05_small_m_sweep.txt, us per launch, planner before -> now):
 //   plain, N <= 4096, K >= 2304 (o_proj / down / SigLIP fc2): 128 x 96 (M > 256) or 128 x 64 tiles, K split 3 ways when the tiles alone
 //     leave the 512 two-per-CU slots under-filled - M 655: o_proj 46.6 -> 37.2, down 97.2 -> 59.4; M 207: 27.1 -> 24.5, 47.1 -> 38.5; fc2 26.9 -> 22.7.
 //     Deeper rings, 256-wide tiles and the register-pipelined loop on these tiles all lost: one 4-wave workgroup per CU serialises DMA wait,
 //     fragment reads and MFMAs (1200-1450 cycles per K-step for 384-512 of MFMA work, warm or cold), two per CU overlap them, and the
-//     launch's fixed costs (prologue 1.5 us, fold / statistics tails 3-15 us) are then as long as the K loop (tools/small_m_timeline.py).
+//     launch's fixed costs (prologue 1.5 us, fold / statistics tails 3-15 us) are then as long as the K loop (tools/attic/small_m_timeline.py).
 //   QKV + RoPE: 128 x 96 tiles (M > 256: 57.8 -> 48.5) or the same on a three-stage ring (M 207: 46.5 -> 31.0).
 //   gate_up + SwiGLU, M <= 256: 128 x 128 on a three-stage ring (47.4 -> 36.8); above that the 256 x 256 tile stays (76 us at M 655).
 static void plan_small_m(int epi, int M, int n_out, int K, bool can_split, int& variant, int& ksplit) {
@@ -1519,7 +1281,7 @@ static void plan_small_m(int epi, int M, int n_out, int K, bool can_split, int& 
   if (epi == EPI_SWIGLU) { if (M <= 256 && nk >= 8) variant = 1; return; }
   if (n_out > 4096 || nk < 36 || !can_split) return;
   const int v = M > 256 ? 3 : 5;
-  const SmallMTile& tl = kSmallMTiles[v];
+  const SmallMTile tl = small_m_tile(v);
   const long tiles = (long)((M + tl.bm - 1) / tl.bm) * ((n_out + tl.bn - 1) / tl.bn);
   const int ks = (int)(512 / tiles) < 3 ? (int)(512 / tiles) : 3;
   if (ks < 2) return;
@@ -1531,48 +1293,7 @@ size_t linear_splitk_plan_ws_bytes(int M, int N, int K) {
   return linear_splitk_ws_bytes(v, ks, M, N);
 }
 
-template <int EPI, int ACT>
-static int launch_variant(GemmParams& p, int variant, int ksplit, hipStream_t stream) {
-  constexpr int SKV = (EPI == EPI_PLAIN && ACT == 0) ? 1 : 0;
-  p.ksplit = SKV ? ksplit : 1;
-  // Every variant exists for the plain GEMM (the one that can split K); the epilogue families that cannot (QKV + RoPE, SwiGLU, GELU) get the
-  // variants whose numbers are on record for them (EXPERIMENTS.md, round 5) - each instantiation is 2-3 s of compile time in the lab object.
-  constexpr bool ALL = EPI == EPI_PLAIN && ACT == 0, MOST = EPI != EPI_PLAIN;
-  switch (variant) {
-    case 0: return launch_gemm<4, 4, 2, 2, EPI, ACT, false, 2, 0, SKV>(p, stream);
-    case 3: return launch_gemm<4, 3, 2, 2, EPI, ACT, false, 2, 0, SKV>(p, stream);
-    case 4: return launch_gemm<4, 3, 2, 2, EPI, ACT, false, 3, 0, SKV>(p, stream);
-    case 6: return launch_gemm<2, 4, 2, 2, EPI, ACT, false, 3, 0, SKV>(p, stream);
-    case 16: p.ksplit = 1; return launch_gemm<4, 3, 2, 2, EPI, ACT, false, 2, 0, 0, 2>(p, stream);
-  }
-  if constexpr (ALL || MOST) {
-    switch (variant) {
-      case 1: return launch_gemm<4, 4, 2, 2, EPI, ACT, false, 3, 0, SKV>(p, stream);
-      case 2: return launch_gemm<4, 4, 2, 2, EPI, ACT, false, 4, 0, SKV>(p, stream);
-      case 5: return launch_gemm<4, 2, 2, 2, EPI, ACT, false, 3, 0, SKV>(p, stream);
-      case 7: return launch_gemm<2, 2, 2, 2, EPI, ACT, false, 4, 0, SKV>(p, stream);
-      case 8: return launch_gemm<4, 2, 2, 2, EPI, ACT, false, 2, 0, SKV>(p, stream);
-      case 9: return launch_gemm<2, 4, 2, 2, EPI, ACT, false, 4, 0, SKV>(p, stream);
-      case 10: return launch_gemm<4, 4, 2, 2, EPI, ACT, false, 2, 1, SKV>(p, stream);
-      case 11: return launch_gemm<4, 3, 2, 2, EPI, ACT, false, 2, 1, SKV>(p, stream);
-      case 17: p.ksplit = 1; return launch_gemm<4, 4, 2, 2, EPI, ACT, false, 2, 0, 0, 2>(p, stream);
-    }
-  }
-  if constexpr (ALL) {
-    switch (variant) {
-      case 12: return launch_gemm<8, 4, 2, 2, EPI, ACT, false, 2, 1, SKV>(p, stream);
-      case 13: return launch_gemm<8, 4, 1, 2, EPI, ACT, false, 2, 1, SKV>(p, stream);     // two waves, wave tile 128 features x 64 tokens
-      case 14: return launch_gemm<8, 2, 2, 2, EPI, ACT, false, 2, 1, SKV>(p, stream);
-      case 15: return launch_gemm<4, 4, 2, 4, EPI, ACT, false, 2, 1, SKV>(p, stream);
-      case 18: p.ksplit = 1; return launch_gemm<4, 2, 2, 2, EPI, ACT, false, 2, 0, 0, 2>(p, stream);
-      case 19: p.ksplit = 1; return launch_gemm<4, 2, 2, 2, EPI, ACT, false, 2, 0, 0, 3>(p, stream);
-      case 20: p.ksplit = 1; return launch_gemm<2, 2, 2, 2, EPI, ACT, false, 2, 0, 0, 4>(p, stream);
-    }
-  }
-  return AKI_ERR_UNSUPPORTED;
-}
-
-// the variants plan_small_m hands out (the product library instantiates these and no others)
+// the variant plan_small_m chose
 template <int EPI, int ACT>
 static int launch_small_m(GemmParams& p, int variant, int ksplit, hipStream_t stream) {
   p.ksplit = ksplit;
@@ -1590,17 +1311,8 @@ static int launch_small_m(GemmParams& p, int variant, int ksplit, hipStream_t st
 
 template <int EPI, int ACT, bool FP8 = false>
 static int run_planned(GemmParams& p, int plan, hipStream_t stream) {
-#ifdef AKI_LAB_HOOKS
-  if constexpr (!FP8) {
-    if (g_sm_variant >= 0) {                       // lab: forced small-M variant
-      int ks = g_sm_ksplit;
-      if (ks > 1 && (p.sk_part == nullptr || ks > p.K / 64)) ks = 1;
-      return launch_variant<EPI, ACT>(p, g_sm_variant, ks, stream);
-    }
-  }
-#endif
   if constexpr (!FP8 && (EPI != EPI_PLAIN || ACT == 0)) {
-    if (g_sm_variant != -2 && (p.w2 == nullptr)) {        // (lab: -2 = the plans as they were before the small-M planner)
+    if (p.w2 == nullptr) {
       int v, ks;
       const int n_out = (EPI == EPI_SWIGLU) ? p.N / 2 : p.N;
       plan_small_m(EPI, p.M, n_out, p.K, p.sk_part != nullptr, v, ks);
@@ -1611,7 +1323,7 @@ static int run_planned(GemmParams& p, int plan, hipStream_t stream) {
   if (plan == 1) return launch_small<EPI, ACT, FP8>(p, stream);
   if (plan == 0) return launch_big<EPI, ACT, FP8>(p, stream);
   if constexpr (EPI == EPI_PLAIN && !FP8) {
-    if (plan == 3) return g_pipe == 3 ? launch_gemm<4, 3, 2, 2, EPI, ACT, FP8>(p, stream) : launch_gemm<4, 3, 2, 2, EPI, ACT, FP8, 2, 8>(p, stream);   // 128 features x 96 tokens (token tiles three deep)
+    if (plan == 3) return launch_gemm<4, 3, 2, 2, EPI, ACT, FP8, 2, 8>(p, stream);   // 128 features x 96 tokens (token tiles three deep)
     if (plan == 4) return launch_gemm<2, 2, 2, 2, EPI, ACT, FP8, 4>(p, stream);   // 64 features x 64 tokens, four-stage ring
   }
   const int m_main = p.M / 256 * 256;
@@ -1689,9 +1401,6 @@ int linear_bf16(const aki_linear_args* a, hipStream_t stream) {
     p.sk_cnt = (unsigned*)a->splitk_workspace;
     p.sk_part = (float*)((char*)a->splitk_workspace + linear_splitk_cnt_bytes());
     p.sk_bytes = a->splitk_workspace_bytes - linear_splitk_cnt_bytes();
-#ifdef AKI_LAB_HOOKS
-    if (g_sm_variant >= 0 && a->splitk_workspace_bytes < linear_splitk_ws_bytes(g_sm_variant, g_sm_ksplit, a->M, n_out)) p.sk_part = nullptr;
-#endif
   }
   const int plan = plan_tiles(a->M, n_out, 256, 128, 0.25, true, a->K / 64);
   switch (a->act) {

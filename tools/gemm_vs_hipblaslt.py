@@ -37,7 +37,7 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--m", type=int, default=8 * 655)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--lab-modes", default="", help="comma-separated aki_lab_set_gemm_tile modes to time as extra arms (lab library), e.g. 1,4")
+    ap.add_argument("--lab-modes", default="", help="comma-separated aki_lab_set_gemm_tile modes to time as extra arms (lab library), e.g. 1,2")
     ap.add_argument("--shapes", default="", help="comma-separated subset of qkv,o_proj,gate_up,down,lm_head")
     ap.add_argument("--set", default="decoder", choices=["decoder", "siglip", "prefill"])
     ap.add_argument("--cold", action="store_true", help="rotate x / w through 8 buffer sets (operands come out of HBM, as in the forward)")

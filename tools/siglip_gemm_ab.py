@@ -4,7 +4,7 @@ LayerNorm, out-proj with bias + residual + statistics, fc1 with folded LayerNorm
 the benchmark batch (8 images x 576 patches), under each tile configuration of the lab library, interleaved rounds in one process.
 Also the decoder's one-round GEMMs with their epilogue pieces switched on one at a time (what residual / statistics cost).
 
-    python tools/siglip_gemm_ab.py [--modes 0,1,2,3,4] [--rounds 5] [--iters 20]
+    python tools/siglip_gemm_ab.py [--modes 0,1,2,3] [--rounds 5] [--iters 20]
 """
 import argparse
 import json
@@ -31,7 +31,7 @@ def loop_us(fn, iters):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--modes", default="0,1,2,3,4")
+    ap.add_argument("--modes", default="0,1,2,3")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--json", default=None)

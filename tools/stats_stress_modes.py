@@ -12,7 +12,7 @@ g = torch.Generator(device=dev).manual_seed(0)
 shapes = [(5240, 3072, 3072), (5240, 3072, 8192), (4608, 1152, 1152), (4608, 1152, 4352), (1380, 3072, 256)]
 data = {s: (torch.randn(s[0], s[2], device=dev, generator=g).to(torch.bfloat16), (torch.randn(s[1], s[2], device=dev, generator=g) * 0.05).to(torch.bfloat16),
             (torch.randn(s[0], s[1], device=dev, generator=g) * 2).to(torch.bfloat16)) for s in shapes}
-modes = {0: "product", 1: "256x256", 2: "128x128", 3: "128x96", 5: "64x64 ring", 2048: "two-stage loops", 3 + 2048: "128x96 two-stage", 4096: "tokens deep", 8192: "weights deep", 1 + 4096: "256x256 tokens deep", 1 + 8192: "256x256 weights deep"}
+modes = {0: "product", 1: "256x256", 2: "128x128", 3: "128x96", 5: "64x64 ring", 4096: "tokens deep", 8192: "weights deep", 1 + 4096: "256x256 tokens deep", 1 + 8192: "256x256 weights deep"}
 for mode, name in modes.items():
     lib.aki_lab_set_gemm_tile(mode)
     want = {}; n = bad = 0; t0 = time.time(); per = {}

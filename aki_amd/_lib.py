@@ -271,7 +271,26 @@ def load_lab() -> C.CDLL:
     lib.aki_lab_set_slice_major.argtypes = [C.c_int]
     lib.aki_lab_set_chain_fault.restype = None
     lib.aki_lab_set_chain_fault.argtypes = [C.c_int, C.c_int]
+    lib.aki_lab_gemm_log_reset.restype = None
+    lib.aki_lab_gemm_log_reset.argtypes = []
+    lib.aki_lab_gemm_log.restype = C.c_int
+    lib.aki_lab_gemm_log.argtypes = [C.c_void_p, C.c_int]
+    lib.aki_lab_set_gemm_dry_run.restype = None
+    lib.aki_lab_set_gemm_dry_run.argtypes = [C.c_int]
     return lib
+
+
+GEMM_LOG_FIELDS = ("NF", "NT", "WN", "WM", "EPI", "ACT", "FP8", "NST", "PIPE", "SK", "ksplit", "M", "m_offset", "grid")
+
+
+def gemm_log(lib: C.CDLL, cap: int = 64) -> list:
+    """The lab library's GEMM route log since the last aki_lab_gemm_log_reset(): one tuple per launch (fields: GEMM_LOG_FIELDS)."""
+    buf = (C.c_int32 * (cap * len(GEMM_LOG_FIELDS)))()
+    count = lib.aki_lab_gemm_log(buf, cap)
+    if count > cap:
+        raise AkiError(f"gemm_log: {count} launches recorded, more than cap = {cap}")
+    f = len(GEMM_LOG_FIELDS)
+    return [tuple(buf[i * f:(i + 1) * f]) for i in range(count)]
 
 
 class use_lab:

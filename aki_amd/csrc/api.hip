@@ -69,6 +69,9 @@ extern int g_deepx;
 extern int g_attn_variant;
 extern long long* g_clock_probe;
 extern int g_probe_block;
+extern int g_gemm_dry_run;
+void gemm_log_reset();
+int gemm_log_copy(int* out, int cap);
 #endif
 size_t attn_bwd_ws_bytes(int B, int H, int Lq);
 int attn_bwd_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, void* dq, void* dk,
@@ -137,6 +140,12 @@ void aki_lab_set_attn_variant(int v) { aki::g_attn_variant = v; }
 // device pointer to two int64: every bf16 GEMM launch then leaves {shader cycles, 100 MHz wall ticks} of its workgroup 0 there
 void aki_lab_set_probe_block(int b) { aki::g_probe_block = b; }   // which workgroup of a GEMM launch stamps
 void aki_lab_set_clock_probe(void* int64x32) { aki::g_clock_probe = (long long*)int64x32; }   // 32 int64 (layout: GemmParams::clock_probe)
+// route log of the bf16 / fp8 GEMM (gemm_bf16.hip, launch_gemm): 14 int32 per launch {NF, NT, WN, WM, EPI, ACT, FP8, NST, PIPE, SK, ksplit,
+// M, m_offset, grid}; aki_lab_gemm_log copies up to `cap` records and returns the number of launches since the last reset
+void aki_lab_gemm_log_reset(void) { aki::gemm_log_reset(); }
+int aki_lab_gemm_log(int32_t* out, int cap) { return aki::gemm_log_copy(out, cap); }
+// 1: every GEMM launch is recorded and returns AKI_OK before any HIP call (the planner without a GPU)
+void aki_lab_set_gemm_dry_run(int on) { aki::g_gemm_dry_run = on ? 1 : 0; }
 #endif
 
 // ---- attention core --------------------------------------------------------------------------------

@@ -1117,6 +1117,25 @@ int g_sk_slice_major = 0;                            // set by aki_lab_set_slice
 int g_force_tile = 0, g_deep_ring = 1, g_res_prefetch = 1, g_deepx = 0;   // set by aki_lab_set_gemm_tile (lab build only)
 long long* g_clock_probe = nullptr;                  // set by aki_lab_set_clock_probe
 int g_probe_block = 0;                               // set by aki_lab_set_probe_block
+// Route log (tests/gemm_routes.py): one record per launch_gemm call - the ten template arguments, the runtime ksplit, M, m_offset and the
+// grid - so that a test can see which instantiation the planner chose.  g_gemm_dry_run (aki_lab_set_gemm_dry_run): record and return before
+// any HIP call, so that the planner runs on a machine without a GPU.
+constexpr int kGemmLogFields = 14, kGemmLogCap = 256;
+static int g_gemm_log[kGemmLogCap][kGemmLogFields];
+static int g_gemm_log_n = 0;
+int g_gemm_dry_run = 0;
+void gemm_log_reset() { g_gemm_log_n = 0; }
+int gemm_log_copy(int* out, int cap) {   // records copied: min(count, cap, kGemmLogCap); returns the number of launches since the reset
+  const int n = g_gemm_log_n < kGemmLogCap ? g_gemm_log_n : kGemmLogCap;
+  for (int i = 0; out && i < n && i < cap; ++i)
+    for (int j = 0; j < kGemmLogFields; ++j) out[i * kGemmLogFields + j] = g_gemm_log[i][j];
+  return g_gemm_log_n;
+}
+static void gemm_log_push(const int (&r)[kGemmLogFields]) {
+  if (g_gemm_log_n < kGemmLogCap)
+    for (int j = 0; j < kGemmLogFields; ++j) g_gemm_log[g_gemm_log_n][j] = r[j];
+  ++g_gemm_log_n;
+}
 #else
 static constexpr int g_force_tile = 0, g_deep_ring = 1, g_res_prefetch = 1, g_deepx = 0, g_sk_slice_major = 0;
 #endif
@@ -1127,6 +1146,15 @@ static int launch_gemm(GemmParams& p, hipStream_t stream) {
   constexpr int SMEM = (PIPE >= 4 && PIPE <= 6) ? (BN > BM ? 3 * BN + 2 * BM : 3 * BM + 2 * BN) * 128   // PIPE 4-6: three + two tiles
                        : (PIPE == 8 ? (2 * BN + 4 * BM) * 128 : NST * (BN + BM) * 128);                      // PIPE 8: two weight, three token slots + a spare
   static_assert(SMEM <= 160 * 1024, "LDS");
+#ifdef AKI_LAB_HOOKS
+  {
+    const int n_out_ = (EPI == EPI_SWIGLU) ? p.N / 2 : p.N, bn_out_ = (EPI == EPI_SWIGLU) ? BN / 2 : BN;
+    const int slices_ = (SK && p.ksplit > 1) ? p.ksplit : 1;
+    const int grid_ = ((p.M + BM - 1) / BM) * ((n_out_ + bn_out_ - 1) / bn_out_) * slices_;
+    gemm_log_push({NF, NT, WN, WM, EPI, ACT, FP8 ? 1 : 0, NST, PIPE, SK, slices_, p.M, p.m_offset, grid_});
+    if (g_gemm_dry_run) return AKI_OK;
+  }
+#endif
   static bool attr_set = false;
   if (!attr_set) {
     if (hipFuncSetAttribute((const void*)gemm_bf16_kernel<NF, NT, WN, WM, EPI, ACT, FP8, NST, PIPE, SK>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)

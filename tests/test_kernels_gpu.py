@@ -16,6 +16,7 @@ import torch
 from conftest import load_golden
 from golden import gen
 import aki_oracle as O
+import gemm_routes as R
 
 pytestmark = pytest.mark.gpu
 
@@ -335,17 +336,33 @@ def test_qkv_rope_stage_bf16():
     check(n(v), hd(qkv[..., 2 * d:]), torch.bfloat16, "v")
 
 
-def test_qkv_rope_full_width_with_m_tail_split_bf16():
-    """AKI-4B width (d=3072, 32 heads) at M = 1380 = 5*256 + 100: exercises the big-tile + M-tail launch pair of the
-    QKV kernel (token index / position ids must stay global in the tail launch)."""
+def _planned(run):
+    """Run `run()` on the lab library in heuristic mode (the product's planner) and return (its result, the GEMM route log)."""
+    from aki_amd import _lib
+    with _lib.use_lab(0) as lib:
+        lib.aki_lab_gemm_log_reset()
+        out = run()
+        torch.cuda.synchronize()
+        return out, _lib.gemm_log(lib)
+
+
+@pytest.mark.parametrize("L,expect", [
+    (690, [R.big(R.EPI_QKV, 0, 4, 1380, 216)]),                                                   # 1380 rows: all 256 x 256 tiles
+    (1000, [R.big(R.EPI_QKV, 0, 4, 1792, 252), R.small(R.EPI_QKV, 0, 208, 144, m_offset=1792)])],  # 2000 = 7 * 256 + 208: big + M tail
+    ids=["L690-big", "L1000-big+tail"])
+def test_qkv_rope_full_width_with_m_tail_split_bf16(L, expect):
+    """AKI-4B width (d=3072, 32 heads), B = 2.  At L = 1000 the planner takes the big-tile + M-tail launch pair of the QKV kernel
+    (token index / position ids must stay global in the tail launch: the tail starts inside sample 1); at L = 690 it takes the big
+    tiles alone.  The route log pins which one each shape reaches."""
     ops = _ops()
-    B, L, H = 2, 690, 32
+    B, H = 2, 32
     d = 96 * H
     g = torch.Generator(device="cpu").manual_seed(5)
     x = torch.randn(B, L, d, generator=g).to(torch.bfloat16)
     w = (torch.randn(3 * d, d, generator=g) * 0.02).to(torch.bfloat16)
     cos, sin = O.rope_cos_sin(np.arange(L)[None], 96)
-    q, k, v = ops.qkv_rope(x.to(DEV), w.to(DEV), torch.from_numpy(cos[0]).to(DEV), torch.from_numpy(sin[0]).to(DEV), H)
+    (q, k, v), log = _planned(lambda: ops.qkv_rope(x.to(DEV), w.to(DEV), torch.from_numpy(cos[0]).to(DEV), torch.from_numpy(sin[0]).to(DEV), H))
+    assert log == expect, f"L = {L}: planned {log}"
     qkv = x.float().numpy().reshape(B * L, d) @ w.float().numpy().T
     qkv = qkv.reshape(B, L, 3 * d)
     hd = lambda a: a.reshape(B, L, H, 96).transpose(0, 2, 1, 3)
@@ -355,16 +372,23 @@ def test_qkv_rope_full_width_with_m_tail_split_bf16():
     check(n(v), hd(qkv[..., 2 * d:]), torch.bfloat16, "v (tail split)")
 
 
-def test_linear_m_tail_split_with_row_mod_residual_bf16():
-    """Split launch + residual row-modulo (position-embedding style): the modulo must use the global row index."""
+@pytest.mark.parametrize("M,expect", [
+    (1380, [R.small(R.EPI_PLAIN, 0, 1380, 1408)]),                                                             # all 128 x 128 tiles
+    (2100, [R.big(R.EPI_PLAIN, 0, 4, 2048, 512), R.small(R.EPI_PLAIN, 0, 52, 256, m_offset=2048, ring="64x128")])],   # big + M tail
+    ids=["M1380-small", "M2100-big+tail"])
+def test_linear_m_tail_split_with_row_mod_residual_bf16(M, expect):
+    """Residual row-modulo (position-embedding style) with bias.  At M = 2100 the planner takes the big-tile + M-tail launch pair,
+    where the modulo must use the global row index (the tail launch starts at row 2048) and the tail launch must add the bias; at
+    M = 1380 it takes 128 x 128 tiles alone.  The route log pins which one each shape reaches."""
     ops = _ops()
-    M, N, K, mod = 1380, 16384, 256, 729
+    N, K, mod = 16384, 256, 729
     g = torch.Generator(device="cpu").manual_seed(6)
     x = torch.randn(M, K, generator=g).to(torch.bfloat16)
     w = (torch.randn(N, K, generator=g) * 0.05).to(torch.bfloat16)
     r = torch.randn(mod, N, generator=g).to(torch.bfloat16)
     b = (torch.randn(N, generator=g) * 0.1).to(torch.bfloat16)
-    y = ops.linear(x.to(DEV), w.to(DEV), bias=b.to(DEV), residual=r.to(DEV), res_row_mod=mod)
+    y, log = _planned(lambda: ops.linear(x.to(DEV), w.to(DEV), bias=b.to(DEV), residual=r.to(DEV), res_row_mod=mod))
+    assert log == expect, f"M = {M}: planned {log}"
     want = x.float().numpy() @ w.float().numpy().T + b.float().numpy() + r.float().numpy()[np.arange(M) % mod]
     check(n(y), want, torch.bfloat16, "tail split + row-mod residual")
     y2 = ops.linear(x.to(DEV), w.to(DEV), residual=y)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - image+text tokens/s of the AKI-4B forward pass on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one forward pass of the whole AKI-4B model (SigLIP tower -> Perceiver connector -> splice ->
@@ -14,11 +14,14 @@ the only collectives are the timing barrier and the max-over-ranks of the elapse
 Prints ONE JSON line (rank 0) with the contract's fields plus
   "roofline"     for the dominant kernel (by time in the timed region), timed live with HIP events on the launch stream
   "mma_kernel"   the same object for the north-star's MMA op (QKV projection + RoPE + span-driven attention)
-  "mma_core"     the attention core alone (the op's second launch), timed live on the benchmark's own mask table and shapes
-                 right after the timed region: algorithmic bytes / flops per launch against the HBM and MFMA peaks
-  "cpu_baseline" the oracle (numpy port of the reference's eager path) timed on this box's host cores (N=1 only)
+A plain run does nothing else: set up, warm up, time the K steps, dump (--dump-outputs), print.  With --full, after the timed
+region and the dump, it also measures
+  "ms_per_step_untapped"  the same loop once more without the event probes (up to 10 steps)
+  "mma_core"     the attention core alone (the op's second launch), timed live on the benchmark's own mask table and shapes:
+                 algorithmic bytes / flops per launch against the HBM and MFMA peaks
+  "cpu_baseline" the oracle (numpy port of the reference's eager path) timed on the host's cores (N=1 only; --no-cpu-baseline skips it)
   "secondary"    (N=1 only, after the headline) the other BASELINE configurations and the decode / first-token / 384-px legs, each with
-                 its own ms, steps, config.workload and roofline object - bench_legs.py
+                 its own ms, steps, config.workload and roofline object - bench_legs.py (--no-secondary skips them)
 """
 import argparse
 import json
@@ -265,14 +268,17 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=BATCH, help="per-GPU batch (BASELINE configs[1]: 8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what it does not need: ms_per_step_untapped, mma_core, and at N = 1 the CPU "
+                         "baselines and the secondary legs (about 45 s more)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--dtype", choices=["bf16", "fp8"], default="bf16",
                     help="fp8 = BASELINE configs[4]: e4m3 weights/activations for the decoder projections (use with --batch 16)")
     ap.add_argument("--kernel-table", action="store_true", help="also print the per-kernel timing table to stderr")
     ap.add_argument("--px", type=int, default=IMG_PX, choices=[336, 384],
                     help="image side of the synthetic batch: 336 = BASELINE's metric resolution (default), 384 = the tower's native size, what the "
                          "reference's SFT collate and demo feed (train/sft_data_utils/loader_utils.py:8, local_demo.py:20): 729 patches, M = 5832 rows in the tower at batch 8")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary legs (the other BASELINE configs, decode, first token, 384 px) that run after the headline at N = 1")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary legs (the other BASELINE configs, decode, first token, 384 px) that run after the headline at N = 1")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (rank 0) to DIR/*.npy: "
                          f"logits_sample.npy = float32 logits of {DUMP_ROWS} (sample, position) rows drawn once from a seed-0 generator "
@@ -362,18 +368,19 @@ def main():
     assert torch.isfinite(out.logits.float()).all()
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, out)
-    # the same loop once more WITHOUT the event probes (reported next to ms_per_step: what the probes cost)
-    n_un = min(args.steps, 10)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n_un):
-        out = step()
-    torch.cuda.synchronize()
-    ms_untapped = (time.perf_counter() - t0) / n_un * 1e3
+    ms_untapped = core = None
+    if args.full:
+        # the same loop once more WITHOUT the event probes (reported next to ms_per_step: what the probes cost)
+        n_un = min(args.steps, 10)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n_un):
+            out = step()
+        torch.cuda.synchronize()
+        ms_untapped = (time.perf_counter() - t0) / n_un * 1e3
 
     # the attention core on its own (second launch of the fused MMA op): same shapes, the batch's own mask table
-    core = None
-    if rank == 0:
+    if args.full and rank == 0:
         with torch.no_grad():
             prep = model._prepare_inputs_for_forward(vision_tokens=model.vision_tokenizer(model._encode_vision_x(vx)), lang_x=ids,
                                                      attention_mask=am, padding_side="right")
@@ -447,7 +454,8 @@ def main():
         res = {
             "metric": f"image+text tokens/sec forward, AKI-4B, {IMG_PX}px img + 512 txt",
             "value": round(value, 1), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "ms_per_step_untapped": round(ms_untapped, 3), "rccl_ranks": ranks_seen,
+            "ms_per_step": round(ms_per_step, 3),
+            **({"ms_per_step_untapped": round(ms_untapped, 3)} if ms_untapped is not None else {}), "rccl_ranks": ranks_seen,
             # every rank's own clock around the same K steps: `ms_per_step` is the slowest rank's (what `value` uses); a straggler shows here
             "ms_per_step_rank_min": round(elapsed_min / args.steps * 1e3, 3), "ms_per_step_rank_max": round(ms_per_step, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -486,14 +494,14 @@ def main():
                                "note": "219 FLOP/B: just on the HBM side of the ridge (312 FLOP/B); both fractions are given"}
             if src:
                 res["mma_core"].update(traffic_unit=TUNIT, traffic_source=src, traffic_stale=bool(stale))
-        if world == 1 and not args.no_cpu_baseline and IMG_PX == 336:
+        if args.full and world == 1 and not args.no_cpu_baseline and IMG_PX == 336:
             thr = _cpu_threads()
             res["cpu_baseline"] = cpu_baseline(model.state_dict(), model.media_token_id, thr)
             res["cpu_baseline"]["gpu_over_cpu"] = round(value / res["cpu_baseline"]["value"], 1)
             res["cpu_baseline_c2_est"] = cpu_baseline_c2_est(thr)
         # The other BASELINE configurations on the same clock, AFTER the headline's numbers exist: each leg is fenced (a failing leg
         # reports {"error": ...}), the headline values above are final, and the line is printed once.
-        if world == 1 and not args.no_secondary and not fp8 and B == BATCH and IMG_PX == 336:
+        if args.full and world == 1 and not args.no_secondary and not fp8 and B == BATCH and IMG_PX == 336:
             try:
                 import bench_legs
                 res["secondary"] = bench_legs.run_all(model, dev, sys.modules[__name__])

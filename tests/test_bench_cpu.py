@@ -50,6 +50,14 @@ def test_zero_timed_steps_is_an_error():
     assert "--steps must be >= 1" in r.stderr
 
 
+def test_full_is_an_option():
+    """What the headline does not need waits for --full (tests/test_bench_gpu.py runs both forms)."""
+    r = _run(["--help"])
+    assert r.returncode == 0 and "--full" in r.stdout
+    r = _run(["--steps", "0", "--full"])
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr and "unrecognized" not in r.stderr
+
+
 def test_dump_outputs_writes_a_fixed_float32_sample_of_the_logits(tmp_path):
     """--dump-outputs: the same rows of the logits on every run (so two builds compare output for output), float32, under 64 MB."""
     import types

@@ -26,6 +26,10 @@ int decode_attn_split_launch(const void* q_or_qkv, const float* cos, const float
                              void* ws, size_t ws_bytes, hipStream_t s);
 int rope_append_launch(const void* qkv, const float* cos, const float* sin, const int* pos, const int* cache_len, void* q_out,
                        void* k_cache, void* v_cache, int B, int H, int Dh, int cap, int dtype, hipStream_t s);
+int kv_cache_quant_fp8_launch(const void* src, int src_cap, void* dst, float* scale, int dst_cap, int slabs, int rows, hipStream_t s);
+int decode_attn_split_fp8kv_launch(const void* qkv, const float* cos, const float* sin, const int* len, void* kc, void* vc, float* ks, float* vs,
+                                   void* o, const uint64_t* vbits, int nwords, int B, int H, int cap, int max_keys, float scale, void* ws,
+                                   size_t ws_bytes, hipStream_t s);
 size_t decode_chain_ws_bytes(int n_layers, int d, int H, int F, int cap);
 size_t decode_chain_err_offset(int n_layers, int H);
 size_t decode_chain_b_ws_bytes(int n_layers, int d, int H, int F, int cap, int B);
@@ -424,6 +428,30 @@ int aki_decode_attn_fused_fwd(const void* qkv, const float* cos, const float* si
     return decode_attn_split_launch(qkv, cos, sin, cache_len, k_cache, v_cache, o, col_valid_bits, nwords, B, H, capacity, max_keys,
                                     scale, true, ws, ws_bytes, (hipStream_t)stream);
   return AKI_ERR_UNSUPPORTED;   // f32 / other head sizes: call aki_rope_append_fwd + aki_decode_attn_fwd
+}
+
+int aki_kv_cache_quant_fp8(const void* src, int32_t src_capacity, void* dst, float* scale, int32_t dst_capacity, int32_t slabs, int32_t rows,
+                           int32_t Dh, int32_t dtype, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(src && dst && scale);
+  AKI_CHECK_ARG(src_capacity > 0 && dst_capacity > 0 && slabs > 0 && rows >= 0 && rows <= src_capacity && rows <= dst_capacity);
+  if (Dh != 96 || dtype != AKI_DT_BF16) return AKI_ERR_UNSUPPORTED;
+  if (((uintptr_t)src & 15) || ((uintptr_t)dst & 7) || ((uintptr_t)scale & 3)) return AKI_ERR_ALIGNMENT;
+  return kv_cache_quant_fp8_launch(src, src_capacity, dst, scale, dst_capacity, slabs, rows, (hipStream_t)stream);
+}
+
+int aki_decode_attn_fused_fp8kv_fwd(const void* qkv, const float* cos, const float* sin, const int32_t* cache_len, void* k_cache,
+                                    void* v_cache, float* k_scale, float* v_scale, void* o, const uint64_t* col_valid_bits, int32_t nwords,
+                                    int32_t B, int32_t H, int32_t Dh, int32_t capacity, int32_t max_keys, float scale, int32_t dtype, void* ws,
+                                    size_t ws_bytes, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(qkv && cos && sin && cache_len && k_cache && v_cache && k_scale && v_scale && o);
+  AKI_CHECK_ARG(B > 0 && H > 0 && Dh > 0 && capacity > 0 && scale > 0.f);
+  AKI_CHECK_ARG(!col_valid_bits || nwords > 0);
+  if (Dh != 96 || dtype != AKI_DT_BF16) return AKI_ERR_UNSUPPORTED;
+  if (((uintptr_t)k_cache & 15) || ((uintptr_t)v_cache & 15) || ((uintptr_t)o & 15)) return AKI_ERR_ALIGNMENT;
+  return decode_attn_split_fp8kv_launch(qkv, cos, sin, cache_len, k_cache, v_cache, k_scale, v_scale, o, col_valid_bits, nwords, B, H, capacity,
+                                        max_keys, scale, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int aki_decode_linear_fwd(const aki_linear_args* a, const void* rms_weight, float rms_eps, void* stream) {

@@ -9,6 +9,8 @@
 //   rope_append_kernel  split the fused qkv row, rotate q/k at the token's position, append k/v to the KV cache
 //   decode_attn_kernel  one query per (batch, head) against the cache: keys are spread over the 256 lanes, each
 //                       lane keeps an online-softmax partial (m, l, acc[Dh]) that is merged through LDS
+//   decode_attn_split_fp8kv_kernel  the fused split-KV step on an opt-in e4m3 KV cache (one f32 scale per cached head row),
+//                       with kv_cache_quant_fp8_kernel converting the prefill's bf16 rows into it
 // After the prefill the reference switches to an all-ones 2-D mask (src/aki_generation.py:58-62), i.e. plain causal
 // attention over everything cached; per-sample cache lengths and the prefill's valid-column bits are honoured here,
 // which lifts the reference's batch-1 restriction.
@@ -1074,6 +1076,307 @@ int decode_attn_split_launch(const void* q_or_qkv, const float* cos, const float
   AKI_CLEAR_ERR();
   if (fused) hipLaunchKernelGGL(decode_attn_split_kernel<true>, grid, block, 0, s, p);
   else hipLaunchKernelGGL(decode_attn_split_kernel<false>, grid, block, 0, s, p);
+  AKI_LAUNCH_CHECK();
+  return AKI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// fp8 (e4m3) KV cache.  Every cached K / V row (one head, one position: 96 values) is stored as 96 e4m3 bytes with one f32
+// dequantisation scale, s = max(amax, 1e-12) / 448 over the row, bytes = e4m3(x / s) rounded to nearest even and saturated at
+// +-448 (the rule of quant_rows_fp8_kernel, with true divisions).  The rows are those the bf16 cache would hold: the prefill's bf16
+// K / V (kv_cache_quant_fp8_kernel, one launch for all layers) and, per decode step, the bf16-rounded rotated k and the v of the new
+// token.  Half the bytes of a bf16 row plus 4 per scale: 0.52x the cache traffic of a batched or long-context decode step.
+// ------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float kv8_scale(float amax) { return fmaxf(amax, 1e-12f) / 448.0f; }
+
+// two values -> two e4m3 bytes in the low 16 bits
+__device__ __forceinline__ unsigned kv8_pack2(float a, float b, float s) {
+  return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(a / s, -448.f), 448.f), fminf(fmaxf(b / s, -448.f), 448.f), 0, false) & 0xffffu;
+}
+
+// src bf16 [slabs][src_cap][96] -> dst e4m3 [slabs][dst_cap][96] + scale f32 [slabs][dst_cap], rows [0, rows) of every slab.
+// Sixteen lanes per row: lane i < 12 holds values 8i .. 8i+7, the row's amax meets within the 16 lanes.
+__global__ __launch_bounds__(256) void kv_cache_quant_fp8_kernel(const bf16_t* src, uint8_t* dst, float* scale, int src_cap, int dst_cap,
+                                                                 int rows, long long total) {
+  const int i = threadIdx.x & 15;
+  const long long r = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const bool live = r < total && i < 12;
+  const long long slab = r / rows, j = r - slab * rows;
+  float v[8];
+  u32x4 x = {0u, 0u, 0u, 0u};
+  if (live) x = *(const u32x4*)(src + ((size_t)slab * src_cap + j) * 96 + i * 8);
+  float amax = 0.f;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    v[2 * e] = bf16_lo(x[e]);
+    v[2 * e + 1] = bf16_hi(x[e]);
+    amax = fmaxf(amax, fmaxf(fabsf(v[2 * e]), fabsf(v[2 * e + 1])));
+  }
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+  const float s = kv8_scale(amax);
+  if (!live) return;
+  const unsigned b0 = kv8_pack2(v[0], v[1], s), b1 = kv8_pack2(v[2], v[3], s), b2 = kv8_pack2(v[4], v[5], s), b3 = kv8_pack2(v[6], v[7], s);
+  const size_t at = (size_t)slab * dst_cap + j;
+  *(u32x2*)(dst + at * 96 + i * 8) = u32x2{b0 | (b1 << 16), b2 | (b3 << 16)};
+  if (i == 0) scale[at] = s;
+}
+
+int kv_cache_quant_fp8_launch(const void* src, int src_cap, void* dst, float* scale, int dst_cap, int slabs, int rows, hipStream_t s) {
+  const long long total = (long long)slabs * rows;
+  const long long blocks = (total + 15) / 16;
+  if (blocks > 0x7fffffffLL) return AKI_ERR_UNSUPPORTED;
+  if (blocks == 0) return AKI_OK;
+  AKI_CLEAR_ERR();
+  hipLaunchKernelGGL(kv_cache_quant_fp8_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)src, (uint8_t*)dst, scale, src_cap,
+                     dst_cap, rows, total);
+  AKI_LAUNCH_CHECK();
+  return AKI_OK;
+}
+
+// The fused decode step (decode_attn_split_kernel<true>: RoPE, append, split-KV attention, merge) on the e4m3 cache.  Same items,
+// workspace, counters and merge; what changes is the row format:
+//   append       the owner of the new position rotates k as the bf16 kernel does (bf16-rounded), quantises k and v per head and
+//                writes bytes + scales; the new row is attended through its quantised copy, from LDS, like any cached key
+//   score phase  lane = key: 6 x 16-byte loads of its K row; pairs of e4m3 widen to bf16 exactly (v_cvt_scalef32_pk_bf16_fp8, as
+//                the W8 GEMV) into the bf16 dot2 against q; score = (q . k8) * s_k * scale
+//   PV phase     lane = (row group g = lane>>3, 16-byte column chunk i8 = lane&7 < 6): 8 loads cover the tile's 64 V rows; row j
+//                carries p_j * s_v[j] while the softmax denominator sums the unscaled p_j
+// ------------------------------------------------------------------------------------------------------------
+struct DecodeAttn8Params {
+  const bf16_t* qkv;          // [B][3*H*96] un-rotated
+  const float* cos; const float* sin;   // [capacity][96]
+  const int* len;             // cache_len[b]
+  uint8_t* kc; uint8_t* vc;   // [B][H][cap][96] e4m3
+  float* ks; float* vs;       // [B][H][cap] dequantisation scales
+  bf16_t* o;                  // [B][H*96]
+  const uint64_t* vbits; int nwords;
+  unsigned* cnt; float* part;
+  int H, cap, S, T; float scale;
+};
+
+__global__ __launch_bounds__(64) void decode_attn_split_fp8kv_kernel(const DecodeAttn8Params p) {
+  __shared__ __attribute__((aligned(16))) bf16_t s_q[96];
+  __shared__ __attribute__((aligned(16))) uint8_t s_k[96], s_v[96];
+  __shared__ float s_sc[2];
+  const int lane = threadIdx.x, split = blockIdx.x, bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
+  const int ln = p.len[b];
+  const int n = ln + 1;
+  const int k_begin = split * p.T * 64;
+  const int k_end = min(n, k_begin + p.T * 64);
+  uint8_t* kb = p.kc + (size_t)bh * p.cap * 96;
+  uint8_t* vb = p.vc + (size_t)bh * p.cap * 96;
+  float* ksb = p.ks + (size_t)bh * p.cap;
+  float* vsb = p.vs + (size_t)bh * p.cap;
+  float* part = p.part + ((size_t)bh * p.S + split) * DEC_PSTRIDE;
+  const int g = lane >> 3, i8 = lane & 7;
+  float m = -INFINITY, l = 0.f, acc[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+  if (k_begin < k_end) {
+    const bool owner = ln >= k_begin;                    // ln < k_end holds by construction (k_end <= ln + 1)
+    u32x4 kr[6], vr[8];
+    float ksc, vsc;
+    auto issue_tile = [&](int base) {                    // all 16 loads (+ the lane's two scales) of a tile go out back to back
+      const int jr = min(base + lane, k_end - 1);       // clamped rows carry probability 0
+      const uint8_t* krow = kb + (size_t)jr * 96;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) kr[i] = *(const u32x4*)(krow + i * 16);
+      ksc = ksb[jr];
+      vsc = vsb[jr];
+#pragma unroll
+      for (int t2 = 0; t2 < 8; ++t2) {
+        const int r = min(base + 8 * t2 + g, k_end - 1);
+        vr[t2] = *(const u32x4*)(vb + (size_t)r * 96 + min(i8, 5) * 16);
+      }
+    };
+    issue_tile(k_begin);                                 // in flight while q is rotated
+    float kn0 = 0.f, kn1 = 0.f, vn0 = 0.f, vn1 = 0.f;
+    if (lane < 48) {
+      const bf16_t* row = p.qkv + (size_t)b * 3 * p.H * 96 + h * 96;
+      const float c0 = p.cos[(size_t)ln * 96 + lane], c1 = p.cos[(size_t)ln * 96 + lane + 48];
+      const float s0 = p.sin[(size_t)ln * 96 + lane], s1 = p.sin[(size_t)ln * 96 + lane + 48];
+      const float q0 = bf16_bits_to_f32(row[lane]), q1 = bf16_bits_to_f32(row[lane + 48]);
+      ((__bf16*)s_q)[lane] = (__bf16)(q0 * c0 - q1 * s0);          // rotate-half: d < 48 pairs with -x[d+48]
+      ((__bf16*)s_q)[lane + 48] = (__bf16)(q1 * c1 + q0 * s1);
+      if (owner) {
+        const bf16_t* krw = row + p.H * 96;
+        const bf16_t* vrw = row + 2 * p.H * 96;
+        const float k0 = bf16_bits_to_f32(krw[lane]), k1 = bf16_bits_to_f32(krw[lane + 48]);
+        kn0 = (float)(__bf16)(k0 * c0 - k1 * s0);                   // the bf16 row the bf16 cache would hold
+        kn1 = (float)(__bf16)(k1 * c1 + k0 * s1);
+        vn0 = bf16_bits_to_f32(vrw[lane]);
+        vn1 = bf16_bits_to_f32(vrw[lane + 48]);
+      }
+    }
+    if (owner) {                                         // workgroup-uniform: the amax reductions run on the whole wave (lanes >= 48 hold 0)
+      const float sk = kv8_scale(wave_max(fmaxf(fabsf(kn0), fabsf(kn1))));
+      const float sv = kv8_scale(wave_max(fmaxf(fabsf(vn0), fabsf(vn1))));
+      if (lane < 48) {
+        const unsigned kq = kv8_pack2(kn0, kn1, sk), vq = kv8_pack2(vn0, vn1, sv);
+        s_k[lane] = (uint8_t)kq;
+        s_k[lane + 48] = (uint8_t)(kq >> 8);
+        s_v[lane] = (uint8_t)vq;
+        s_v[lane + 48] = (uint8_t)(vq >> 8);
+        kb[(size_t)ln * 96 + lane] = (uint8_t)kq;
+        kb[(size_t)ln * 96 + lane + 48] = (uint8_t)(kq >> 8);
+        vb[(size_t)ln * 96 + lane] = (uint8_t)vq;
+        vb[(size_t)ln * 96 + lane + 48] = (uint8_t)(vq >> 8);
+      }
+      if (lane == 0) {
+        s_sc[0] = sk;
+        s_sc[1] = sv;
+        ksb[ln] = sk;
+        vsb[ln] = sv;
+      }
+    }
+    __syncthreads();
+    for (int t = 0; t < p.T; ++t) {
+      const int base = k_begin + t * 64;
+      if (base >= k_end) break;
+      const int j = base + lane;
+      if (t > 0) issue_tile(base);
+      if (owner && base <= ln && ln < base + 64) {
+        // the new row lives in LDS (the tile's loads were issued before it was stored): every lane whose clamped row is ln takes it from there
+        if (min(j, k_end - 1) == ln) {
+#pragma unroll
+          for (int i = 0; i < 6; ++i) kr[i] = *(const u32x4*)(s_k + i * 16);
+          ksc = s_sc[0];
+          vsc = s_sc[1];
+        }
+#pragma unroll
+        for (int t2 = 0; t2 < 8; ++t2)
+          if (min(base + 8 * t2 + g, k_end - 1) == ln) vr[t2] = *(const u32x4*)(s_v + min(i8, 5) * 16);
+      }
+      bool ok = j < k_end;
+      if (p.vbits && (base >> 6) < p.nwords) ok = ok && ((p.vbits[(size_t)b * p.nwords + (base >> 6)] >> lane) & 1ull);
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) s = dot16_w8(kr[i], *(const u32x4*)(s_q + i * 16), *(const u32x4*)(s_q + i * 16 + 8), s);
+      s = ok ? s * ksc * p.scale : -INFINITY;
+      const float mn = fmaxf(m, wave_max(s));
+      if (mn == -INFINITY) continue;                                   // wave-uniform: nothing visible yet
+      const float a = __expf(m - mn);
+      const float pr = ok ? __expf(s - mn) : 0.f;
+      l = l * a + wave_sum(pr);
+      const float pw = ok ? pr * vsc : 0.f;                            // a masked row's scale may be anything: 0 * NaN must not reach acc
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[e] *= a;
+#pragma unroll
+      for (int t2 = 0; t2 < 8; ++t2) {
+        const float w = __shfl(pw, 8 * t2 + g);
+        u32x4 vt = vr[t2];
+        asm volatile("" : "+v"(vt));                     // widened here, row by row
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)vt[e], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)vt[e], true);
+          acc[4 * e] = __builtin_fmaf(w, lo[0], acc[4 * e]);
+          acc[4 * e + 1] = __builtin_fmaf(w, lo[1], acc[4 * e + 1]);
+          acc[4 * e + 2] = __builtin_fmaf(w, hi[0], acc[4 * e + 2]);
+          acc[4 * e + 3] = __builtin_fmaf(w, hi[1], acc[4 * e + 3]);
+        }
+      }
+      m = mn;
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      acc[e] += __shfl_xor(acc[e], 8);
+      acc[e] += __shfl_xor(acc[e], 16);
+      acc[e] += __shfl_xor(acc[e], 32);
+    }
+  }
+  // From here on the bf16 kernel's code (partials as agent-scope relaxed atomics, arrival counter, merge by the last item), repeated
+  // rather than shared so that the bf16 kernel's code stays exactly as it was.
+#define AKI_ST_AGENT(ptr, v) __hip_atomic_store((ptr), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define AKI_LD_AGENT(ptr) __hip_atomic_load((ptr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+  if (lane == 0) { AKI_ST_AGENT(part, m); AKI_ST_AGENT(part + 1, l); }
+  if (lane < 6) {                                        // lane i8 < 6 of row group 0 holds columns 16 i8 .. 16 i8 + 15
+#pragma unroll
+    for (int e = 0; e < 16; ++e) AKI_ST_AGENT(part + 8 + lane * 16 + e, acc[e]);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  unsigned prev = 0;
+  if (lane == 0) prev = __hip_atomic_fetch_add(p.cnt + bh, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  prev = __shfl(prev, 0);
+  if (prev != (unsigned)(p.S - 1)) return;
+  asm volatile("" ::: "memory");
+  __shared__ float s_mg[5][12][10];
+  const float* pp = p.part + (size_t)bh * p.S * DEC_PSTRIDE;
+  const int sl = lane / 12, ch = lane - sl * 12;
+  float gm = -INFINITY, lt = 0.f, o8[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o8[e] = 0.f;
+  if (sl < 5) {
+    for (int s2 = sl; s2 < p.S; s2 += 5) {
+      const float* ps = pp + (size_t)s2 * DEC_PSTRIDE;
+      const float ms = AKI_LD_AGENT(ps), ls = AKI_LD_AGENT(ps + 1);
+      float a[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) a[e] = AKI_LD_AGENT(ps + 8 + ch * 8 + e);
+      const float mn = fmaxf(gm, ms);
+      const float f0 = gm == -INFINITY ? 0.f : __expf(gm - mn), f1 = ms == -INFINITY ? 0.f : __expf(ms - mn);
+      lt = lt * f0 + ls * f1;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o8[e] = o8[e] * f0 + a[e] * f1;
+      gm = mn;
+    }
+    s_mg[sl][ch][0] = gm;
+    s_mg[sl][ch][1] = lt;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s_mg[sl][ch][2 + e] = o8[e];
+  }
+  __syncthreads();
+  if (lane < 12) {
+    float sv[5][10];
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+#pragma unroll
+      for (int e = 0; e < 10; ++e) sv[q][e] = s_mg[q][lane][e];
+    lds_reads_landed();
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+#pragma unroll
+      for (int e = 0; e < 10; ++e) asm volatile("" : "+v"(sv[q][e]));
+    float M5 = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) M5 = fmaxf(M5, sv[q][0]);
+    lt = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o8[e] = 0.f;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      const float mq = sv[q][0];
+      const float f = mq == -INFINITY ? 0.f : __expf(mq - M5);
+      lt += sv[q][1] * f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o8[e] += sv[q][2 + e] * f;
+    }
+    const float inv = lt > 0.f ? 1.f / lt : 0.f;
+    u32x4 ov;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ov[e] = pack_bf16x2(o8[2 * e] * inv, o8[2 * e + 1] * inv);
+    *(u32x4*)(p.o + (size_t)bh * 96 + lane * 8) = ov;
+  }
+  if (lane == 0) AKI_ST_AGENT(p.cnt + bh, 0u);
+#undef AKI_ST_AGENT
+#undef AKI_LD_AGENT
+}
+
+// The grid of decode_attn_split_launch (same T and S, so the same workspace and the same eager / replayed key cuts) on the e4m3 cache.
+int decode_attn_split_fp8kv_launch(const void* qkv, const float* cos, const float* sin, const int* len, void* kc, void* vc, float* ks, float* vs,
+                                   void* o, const uint64_t* vbits, int nwords, int B, int H, int cap, int max_keys, float scale, void* ws,
+                                   size_t ws_bytes, hipStream_t s) {
+  if (max_keys <= 0 || max_keys > cap) max_keys = cap;
+  const int tiles = (max_keys + 63) / 64, tiles_cap = (cap + 63) / 64;
+  int T = (int)(((size_t)B * H * tiles_cap + AKI_DEC_ITEMS - 1) / AKI_DEC_ITEMS);
+  if (T < 1) T = 1;
+  const int S = (tiles + T - 1) / T;
+  if (ws == nullptr || ws_bytes < dec_cnt_bytes(B, H) + (size_t)B * H * S * DEC_PSTRIDE * 4) return AKI_ERR_WORKSPACE;
+  DecodeAttn8Params p = {(const bf16_t*)qkv, cos, sin, len, (uint8_t*)kc, (uint8_t*)vc, ks, vs, (bf16_t*)o, vbits, nwords,
+                         (unsigned*)ws, (float*)((char*)ws + dec_cnt_bytes(B, H)), H, cap, S, T, scale};
+  const dim3 grid(S, B * H), block(64);
+  AKI_CLEAR_ERR();
+  hipLaunchKernelGGL(decode_attn_split_fp8kv_kernel, grid, block, 0, s, p);
   AKI_LAUNCH_CHECK();
   return AKI_OK;
 }

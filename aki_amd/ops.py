@@ -439,6 +439,20 @@ def decode_attn_workspace(B: int, H: int, Dh: int, capacity: int, device) -> tor
     return torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=device)
 
 
+def kv_cache_quant_fp8(src: torch.Tensor, dst: torch.Tensor, scale: torch.Tensor, rows: int) -> None:
+    """bf16 K/V rows -> the e4m3 cache, in place: src [..., src_cap, 96] bf16, dst [..., cap, 96] uint8, scale [..., cap] f32 (the same
+    leading dims, all contiguous); rows [0, rows) of every (layer, sample, head) slab.  One launch for all layers."""
+    _dev(src, dst, scale)
+    if src.dtype != torch.bfloat16 or dst.dtype != torch.uint8 or scale.dtype != torch.float32:
+        raise AkiError("kv_cache_quant_fp8: bf16 source, uint8 destination, f32 scales")
+    if not (src.is_contiguous() and dst.is_contiguous() and scale.is_contiguous()) or src.shape[:-2] != dst.shape[:-2] \
+            or scale.shape != dst.shape[:-1]:
+        raise AkiError("kv_cache_quant_fp8: contiguous tensors with matching leading dimensions")
+    slabs = dst[..., 0, 0].numel()
+    L.check(L.load().aki_kv_cache_quant_fp8(_ptr(src), src.shape[-2], _ptr(dst), _ptr(scale), dst.shape[-2], slabs, int(rows), dst.shape[-1],
+                                            _dt(src), _stream()), "aki_kv_cache_quant_fp8")
+
+
 def decode_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, n_keys: torch.Tensor, scale: float,
                 col_valid_bits: Optional[torch.Tensor] = None, max_keys: int = 0, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q [B,H,Dh] against the first n_keys[b] rows of the caches [B,H,cap,Dh] -> o [B, H*Dh].
@@ -458,12 +472,27 @@ def decode_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, n
 
 def decode_attn_fused(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, cache_len: torch.Tensor, k_cache: torch.Tensor,
                       v_cache: torch.Tensor, num_heads: int, scale: float, col_valid_bits: Optional[torch.Tensor] = None,
-                      max_keys: int = 0, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      max_keys: int = 0, ws: Optional[torch.Tensor] = None, k_scale: Optional[torch.Tensor] = None,
+                      v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Decode step in one launch: qkv [B, 3*H*Dh] of the new tokens -> RoPE at position cache_len[b], k/v appended at
-    row cache_len[b], attention over cache_len[b]+1 keys -> o [B, H*Dh].  f32 (parity path) runs the two plain kernels."""
-    dev = _dev(qkv, cos, sin, cache_len, k_cache, v_cache, col_valid_bits, ws)
+    row cache_len[b], attention over cache_len[b]+1 keys -> o [B, H*Dh].  f32 (parity path) runs the two plain kernels.
+    An e4m3 cache (uint8 k_cache / v_cache, with the f32 row scales k_scale / v_scale [B, H, cap]) runs the fp8-KV twin of the kernel:
+    the new k / v are quantised per head and appended, and every key is attended through its quantised copy."""
+    dev = _dev(qkv, cos, sin, cache_len, k_cache, v_cache, col_valid_bits, ws, k_scale, v_scale)
     B = qkv.shape[0]
     cap, Dh = k_cache.shape[2], k_cache.shape[3]
+    if k_cache.dtype == torch.uint8:
+        if k_scale is None or v_scale is None or v_cache.dtype != torch.uint8:
+            raise AkiError("an e4m3 KV cache needs uint8 k/v caches and their f32 row scales")
+        if ws is None:
+            ws = decode_attn_workspace(B, num_heads, Dh, cap, dev)
+        o = torch.empty((B, num_heads * Dh), dtype=qkv.dtype, device=dev)
+        nw = 0 if col_valid_bits is None else col_valid_bits.shape[1]
+        L.check(L.load().aki_decode_attn_fused_fp8kv_fwd(_ptr(qkv.contiguous()), _ptr(cos), _ptr(sin), _ptr(cache_len), _ptr(k_cache),
+                                                         _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), _ptr(o), _ptr(col_valid_bits), nw, B,
+                                                         num_heads, Dh, cap, int(max_keys), float(scale), _dt(qkv), _ptr(ws), ws.numel() * 4,
+                                                         _stream()), "aki_decode_attn_fused_fp8kv_fwd")
+        return o
     if qkv.dtype != torch.bfloat16 or Dh != 96:
         q = rope_append(qkv, cos, sin, cache_len, cache_len, k_cache, v_cache, num_heads)
         return decode_attn(q, k_cache, v_cache, cache_len + 1, scale, col_valid_bits, max_keys, ws)

@@ -88,12 +88,31 @@ def _ag(x, *params) -> bool:
             and (x.requires_grad or any(p is not None and p.requires_grad for p in params)))
 
 
+KV_CACHE_DTYPES = ("bf16", "fp8_e4m3")
+
+
 class AkiKVCache:
     """Per-layer K/V caches [B, H, capacity, Dh] written by the prefill (QKV+RoPE epilogue stores straight into them)
-    and appended to by the decode kernels.  Lengths and positions live on the device so a decode step never syncs."""
+    and appended to by the decode kernels.  Lengths and positions live on the device so a decode step never syncs.
+    kv_dtype "fp8_e4m3": K and V are e4m3 bytes (uint8, same shape) with one f32 dequantisation scale per (layer, sample, head,
+    position) in k_scale / v_scale [B, H, capacity] - s = max(amax, 1e-12) / 448 over the head's 96 values, bytes = e4m3(x / s).
+    Needs a bf16 model and Dh = 96; the bf16 cache (the default) has k_scale = v_scale = None."""
 
-    def __init__(self, n_layers, B, H, Dh, capacity, dtype, device):
-        kv = torch.empty((2, n_layers, B, H, capacity, Dh), dtype=dtype, device=device)      # one allocation, per-layer views
+    def __init__(self, n_layers, B, H, Dh, capacity, dtype, device, kv_dtype="bf16"):
+        if kv_dtype not in KV_CACHE_DTYPES:
+            raise ValueError(f"kv_dtype must be one of {KV_CACHE_DTYPES}, got {kv_dtype!r}")
+        self.kv_dtype = kv_dtype
+        self.k_scale = self.v_scale = None
+        sc = None
+        if kv_dtype == "bf16":
+            kv = torch.empty((2, n_layers, B, H, capacity, Dh), dtype=dtype, device=device)      # one allocation, per-layer views
+        else:
+            if dtype != torch.bfloat16 or Dh != 96:
+                raise ops.AkiError(f"an fp8_e4m3 KV cache needs a bf16 model with head_dim 96 (got {dtype}, head_dim {Dh})")
+            kv = torch.empty((2, n_layers, B, H, capacity, Dh), dtype=torch.uint8, device=device)
+            sc = torch.empty((2, n_layers, B, H, capacity), dtype=torch.float32, device=device)
+            self.k_scale, self.v_scale = list(sc[0].unbind(0)), list(sc[1].unbind(0))
+        self._store = (kv, sc)                                                  # the whole allocation, until select_rows splits it
         self.k, self.v = list(kv[0].unbind(0)), list(kv[1].unbind(0))
         self.capacity = capacity
         self.cache_len = torch.zeros((B,), dtype=torch.int32, device=device)   # tokens cached per sample
@@ -105,6 +124,22 @@ class AkiKVCache:
         self.chain, self.chain_sig = None, None                                 # ops.DecodeChain of the one-launch step (batch 1)
         self.chain_disabled = False                                             # set when a chained step failed its check (decode_verified)
 
+    def scales(self, i):
+        """(k_scale, v_scale) of layer i: None, None for a bf16 cache."""
+        return (None, None) if self.k_scale is None else (self.k_scale[i], self.v_scale[i])
+
+    def nbytes(self) -> int:
+        """Device bytes held by the K/V rows (and, for fp8_e4m3, their scales)."""
+        ts = self.k + self.v + (self.k_scale or []) + (self.v_scale or [])
+        return sum(t.numel() * t.element_size() for t in ts)
+
+    def quantise_from(self, stage: "AkiKVCache", rows: int) -> None:
+        """fp8_e4m3: rows [0, rows) of a freshly prefilled bf16 cache of the same layers, batch and heads converted into this cache
+        (one launch, ops.kv_cache_quant_fp8)."""
+        if self.kv_dtype != "fp8_e4m3" or stage.kv_dtype != "bf16" or self._store is None or stage._store is None:
+            raise ops.AkiError("quantise_from: a fresh fp8_e4m3 cache and a bf16 staging cache, both still in one piece")
+        ops.kv_cache_quant_fp8(stage._store[0], self._store[0], self._store[1], rows)
+
     def get_seq_length(self, layer_idx=0):
         return int(self.cache_len.max())
 
@@ -113,6 +148,10 @@ class AkiKVCache:
         (HF `_reorder_cache`) and, with repeated indices, the expansion of a prompt batch to its beams."""
         self.k = [t.index_select(0, index) for t in self.k]
         self.v = [t.index_select(0, index) for t in self.v]
+        if self.k_scale is not None:                  # fp8_e4m3: the row scales travel with their bytes
+            self.k_scale = [t.index_select(0, index) for t in self.k_scale]
+            self.v_scale = [t.index_select(0, index) for t in self.v_scale]
+        self._store = None
         self.cache_len = self.cache_len.index_select(0, index)
         if self.valid_bits is not None:
             self.valid_bits = self.valid_bits.index_select(0, index).contiguous()
@@ -245,8 +284,9 @@ class Phi3Attention(nn.Module):
         """One new token per sequence: h [B, d] (residual stream, pre-norm) -> h + o_proj(attention).  Three launches:
         RMSNorm+qkv GEMV, RoPE+append+split-KV attention, o_proj GEMV with the residual add."""
         qkv = ops.decode_linear(h, self.qkv_proj.weight, norm.weight, norm.variance_epsilon)
+        ks, vs = cache.scales(self.layer_idx)
         o = ops.decode_attn_fused(qkv, cos, sin, cache.cache_len, cache.k[self.layer_idx], cache.v[self.layer_idx], self.num_heads,
-                                  self.scaling, cache.valid_bits, cache.grid_keys, cache.attn_ws)
+                                  self.scaling, cache.valid_bits, cache.grid_keys, cache.attn_ws, ks, vs)
         return ops.linear(o, self.o_proj.weight, residual=h)
 
 
@@ -370,8 +410,9 @@ class Phi3DecoderLayer(nn.Module):
             w, at = self._fp8, self.self_attn
             n1, n2 = self.input_layernorm, self.post_attention_layernorm
             qkv = ops.linear_w8(h, *w["qkv"], rms_weight=n1.weight, eps=n1.variance_epsilon)
+            ks, vs = cache.scales(at.layer_idx)
             o = ops.decode_attn_fused(qkv, cos, sin, cache.cache_len, cache.k[at.layer_idx], cache.v[at.layer_idx], at.num_heads,
-                                      at.scaling, cache.valid_bits, cache.grid_keys, cache.attn_ws)
+                                      at.scaling, cache.valid_bits, cache.grid_keys, cache.attn_ws, ks, vs)
             h = ops.linear_w8(o, *w["o"], residual=h)
             a = ops.linear_w8(h, *w["gate_up"], act=ops.ACT_SWIGLU, rms_weight=n2.weight, eps=n2.variance_epsilon)
             return ops.linear_w8(a, *w["down"], residual=h)
@@ -527,9 +568,10 @@ class Phi3Model(nn.Module):
 
     def _decode_chain(self, h, cache):
         """The one-launch decode step when it applies: one sequence, bf16 stream, Phi-3.5-mini's dimensions, every layer either
-        bf16 or fully e4m3-quantised (the fp8 configuration's weight-only GEMVs).  Built once per (weights, KV cache)."""
+        bf16 or fully e4m3-quantised (the fp8 configuration's weight-only GEMVs), a bf16 KV cache (an fp8_e4m3 cache takes the
+        five-launch-per-layer path).  Built once per (weights, KV cache)."""
         B = h.shape[0]
-        if (not self.use_decode_chain or cache.chain_disabled or B > (8 if self.use_decode_chain_batched else 1) or h.dtype != torch.bfloat16
+        if (not self.use_decode_chain or cache.chain_disabled or getattr(cache, "kv_dtype", "bf16") != "bf16" or B > (8 if self.use_decode_chain_batched else 1) or h.dtype != torch.bfloat16
                 or not h.is_cuda):
             return None
         l0, ll = self.layers[0], self.layers[-1]
@@ -656,10 +698,25 @@ class Phi3ForCausalLM(nn.Module):
         w = self._prep.get("head", [w0, norm.weight], lambda: ops.fold_gain(w0, norm.weight), (T._EPOCH, head._fused[0]))
         return ops.linear(h, w, bias=b, row_scale=st.rstd)[..., :n]
 
+    kv_cache_dtype = "bf16"
+
+    def set_kv_cache_dtype(self, dtype: str = "bf16"):
+        """Format of the KV caches this model allocates from now on (a use_cache=True forward, AKI.generate): "bf16" (the default) or
+        "fp8_e4m3" - e4m3 K/V bytes with one f32 scale per (layer, sample, head, position), 0.52x the bytes that a batched or
+        long-context decode step reads from the cache.  With fp8_e4m3 the prefill runs unchanged on a bf16 staging cache (its logits and
+        first token are bit-identical to the bf16 path's), whose rows one launch then converts; every decode step appends quantised
+        rows and attends through them (aki_decode_attn_fused_fp8kv_fwd), on the five-launch-per-layer path - the one-launch decode chain
+        keeps to bf16 caches.  Independent of enable_fp8() (e4m3 weights).  A live cache is never converted.  Any other value raises
+        ValueError."""
+        if not isinstance(dtype, str) or dtype not in KV_CACHE_DTYPES:
+            raise ValueError(f"kv cache dtype must be one of {KV_CACHE_DTYPES}, got {dtype!r}")
+        self.kv_cache_dtype = dtype
+        return self
+
     def forward(self, input_ids=None, attention_mask=None, inputs_embeds=None, labels=None, position_ids=None,
                 use_cache=False, past_key_values=None, cache_capacity=None, last_token_logits=False, **kwargs):
         """Prefill / full forward.  With use_cache=True the returned past_key_values is an AkiKVCache holding the
-        rotated keys and the values of every layer (capacity = cache_capacity or L + 256).
+        rotated keys and the values of every layer (capacity = cache_capacity or L + 256; format: set_kv_cache_dtype).
         last_token_logits=True (prefill of `generate`, which reads nothing else; HF's `logits_to_keep=1` for a right-padded batch): logits is
         [B, 1, V'] - the head runs on each sample's last valid token only, a weight-streaming GEMV instead of an L-row GEMM against the
         197 MB head."""
@@ -677,18 +734,25 @@ class Phi3ForCausalLM(nn.Module):
             table = ops.MaskTable.causal(B, L, inputs_embeds.device)
         elif isinstance(table, torch.Tensor):
             table = mask_table_from_tensor(table, L)
-        cache = None
+        cache = stage = None
         if use_cache:
             cfg = self.config
             H = cfg.num_attention_heads
             Dh = getattr(cfg, "head_dim", None) or cfg.hidden_size // H
-            cache = AkiKVCache(len(self.model.layers), B, H, Dh, int(cache_capacity or (L + 256)), inputs_embeds.dtype,
-                               inputs_embeds.device)
+            cache = stage = AkiKVCache(len(self.model.layers), B, H, Dh, int(cache_capacity or (L + 256)), inputs_embeds.dtype,
+                                       inputs_embeds.device, self.kv_cache_dtype)
+            if cache.kv_dtype != "bf16":
+                # the prefill writes (and attends over) bf16 K/V exactly as on the bf16 path, into a staging cache of the prompt's length
+                stage = AkiKVCache(len(self.model.layers), B, H, Dh, L, inputs_embeds.dtype, inputs_embeds.device)
         fp8_head = getattr(self, "_fp8_head", None) is not None and not torch.is_grad_enabled()
         self.model.skip_final_norm = fp8_head
         self.model.defer_final_norm = True
-        h = self.model(inputs_embeds, table, position_ids, cache)
+        h = self.model(inputs_embeds, table, position_ids, stage)
         self.model.skip_final_norm = self.model.defer_final_norm = False
+        if stage is not cache:
+            cache.quantise_from(stage, L)                # one launch for every layer; the staging cache is freed here
+            cache.host_len = stage.host_len
+            stage = None
         head_stats, self.model.final_stats = self.model.final_stats, None     # not None: h is the raw stream, norm folded into the head
         self._pre_norm_h = h if fp8_head else None
         if head_stats is not None and _ag(h, *self.lm_head.parameters()):

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define AKI_ABI_VERSION 17
+#define AKI_ABI_VERSION 17   /* not bumped for the fp8 KV-cache functions (aki_kv_cache_quant_fp8, aki_decode_attn_fused_fp8kv_fwd): purely additive */
 
 typedef enum {
   AKI_OK = 0,
@@ -368,6 +368,26 @@ int aki_decode_attn_fused_fwd(const void* qkv, const float* cos, const float* si
                               int32_t Dh, int32_t capacity, int32_t max_keys, float scale, int32_t dtype, void* ws,
                               size_t ws_bytes, void* stream);
 int aki_decode_linear_fwd(const aki_linear_args* args, const void* rms_weight, float rms_eps, void* stream);
+
+/* fp8 (e4m3) KV cache - an opt-in format for batched and long-context decode (Phi3ForCausalLM.set_kv_cache_dtype("fp8_e4m3")).
+ * A cache row (one head, one position, Dh = 96 values) is 96 e4m3 bytes plus one f32 dequantisation scale:
+ *   s = max(amax, 1e-12) / 448 over the row,  byte = e4m3(x / s) rounded to nearest even, saturating at +-448
+ * (the rule of aki_quant_rows_fp8).  Caches are k/v [B, H, capacity, 96] uint8 and k_scale/v_scale [B, H, capacity] f32.
+ * aki_kv_cache_quant_fp8 : rows [0, rows) of every slab of a bf16 cache src [slabs, src_capacity, 96] -> dst [slabs, dst_capacity, 96]
+ *                       bytes + scale [slabs, dst_capacity]: the prefill's K/V (written in bf16 by the unchanged prefill kernels into
+ *                       a staging cache) converted in one launch (slabs = 2 * layers * B * H).
+ * aki_decode_attn_fused_fp8kv_fwd : aki_decode_attn_fused_fwd on the e4m3 cache - the rotated k (rounded to bf16) and v of the new
+ *                       token are quantised per head and appended (bytes + scales) at cache_len[b], then attended through their
+ *                       quantised copy like every cached key: score = (q . k8) * s_k * scale, row j of V weighted by p_j * s_v[j].
+ *                       Same workspace (aki_decode_attn_workspace_bytes) and max_keys as aki_decode_attn_fused_fwd.
+ * Both: NULL pointers -> AKI_ERR_INVALID_ARG; Dh != 96 or dtype != AKI_DT_BF16 -> AKI_ERR_UNSUPPORTED.
+ * AKI_ABI_VERSION was not bumped for these two functions: they are purely additive (no existing symbol or struct changed). */
+int aki_kv_cache_quant_fp8(const void* src, int32_t src_capacity, void* dst, float* scale, int32_t dst_capacity, int32_t slabs, int32_t rows,
+                           int32_t Dh, int32_t dtype, void* stream);
+int aki_decode_attn_fused_fp8kv_fwd(const void* qkv, const float* cos, const float* sin, const int32_t* cache_len, void* k_cache,
+                                    void* v_cache, float* k_scale, float* v_scale, void* o, const uint64_t* col_valid_bits, int32_t nwords,
+                                    int32_t B, int32_t H, int32_t Dh, int32_t capacity, int32_t max_keys, float scale, int32_t dtype, void* ws,
+                                    size_t ws_bytes, void* stream);
 
 /* aki_decode_chain_fwd - ALL decoder layers of one decode step for ONE sequence (batch 1) in one launch (bf16 weights, or
  * AKI_DT_W8A16: e4m3 weights with one f32 scale per weight row).  Same arithmetic as the per-layer calls above

@@ -342,7 +342,9 @@ int aki_splice_fwd(const aki_splice_args* args, void* stream);
  * aki_rope_append_fwd : qkv [B,3*H*Dh] of the new tokens -> rotated q [B,H,Dh]; rotated k and v appended to the caches
  *                       [B,H,capacity,Dh] at index cache_len[b] (device int32); pos[b] = row into cos/sin.
  * aki_decode_attn_fwd : o [B,H*Dh] = softmax(q K^T * scale) V over the first n_keys[b] cache rows (device int32),
- *                       optional valid bits [B][nwords] of the prefill columns (padding), NULL = all valid.
+ *                       optional valid bits [B][nwords] of the prefill columns (padding), NULL = all valid; columns at
+ *                       and past 64 * nwords count as valid.  A row with no visible key at all (every one of its
+ *                       n_keys[b] columns lies inside the words with its bit clear) gets o = 0, not NaN.
  *                       bf16/Dh=96 runs split over the keys (flash-decoding) and needs the workspace below; max_keys is
  *                       a HOST upper bound of max_b n_keys[b] (<= capacity; 0 = capacity) that sizes the grid - keys
  *                       beyond it are not visited.

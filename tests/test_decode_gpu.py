@@ -37,6 +37,8 @@ def test_gemv_linear_bf16(M, N, K):
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_rope_append_and_decode_attention(dtype):
+    """The small shape (B 3, H 4, cap 300) against the oracle: RoPE + append, then attention with one hole in a mask word.
+    Parity over the launch plan's corners, long contexts and adversarial masks lives in test_decode_attn_gpu.py."""
     from aki_amd import ops
     B, H, Dh, cap = 3, 4, 96, 300
     rng = gen.rng_for("decode_attn")
@@ -394,7 +396,9 @@ def test_skinny_gemm_on_e4m3_weights(M, shape):
 
 @pytest.mark.parametrize("B,H,cap,lens", [(3, 4, 300, [17, 200, 298]), (2, 2, 5000, [4100, 63]), (8, 32, 700, [655] * 8), (1, 32, 64, [0])])
 def test_decode_attn_fused_vs_two_kernels(B, H, cap, lens):
-    """RoPE + append + split-KV attention in one launch == rope_append followed by decode_attn; caches end up identical."""
+    """RoPE + append + split-KV attention in one launch == rope_append followed by decode_attn; caches end up identical.
+    This checks that the two paths AGREE - both run decode_attn_split_kernel, so a fault they share passes here; parity against a
+    float64 reference lives in test_decode_attn_gpu.py."""
     from aki_amd import ops
     Dh, dt = 96, torch.bfloat16
     rng = gen.rng_for(f"decfused{B}{H}{cap}")

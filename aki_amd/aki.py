@@ -210,7 +210,9 @@ class AKI(VLMWithLanguageStream):
         `inputs_embeds` only, the return value holds just the NEW tokens [B, <= max_new_tokens]; finished rows are padded
         with pad_token_id.  Decoding modes, selected by the HF keyword arguments the reference forwards (`**kwargs`,
         src/aki.py:160-207): greedy (default), sampling (`do_sample=True` with `temperature`, `top_k`, `top_p`, optional
-        `generator`), beam search (`num_beams=K`, `length_penalty`, `early_stopping`; one returned sequence per sample).
+        `generator`; a `aki_amd.DeviceGenerator(seed)` there selects the device sampler - ops.sample_pick, one launch per token inside the
+        same three-launch / replayed-graph loop as greedy, draws that depend on (seed, call, token index, row) and not on the batch -
+        while None or a `torch.Generator` keeps the `sample_next` path), beam search (`num_beams=K`, `length_penalty`, `early_stopping`; one returned sequence per sample).
         Logits processors, applied on the device in every mode and in HF's order (ops.LogitsProcessors): `repetition_penalty`,
         `no_repeat_ngram_size`, `bad_words_ids`, `min_length` / `min_new_tokens` (eos ids banned until that many tokens are
         generated), `suppress_tokens`, `begin_suppress_tokens`.  As in HF `generate` with inputs_embeds only, they see the generated
@@ -226,6 +228,13 @@ class AKI(VLMWithLanguageStream):
         rng = kwargs.pop("generator", None)
         length_penalty = float(kwargs.pop("length_penalty", 1.0))
         early_stopping = kwargs.pop("early_stopping", False)
+        from . import ops
+        device_rng = rng if isinstance(rng, ops.DeviceGenerator) else None
+        if device_rng is not None:
+            if not do_sample or num_beams > 1:
+                raise ValueError("generator=DeviceGenerator(...) selects the device sampler: it needs do_sample=True and num_beams=1")
+            if not 0.0 < top_p <= 1.0 or top_k < 0:
+                raise ValueError("the device sampler takes 0 < top_p <= 1 and top_k >= 0")
         if int(kwargs.pop("num_return_sequences", 1)) != 1:
             raise NotImplementedError("num_return_sequences > 1")
         if num_beams < 1 or (num_beams > 1 and do_sample):
@@ -260,7 +269,6 @@ class AKI(VLMWithLanguageStream):
         cache = out.past_key_values
         B = lang_x.shape[0]
         logits = out.logits[:, 0]                                                  # logits of each sample's last real token
-        from . import ops
         proc = ops.LogitsProcessors(logits.shape[-1], logits.device, pk["repetition_penalty"], pk["no_repeat_ngram_size"],
                                     max(int(pk["min_length"]), int(pk["min_new_tokens"])), sorted(eos_ids), pk["suppress_tokens"],
                                     pk["begin_suppress_tokens"], pk["bad_words_ids"])
@@ -279,8 +287,15 @@ class AKI(VLMWithLanguageStream):
         # ever returned (lm.decode_verified switches the chain off for this cache and warns).
         chained = lambda: getattr(cache, "chain", None) is not None
         stepper = None
-        if use_graph and not do_sample and logits.is_cuda and logits.dtype == torch.bfloat16:
-            # Greedy: the pick (argmax, pad for finished rows, append, eos check, cache_len advance, the next step's embedding row) is one launch
+        on_device = logits.is_cuda and logits.dtype == torch.bfloat16
+        if device_rng is not None and not on_device:
+            raise ValueError("the device sampler needs bf16 logits on the GPU")
+        sampler = None                              # ops.sample_pick's own arguments: one offset per generate call
+        if device_rng is not None:
+            sampler = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=device_rng.seed, offset=device_rng.next_offset())
+        if use_graph and (not do_sample or sampler is not None) and on_device:
+            # Greedy, or sampling on the device (ops.sample_pick in the pick's place: the same loop, the same three launches per token).
+            # The pick (argmax, pad for finished rows, append, eos check, cache_len advance, the next step's embedding row) is one launch
             # behind the decode step (inside the replayed graph where there is one); the host looks at the finished flags every 8th token
             # instead of syncing per token.
             from . import ops
@@ -289,6 +304,10 @@ class AKI(VLMWithLanguageStream):
             done_at = torch.full((B,), -1, dtype=torch.int32, device=lang_x.device)
             start_len, host_len0 = cache.cache_len.clone(), cache.host_len
             pick = dict(pad_token_id=pad_id, eos_ids=eos_t, done=done8, tokens=tokens, start_len=start_len, done_at=done_at)
+            pick_op = ops.greedy_pick
+            if sampler is not None:
+                pick.update(sampler)
+                pick_op = ops.sample_pick
             if proc is not None:                    # the processors read tokens[:, :t] and t from cache_len: replays and rewinds stay right
                 pick["processors"] = proc
             ids = torch.zeros(B, dtype=torch.long, device=lang_x.device)
@@ -296,7 +315,7 @@ class AKI(VLMWithLanguageStream):
             embed = _embedding_tables(emb_mod, logits)
             nxt_emb = None if embed is None else torch.empty((B, emb_mod.weight.shape[1]), dtype=torch.bfloat16, device=lang_x.device)
             pick_e = pick if embed is None else dict(pick, embed=embed, next_embeds=nxt_emb)
-            ops.greedy_pick(logits.contiguous(), ids, cache_len=cache.cache_len, advance=False, **pick_e)      # token 0, from the prefill
+            pick_op(logits.contiguous(), ids, cache_len=cache.cache_len, advance=False, **pick_e)      # token 0, from the prefill
             t, t_ok = 1, 1                                  # tokens[:, :t_ok] are verified (token 0 comes from the prefill, not from the chain)
             period = 8 if eos_t is not None else 32         # host synchronisations: the EOS check needs them often, the chain's verification alone does not
             while True:
@@ -320,7 +339,7 @@ class AKI(VLMWithLanguageStream):
                             lg = lm.decode_step(inputs_embeds=nxt_emb, past_key_values=cache, advance=False)
                         else:
                             lg = lm.decode_step(input_ids=ids, past_key_values=cache, advance=False)
-                        ops.greedy_pick(lg, ids, cache_len=cache.cache_len, advance=True, **pick_e)
+                        pick_op(lg, ids, cache_len=cache.cache_len, advance=True, **pick_e)
                         if not chained():
                             stepper = DecodeGraph(lm, cache, greedy=pick)
                             stepper.ids.copy_(ids)
@@ -363,8 +382,12 @@ class AKI(VLMWithLanguageStream):
                         ok = False
                         break
                     ck = (t, logits.clone(), done.clone(), cache.cache_len.clone(), cache.host_len)
-                x = logits if proc is None else proc.apply(logits, tokens=tokens, step=t)
-                nxt = sample_next(x, temperature, top_k, top_p, rng) if do_sample else x.float().argmax(dim=-1)
+                if sampler is not None:             # the device sampler outside a graph: one launch, the draw of token t (no cache_len: n = step)
+                    nxt = ops.sample_pick(logits.contiguous(), torch.empty(B, dtype=torch.long, device=logits.device), processors=proc,
+                                          tokens=tokens, step=t, **sampler)
+                else:
+                    x = logits if proc is None else proc.apply(logits, tokens=tokens, step=t)
+                    nxt = sample_next(x, temperature, top_k, top_p, rng) if do_sample else x.float().argmax(dim=-1)
                 nxt = torch.where(done, torch.full_like(nxt, pad_id), nxt)
                 tokens[:, t] = nxt
                 t += 1

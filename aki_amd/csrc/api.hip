@@ -57,6 +57,12 @@ int greedy_pick_processed_launch(const void* logits, int B, int V, int ld, const
                                  int ld_scores, float penalty, int ngram, int min_len, const int64_t* suppress, int n_suppress,
                                  const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad,
                                  int n_bad_ids, hipStream_t s);
+int sample_pick_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done, int64_t* ids,
+                       int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at, const void* emb_main,
+                       const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores, int ld_scores, float penalty, int ngram,
+                       int min_len, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids,
+                       const int* bad_off, int n_bad, int n_bad_ids, int step, float temperature, int top_k, float top_p, uint64_t seed,
+                       uint64_t offset, float* probs, int ld_probs, hipStream_t s);
 int sft_collate_launch(const int64_t* ids, const int64_t* labels, const int64_t* mask, const int* offsets, int B, int T_out,
                        int64_t pad_id, int64_t ignore_index, int left, int64_t* out_ids, int64_t* out_labels, int64_t* out_mask,
                        hipStream_t s);
@@ -749,6 +755,37 @@ int aki_greedy_pick_processed(const void* logits, int32_t B, int32_t V, int64_t 
                                       advance, done_at, embed_weight, additional_weight, max_original_id, d, next_embeds, scores, (int)ld_scores,
                                       repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
                                       n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids, (hipStream_t)stream);
+}
+
+int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                    uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                    int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                    int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                    int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                    const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                    int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                    uint64_t offset, float* probs_out, int64_t ld_probs, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(logits && next_ids && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && n_eos >= 0 && (n_eos == 0 || eos_ids));
+  AKI_CHECK_ARG((!tokens || tokens_ld > 0) && (!advance || cache_len) && (advance == 0 || advance == 1) && step >= 0);
+  AKI_CHECK_ARG(scores && ld_scores >= V && ld_scores < (1ll << 31));
+  AKI_CHECK_ARG(processors_ok(V, repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
+                              n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids));
+  AKI_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f && top_p > 0.f && top_p <= 1.f && top_k >= 0);
+  AKI_CHECK_ARG(!probs_out || (ld_probs >= V && ld_probs < (1ll << 31)));
+  if ((((uintptr_t)scores) & 15) != 0 || (ld_scores & 3) != 0) return AKI_ERR_ALIGNMENT;
+  if (embed_weight) {
+    AKI_CHECK_ARG(next_embeds && d > 0 && d % 8 == 0 && max_original_id >= 0 && num_additional >= 0);
+    AKI_CHECK_ARG((((uintptr_t)embed_weight | (uintptr_t)additional_weight | (uintptr_t)next_embeds) & 15) == 0);
+    AKI_CHECK_ARG((int64_t)V <= max_original_id + 1 + (additional_weight ? num_additional : 0) && pad_token_id >= 0 &&
+                  pad_token_id <= max_original_id + (additional_weight ? num_additional : 0));
+  } else {
+    AKI_CHECK_ARG(!additional_weight && !next_embeds);
+  }
+  return sample_pick_launch(logits, B, V, (int)ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
+                            done_at, embed_weight, additional_weight, max_original_id, d, next_embeds, scores, (int)ld_scores, repetition_penalty,
+                            no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets,
+                            n_bad, n_bad_ids, step, temperature, top_k, top_p, seed, offset, probs_out, (int)ld_probs, (hipStream_t)stream);
 }
 
 size_t aki_mma_mask_to_table_workspace_bytes(int32_t B, int32_t L) {

@@ -1423,6 +1423,7 @@ struct PickParams {
   // optional: the NEXT decode step's input row, gathered here (DecoupledEmbedding, src/helpers.py:350-492: ids above max_original_id index the
   // additional table) so that a greedy token needs no embedding launch
   const bf16_t* emb_main; const bf16_t* emb_extra; int64_t max_original_id; int d; bf16_t* emb_out;
+  int step;   // added to t (the sampler's eager loop passes the token index here when it has no cache_len); 0 for the greedy picks
 };
 
 __device__ __forceinline__ bool pick_better(float a, int ia, float b, int ib) {
@@ -1432,15 +1433,49 @@ __device__ __forceinline__ bool pick_better(float a, int ia, float b, int ib) {
   return a > b || (a == b && ia < ib);
 }
 
+constexpr int PICK_THREADS = 1024;
+// The pick's bookkeeping tail, shared by the greedy and the sampling kernels: thread 0 holds the picked id `bi` and what it requested before
+// the scan (was_done, len0, start0, eos4); pad for finished rows, append, eos check, cache_len advance, then every thread gathers the
+// next step's embedding row.
+__device__ __forceinline__ void pick_finish(const PickParams& p, int b, bool was_done, int len0, int start0, const int64_t (&eos4)[4], int bi) {
+  __shared__ int64_t s_next;
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    const int64_t nxt = was_done ? p.pad : (int64_t)bi;
+    int t = p.step;
+    if (p.cache_len != nullptr) {
+      t += len0 + p.advance - start0;
+      if (p.advance) p.cache_len[b] = len0 + 1;
+    }
+    if (p.tokens != nullptr && t >= 0 && t < p.tokens_ld) p.tokens[(size_t)b * p.tokens_ld + t] = nxt;
+    p.ids[b] = nxt;
+    s_next = nxt;
+    if (p.done != nullptr && !was_done) {
+      bool hit = eos4[0] == nxt || eos4[1] == nxt || eos4[2] == nxt || eos4[3] == nxt;
+      for (int i = 4; i < p.n_eos; ++i) hit = hit || p.eos[i] == nxt;
+      if (hit) {
+        p.done[b] = 1;
+        if (p.done_at) p.done_at[b] = t;
+      }
+    }
+  }
+  if (p.emb_out != nullptr) {
+    __syncthreads();
+    const int64_t nxt = s_next;
+    const bool extra = p.emb_extra != nullptr && nxt > p.max_original_id;
+    const bf16_t* src = extra ? p.emb_extra + (size_t)(nxt - p.max_original_id - 1) * p.d : p.emb_main + (size_t)nxt * p.d;
+    bf16_t* dst = p.emb_out + (size_t)b * p.d;
+    for (int c = tid; c < p.d / 8; c += PICK_THREADS) *(u32x4*)(dst + (size_t)c * 8) = *(const u32x4*)(src + (size_t)c * 8);
+  }
+}
+
 // One workgroup of 16 waves per row: the scan of 32 064 logits is a latency chain (load, eight compares, next load); 1024 threads walk it in 4 trips of two
 // loads each instead of 16 trips of one (19.4 -> measured in profiles/r05_decode_token_trace.txt).
-constexpr int PICK_THREADS = 1024;
 // F32: the row to scan is `rowf` (an f32 row of processed scores, see logits processors below), not p.logits
 template <bool F32>
 __device__ __forceinline__ void greedy_pick_row(const PickParams& p, const float* rowf) {
   __shared__ float s_v[PICK_THREADS / 64];
   __shared__ int s_i[PICK_THREADS / 64];
-  __shared__ int64_t s_next;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // What the bookkeeping needs does not depend on the argmax: thread 0 requests it BEFORE the scan, so that behind the scan only stores are
   // left (it used to be a chain of five dependent round trips behind the reduction, about a third of the launch).
@@ -1517,32 +1552,8 @@ __device__ __forceinline__ void greedy_pick_row(const PickParams& p, const float
 #pragma unroll
     for (int w = 1; w < PICK_THREADS / 64; ++w)
       if (pick_better(s_v[w], s_i[w], best, bi)) { best = s_v[w]; bi = s_i[w]; }
-    const int64_t nxt = was_done ? p.pad : (int64_t)bi;
-    int t = 0;
-    if (p.cache_len != nullptr) {
-      t = len0 + p.advance - start0;
-      if (p.advance) p.cache_len[b] = len0 + 1;
-    }
-    if (p.tokens != nullptr && t >= 0 && t < p.tokens_ld) p.tokens[(size_t)b * p.tokens_ld + t] = nxt;
-    p.ids[b] = nxt;
-    s_next = nxt;
-    if (p.done != nullptr && !was_done) {
-      bool hit = eos4[0] == nxt || eos4[1] == nxt || eos4[2] == nxt || eos4[3] == nxt;
-      for (int i = 4; i < p.n_eos; ++i) hit = hit || p.eos[i] == nxt;
-      if (hit) {
-        p.done[b] = 1;
-        if (p.done_at) p.done_at[b] = t;
-      }
-    }
   }
-  if (p.emb_out != nullptr) {
-    __syncthreads();
-    const int64_t nxt = s_next;
-    const bool extra = p.emb_extra != nullptr && nxt > p.max_original_id;
-    const bf16_t* src = extra ? p.emb_extra + (size_t)(nxt - p.max_original_id - 1) * p.d : p.emb_main + (size_t)nxt * p.d;
-    bf16_t* dst = p.emb_out + (size_t)b * p.d;
-    for (int c = tid; c < p.d / 8; c += PICK_THREADS) *(u32x4*)(dst + (size_t)c * 8) = *(const u32x4*)(src + (size_t)c * 8);
-  }
+  pick_finish(p, b, was_done, len0, start0, eos4, bi);
 }
 
 __global__ __launch_bounds__(PICK_THREADS) void greedy_pick_kernel(const PickParams p) { greedy_pick_row<false>(p, nullptr); }
@@ -1669,6 +1680,270 @@ __global__ __launch_bounds__(PICK_THREADS) void greedy_pick_processed_kernel(con
   greedy_pick_row<true>(p, rowf);
 }
 
+// ---- sampling pick: HF's `do_sample` step (processors -> temperature -> top-k -> top-p -> softmax -> multinomial) with the greedy pick's
+// bookkeeping and embedding gather, as ONE launch, one workgroup per row.  No sort: both filters are thresholds on the order-preserving
+// 32-bit key of y = x / T, "keep i iff the weight of the strictly larger keys is below P" - weight 1 and P = k for top-k, weight
+// exp(y - max) and P = top_p * (mass top-k kept) for top-p - found by a three-digit (11 + 11 + 10 bit) radix select over LDS histograms.
+// The histograms are 64-bit INTEGERS (the mass as 2^-40 fixed point) filled with integer atomics, so the result does not depend on the
+// order the atomics land in: run-to-run deterministic without a float atomic.  The draw is a counter-based Philox4x32-10 word per
+// (token index, row, call), inverted through the cumulative sum in index order: per-thread chunk sums and a fixed-order block scan.
+struct SampleParams {
+  float temperature; int top_k; float top_p;
+  unsigned seed_lo, seed_hi, off_lo, off_hi;
+  float* probs; int ld_probs;
+  int processed;                                            // the processors ran: x is the f32 scratch row, not the bf16 logits
+};
+
+__device__ __forceinline__ unsigned sample_key(float y) {   // larger y <=> larger key; -0 and +0 share one
+  unsigned u = __float_as_uint(y);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ unsigned philox4x32_10_word0(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long m0 = 0xD2511F53ull * c0, m1 = 0xCD9E8D57ull * c2;
+    const unsigned n0 = (unsigned)(m1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(m0 >> 32) ^ c3 ^ k1;
+    c1 = (unsigned)m1; c3 = (unsigned)m0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return c0;
+}
+
+// exclusive scan in thread order over the workgroup, one fixed association: 6 shuffle levels in a wave, 4 over the 16 wave totals, 1 add
+template <typename T>
+__device__ __forceinline__ T block_excl_scan(T v, T* s_w, T* incl, T* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  T inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T n = __shfl_up(inc, o);
+    if (lane >= o) inc += n;
+  }
+  T exl = __shfl_up(inc, 1);
+  if (lane == 0) exl = T(0);
+  __syncthreads();                                          // s_w may still be read from the scan before
+  if (lane == 63) s_w[wave] = inc;
+  __syncthreads();
+  T wt = lane < PICK_THREADS / 64 ? s_w[lane] : T(0);
+#pragma unroll
+  for (int o = 1; o < PICK_THREADS / 64; o <<= 1) {
+    const T n = __shfl_up(wt, o);
+    if (lane >= o) wt += n;
+  }
+  *total = __shfl(wt, PICK_THREADS / 64 - 1);
+  const T pre = __shfl(wt, wave > 0 ? wave - 1 : 0);
+  if (wave > 0) { exl = pre + exl; inc = pre + inc; }
+  *incl = inc;
+  return exl;
+}
+
+constexpr int SEL_BINS = 2048;                              // 16 KB of 64-bit bins: the processors' bitmap, free once they have run
+constexpr float SEL_FIX = 1099511627776.f;                  // 2^40: exp(y - max) in (0, 1] as fixed point; V * 2^40 < 2^57
+
+// The smallest key tau such that the weight of the keys above it (among keys >= lo_key) is below P: kept <=> key >= tau.
+// MASS: weight exp(y - ymax) and P = ceil(top_p * total weight); else weight 1 and P = P_count.
+template <bool MASS>
+__device__ unsigned select_threshold(const float* rowf, int V, unsigned lo_key, float ymax, unsigned long long P_count, float top_p,
+                                     unsigned long long* hist, unsigned long long* s_w, unsigned long long* s_pick) {
+  const int tid = threadIdx.x, ngroups = (V + 3) / 4;
+  unsigned pre = 0;
+  unsigned long long P = P_count;
+#pragma unroll 1
+  for (int pass = 0; pass < 3; ++pass) {
+    const int shift = pass == 0 ? 21 : pass == 1 ? 10 : 0, bits = pass == 2 ? 10 : 11;
+    for (int i = tid; i < SEL_BINS; i += PICK_THREADS) hist[i] = 0ull;
+    if (tid == 0) { s_pick[0] = 0ull; s_pick[1] = 1ull; }
+    __syncthreads();
+    for (int g = tid; g < ngroups; g += PICK_THREADS) {
+      const float4 v = *(const float4*)(rowf + (size_t)g * 4);
+      const float ve[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (g * 4 + e >= V) continue;
+        const unsigned key = sample_key(ve[e]);
+        if (key < lo_key || (pass > 0 && (key >> (shift + bits)) != pre)) continue;
+        const unsigned long long w = MASS ? (unsigned long long)(expf(ve[e] - ymax) * SEL_FIX) : 1ull;
+        if (w) atomicAdd(&hist[(key >> shift) & ((1u << bits) - 1u)], w);
+      }
+    }
+    __syncthreads();
+    // bins from the top: thread t owns bins 2047 - 2t and 2046 - 2t; `above` = the weight of the bins above its first one
+    const int d = SEL_BINS - 1 - 2 * tid;
+    const unsigned long long a = hist[d], b = hist[d - 1];
+    unsigned long long incl, total;
+    const unsigned long long above = block_excl_scan<unsigned long long>(a + b, s_w, &incl, &total);
+    if (MASS && pass == 0) {
+      P = (unsigned long long)ceil((double)top_p * (double)total);
+      if (P < 1ull) P = 1ull;
+    }
+    // exactly one bin holds the threshold: above(d) < P <= above(d) + hist[d]
+    if (above < P && P <= above + a) { s_pick[0] = (unsigned long long)d; s_pick[1] = P - above; }
+    else if (above + a < P && P <= above + a + b) { s_pick[0] = (unsigned long long)(d - 1); s_pick[1] = P - above - a; }
+    __syncthreads();
+    pre = (pre << bits) | (unsigned)s_pick[0];
+    P = s_pick[1];
+    __syncthreads();
+  }
+  return pre;
+}
+
+__global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickParams p, const ProcParams q, const SampleParams sp) {
+  __shared__ unsigned long long s_hist[SEL_BINS];           // first the processors' bitmap (PROC_MAX_V / 32 words), then the select's bins
+  __shared__ unsigned long long s_w64[PICK_THREADS / 64], s_pick[2];
+  __shared__ float s_wf[PICK_THREADS / 64];
+  __shared__ float s_v[PICK_THREADS / 64];
+  __shared__ int s_i[PICK_THREADS / 64];
+  __shared__ int s_owner, s_last, s_tok;
+  static_assert(sizeof(s_hist) >= PROC_MAX_V / 8, "the bitmap has to fit the bins");
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, V = p.V;
+  float* rowf = q.out + (size_t)b * q.ld_out;
+  if (sp.processed) process_row(q, b, rowf, (unsigned*)s_hist);
+  bool was_done = false;
+  int len0 = 0, start0 = 0;
+  int64_t eos4[4] = {-1, -1, -1, -1};
+  if (tid == 0) {
+    was_done = p.done != nullptr && p.done[b] != 0;
+    if (p.cache_len != nullptr) {
+      len0 = p.cache_len[b];
+      if (p.start_len) start0 = p.start_len[b];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (i < p.n_eos) eos4[i] = p.eos[i];
+    s_owner = 0x7fffffff; s_last = -1; s_tok = -1;
+  }
+  const bool row_done = p.done != nullptr && p.done[b] != 0;   // uniform: every thread reads the same byte, before thread 0 can set it
+  float* probs = sp.probs ? sp.probs + (size_t)b * sp.ld_probs : nullptr;
+  const float T = sp.temperature;
+  // pass 0: argmax of x in the greedy pick's ordering, y = x / T (correctly rounded) into the scratch row
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  if (sp.processed) {
+    for (int g = tid; g < V / 4; g += PICK_THREADS) {
+      float4 v = *(const float4*)(rowf + (size_t)g * 4);
+      const int c = g * 4;
+      if (pick_better(v.x, c, best, bi)) { best = v.x; bi = c; }
+      if (pick_better(v.y, c + 1, best, bi)) { best = v.y; bi = c + 1; }
+      if (pick_better(v.z, c + 2, best, bi)) { best = v.z; bi = c + 2; }
+      if (pick_better(v.w, c + 3, best, bi)) { best = v.w; bi = c + 3; }
+      v.x = __fdiv_rn(v.x, T); v.y = __fdiv_rn(v.y, T); v.z = __fdiv_rn(v.z, T); v.w = __fdiv_rn(v.w, T);
+      *(float4*)(rowf + (size_t)g * 4) = v;
+    }
+    for (int i = V / 4 * 4 + tid; i < V; i += PICK_THREADS) {
+      const float x = rowf[i];
+      if (pick_better(x, i, best, bi)) { best = x; bi = i; }
+      rowf[i] = __fdiv_rn(x, T);
+    }
+  } else {
+    const bf16_t* row = p.logits + (size_t)b * p.ld;
+    const bool vec = ((p.ld & 7) == 0) && ((((uintptr_t)p.logits) & 15) == 0);
+    const int nvec = vec ? V / 8 : 0;
+    for (int c = tid; c < nvec; c += PICK_THREADS) {
+      const u32x4 v = *(const u32x4*)(row + (size_t)c * 8);
+      float y[8];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float lo = bf16_lo(v[e]), hi = bf16_hi(v[e]);
+        if (pick_better(lo, c * 8 + 2 * e, best, bi)) { best = lo; bi = c * 8 + 2 * e; }
+        if (pick_better(hi, c * 8 + 2 * e + 1, best, bi)) { best = hi; bi = c * 8 + 2 * e + 1; }
+        y[2 * e] = __fdiv_rn(lo, T); y[2 * e + 1] = __fdiv_rn(hi, T);
+      }
+      *(float4*)(rowf + (size_t)c * 8) = make_float4(y[0], y[1], y[2], y[3]);
+      *(float4*)(rowf + (size_t)c * 8 + 4) = make_float4(y[4], y[5], y[6], y[7]);
+    }
+    for (int i = nvec * 8 + tid; i < V; i += PICK_THREADS) {
+      const float x = bf16_bits_to_f32(row[i]);
+      if (pick_better(x, i, best, bi)) { best = x; bi = i; }
+      rowf[i] = __fdiv_rn(x, T);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o);
+    const int oi = __shfl_xor(bi, o);
+    if (pick_better(ov, oi, best, bi)) { best = ov; bi = oi; }
+  }
+  if (lane == 0) { s_v[wave] = best; s_i[wave] = bi; }
+  __syncthreads();                                          // also: the scratch row is written
+  best = s_v[0]; bi = s_i[0];
+#pragma unroll
+  for (int w = 1; w < PICK_THREADS / 64; ++w)
+    if (pick_better(s_v[w], s_i[w], best, bi)) { best = s_v[w]; bi = s_i[w]; }
+  const float ymax = __fdiv_rn(best, T);
+  // rows the draw has nothing to say about take the greedy pick: finished (pad), a NaN / +inf / -inf maximum, top_k == 1
+  const bool greedy = row_done || !(ymax == ymax) || ymax == INFINITY || ymax == -INFINITY || sp.top_k == 1;
+  int tok = bi;
+  if (greedy) {
+    if (probs)
+      for (int i = tid; i < V; i += PICK_THREADS) probs[i] = (!row_done && i == bi) ? 1.f : 0.f;
+  } else {
+    unsigned tau = 0u;
+    if (sp.top_k > 0 && sp.top_k < V)
+      tau = select_threshold<false>(rowf, V, 0u, ymax, (unsigned long long)sp.top_k, 1.f, s_hist, s_w64, s_pick);
+    if (sp.top_p < 1.f) {
+      const unsigned tp = select_threshold<true>(rowf, V, tau, ymax, 0ull, sp.top_p, s_hist, s_w64, s_pick);
+      tau = tp > tau ? tp : tau;
+    }
+    // the draw: thread t owns the groups of four [t * gpt, (t + 1) * gpt); group sums pairwise, chunk sums in order, then the block scan
+    const int ngroups = (V + 3) / 4, gpt = (ngroups + PICK_THREADS - 1) / PICK_THREADS;
+    const int g0 = tid * gpt, g1 = min(g0 + gpt, ngroups);
+    float csum = 0.f;
+    int last = -1;
+    for (int g = g0; g < g1; ++g) {
+      const float4 v = *(const float4*)(rowf + (size_t)g * 4);
+      const float ve[4] = {v.x, v.y, v.z, v.w};
+      float w[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const bool keep = g * 4 + e < V && sample_key(ve[e]) >= tau;
+        w[e] = keep ? expf(ve[e] - ymax) : 0.f;
+        if (keep) last = g * 4 + e;
+      }
+      csum += (w[0] + w[1]) + (w[2] + w[3]);
+    }
+    float incl, total;
+    const float excl = block_excl_scan<float>(csum, s_wf, &incl, &total);
+    const int n = p.step + (p.cache_len != nullptr ? p.cache_len[b] + p.advance - (p.start_len ? p.start_len[b] : 0) : 0);
+    const unsigned x0 = philox4x32_10_word0((unsigned)n, (unsigned)b, sp.off_lo, sp.off_hi, sp.seed_lo, sp.seed_hi);
+    const float target = (float)((((double)(x0 >> 8)) + 0.5) * (1.0 / 16777216.0) * (double)total);
+    if (csum > 0.f && incl > target) atomicMin(&s_owner, tid);
+    if (last >= 0) atomicMax(&s_last, last);
+    __syncthreads();
+    if (tid == s_owner) {
+      float run = 0.f;
+      int pick = -1, lastpos = -1;
+      for (int g = g0; g < g1 && pick < 0; ++g) {
+        const float4 v = *(const float4*)(rowf + (size_t)g * 4);
+        const float ve[4] = {v.x, v.y, v.z, v.w};
+        float w[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w[e] = (g * 4 + e < V && sample_key(ve[e]) >= tau) ? expf(ve[e] - ymax) : 0.f;
+        const float c[4] = {w[0], w[0] + w[1], (w[0] + w[1]) + w[2], (w[0] + w[1]) + (w[2] + w[3])};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          if (!(w[e] > 0.f)) continue;
+          lastpos = g * 4 + e;
+          if (pick < 0 && excl + (run + c[e]) > target) pick = g * 4 + e;
+        }
+        run += c[3];
+      }
+      s_tok = pick >= 0 ? pick : lastpos;
+    }
+    __syncthreads();
+    tok = s_owner == 0x7fffffff ? s_last : s_tok;
+    if (probs) {
+      for (int i = tid; i < V; i += PICK_THREADS) {
+        const float y = rowf[i];
+        probs[i] = sample_key(y) >= tau ? expf(y - ymax) / total : 0.f;
+      }
+    }
+  }
+  pick_finish(p, b, was_done, len0, start0, eos4, tok);
+}
+
+
 static ProcParams proc_params(const void* in, int in_f32, int ld_in, float* out, int ld_out, int V, const int64_t* tokens, int tokens_ld,
                               const int* cache_len, const int* start_len, int step, const unsigned char* done, float penalty, int ngram,
                               int min_len, const int64_t* eos, int n_eos, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress,
@@ -1703,6 +1978,26 @@ int greedy_pick_processed_launch(const void* logits, int B, int V, int ld, const
                                    n_bad_ids);
   AKI_CLEAR_ERR();
   hipLaunchKernelGGL(greedy_pick_processed_kernel, dim3(B), dim3(PICK_THREADS), 0, s, p, q);
+  AKI_LAUNCH_CHECK();
+  return AKI_OK;
+}
+
+int sample_pick_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done, int64_t* ids,
+                       int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at, const void* emb_main,
+                       const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores, int ld_scores, float penalty, int ngram,
+                       int min_len, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids,
+                       const int* bad_off, int n_bad, int n_bad_ids, int step, float temperature, int top_k, float top_p, uint64_t seed,
+                       uint64_t offset, float* probs, int ld_probs, hipStream_t s) {
+  PickParams p = {(const bf16_t*)logits, B, V, ld, eos, n_eos, pad, done, ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
+                  (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out, step};
+  const ProcParams q = proc_params(logits, 0, ld, scores, ld_scores, V, tokens, tokens_ld, cache_len, start_len, step + (cache_len ? advance : 0),
+                                   done, penalty, ngram, min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off,
+                                   n_bad, n_bad_ids);
+  const bool processed = penalty != 1.f || ngram > 0 || n_bad > 0 || (min_len > 0 && n_eos > 0) || n_suppress > 0 || n_begin > 0;
+  const SampleParams sp = {temperature, top_k, top_p, (unsigned)seed, (unsigned)(seed >> 32), (unsigned)offset, (unsigned)(offset >> 32),
+                           probs, ld_probs, processed ? 1 : 0};
+  AKI_CLEAR_ERR();
+  hipLaunchKernelGGL(sample_pick_kernel, dim3(B), dim3(PICK_THREADS), 0, s, p, q, sp);
   AKI_LAUNCH_CHECK();
   return AKI_OK;
 }

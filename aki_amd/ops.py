@@ -742,6 +742,90 @@ def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
     return next_ids
 
 
+class DeviceGenerator:
+    """The random state of the device sampler (`generate(..., do_sample=True, generator=DeviceGenerator(seed))`, ops.sample_pick): a 64-bit
+    `seed` (the Philox key) and an `offset` that every `generate` call takes and bumps by one.  A draw depends on (seed, offset, generated-token
+    index, row) only - never on the batch a sample sits in, nor on how often a step is replayed."""
+
+    def __init__(self, seed: int = 0):
+        self.manual_seed(seed)
+
+    def manual_seed(self, seed: int) -> "DeviceGenerator":
+        self.seed, self.offset = int(seed) & 0xFFFFFFFFFFFFFFFF, 0
+        return self
+
+    def next_offset(self) -> int:
+        o = self.offset
+        self.offset += 1
+        return o
+
+
+def sample_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int = 0, eos_ids: Optional[torch.Tensor] = None,
+                done: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, cache_len: Optional[torch.Tensor] = None,
+                start_len: Optional[torch.Tensor] = None, advance: bool = False, done_at: Optional[torch.Tensor] = None,
+                embed=None, next_embeds: Optional[torch.Tensor] = None, processors: Optional[LogitsProcessors] = None, step: int = 0,
+                temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, offset: int = 0,
+                probs_out: Optional[torch.Tensor] = None, scores: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ops.greedy_pick's sibling for `do_sample=True`, one launch (aki_sample_pick): processors, temperature, top-k, top-p and one
+    counter-based draw per row, then the same bookkeeping and embedding gather.  The draw of row b is u = Philox4x32-10(key = seed,
+    counter = (n, b, offset))[0], n = step + (cache_len[b] + advance - start_len[b] when cache_len is given) - the index tokens[b, n] is
+    written at.  probs_out: optional f32 [B, V], the filtered distribution the draw was made from.  scores: the f32 [B, >= V] scratch
+    (default: the processors' own, or one kept per shape).  Capturable: no host value is read."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise AkiError("sample_pick takes bf16 logits [B, V] with unit column stride")
+    B, V = logits.shape
+    for t_, dt in ((next_ids, torch.int64), (tokens, torch.int64), (eos_ids, torch.int64), (done, torch.uint8), (cache_len, torch.int32),
+                   (start_len, torch.int32), (done_at, torch.int32), (probs_out, torch.float32), (scores, torch.float32)):
+        if t_ is not None and (t_.dtype != dt or not t_.is_contiguous() or t_.device != logits.device):
+            raise AkiError(f"sample_pick: a {dt} contiguous tensor on {logits.device} is expected, got {t_.dtype} {tuple(t_.shape)}")
+    if tokens is not None and (tokens.dim() != 2 or tokens.shape[0] != B):
+        raise AkiError("sample_pick: tokens is [B, max_new_tokens]")
+    if probs_out is not None and tuple(probs_out.shape) != (B, V):
+        raise AkiError("sample_pick: probs_out is f32 [B, V]")
+    if not (float(temperature) > 0.0) or not (0.0 < float(top_p) <= 1.0) or int(top_k) < 0 or int(step) < 0:
+        raise ValueError(f"sample_pick: temperature > 0, 0 < top_p <= 1, top_k >= 0 and step >= 0 are expected, got {temperature}, {top_p}, {top_k}, {step}")
+    common = (_ptr(logits), B, V, logits.stride(0), _ptr(eos_ids), 0 if eos_ids is None else eos_ids.numel(), int(pad_token_id), _ptr(done),
+              _ptr(next_ids), _ptr(tokens), 0 if tokens is None else tokens.shape[1], _ptr(cache_len), _ptr(start_len), 1 if advance else 0,
+              _ptr(done_at))
+    emb = (None, None, 0, 0, 0, None)
+    if embed is not None:
+        w, extra, max_orig = embed
+        d = w.shape[1]
+        for t_ in (w, extra, next_embeds):
+            if t_ is not None and (t_.dtype != torch.bfloat16 or not t_.is_contiguous() or t_.device != logits.device or t_.shape[-1] != d):
+                raise AkiError("sample_pick: embedding tables and next_embeds are contiguous bf16 [*, d] on the logits' device")
+        if next_embeds is None or next_embeds.numel() != B * d:
+            raise AkiError("sample_pick: next_embeds is [B, d]")
+        if w.shape[0] <= max_orig:
+            raise AkiError("sample_pick: the embedding table has fewer than max_original_id + 1 rows")
+        emb = (_ptr(w), _ptr(extra), int(max_orig), 0 if extra is None else extra.shape[0], d, _ptr(next_embeds))
+    active = processors is not None and processors.active
+    if active and processors.V != V:
+        raise AkiError(f"sample_pick: the processors were built for V = {processors.V}, the logits have {V} columns")
+    if V > L.AKI_LOGITS_PROCESS_MAX_V:
+        raise AkiError(f"sample_pick: a vocabulary of {V} is above {L.AKI_LOGITS_PROCESS_MAX_V}")
+    if scores is None:
+        scores = processors.scores(B, logits.device) if active else _sample_scratch(B, V, logits.device)
+    if scores.dim() != 2 or scores.shape[0] != B or scores.shape[1] < V:
+        raise AkiError("sample_pick: scores is f32 [B, >= V]")
+    head, tail = processors._tail() if active else ((1.0, 0, 0), (None, 0, None, 0, None, None, 0, 0))
+    L.check(L.load().aki_sample_pick(*common, *emb, _ptr(scores), scores.stride(0), *head, *tail, int(step), float(temperature), int(top_k),
+                                     float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _ptr(probs_out),
+                                     0 if probs_out is None else probs_out.stride(0), _stream()), "aki_sample_pick")
+    return next_ids
+
+
+_SAMPLE_SCRATCH = {}
+
+
+def _sample_scratch(B: int, V: int, dev) -> torch.Tensor:
+    """The sampler's f32 [B, V rounded up to 4] row scratch when no processors own one (kept per shape: a captured graph holds its address)."""
+    key = (B, V, str(dev))
+    if key not in _SAMPLE_SCRATCH:
+        _SAMPLE_SCRATCH[key] = torch.empty((B, (V + 3) // 4 * 4), dtype=torch.float32, device=dev)
+    return _SAMPLE_SCRATCH[key]
+
+
 SKINNY_NORM_FUSED = True          # tools (decode_bench.py --norm-launch): False = the RMSNorm of 2-8 row decode GEMMs as a launch of its own
 
 

@@ -764,6 +764,30 @@ int aki_greedy_pick_processed(const void* logits, int32_t B, int32_t V, int64_t 
                               const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
                               int32_t n_bad, int32_t n_bad_ids, void* stream);
 
+/* aki_sample_pick - the `do_sample` step of HF `generate` with aki_greedy_pick_processed's bookkeeping, in ONE launch (one workgroup per
+ * row): processors (neutral arguments: none) -> y = x / temperature (correctly rounded f32) -> top-k -> top-p -> softmax -> one draw.
+ *   top_k        0 < top_k < V: keep y >= the top_k-th largest y, ties at the threshold all kept (TopKLogitsWarper); 0 or >= V: off
+ *   top_p        < 1: among what top-k kept, keep token i iff the softmax mass of the tokens with strictly larger y is < top_p
+ *                (TopPLogitsWarper's set; equal values stay together, the maximum is always kept); 1: off
+ *   draw         w = exp(y - max) over the kept set, C = its inclusive cumulative sum in index order; the token is the smallest kept i
+ *                with C_i > u * C_total (the last kept index if rounding leaves none), u = ((x0 >> 8) + 0.5) * 2^-24, x0 = the first word
+ *                of Philox4x32-10 with key (seed lo, seed hi) and counter (n, b, offset lo, offset hi)
+ *   n            = step + (cache_len ? cache_len[b] + advance - start_len[b] : 0): the generated-token index, which is also where the pick
+ *                writes tokens[b, n] and what the processors take as the history length.  A replayed graph or a rewind redraws the same u.
+ * Rows with done[b] take pad_token_id; a row whose maximum is NaN or +-inf, and every row when top_k == 1, takes aki_greedy_pick's id.
+ * Both filters are exact threshold selections (radix select on order-preserving keys, 64-bit integer histograms): no sort, and the
+ * same inputs give the same bits on every run.  scores: f32 scratch [B, ld_scores] as in aki_greedy_pick_processed, always needed (it
+ * holds y).  probs_out (may be NULL): f32 [B, ld_probs], the normalised filtered distribution the draw was made from, 0 for removed
+ * tokens; one-hot for the greedy rows, all 0 for finished rows.  embed_weight NULL: no embedding row.  V <= AKI_LOGITS_PROCESS_MAX_V. */
+int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                    uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                    int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                    int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                    int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                    const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                    int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                    uint64_t offset, float* probs_out, int64_t ld_probs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,11 @@ first token (vision tower + connector + splice + MMA prefill into the KV cache) 
 each, the greedy pick inside it), with bf16 and with e4m3 weights.  No EOS (random weights never emit one on cue): all 256 tokens.
 --repetition-penalty / --no-repeat-ngram: every round also runs with those logits processors on (the processed greedy pick) and reports the
 per-token cost they add, measured on the same box in the same process.
-    python tools/generate_bench.py [--new 256] [--fp8] [--txt 64] [--repetition-penalty 1.2] [--no-repeat-ngram 3]"""
+--sample: every round also runs `do_sample=True` twice in the same process - with a torch.Generator (the `sample_next` loop) and with a
+DeviceGenerator (ops.sample_pick inside the greedy loop) - and reports both per-token times and the device sampler's excess over greedy.
+--batch B: B copies of the sample (the batched decode path; a hipGraph replay per token).
+    python tools/generate_bench.py [--new 256] [--fp8] [--txt 64] [--repetition-penalty 1.2] [--no-repeat-ngram 3]
+                                   [--sample --temperature 0.8 --top-k 50 --top-p 0.9] [--batch 8]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -19,6 +23,11 @@ def main():
     ap.add_argument("--txt", type=int, default=512, help="prompt tokens: 512 = the headline prompt (L = 655), 64 = BASELINE configs[0] (L = 207)")
     ap.add_argument("--repetition-penalty", type=float, default=1.0)
     ap.add_argument("--no-repeat-ngram", type=int, default=0)
+    ap.add_argument("--sample", action="store_true")
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=0)
+    ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--batch", type=int, default=1)
     a = ap.parse_args()
     proc_kw = {}
     if a.repetition_penalty != 1.0:
@@ -33,13 +42,15 @@ def main():
     if a.fp8:
         model.lang_model.enable_fp8()
     vx, ids, am = bench.synth_batch(1, dev, torch.bfloat16, model.media_token_id, seed=1000)
+    if a.batch > 1:
+        vx, ids, am = vx.repeat(a.batch, 1, 1, 1, 1, 1), ids.repeat(a.batch, 1), am.repeat(a.batch, 1)
 
     host = [0.0]
 
     def run(n_new, **kw):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        toks = model.generate(vx, ids, attention_mask=am, max_new_tokens=n_new, do_sample=False, eos_token_id=[], **kw)
+        toks = model.generate(vx, ids, attention_mask=am, max_new_tokens=n_new, eos_token_id=[], **dict({"do_sample": False}, **kw))
         host[0] = time.perf_counter() - t0          # the call has returned; with one new token and no EOS set nothing in it synchronises
         torch.cuda.synchronize()
         return time.perf_counter() - t0, toks
@@ -47,15 +58,24 @@ def main():
     run(16)                                   # warm-up: allocator, lazily-built folds, the graph capture path
     if proc_kw:
         run(16, **proc_kw)
+    sample_kw = dict(do_sample=True, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
+    if a.sample:
+        import aki_amd
+        run(16, generator=torch.Generator(device=dev).manual_seed(0), **sample_kw)
+        run(16, generator=aki_amd.DeviceGenerator(0), **sample_kw)
     res = {"prompt_tokens_lm_stream": bench.N_TXT - 1 + bench.NV, "new_tokens": a.new, "fp8": bool(a.fp8), "rounds": []}
     if proc_kw:
         res["processors"] = proc_kw
-    ref = ref_p = None
+    if a.sample:
+        res["sampling"] = dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
+    if a.batch > 1:
+        res["batch"] = a.batch
+    ref = ref_p = ref_s = None
     for _ in range(a.rounds):
         t1, _ = run(1)                        # prefill + first token
         h1 = host[0]
         tn, toks = run(a.new)
-        assert toks.shape == (1, a.new)
+        assert toks.shape == (a.batch, a.new)
         if ref is None:
             ref = toks.clone()
         assert torch.equal(ref, toks), "generate is not reproducible from call to call"
@@ -73,6 +93,23 @@ def main():
             r = res["rounds"][-1]
             r["processed_ms_per_new_token_after_the_first"] = round(per_p, 4)
             r["processors_added_us_per_token"] = round((per_p - r["ms_per_new_token_after_the_first"]) * 1e3, 2)
+        if a.sample:
+            r = res["rounds"][-1]
+            for leg, gen in (("torch_generator", lambda: torch.Generator(device=dev).manual_seed(0)), ("device_generator", lambda: aki_amd.DeviceGenerator(0))):
+                t1s, _ = run(1, generator=gen(), **sample_kw)
+                tns, toks_s = run(a.new, generator=gen(), **sample_kw)
+                assert toks_s.shape == (a.batch, a.new)
+                r[f"sample_{leg}_ms_per_new_token_after_the_first"] = round((tns - t1s) * 1e3 / (a.new - 1), 4)
+            if ref_s is None:
+                ref_s = toks_s.clone()
+            assert torch.equal(ref_s, toks_s), "the device sampler is not reproducible from call to call"
+            r["device_sampler_excess_over_greedy_us_per_token"] = round(
+                (r["sample_device_generator_ms_per_new_token_after_the_first"] - r["ms_per_new_token_after_the_first"]) * 1e3, 2)
+            r["device_sampler_faster_than_torch_path"] = bool(
+                r["sample_device_generator_ms_per_new_token_after_the_first"] < r["sample_torch_generator_ms_per_new_token_after_the_first"])
+    if a.sample:
+        ex = sorted(r["device_sampler_excess_over_greedy_us_per_token"] for r in res["rounds"])
+        res["device_sampler_excess_over_greedy_us_per_token_median"] = ex[len(ex) // 2]
     if proc_kw:
         add = sorted(r["processors_added_us_per_token"] for r in res["rounds"])
         res["processors_added_us_per_token_median"] = add[len(add) // 2]

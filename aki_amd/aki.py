@@ -212,7 +212,11 @@ class AKI(VLMWithLanguageStream):
         src/aki.py:160-207): greedy (default), sampling (`do_sample=True` with `temperature`, `top_k`, `top_p`, optional
         `generator`; a `aki_amd.DeviceGenerator(seed)` there selects the device sampler - ops.sample_pick, one launch per token inside the
         same three-launch / replayed-graph loop as greedy, draws that depend on (seed, call, token index, row) and not on the batch -
-        while None or a `torch.Generator` keeps the `sample_next` path), beam search (`num_beams=K`, `length_penalty`, `early_stopping`; one returned sequence per sample).
+        while None or a `torch.Generator` keeps the `sample_next` path; `num_return_sequences=N` with sampling returns [B*N, <= max_new_tokens]
+        in HF order, row b*N + j being continuation j of sample b: one prefill, token 0 of each row drawn from its sample's prefill logits, then
+        the same loops at batch B*N - the device sampler's row index is b*N + j.  The prompt's K/V rows are replicated N times (select_rows)
+        unless `lang_model.share_prompt_kv = True`, with which the N rows of a sample read ONE copy of them (AkiKVCache.share_prefix +
+        ops.decode_attn_group; bf16 model and cache, head_dim 96, more than one new token - anything else stays replicated); without sampling it raises ValueError, with beams NotImplementedError), beam search (`num_beams=K`, `length_penalty`, `early_stopping`; one returned sequence per sample).
         Logits processors, applied on the device in every mode and in HF's order (ops.LogitsProcessors): `repetition_penalty`,
         `no_repeat_ngram_size`, `bad_words_ids`, `min_length` / `min_new_tokens` (eos ids banned until that many tokens are
         generated), `suppress_tokens`, `begin_suppress_tokens`.  As in HF `generate` with inputs_embeds only, they see the generated
@@ -235,10 +239,15 @@ class AKI(VLMWithLanguageStream):
                 raise ValueError("generator=DeviceGenerator(...) selects the device sampler: it needs do_sample=True and num_beams=1")
             if not 0.0 < top_p <= 1.0 or top_k < 0:
                 raise ValueError("the device sampler takes 0 < top_p <= 1 and top_k >= 0")
-        if int(kwargs.pop("num_return_sequences", 1)) != 1:
-            raise NotImplementedError("num_return_sequences > 1")
+        n_ret = int(kwargs.pop("num_return_sequences", 1))
+        if n_ret < 1:
+            raise ValueError("num_return_sequences must be at least 1")
+        if n_ret > 1 and num_beams > 1:
+            raise NotImplementedError("num_return_sequences > 1 with beam search")
         if num_beams < 1 or (num_beams > 1 and do_sample):
             raise NotImplementedError("beam-sample decoding (num_beams > 1 with do_sample=True)")
+        if n_ret > 1 and not do_sample:
+            raise ValueError("num_return_sequences > 1 needs do_sample=True: greedy decoding returns one sequence per sample")
         if do_sample and temperature <= 0:
             raise ValueError("temperature must be positive")
         if past_key_values is not None:
@@ -277,6 +286,17 @@ class AKI(VLMWithLanguageStream):
             tokens = self._beam_search(cache, logits, num_beams, max_new_tokens, eos_ids, pad_id, length_penalty, early_stopping, proc)
             self._post_forward_hook()
             return tokens
+        if n_ret > 1:
+            # N continuations per sample: one prefill, then row b * N + j continues sample b.  Token 0 of every row is drawn from its
+            # sample's prefill logits; with lang_model.share_prompt_kv = True the rows of a sample read ONE copy of its prompt K/V where a
+            # grouped cache is possible (a bf16 model and cache, head_dim 96), otherwise the prompt rows are replicated.
+            from .phi3 import AkiKVCache
+            logits = logits.repeat_interleave(n_ret, dim=0)
+            if getattr(self.lang_model, "share_prompt_kv", False) and max_new_tokens > 1 and AkiKVCache.can_share_prefix(cache):
+                cache.share_prefix(n_ret)
+            else:
+                cache.select_rows(torch.arange(B, device=logits.device).repeat_interleave(n_ret))
+            B = B * n_ret
         tokens = torch.full((B, max_new_tokens), pad_id, dtype=torch.long, device=lang_x.device)
         done = torch.zeros(B, dtype=torch.bool, device=lang_x.device)
         eos_t = torch.tensor(sorted(eos_ids), dtype=torch.long, device=lang_x.device) if eos_ids else None

@@ -30,6 +30,10 @@ int kv_cache_quant_fp8_launch(const void* src, int src_cap, void* dst, float* sc
 int decode_attn_split_fp8kv_launch(const void* qkv, const float* cos, const float* sin, const int* len, void* kc, void* vc, float* ks, float* vs,
                                    void* o, const uint64_t* vbits, int nwords, int B, int H, int cap, int max_keys, float scale, void* ws,
                                    size_t ws_bytes, hipStream_t s);
+size_t decode_attn_group_ws_bytes(int B0, int N, int H, int pcap, int scap);
+int decode_attn_group_launch(const void* qkv, const float* cos, const float* sin, const int* len, const int* plen, const void* kp,
+                             const void* vp, void* ks, void* vs, void* o, const uint64_t* vbits, int nwords, int B0, int N, int H, int pcap,
+                             int scap, int max_pkeys, int max_skeys, float scale, void* ws, size_t ws_bytes, hipStream_t s);
 size_t decode_chain_ws_bytes(int n_layers, int d, int H, int F, int cap);
 size_t decode_chain_err_offset(int n_layers, int H);
 size_t decode_chain_b_ws_bytes(int n_layers, int d, int H, int F, int cap, int B);
@@ -458,6 +462,28 @@ int aki_decode_attn_fused_fp8kv_fwd(const void* qkv, const float* cos, const flo
   if (((uintptr_t)k_cache & 15) || ((uintptr_t)v_cache & 15) || ((uintptr_t)o & 15)) return AKI_ERR_ALIGNMENT;
   return decode_attn_split_fp8kv_launch(qkv, cos, sin, cache_len, k_cache, v_cache, k_scale, v_scale, o, col_valid_bits, nwords, B, H, capacity,
                                         max_keys, scale, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t aki_decode_attn_group_workspace_bytes(int32_t B0, int32_t N, int32_t H, int32_t Dh, int32_t prefix_capacity, int32_t suffix_capacity) {
+  if (B0 <= 0 || N <= 0 || H <= 0 || Dh != 96 || prefix_capacity <= 0 || suffix_capacity <= 0) return 0;
+  return decode_attn_group_ws_bytes(B0, N, H, prefix_capacity, suffix_capacity);
+}
+
+int aki_decode_attn_group_fwd(const void* qkv, const float* cos, const float* sin, const int32_t* cache_len, const int32_t* prefix_len,
+                              const void* k_prefix, const void* v_prefix, void* k_suffix, void* v_suffix, void* o,
+                              const uint64_t* col_valid_bits, int32_t nwords, int32_t B0, int32_t N, int32_t H, int32_t Dh,
+                              int32_t prefix_capacity, int32_t suffix_capacity, int32_t max_prefix_keys, int32_t max_suffix_keys, float scale,
+                              int32_t dtype, void* ws, size_t ws_bytes, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(qkv && cos && sin && cache_len && prefix_len && k_prefix && v_prefix && k_suffix && v_suffix && o);
+  AKI_CHECK_ARG(B0 > 0 && N > 0 && H > 0 && Dh > 0 && prefix_capacity > 0 && suffix_capacity > 0 && scale > 0.f);
+  AKI_CHECK_ARG(!col_valid_bits || nwords > 0);
+  if (Dh != 96 || dtype != AKI_DT_BF16) return AKI_ERR_UNSUPPORTED;
+  if (((uintptr_t)k_prefix & 15) || ((uintptr_t)v_prefix & 15) || ((uintptr_t)k_suffix & 15) || ((uintptr_t)v_suffix & 15) || ((uintptr_t)o & 15))
+    return AKI_ERR_ALIGNMENT;
+  return decode_attn_group_launch(qkv, cos, sin, cache_len, prefix_len, k_prefix, v_prefix, k_suffix, v_suffix, o, col_valid_bits, nwords, B0, N,
+                                  H, prefix_capacity, suffix_capacity, max_prefix_keys, max_suffix_keys, scale, ws, ws_bytes,
+                                  (hipStream_t)stream);
 }
 
 int aki_decode_linear_fwd(const aki_linear_args* a, const void* rms_weight, float rms_eps, void* stream) {

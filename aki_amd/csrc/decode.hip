@@ -9,6 +9,7 @@
 //   rope_append_kernel  split the fused qkv row, rotate q/k at the token's position, append k/v to the KV cache
 //   decode_attn_kernel  one query per (batch, head) against the cache: keys are spread over the 256 lanes, each
 //                       lane keeps an online-softmax partial (m, l, acc[Dh]) that is merged through LDS
+//   decode_attn_group_kernel  the fused split-KV step for N sampled rows per prompt over one shared copy of the prompt's K/V
 //   decode_attn_split_fp8kv_kernel  the fused split-KV step on an opt-in e4m3 KV cache (one f32 scale per cached head row),
 //                       with kv_cache_quant_fp8_kernel converting the prefill's bf16 rows into it
 // After the prefill the reference switches to an all-ones 2-D mask (src/aki_generation.py:58-62), i.e. plain causal
@@ -1377,6 +1378,409 @@ int decode_attn_split_fp8kv_launch(const void* qkv, const float* cos, const floa
   const dim3 grid(S, B * H), block(64);
   AKI_CLEAR_ERR();
   hipLaunchKernelGGL(decode_attn_split_fp8kv_kernel, grid, block, 0, s, p);
+  AKI_LAUNCH_CHECK();
+  return AKI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Grouped split-KV decode attention (bf16, Dh = 96): N returned rows per prompt sample over ONE copy of the prompt's K/V.
+//   prefix  kp / vp [B0][H][pcap][96]    the prompt's rows as the prefill wrote them; read-only here
+//   suffix  ks / vs [B0*N][H][scap][96]  one slab per returned row: the tokens decoded so far
+// Row r belongs to sample b = r / N.  Its keys are prefix rows [0, plen[b]) - filtered by the sample's valid bits - followed by suffix
+// rows [0, len[r] - plen[b]]; the last of those is the new token, rotated at position len[r] and appended by the item that owns it
+// (decode_attn_split_kernel<true>'s rule, stale-row care included).
+// Items (one wave each):
+//   prefix item (sample, head, key split, chunk of <= 16 rows): every 64-key K/V tile is loaded ONCE and serves all rows of the chunk -
+//               their rotated q's sit in LDS, one (m, l, acc) state per row lives in registers.  The K rows of the next tile are
+//               requested once the scores of this one are done, its V rows once the PV products are: the loads of a tile fly under
+//               the arithmetic of the one before it (with <= 16 queries per K byte the item is no longer purely HBM-bound).
+//   suffix item (row, head, key split): the fused kernel's item on the row's own slab.
+// Every item leaves (m, l, acc[96]) per row in the workspace; the counter of a (row, head) expects Sp + Ss arrivals and the last arriver
+// merges: prefix splits in order, then suffix splits in order (each segment strided over five lane groups on its own, so trailing
+// empty items of either segment - a captured step's larger grid - fold exactly and the bits do not depend on the grid).
+// ------------------------------------------------------------------------------------------------------------
+struct DecodeGroupParams {
+  const bf16_t* qkv;                     // [B0*N][3*H*96], un-rotated
+  const float* cos; const float* sin;    // [positions][96]
+  const int* len;                        // cache_len[r]: keys before the new token = its RoPE position
+  const int* plen;                       // prefix_len[b]
+  const bf16_t* kp; const bf16_t* vp;
+  bf16_t* ks; bf16_t* vs;
+  bf16_t* o;                             // [B0*N][H*96]
+  const uint64_t* vbits; int nwords;     // [B0][nwords]
+  unsigned* cnt; float* part;            // counters [B0*N*H], partials [B0*N*H][Sp + Ss][DEC_PSTRIDE]
+  int N, H, pcap, scap, Sp, Tp, Ss, Ts, NC; float scale;
+};
+
+#define AKI_ST_AGENT(ptr, v) __hip_atomic_store((ptr), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define AKI_LD_AGENT(ptr) __hip_atomic_load((ptr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+
+// q (and, for the owner of the new token, k) of one head rotated at table row `pos`: lane < 48 handles dims lane and lane + 48
+__device__ __forceinline__ void group_rotate(const bf16_t* x, const float* cos, const float* sin, int pos, int lane, __bf16& r0, __bf16& r1) {
+  const float c0 = cos[(size_t)pos * 96 + lane], c1 = cos[(size_t)pos * 96 + lane + 48];
+  const float s0 = sin[(size_t)pos * 96 + lane], s1 = sin[(size_t)pos * 96 + lane + 48];
+  const float x0 = bf16_bits_to_f32(x[lane]), x1 = bf16_bits_to_f32(x[lane + 48]);
+  r0 = (__bf16)(x0 * c0 - x1 * s0);
+  r1 = (__bf16)(x1 * c1 + x0 * s1);
+}
+
+// nothing moves across this point, neither in the optimiser (memory operations) nor in the machine scheduler (anything)
+__device__ __forceinline__ void group_order() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// a wave-uniform value moved to a scalar register
+__device__ __forceinline__ float uniform_f32(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+
+// The last arriver of (row, head) = rh: all Sp + Ss partials -> o.  The whole wave calls it.
+__device__ __forceinline__ void group_merge(const DecodeGroupParams& p, int rh, int lane, float (*s_mg)[12][10]) {
+  const float* pp = p.part + (size_t)rh * (p.Sp + p.Ss) * DEC_PSTRIDE;
+  const int sl = lane / 12, ch = lane - sl * 12;
+  float gm = -INFINITY, lt = 0.f, o8[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o8[e] = 0.f;
+  if (sl < 5) {
+    auto fold = [&](const float* ps) {
+      const float ms = AKI_LD_AGENT(ps), ls = AKI_LD_AGENT(ps + 1);
+      float a[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) a[e] = AKI_LD_AGENT(ps + 8 + ch * 8 + e);
+      const float mn = fmaxf(gm, ms);
+      const float f0 = gm == -INFINITY ? 0.f : __expf(gm - mn), f1 = ms == -INFINITY ? 0.f : __expf(ms - mn);
+      lt = lt * f0 + ls * f1;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o8[e] = o8[e] * f0 + a[e] * f1;
+      gm = mn;
+    };
+    for (int s2 = sl; s2 < p.Sp; s2 += 5) fold(pp + (size_t)s2 * DEC_PSTRIDE);
+    for (int s2 = sl; s2 < p.Ss; s2 += 5) fold(pp + (size_t)(p.Sp + s2) * DEC_PSTRIDE);
+    s_mg[sl][ch][0] = gm;
+    s_mg[sl][ch][1] = lt;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s_mg[sl][ch][2 + e] = o8[e];
+  }
+  __syncthreads();
+  if (lane < 12) {
+    float sv[50];
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+#pragma unroll
+      for (int e = 0; e < 10; ++e) sv[q * 10 + e] = s_mg[q][lane][e];
+    lds_fold_ready(sv);
+    float M5 = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) M5 = fmaxf(M5, sv[q * 10]);
+    lt = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o8[e] = 0.f;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      const float mq = sv[q * 10];
+      const float f = mq == -INFINITY ? 0.f : __expf(mq - M5);
+      lt += sv[q * 10 + 1] * f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o8[e] += sv[q * 10 + 2 + e] * f;
+    }
+    const float inv = lt > 0.f ? 1.f / lt : 0.f;
+    u32x4 ov;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ov[e] = pack_bf16x2(o8[2 * e] * inv, o8[2 * e + 1] * inv);
+    *(u32x4*)(p.o + (size_t)rh * 96 + lane * 8) = ov;
+  }
+  __syncthreads();                                     // s_mg is free again: a prefix item may merge several rows
+  if (lane == 0) AKI_ST_AGENT(p.cnt + rh, 0u);          // re-armed for the next launch
+}
+
+// rows r0 .. r0 + nr - 1 (nr <= NR) of sample b against keys [split * Tp * 64, ...) of the sample's prefix
+template <int NR>
+__device__ __forceinline__ void group_prefix_item(const DecodeGroupParams& p, int b, int h, int split, int r0, int nr, int lane, bf16_t* s_q,
+                                                  float* s_p, float (*s_mg)[12][10]) {
+  const int g = lane >> 4, i16 = lane & 15, S = p.Sp + p.Ss;
+  const int plen = min(p.plen[b], p.pcap);
+  const int k_begin = split * p.Tp * 64;
+  const int k_end = min(plen, k_begin + p.Tp * 64);
+  float m[NR], l[NR], acc[NR][8];
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    m[j] = -INFINITY;
+    l[j] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
+  }
+  if (k_begin < k_end) {
+    const bf16_t* kb = p.kp + ((size_t)b * p.H + h) * p.pcap * 96;
+    const bf16_t* vb = p.vp + ((size_t)b * p.H + h) * p.pcap * 96;
+    u32x4 kr[12], vr[16];
+    auto issue_k = [&](int base) {
+      const bf16_t* krow = kb + (size_t)min(base + lane, k_end - 1) * 96;       // clamped rows carry probability 0
+#pragma unroll
+      for (int i = 0; i < 12; ++i) kr[i] = *(const u32x4*)(krow + i * 8);
+    };
+    auto issue_v = [&](int base) {
+#pragma unroll
+      for (int t2 = 0; t2 < 16; ++t2) {
+        const int r = min(base + 4 * t2 + g, k_end - 1);
+        vr[t2] = *(const u32x4*)(vb + (size_t)r * 96 + min(i16, 11) * 8);
+      }
+    };
+    issue_k(k_begin);                                    // in flight while the q's are rotated
+    issue_v(k_begin);
+    if (lane < 48) {
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        __bf16 q0 = (__bf16)0.f, q1 = (__bf16)0.f;       // rows past the chunk: q = 0, finite scores that nobody stores
+        if (j < nr) group_rotate(p.qkv + (size_t)(r0 + j) * 3 * p.H * 96 + h * 96, p.cos, p.sin, p.len[r0 + j], lane, q0, q1);
+        ((__bf16*)s_q)[j * 96 + lane] = q0;
+        ((__bf16*)s_q)[j * 96 + lane + 48] = q1;
+      }
+    }
+    __syncthreads();
+    for (int t = 0; t < p.Tp; ++t) {
+      const int base = k_begin + t * 64;
+      if (base >= k_end) break;
+      const bool more = base + 64 < k_end;
+      bool ok = base + lane < k_end;
+      if (p.vbits && (base >> 6) < p.nwords) ok = ok && ((p.vbits[(size_t)b * p.nwords + (base >> 6)] >> lane) & 1ull);
+      // scores, row by row.  The compiler barriers keep the LDS reads of a row (q: 48 VGPRs) from being gathered ahead of the rows before
+      // it - hoisted, the q's (NR * 48 VGPRs) push the row states into scratch.  m and l are wave-uniform and live in scalar registers.
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        group_order();
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) s = dot8_bf16(kr[i], *(const u32x4*)(s_q + j * 96 + i * 8), s);
+        s = ok ? s * p.scale : -INFINITY;
+        const float mn = uniform_f32(fmaxf(m[j], wave_max(s)));
+        float pj = 0.f;
+        if (mn != -INFINITY) {                           // wave-uniform
+          const float a = __expf(m[j] - mn);
+          pj = ok ? __expf(s - mn) : 0.f;
+          l[j] = uniform_f32(l[j] * a + wave_sum(pj));
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[j][e] *= a;
+          m[j] = mn;
+        }
+        s_p[lane * NR + j] = pj;                         // probabilities meet the PV phase through LDS: [key][row]
+      }
+      group_order();
+      if (more) issue_k(base + 64);                      // the K registers are free: the next tile's rows fly under the PV products
+      __syncthreads();
+#pragma unroll
+      for (int t2 = 0; t2 < 16; ++t2) {
+        group_order();
+        u32x4 vt = vr[t2];
+        asm volatile("" : "+v"(vt));                     // widened row by row, once for all the chunk's rows
+        float vf[8], w[NR];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          vf[2 * e] = bf16_lo(vt[e]);
+          vf[2 * e + 1] = bf16_hi(vt[e]);
+        }
+#pragma unroll
+        for (int j = 0; j < NR; ++j) w[j] = s_p[(4 * t2 + g) * NR + j];        // one key's weights for all rows: NR / 4 16-byte reads
+#pragma unroll
+        for (int j = 0; j < NR; ++j)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[j][e] = __builtin_fmaf(w[j], vf[e], acc[j][e]);
+      }
+      group_order();
+      __syncthreads();                                   // s_p is free for the next tile
+      if (more) issue_v(base + 64);
+    }
+#pragma unroll
+    for (int j = 0; j < NR; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        acc[j][e] += __shfl_xor(acc[j][e], 16);
+        acc[j][e] += __shfl_xor(acc[j][e], 32);
+      }
+  }
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    if (j < nr) {
+      float* part = p.part + (((size_t)(r0 + j) * p.H + h) * S + split) * DEC_PSTRIDE;
+      if (lane == 0) { AKI_ST_AGENT(part, m[j]); AKI_ST_AGENT(part + 1, l[j]); }
+      if (lane < 12) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) AKI_ST_AGENT(part + 8 + lane * 8 + e, acc[j][e]);
+      }
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the stores above have reached the coherence point
+  unsigned prev = 0;
+  if (lane < nr) prev = __hip_atomic_fetch_add(p.cnt + (size_t)(r0 + lane) * p.H + h, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  unsigned long long last = __ballot(lane < nr && prev == (unsigned)(S - 1));
+  group_order();
+  while (last) {                                         // wave-uniform: the rows this item was the last to reach
+    const int j = __builtin_ctzll(last);
+    last &= last - 1;
+    group_merge(p, (r0 + j) * p.H + h, lane, s_mg);
+  }
+}
+
+// row r of sample b against keys [split * Ts * 64, ...) of its own suffix slab: decode_attn_split_kernel<true>'s item
+__device__ __forceinline__ void group_suffix_item(const DecodeGroupParams& p, int b, int r, int h, int split, int lane, bf16_t* s_q, bf16_t* s_k,
+                                                  bf16_t* s_v, float (*s_mg)[12][10]) {
+  const int g = lane >> 4, i16 = lane & 15, S = p.Sp + p.Ss, rh = r * p.H + h;
+  const int ln = p.len[r];                               // RoPE position
+  const int la = ln - p.plen[b];                         // append row in the suffix slab
+  const int n = (la >= 0 && la < p.scap) ? la + 1 : 0;   // a length outside the slab touches no memory: the row sees its prefix only
+  const int k_begin = split * p.Ts * 64;
+  const int k_end = min(n, k_begin + p.Ts * 64);
+  bf16_t* kb = p.ks + (size_t)rh * p.scap * 96;
+  bf16_t* vb = p.vs + (size_t)rh * p.scap * 96;
+  float m = -INFINITY, l = 0.f, acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+  if (k_begin < k_end) {
+    const bool owner = la >= k_begin;                    // la < k_end holds by construction (k_end <= la + 1)
+    u32x4 kr[12], vr[16];
+    auto issue_tile = [&](int base) {
+      const bf16_t* krow = kb + (size_t)min(base + lane, k_end - 1) * 96;
+#pragma unroll
+      for (int i = 0; i < 12; ++i) kr[i] = *(const u32x4*)(krow + i * 8);
+#pragma unroll
+      for (int t2 = 0; t2 < 16; ++t2) {
+        const int rr = min(base + 4 * t2 + g, k_end - 1);
+        vr[t2] = *(const u32x4*)(vb + (size_t)rr * 96 + min(i16, 11) * 8);
+      }
+    };
+    issue_tile(k_begin);
+    if (lane < 48) {
+      const bf16_t* row = p.qkv + (size_t)r * 3 * p.H * 96 + h * 96;
+      __bf16 q0, q1;
+      group_rotate(row, p.cos, p.sin, ln, lane, q0, q1);
+      ((__bf16*)s_q)[lane] = q0;
+      ((__bf16*)s_q)[lane + 48] = q1;
+      if (owner) {
+        const bf16_t* vn = row + 2 * p.H * 96;
+        __bf16 kn0, kn1;
+        group_rotate(row + p.H * 96, p.cos, p.sin, ln, lane, kn0, kn1);
+        ((__bf16*)s_k)[lane] = kn0;
+        ((__bf16*)s_k)[lane + 48] = kn1;
+        ((__bf16*)kb)[(size_t)la * 96 + lane] = kn0;
+        ((__bf16*)kb)[(size_t)la * 96 + lane + 48] = kn1;
+        s_v[lane] = vn[lane];
+        s_v[lane + 48] = vn[lane + 48];
+        vb[(size_t)la * 96 + lane] = vn[lane];
+        vb[(size_t)la * 96 + lane + 48] = vn[lane + 48];
+      }
+    }
+    __syncthreads();
+    for (int t = 0; t < p.Ts; ++t) {
+      const int base = k_begin + t * 64;
+      if (base >= k_end) break;
+      const int j = base + lane;
+      if (t > 0) issue_tile(base);
+      if (owner && base <= la && la < base + 64) {
+        // the tile loads went out before the new row was stored: every lane whose (clamped) row index is la takes it from LDS,
+        // so no stale cache contents (0 * NaN) can reach the sums
+        if (min(j, k_end - 1) == la) {
+#pragma unroll
+          for (int i = 0; i < 12; ++i) kr[i] = *(const u32x4*)(s_k + i * 8);
+        }
+#pragma unroll
+        for (int t2 = 0; t2 < 16; ++t2)
+          if (min(base + 4 * t2 + g, k_end - 1) == la) vr[t2] = *(const u32x4*)(s_v + min(i16, 11) * 8);
+      }
+      const bool ok = j < k_end;
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < 12; ++i) s = dot8_bf16(kr[i], *(const u32x4*)(s_q + i * 8), s);
+      s = ok ? s * p.scale : -INFINITY;
+      const float mn = fmaxf(m, wave_max(s));
+      const float a = __expf(m - mn);
+      const float pr = ok ? __expf(s - mn) : 0.f;
+      l = l * a + wave_sum(pr);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] *= a;
+#pragma unroll
+      for (int t2 = 0; t2 < 16; ++t2) {
+        const float w = __shfl(pr, 4 * t2 + g);
+        u32x4 vt = vr[t2];
+        asm volatile("" : "+v"(vt));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          acc[2 * e] = __builtin_fmaf(w, bf16_lo(vt[e]), acc[2 * e]);
+          acc[2 * e + 1] = __builtin_fmaf(w, bf16_hi(vt[e]), acc[2 * e + 1]);
+        }
+      }
+      m = mn;
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      acc[e] += __shfl_xor(acc[e], 16);
+      acc[e] += __shfl_xor(acc[e], 32);
+    }
+  }
+  float* part = p.part + ((size_t)rh * S + p.Sp + split) * DEC_PSTRIDE;
+  if (lane == 0) { AKI_ST_AGENT(part, m); AKI_ST_AGENT(part + 1, l); }
+  if (lane < 12) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) AKI_ST_AGENT(part + 8 + lane * 8 + e, acc[e]);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  unsigned prev = 0;
+  if (lane == 0) prev = __hip_atomic_fetch_add(p.cnt + rh, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  prev = __shfl(prev, 0);
+  asm volatile("" ::: "memory");
+  if (prev == (unsigned)(S - 1)) group_merge(p, rh, lane, s_mg);
+}
+
+// grid (NC * Sp + N * Ss, B0 * H): the prefix items of a (sample, head) come first, they are the long ones.  One instance per chunk
+// width NR = 2 / 4 / 8 / 16 rows (the launch picks the smallest that holds min(N, 16)): a kernel's registers are those of its largest
+// item, and the 16-row prefix item (160 accumulator registers beside a 112-register tile) must not set them for N = 2 or 4.
+template <int NR>
+__global__ __launch_bounds__(64) void decode_attn_group_kernel(const DecodeGroupParams p) {
+  __shared__ __attribute__((aligned(16))) bf16_t s_q[NR * 96], s_k[96], s_v[96];
+  __shared__ __attribute__((aligned(16))) float s_p[64 * NR];
+  __shared__ float s_mg[5][12][10];
+  const int lane = threadIdx.x, x = blockIdx.x, b = blockIdx.y / p.H, h = blockIdx.y - b * p.H;
+  if (x < p.NC * p.Sp) {
+    const int c = x / p.Sp, split = x - c * p.Sp;
+    group_prefix_item<NR>(p, b, h, split, b * p.N + c * 16, min(min(16, NR), p.N - c * 16), lane, s_q, s_p, s_mg);
+  } else {
+    const int y = x - p.NC * p.Sp, j = y / p.Ss, split = y - j * p.Ss;
+    group_suffix_item(p, b, b * p.N + j, h, split, lane, s_q, s_k, s_v, s_mg);
+  }
+}
+#undef AKI_ST_AGENT
+#undef AKI_LD_AGENT
+
+size_t decode_attn_group_ws_bytes(int B0, int N, int H, int pcap, int scap) {
+  const size_t tiles = ((size_t)pcap + 63) / 64 + ((size_t)scap + 63) / 64;
+  return dec_cnt_bytes(B0 * N, H) + (size_t)B0 * N * H * tiles * DEC_PSTRIDE * 4;
+}
+
+// max_pkeys / max_skeys: host upper bounds of prefix_len[b] and of the suffix keys (new token included) - they size the grid.
+// Tiles per item from the CAPACITIES, items from the bounds (decode_attn_split_launch's rule): eager and captured steps cut alike.
+int decode_attn_group_launch(const void* qkv, const float* cos, const float* sin, const int* len, const int* plen, const void* kp,
+                             const void* vp, void* ks, void* vs, void* o, const uint64_t* vbits, int nwords, int B0, int N, int H, int pcap,
+                             int scap, int max_pkeys, int max_skeys, float scale, void* ws, size_t ws_bytes, hipStream_t s) {
+  if (max_pkeys <= 0 || max_pkeys > pcap) max_pkeys = pcap;
+  if (max_skeys <= 0 || max_skeys > scap) max_skeys = scap;
+  const int NC = (N + 15) / 16;
+  const int ptiles_cap = (pcap + 63) / 64, stiles_cap = (scap + 63) / 64;
+  int Tp = (int)(((size_t)B0 * NC * H * ptiles_cap + AKI_DEC_ITEMS - 1) / AKI_DEC_ITEMS);
+  int Ts = (int)(((size_t)B0 * N * H * stiles_cap + AKI_DEC_ITEMS - 1) / AKI_DEC_ITEMS);
+  if (Tp < 1) Tp = 1;
+  if (Ts < 1) Ts = 1;
+  const int Sp = ((max_pkeys + 63) / 64 + Tp - 1) / Tp, Ss = ((max_skeys + 63) / 64 + Ts - 1) / Ts;
+  const size_t cnt_bytes = dec_cnt_bytes(B0 * N, H);
+  if (ws == nullptr || ws_bytes < cnt_bytes + (size_t)B0 * N * H * (Sp + Ss) * DEC_PSTRIDE * 4) return AKI_ERR_WORKSPACE;
+  if ((size_t)B0 * H > 65535 || (size_t)NC * Sp + (size_t)N * Ss > 0x7fffffffu) return AKI_ERR_UNSUPPORTED;
+  DecodeGroupParams p = {(const bf16_t*)qkv, cos, sin, len, plen, (const bf16_t*)kp, (const bf16_t*)vp, (bf16_t*)ks, (bf16_t*)vs, (bf16_t*)o,
+                         vbits, nwords, (unsigned*)ws, (float*)((char*)ws + cnt_bytes), N, H, pcap, scap, Sp, Tp, Ss, Ts, NC, scale};
+  const dim3 grid(NC * Sp + N * Ss, B0 * H), block(64);
+  AKI_CLEAR_ERR();
+  const int width = N < 16 ? N : 16;
+  if (width <= 2) hipLaunchKernelGGL(decode_attn_group_kernel<2>, grid, block, 0, s, p);
+  else if (width <= 4) hipLaunchKernelGGL(decode_attn_group_kernel<4>, grid, block, 0, s, p);
+  else if (width <= 8) hipLaunchKernelGGL(decode_attn_group_kernel<8>, grid, block, 0, s, p);
+  else hipLaunchKernelGGL(decode_attn_group_kernel<16>, grid, block, 0, s, p);
   AKI_LAUNCH_CHECK();
   return AKI_OK;
 }

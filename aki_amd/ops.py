@@ -507,6 +507,48 @@ def decode_attn_fused(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, c
     return o
 
 
+def decode_attn_group_workspace(B0: int, N: int, H: int, Dh: int, prefix_cap: int, suffix_cap: int, device) -> torch.Tensor:
+    """Zero-filled workspace for decode_attn_group (allocate once per grouped KV cache and keep passing it)."""
+    nbytes = int(L.load().aki_decode_attn_group_workspace_bytes(B0, N, H, Dh, prefix_cap, suffix_cap))
+    if nbytes <= 0:
+        raise AkiError("decode_attn_group: bf16, head_dim 96 and positive sizes")
+    return torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=device)
+
+
+def decode_attn_group(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, cache_len: torch.Tensor, prefix_len: torch.Tensor,
+                      k_prefix: torch.Tensor, v_prefix: torch.Tensor, k_suffix: torch.Tensor, v_suffix: torch.Tensor, num_heads: int,
+                      scale: float, col_valid_bits: Optional[torch.Tensor] = None, max_prefix_keys: int = 0, max_suffix_keys: int = 0,
+                      ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Decode step of N sampled rows per prompt over ONE copy of the prompt's K/V, in one launch (bf16, head_dim 96):
+    qkv [B0*N, 3*H*96] of the new tokens; k_prefix / v_prefix [B0, H, prefix_cap, 96] (read-only), k_suffix / v_suffix [B0*N, H, suffix_cap, 96].
+    Row r (sample r // N) attends to prefix rows [0, prefix_len[b]) (filtered by col_valid_bits [B0, nwords]) and to its suffix rows
+    [0, cache_len[r] - prefix_len[b]], the last of which is the new token: rotated at position cache_len[r] and appended here.  -> o [B0*N, H*96].
+    max_prefix_keys / max_suffix_keys: host bounds that size the grid (0 = the capacities)."""
+    dev = _dev(qkv, cos, sin, cache_len, prefix_len, k_prefix, v_prefix, k_suffix, v_suffix, col_valid_bits, ws)
+    R, B0 = qkv.shape[0], k_prefix.shape[0]
+    pcap, scap, Dh = k_prefix.shape[2], k_suffix.shape[2], k_prefix.shape[3]
+    if B0 <= 0 or R % B0 or k_suffix.shape[0] != R or cache_len.shape[0] != R or prefix_len.shape[0] != B0 \
+            or qkv.shape[1] != 3 * num_heads * Dh or k_prefix.shape[1] != num_heads or k_suffix.shape[1] != num_heads:
+        raise AkiError("decode_attn_group: rows must be samples * N, with one suffix slab and one length per row")
+    if col_valid_bits is not None and col_valid_bits.shape[0] != B0:
+        raise AkiError("decode_attn_group: col_valid_bits holds one row of words per prompt sample")
+    for t in (k_prefix, v_prefix, k_suffix, v_suffix):
+        if not t.is_contiguous() or t.dtype != torch.bfloat16:
+            raise AkiError("decode_attn_group: contiguous bf16 caches")
+    if cache_len.dtype != torch.int32 or prefix_len.dtype != torch.int32:
+        raise AkiError("decode_attn_group: int32 lengths")
+    N = R // B0
+    if ws is None:
+        ws = decode_attn_group_workspace(B0, N, num_heads, Dh, pcap, scap, dev)
+    o = torch.empty((R, num_heads * Dh), dtype=qkv.dtype, device=dev)
+    nw = 0 if col_valid_bits is None else col_valid_bits.shape[1]
+    L.check(L.load().aki_decode_attn_group_fwd(_ptr(qkv.contiguous()), _ptr(cos), _ptr(sin), _ptr(cache_len), _ptr(prefix_len), _ptr(k_prefix),
+                                               _ptr(v_prefix), _ptr(k_suffix), _ptr(v_suffix), _ptr(o), _ptr(col_valid_bits), nw, B0, N,
+                                               num_heads, Dh, pcap, scap, int(max_prefix_keys), int(max_suffix_keys), float(scale), _dt(qkv),
+                                               _ptr(ws), ws.numel() * 4, _stream()), "aki_decode_attn_group_fwd")
+    return o
+
+
 _CHAIN_LAST = {}                      # device index -> the torch stream of the last chain launch
 _CHAIN_LOCK = threading.Lock()
 

@@ -123,14 +123,21 @@ class AkiKVCache:
         self.attn_ws_rows = B
         self.chain, self.chain_sig = None, None                                 # ops.DecodeChain of the one-launch step (batch 1)
         self.chain_disabled = False                                             # set when a chained step failed its check (decode_verified)
+        # share_prefix(n): n returned rows per prompt sample over ONE copy of the prompt's rows.  k / v are then the read-only prefix
+        # [B0, H, capacity, Dh]; every row owns a suffix slab in k_suffix / v_suffix [B0 * n, H, suffix_capacity, Dh]
+        self.group = 1
+        self.prefix_len = None                                                  # int32 [B0]: prompt rows per sample
+        self.k_suffix = self.v_suffix = None
+        self.suffix_capacity = 0
+        self.prefix_host_len = 0                                                # host copy of max(prefix_len)
 
     def scales(self, i):
         """(k_scale, v_scale) of layer i: None, None for a bf16 cache."""
         return (None, None) if self.k_scale is None else (self.k_scale[i], self.v_scale[i])
 
     def nbytes(self) -> int:
-        """Device bytes held by the K/V rows (and, for fp8_e4m3, their scales)."""
-        ts = self.k + self.v + (self.k_scale or []) + (self.v_scale or [])
+        """Device bytes held by the K/V rows (and, for fp8_e4m3, their scales; for a grouped cache, the rows' suffix slabs)."""
+        ts = self.k + self.v + (self.k_scale or []) + (self.v_scale or []) + (self.k_suffix or []) + (self.v_suffix or [])
         return sum(t.numel() * t.element_size() for t in ts)
 
     def quantise_from(self, stage: "AkiKVCache", rows: int) -> None:
@@ -140,12 +147,43 @@ class AkiKVCache:
             raise ops.AkiError("quantise_from: a fresh fp8_e4m3 cache and a bf16 staging cache, both still in one piece")
         ops.kv_cache_quant_fp8(stage._store[0], self._store[0], self._store[1], rows)
 
+    @staticmethod
+    def can_share_prefix(cache) -> bool:
+        """A grouped cache needs bf16 K/V rows with head_dim 96, still as the prefill left them."""
+        return (isinstance(cache, AkiKVCache) and cache.kv_dtype == "bf16" and cache.group == 1 and cache.k[0].dtype == torch.bfloat16
+                and cache.k[0].shape[3] == 96 and cache.k[0].is_cuda and cache.k[0].is_contiguous() and cache.capacity > cache.host_len)
+
+    def share_prefix(self, n: int) -> None:
+        """A freshly prefilled bf16 cache of B0 samples becomes the cache of B0 * n rows (row b * n + j continues sample b) WITHOUT copying
+        a prompt row: k / v stay where they are as the read-only prefix, every row gets a suffix slab of capacity - (prompt rows) for
+        the tokens it decodes, cache_len is expanded, prefix_len remembers the samples' prompt lengths.  The decode step then runs
+        ops.decode_attn_group, which reads a prefix tile once for all rows of a sample."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("share_prefix: n >= 1")
+        if not AkiKVCache.can_share_prefix(self):
+            raise ops.AkiError("share_prefix: a freshly prefilled bf16 KV cache with head_dim 96 and room for new tokens")
+        k0 = self.k[0]
+        B0, H, _, Dh = k0.shape
+        self.suffix_capacity = self.capacity - self.host_len
+        sfx = torch.empty((2, len(self.k), B0 * n, H, self.suffix_capacity, Dh), dtype=k0.dtype, device=k0.device)
+        self.k_suffix, self.v_suffix = list(sfx[0].unbind(0)), list(sfx[1].unbind(0))
+        self.group = n
+        self.prefix_len = self.cache_len.clone()
+        self.prefix_host_len = self.host_len
+        self.cache_len = self.cache_len.repeat_interleave(n).contiguous()
+        self.attn_ws = None                           # sized per row: rebuilt (zero-filled) by the next decode step
+        self.attn_ws_rows = B0 * n
+        self.chain, self.chain_sig = None, None
+
     def get_seq_length(self, layer_idx=0):
         return int(self.cache_len.max())
 
     def select_rows(self, index: torch.Tensor) -> None:
         """Rows (sequences) of every per-sequence buffer gathered by `index` (int64 [B']): beam search's cache re-ordering
         (HF `_reorder_cache`) and, with repeated indices, the expansion of a prompt batch to its beams."""
+        if self.group > 1:
+            raise ops.AkiError("select_rows: the rows of a grouped cache (share_prefix) are never re-ordered")
         self.k = [t.index_select(0, index) for t in self.k]
         self.v = [t.index_select(0, index) for t in self.v]
         if self.k_scale is not None:                  # fp8_e4m3: the row scales travel with their bytes
@@ -287,10 +325,20 @@ class Phi3Attention(nn.Module):
         """One new token per sequence: h [B, d] (residual stream, pre-norm) -> h + o_proj(attention).  Three launches:
         RMSNorm+qkv GEMV, RoPE+append+split-KV attention, o_proj GEMV with the residual add."""
         qkv = ops.decode_linear(h, self.qkv_proj.weight, norm.weight, norm.variance_epsilon)
-        ks, vs = cache.scales(self.layer_idx)
-        o = ops.decode_attn_fused(qkv, cos, sin, cache.cache_len, cache.k[self.layer_idx], cache.v[self.layer_idx], self.num_heads,
-                                  self.scaling, cache.valid_bits, cache.grid_keys, cache.attn_ws, ks, vs)
+        o = self.decode_attn(qkv, cos, sin, cache)
         return ops.linear(o, self.o_proj.weight, residual=h)
+
+    def decode_attn(self, qkv, cos, sin, cache):
+        """RoPE + append + single-query attention of one decode step: the grouped launch on a cache whose rows share their prompt's K/V
+        (AkiKVCache.share_prefix), the fused split-KV launch otherwise."""
+        i = self.layer_idx
+        if cache.group > 1:
+            return ops.decode_attn_group(qkv, cos, sin, cache.cache_len, cache.prefix_len, cache.k[i], cache.v[i], cache.k_suffix[i],
+                                         cache.v_suffix[i], self.num_heads, self.scaling, cache.valid_bits, cache.prefix_host_len,
+                                         cache.grid_keys, cache.attn_ws)
+        ks, vs = cache.scales(i)
+        return ops.decode_attn_fused(qkv, cos, sin, cache.cache_len, cache.k[i], cache.v[i], self.num_heads, self.scaling, cache.valid_bits,
+                                     cache.grid_keys, cache.attn_ws, ks, vs)
 
 
 class Phi3MLP(nn.Module):
@@ -413,9 +461,7 @@ class Phi3DecoderLayer(nn.Module):
             w, at = self._fp8, self.self_attn
             n1, n2 = self.input_layernorm, self.post_attention_layernorm
             qkv = ops.linear_w8(h, *w["qkv"], rms_weight=n1.weight, eps=n1.variance_epsilon)
-            ks, vs = cache.scales(at.layer_idx)
-            o = ops.decode_attn_fused(qkv, cos, sin, cache.cache_len, cache.k[at.layer_idx], cache.v[at.layer_idx], at.num_heads,
-                                      at.scaling, cache.valid_bits, cache.grid_keys, cache.attn_ws, ks, vs)
+            o = at.decode_attn(qkv, cos, sin, cache)
             h = ops.linear_w8(o, *w["o"], residual=h)
             a = ops.linear_w8(h, *w["gate_up"], act=ops.ACT_SWIGLU, rms_weight=n2.weight, eps=n2.variance_epsilon)
             return ops.linear_w8(a, *w["down"], residual=h)
@@ -533,10 +579,21 @@ class Phi3Model(nn.Module):
         cache.host_len += 1                         # host-side upper bound of max(cache_len)+1: no device sync per step
         cos, sin = self.rotary_emb.tables(cache.capacity, inputs_embeds.device, cache.host_len)
         # position of the new token = its cache row = number of tokens before it (cache.cache_len, on the device)
-        if cache.attn_ws is None:
-            cache.attn_ws = ops.decode_attn_workspace(inputs_embeds.shape[0], cache.k[0].shape[1], cache.k[0].shape[3],
-                                                      cache.capacity, inputs_embeds.device)
-        cache.grid_keys = cache.capacity if torch.cuda.is_current_stream_capturing() else min(cache.capacity, cache.host_len)
+        capturing = torch.cuda.is_current_stream_capturing()
+        if cache.group > 1:
+            # grouped cache: the prefix never grows (its bound is the prompt's length, eager or captured); grid_keys bounds the SUFFIX keys,
+            # the new token included.  host_len <= capacity (the guard above) keeps the append row inside the suffix slab.
+            if inputs_embeds.shape[0] != cache.cache_len.shape[0]:
+                raise ops.AkiError(f"a grouped KV cache holds {cache.cache_len.shape[0]} rows, the step brings {inputs_embeds.shape[0]}")
+            if cache.attn_ws is None:
+                cache.attn_ws = ops.decode_attn_group_workspace(cache.k[0].shape[0], cache.group, cache.k[0].shape[1], cache.k[0].shape[3],
+                                                                cache.capacity, cache.suffix_capacity, inputs_embeds.device)
+            cache.grid_keys = cache.suffix_capacity if capturing else min(cache.suffix_capacity, cache.host_len - cache.prefix_host_len)
+        else:
+            if cache.attn_ws is None:
+                cache.attn_ws = ops.decode_attn_workspace(inputs_embeds.shape[0], cache.k[0].shape[1], cache.k[0].shape[3],
+                                                          cache.capacity, inputs_embeds.device)
+            cache.grid_keys = cache.capacity if capturing else min(cache.capacity, cache.host_len)
         h = inputs_embeds
         chain = self._decode_chain(h, cache)
         if chain is not None:                       # 1..8 sequences: the 32 layers as ONE launch (decode_chain.hip)
@@ -574,6 +631,8 @@ class Phi3Model(nn.Module):
         bf16 or fully e4m3-quantised (the fp8 configuration's weight-only GEMVs), a bf16 KV cache (an fp8_e4m3 cache takes the
         five-launch-per-layer path).  Built once per (weights, KV cache)."""
         B = h.shape[0]
+        if getattr(cache, "group", 1) > 1:
+            return None                             # a grouped cache (share_prefix) is batched: the five-launch-per-layer path
         if (not self.use_decode_chain or cache.chain_disabled or getattr(cache, "kv_dtype", "bf16") != "bf16" or B > (8 if self.use_decode_chain_batched else 1) or h.dtype != torch.bfloat16
                 or not h.is_cuda):
             return None
@@ -702,6 +761,10 @@ class Phi3ForCausalLM(nn.Module):
         return ops.linear(h, w, bias=b, row_scale=st.rstd)[..., :n]
 
     kv_cache_dtype = "bf16"
+    share_prompt_kv = False                         # True: generate(num_return_sequences=N) lets the N rows of a sample read ONE copy of its
+                                                    # prompt K/V (AkiKVCache.share_prefix); False replicates the prompt rows N times.  Off
+                                                    # until tools/kv_share_bench.py has been run on an MI355X: the step times of the two forms
+                                                    # are not measured, and the default may not be slower than what it replaces
 
     def set_kv_cache_dtype(self, dtype: str = "bf16"):
         """Format of the KV caches this model allocates from now on (a use_cache=True forward, AKI.generate): "bf16" (the default) or

@@ -391,6 +391,27 @@ int aki_decode_attn_fused_fp8kv_fwd(const void* qkv, const float* cos, const flo
                                     int32_t B, int32_t H, int32_t Dh, int32_t capacity, int32_t max_keys, float scale, int32_t dtype, void* ws,
                                     size_t ws_bytes, void* stream);
 
+/* Grouped decode attention - N returned rows per prompt sample over ONE copy of the prompt's K/V (AKI.generate(num_return_sequences=N);
+ * bf16, Dh = 96).  The cache has two parts:
+ *   k_prefix / v_prefix [B0, H, prefix_capacity, 96]   the prompt's rows as the prefill wrote them, one slab per prompt sample; READ-ONLY here
+ *   k_suffix / v_suffix [B0*N, H, suffix_capacity, 96] one slab per returned row: the tokens decoded so far
+ * Row r belongs to sample b = r / N.  Its keys are prefix rows [0, prefix_len[b]) - filtered by the sample's col_valid_bits words
+ * ([B0][nwords], NULL = all valid) - followed by suffix rows [0, cache_len[r] - prefix_len[b]].  The last of those is the new token: its k is
+ * rotated at position cache_len[r] (= the cos/sin row) and appended with its v at suffix row cache_len[r] - prefix_len[b], which must lie
+ * in [0, suffix_capacity) (a row outside it is not appended and sees its prefix only).  qkv [B0*N, 3*H*96] un-rotated, o [B0*N, H*96].
+ * A 64-key prefix tile is loaded once per (sample, head, chunk of 16 rows) and dotted with all of the chunk's queries.
+ * max_prefix_keys / max_suffix_keys: HOST upper bounds of prefix_len[b] and of the suffix keys (new token included); 0 = the capacity.
+ * They size the grid only: the result does not depend on them, bit for bit, while they cover the keys.
+ * Workspace: aki_decode_attn_group_workspace_bytes(...) bytes, caller-owned, ZERO-FILLED ONCE, then passed unchanged (stream-ordered).
+ * NULL pointers -> AKI_ERR_INVALID_ARG; Dh != 96 or dtype != AKI_DT_BF16 -> AKI_ERR_UNSUPPORTED; a short workspace -> AKI_ERR_WORKSPACE.
+ * Purely additive: AKI_ABI_VERSION was not bumped. */
+size_t aki_decode_attn_group_workspace_bytes(int32_t B0, int32_t N, int32_t H, int32_t Dh, int32_t prefix_capacity, int32_t suffix_capacity);
+int aki_decode_attn_group_fwd(const void* qkv, const float* cos, const float* sin, const int32_t* cache_len, const int32_t* prefix_len,
+                              const void* k_prefix, const void* v_prefix, void* k_suffix, void* v_suffix, void* o,
+                              const uint64_t* col_valid_bits, int32_t nwords, int32_t B0, int32_t N, int32_t H, int32_t Dh,
+                              int32_t prefix_capacity, int32_t suffix_capacity, int32_t max_prefix_keys, int32_t max_suffix_keys, float scale,
+                              int32_t dtype, void* ws, size_t ws_bytes, void* stream);
+
 /* aki_decode_chain_fwd - ALL decoder layers of one decode step for ONE sequence (batch 1) in one launch (bf16 weights, or
  * AKI_DT_W8A16: e4m3 weights with one f32 scale per weight row).  Same arithmetic as the per-layer calls above
  * (aki_decode_linear_fwd -> aki_decode_attn_fused_fwd -> aki_linear_fwd + residual -> aki_decode_linear_fwd SwiGLU -> aki_linear_fwd

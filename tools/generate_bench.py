@@ -28,6 +28,9 @@ def main():
     ap.add_argument("--top-k", type=int, default=0)
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--num-return-sequences", type=int, default=1, help="N sampled continuations per prompt (device sampler): one more leg per round")
+    ap.add_argument("--no-share-prompt-kv", action="store_true", help="with --num-return-sequences: replicate the prompt K/V N times (the A/B form; "
+                    "without it the leg switches lang_model.share_prompt_kv on)")
     a = ap.parse_args()
     proc_kw = {}
     if a.repetition_penalty != 1.0:
@@ -107,6 +110,17 @@ def main():
                 (r["sample_device_generator_ms_per_new_token_after_the_first"] - r["ms_per_new_token_after_the_first"]) * 1e3, 2)
             r["device_sampler_faster_than_torch_path"] = bool(
                 r["sample_device_generator_ms_per_new_token_after_the_first"] < r["sample_torch_generator_ms_per_new_token_after_the_first"])
+    if a.num_return_sequences > 1:
+        import aki_amd
+        model.lang_model.share_prompt_kv = not a.no_share_prompt_kv
+        nkw = dict(sample_kw, num_return_sequences=a.num_return_sequences)
+        run(16, generator=aki_amd.DeviceGenerator(0), **nkw)
+        res["num_return_sequences"] = {"n": a.num_return_sequences, "share_prompt_kv": not a.no_share_prompt_kv, "rounds": []}
+        for _ in range(a.rounds):
+            t1n, _ = run(1, generator=aki_amd.DeviceGenerator(0), **nkw)
+            tnn, toks_n = run(a.new, generator=aki_amd.DeviceGenerator(0), **nkw)
+            assert toks_n.shape == (a.batch * a.num_return_sequences, a.new)
+            res["num_return_sequences"]["rounds"].append({"ms_per_new_token_after_the_first": round((tnn - t1n) * 1e3 / (a.new - 1), 4)})
     if a.sample:
         ex = sorted(r["device_sampler_excess_over_greedy_us_per_token"] for r in res["rounds"])
         res["device_sampler_excess_over_greedy_us_per_token_median"] = ex[len(ex) // 2]

@@ -20,6 +20,9 @@ int attn_nc_bf16(const aki_attn_args* a, hipStream_t stream);
 int gemv_bf16(const aki_linear_args* a, const void* rms_w, float eps, hipStream_t stream);
 int skinny_gemm_bf16(const aki_linear_args* a, const void* rms_w, float eps, hipStream_t stream);
 int skinny_gemm_w8(const aki_linear_args* a, const void* rms_w, float eps, hipStream_t stream);
+int quant_mxfp4_launch(const void* w, int N, int K, int ldw, uint8_t* wq, uint8_t* ws, hipStream_t s);
+int gemv_w4(const aki_linear_args* a, const uint8_t* ws, const void* rms_w, float eps, hipStream_t stream);
+int skinny_gemm_w4(const aki_linear_args* a, const uint8_t* ws, const void* rms_w, float eps, hipStream_t stream);
 size_t decode_attn_ws_bytes(int B, int H, int Dh, int cap);
 int decode_attn_split_launch(const void* q_or_qkv, const float* cos, const float* sin, const int* len, void* kc, void* vc, void* o,
                              const uint64_t* vbits, int nwords, int B, int H, int cap, int max_keys, float scale, bool fused,
@@ -499,6 +502,25 @@ int aki_decode_linear_fwd(const aki_linear_args* a, const void* rms_weight, floa
     if (rc != AKI_ERR_UNSUPPORTED) return rc;
   }
   return gemv_bf16(a, rms_weight, rms_eps, (hipStream_t)stream);
+}
+
+// ---- MXFP4 weight-only decode (mxfp4.hip) ------------------------------------------------------------------
+int aki_quant_mxfp4(const void* w, int32_t N, int32_t K, int32_t ldw, uint8_t* wq, uint8_t* ws, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(w && wq && ws && N > 0 && K > 0 && ldw >= K);
+  return quant_mxfp4_launch(w, N, K, ldw, wq, ws, (hipStream_t)stream);
+}
+
+int aki_linear_w4_fwd(const aki_linear_args* a, const uint8_t* w_scale_e8m0, const void* rms_weight, float rms_eps, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(a && a->x && a->w && a->y && w_scale_e8m0 && (!rms_weight || rms_eps > 0.f));
+  AKI_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0);
+  AKI_CHECK_ARG(a->act >= AKI_ACT_NONE && a->act <= AKI_ACT_SWIGLU);
+  if (a->dtype != AKI_DT_BF16 || a->K % 32 || a->M > 16) return AKI_ERR_UNSUPPORTED;
+  const int n_out = a->act == AKI_ACT_SWIGLU ? a->N / 2 : a->N;
+  AKI_CHECK_ARG(a->ldx >= a->K && a->ldw >= a->K / 2 && a->ldy >= n_out && (!a->residual || a->ldr >= n_out));
+  if (a->M == 1) return gemv_w4(a, w_scale_e8m0, rms_weight, rms_eps, (hipStream_t)stream);
+  return skinny_gemm_w4(a, w_scale_e8m0, rms_weight, rms_eps, (hipStream_t)stream);
 }
 
 size_t aki_decode_chain_workspace_bytes(int32_t n_layers, int32_t d, int32_t H, int32_t F, int32_t capacity) {

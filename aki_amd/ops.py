@@ -1145,6 +1145,71 @@ def linear_w8(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias: Optiona
     return out
 
 
+# ---- MXFP4 weight-only decode (csrc/mxfp4.hip): e2m1 nibbles + one e8m0 scale byte per block of 32 k ---------------------------
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quant_mxfp4(w: torch.Tensor):
+    """bf16 weight [N, K] (K % 32 == 0, rows 16-byte aligned) -> (wq uint8 [N, K/2], ws uint8 [N, K/32]): OCP MXFP4, the format of
+    aki_quant_mxfp4 (include/aki_mi355x.h).  The values must be finite; the caller checks (Phi3ForCausalLM.enable_mxfp4 does)."""
+    dev = _dev(w)
+    if w.dtype != torch.bfloat16 or w.dim() != 2 or w.stride(1) != 1 or w.shape[1] % 32:
+        raise AkiError("quant_mxfp4 takes a bf16 matrix [N, K] with contiguous rows and K a multiple of 32")
+    N, K = w.shape
+    wq = torch.empty((N, K // 2), dtype=torch.uint8, device=dev)
+    ws = torch.empty((N, K // 32), dtype=torch.uint8, device=dev)
+    L.check(L.load().aki_quant_mxfp4(_ptr(w), N, K, w.stride(0), _ptr(wq), _ptr(ws), _stream()), "aki_quant_mxfp4")
+    return wq, ws
+
+
+def dequant_mxfp4(wq: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+    """The bf16 matrix [N, K] that (wq, ws) stand for - exact (e2m1 x 2^e has two significant bits).  A torch expression for tests, tools and
+    twin models; the decode kernels never materialise it."""
+    N, K2 = wq.shape
+    lut = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float32, device=wq.device)
+    nib = torch.stack((wq & 0xF, wq >> 4), dim=-1).reshape(N, K2 * 2).long()
+    scale = torch.ldexp(torch.ones((), dtype=torch.float32, device=wq.device), ws.to(torch.int32) - 127)
+    return (lut[nib].view(N, -1, 32) * scale.unsqueeze(-1)).reshape(N, K2 * 2).to(torch.bfloat16)
+
+
+def linear_w4(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, bias: Optional[torch.Tensor] = None,
+              residual: Optional[torch.Tensor] = None, act: int = ACT_NONE, rms_weight: Optional[torch.Tensor] = None,
+              eps: float = 0.0, res_row_mod: int = 0) -> torch.Tensor:
+    """Weight-only MXFP4 (opt-in decode format): x bf16 [M <= 16, K], wq [N, K/2] nibbles with ws [N, K/32] e8m0 block scales (quant_mxfp4);
+    optional fused RMSNorm of x (rms_weight).  One row: the dot-product GEMV; 2-16 rows: the skinny MFMA GEMM on e2m1 weights.  y bf16 [M, N_out].
+    2-16 rows of a shape outside the skinny GEMM's gates are served by the GEMV one row at a time; anything else the kernels do not take
+    raises AkiError - there is no other route for these weights."""
+    dev = _dev(x, wq, ws, bias, residual, rms_weight)
+    x2 = _rows2d(x)
+    M, K = x2.shape
+    if M > 16 or x.dtype != torch.bfloat16 or wq.dtype != torch.uint8 or ws.dtype != torch.uint8:
+        raise AkiError("linear_w4 serves up to 16 bf16 rows on uint8 nibbles and scale bytes")
+    N = wq.shape[0]
+    if wq.shape[1] * 2 != K or tuple(ws.shape) != (N, K // 32) or not ws.is_contiguous() or wq.stride(1) != 1:
+        raise AkiError("linear_w4: wq [N, K/2] and a dense ws [N, K/32] for x [M, K]")
+    n_out = N // 2 if act == ACT_SWIGLU else N
+    if M > 1 and rms_weight is not None and (M > 8 or K > 8192 or K % 512 or (n_out + 15) // 16 >= 1536):
+        x2 = _rows2d(rmsnorm(x, rms_weight, eps))      # shapes whose rows the GEMM does not normalise itself (wide outputs, more than eight rows)
+        rms_weight = None
+    out = torch.empty((*x.shape[:-1], n_out), dtype=torch.bfloat16, device=dev)
+    o2 = out.view(-1, n_out)
+    r2 = None if residual is None else _rows2d(residual)
+    a = L.LinearArgs(_ptr(x2), _ptr(wq), _ptr(bias), _ptr(r2), _ptr(o2), M, N, K, x2.stride(0), wq.stride(0), o2.stride(0),
+                     0 if r2 is None else r2.stride(0), int(res_row_mod), act, L.AKI_DT_BF16)
+    lib = L.load()
+    rc = lib.aki_linear_w4_fwd(C.byref(a), _ptr(ws), _ptr(rms_weight), float(eps), _stream())
+    if rc == -2 and M > 1:
+        # AKI_ERR_UNSUPPORTED: a shape outside the skinny GEMM's gates (K no multiple of 256, N_out no multiple of 4): the one-row GEMV, row by row
+        for m in range(M):
+            rr = None if r2 is None else r2[m % res_row_mod if res_row_mod > 0 else m]
+            a = L.LinearArgs(_ptr(x2[m]), _ptr(wq), _ptr(bias), _ptr(rr), _ptr(o2[m]), 1, N, K, x2.stride(0), wq.stride(0), o2.stride(0),
+                             n_out, 0, act, L.AKI_DT_BF16)
+            L.check(lib.aki_linear_w4_fwd(C.byref(a), _ptr(ws), _ptr(rms_weight), float(eps), _stream()), "aki_linear_w4_fwd[row]")
+        return out
+    L.check(rc, "aki_linear_w4_fwd")
+    return out
+
+
 def pad_k(w: torch.Tensor, mult: int = 64) -> torch.Tensor:
     """Zero-pad the K (last) dimension of a weight to a multiple of `mult` (one-time host-side prep)."""
     K = w.shape[-1]

@@ -370,6 +370,7 @@ class Phi3DecoderLayer(nn.Module):
         self.input_layernorm = Phi3RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
         self.post_attention_layernorm = Phi3RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
         self._fp8 = None
+        self._w4 = None
         self._prep = ops.Prepared()
 
     def folds(self, h) -> bool:
@@ -455,7 +456,22 @@ class Phi3DecoderLayer(nn.Module):
                      "gate_up": ops.quant_rows_fp8(mlp.gate_up_proj.weight.detach()),
                      "down": ops.quant_rows_fp8(mlp.down_proj.weight.detach()) if residual_writers else None}
 
+    def quantize_mxfp4(self):
+        """MXFP4 copies (nibbles, e8m0 block scales) of the four projections for the decode rows (ops.linear_w4); the bf16 weights stay."""
+        at, mlp = self.self_attn, self.mlp
+        self._w4 = {"qkv": ops.quant_mxfp4(at.qkv_proj.weight.detach()), "o": ops.quant_mxfp4(at.o_proj.weight.detach()),
+                    "gate_up": ops.quant_mxfp4(mlp.gate_up_proj.weight.detach()), "down": ops.quant_mxfp4(mlp.down_proj.weight.detach())}
+
     def decode(self, h, cos, sin, cache):
+        if self._w4 is not None and h.shape[0] <= 16:
+            # MXFP4 weights (opt-in): the same five launches as the e4m3 branch below over 4.25 bits per weight
+            w, at = self._w4, self.self_attn
+            n1, n2 = self.input_layernorm, self.post_attention_layernorm
+            qkv = ops.linear_w4(h, *w["qkv"], rms_weight=n1.weight, eps=n1.variance_epsilon)
+            o = at.decode_attn(qkv, cos, sin, cache)
+            h = ops.linear_w4(o, *w["o"], residual=h)
+            a = ops.linear_w4(h, *w["gate_up"], act=ops.ACT_SWIGLU, rms_weight=n2.weight, eps=n2.variance_epsilon)
+            return ops.linear_w4(a, *w["down"], residual=h)
         if self._fp8 is not None and self._fp8["o"] is not None and h.shape[0] <= 16:
             # fp8 configuration: weight-only e4m3 GEMVs (one sequence) / skinny MFMA GEMMs (2-16) - half the bytes of the HBM-bound step, same 5 launches
             w, at = self._fp8, self.self_attn
@@ -633,6 +649,9 @@ class Phi3Model(nn.Module):
         B = h.shape[0]
         if getattr(cache, "group", 1) > 1:
             return None                             # a grouped cache (share_prefix) is batched: the five-launch-per-layer path
+        if self.layers[0]._w4 is not None:
+            cache.chain = None                      # MXFP4 weights: the chain knows bf16 and e4m3 only - the five-launch-per-layer path
+            return None
         if (not self.use_decode_chain or cache.chain_disabled or getattr(cache, "kv_dtype", "bf16") != "bf16" or B > (8 if self.use_decode_chain_batched else 1) or h.dtype != torch.bfloat16
                 or not h.is_cuda):
             return None
@@ -738,6 +757,34 @@ class Phi3ForCausalLM(nn.Module):
             else:
                 w, b, n = hd._fused_weight()
             self._fp8_head = (*ops.quant_rows_fp8(w), b, n)
+        return self
+
+    def enable_mxfp4(self, enable: bool = True, head: bool = True):
+        """Opt-in MXFP4 weight-only decode: quantise the decoder's projection weights (and, with `head`, the lm_head) once to OCP MXFP4 -
+        e2m1 elements in blocks of 32 with one e8m0 scale byte, 4.25 bits per weight - for the decode rows (up to 16: ops.linear_w4, five
+        launches per layer; the one-launch chain is not used).  Prefill and training are untouched and the bf16 weights stay in place.
+        Independent of enable_fp8() (with both on, prefill runs e4m3 and the decode rows MXFP4) and of set_kv_cache_dtype().  4-bit rounding
+        costs accuracy (DESIGN section 4 gives the measured figure); enable_mxfp4(False) drops the copies."""
+        self.model._weights_version += 1
+        if not enable:
+            for layer in self.model.layers:
+                layer._w4 = None
+            self._w4_head = None
+            return self
+        hd = self.lm_head
+        if type(hd) is nn.Linear:
+            hw, hb, hn = hd.weight.detach(), hd.bias, hd.weight.shape[0]
+        else:
+            hw, hb, hn = hd._fused_weight()
+        mats = [m.weight for ly in self.model.layers for m in (ly.self_attn.qkv_proj, ly.self_attn.o_proj, ly.mlp.gate_up_proj, ly.mlp.down_proj)]
+        mats += [hw] if head else []
+        if any(m.dtype != torch.bfloat16 or not m.is_cuda for m in mats):
+            raise ops.AkiError("enable_mxfp4: the model must hold bf16 weights on the GPU")
+        if not all(bool(torch.isfinite(m).all()) for m in mats):
+            raise ops.AkiError("enable_mxfp4: a weight matrix holds non-finite values")
+        for layer in self.model.layers:
+            layer.quantize_mxfp4()
+        self._w4_head = (*ops.quant_mxfp4(hw), hb, hn) if head else None
         return self
 
     def _head(self, h):
@@ -903,6 +950,9 @@ class Phi3ForCausalLM(nn.Module):
         """lm_head(norm(h)) for a few rows of the RAW residual stream [B, d] (a decode step; the last prompt token of a prefill): the final
         RMSNorm is applied inside the weight-streaming GEMV."""
         norm = self.model.norm
+        if getattr(self, "_w4_head", None) is not None and h.shape[0] <= 16:
+            wq, ws, b, n = self._w4_head
+            return ops.linear_w4(h, wq, ws, bias=b, rms_weight=norm.weight, eps=norm.variance_epsilon)[..., :n]
         if getattr(self, "_fp8_head", None) is not None and h.shape[0] <= 16:
             wq, ws, b, n = self._fp8_head
             return ops.linear_w8(h, wq, ws, bias=b, rms_weight=norm.weight, eps=norm.variance_epsilon)[..., :n]

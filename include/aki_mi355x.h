@@ -571,6 +571,23 @@ int aki_adamw_step_g32(float* p, float* m, float* v, const float* g, void* w16, 
 int aki_quant_rows_fp8(const void* x, const void* rms_weight, float rms_eps, void* q, float* scale, int32_t rows, int32_t cols,
                        int32_t ldx, int32_t ldq, void* stream);
 
+/* MXFP4 weight-only decode - an opt-in 4.25-bit weight format for the decode rows (Phi3ForCausalLM.enable_mxfp4()).  OCP microscaling: a weight
+ * row [K] (K % 32 == 0) is cut into blocks of 32 consecutive k; a block is 32 e2m1 nibbles (sign in bit 3; magnitudes 0, 0.5, 1, 1.5, 2, 3,
+ * 4, 6) and one e8m0 scale byte, value = nibble * 2^(byte - 127).  wq is [N, K/2] bytes (byte j of a row: k = 2j in the low nibble, k = 2j+1
+ * in the high one), ws is [N, K/32] bytes, both dense.
+ * aki_quant_mxfp4   : bf16 w [N, ldw] -> wq, ws.  Per block: e = floor(log2(amax)) - 2, byte = clamp(e + 127, 0, 254) (never 255), elements
+ *                     v / 2^e rounded to the nearest e2m1 value, ties to the even code, saturating at +-6; an all-zero block gets byte 127 and
+ *                     zero nibbles.  Inputs must be finite (the caller checks).  ldw % 8 == 0; w and wq 16-byte aligned.
+ * aki_linear_w4_fwd : y = act(x W^T + bias) [+ residual] for M <= 16 bf16 rows on such weights, optionally with the RMSNorm of
+ *                     aki_decode_linear_fwd applied to x first (rms_weight != NULL; M <= 8 and narrow outputs only, as there).
+ *                     args->w = the nibbles, args->ldw in BYTES (% 16), args->dtype = AKI_DT_BF16 (x and y), args->w_scale is ignored;
+ *                     w_scale_e8m0 = ws.  M = 1: a dot-product GEMV; 2..16: the skinny MFMA GEMM with the K / N / alignment limits of the
+ *                     AKI_DT_W8A16 one.  K % 32 != 0, M > 16 or a shape outside those limits -> AKI_ERR_UNSUPPORTED; NULL pointers ->
+ *                     AKI_ERR_INVALID_ARG; x / w / rms_weight not 16-byte aligned -> AKI_ERR_ALIGNMENT.  Nothing is launched on an error.
+ * Purely additive: AKI_ABI_VERSION was not bumped. */
+int aki_quant_mxfp4(const void* w, int32_t N, int32_t K, int32_t ldw, uint8_t* wq, uint8_t* ws, void* stream);
+int aki_linear_w4_fwd(const aki_linear_args* args, const uint8_t* w_scale_e8m0, const void* rms_weight, float rms_eps, void* stream);
+
 /* aki_mma_mask_dense - materialise the reference's (B,1,L,L) int64 0/1 mask from the table, for
  * callers that still want it (bit-exact vs src/vlm.py:410-443 + src/utils.py:99-108). */
 int aki_mma_mask_dense(const aki_mma_rect* rects, int32_t max_rects, const uint64_t* col_valid_bits,

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AKI_MI355X_LIB") or os.path.join(_HERE, "lib", "libaki_mi355x.so")
 LAB_LIB_PATH = os.path.join(_HERE, "lib", "libaki_mi355x_lab.so")
 
-AKI_DT_BF16, AKI_DT_F32, AKI_DT_FP8_E4M3, AKI_DT_W8A16 = 0, 1, 2, 3
+AKI_DT_BF16, AKI_DT_F32, AKI_DT_FP8_E4M3, AKI_DT_W8A16, AKI_DT_W4A16 = 0, 1, 2, 3, 4
 AKI_ACT_NONE, AKI_ACT_GELU_ERF, AKI_ACT_GELU_TANH, AKI_ACT_SWIGLU = 0, 1, 2, 3
 AKI_DEAD_ROWS_ZERO, AKI_DEAD_ROWS_UNIFORM = 0, 1
 AKI_MAX_RECTS = 8

@@ -64,6 +64,25 @@ __device__ __forceinline__ float cdot16_w8(const u32x4 w, const u32x4 x0, const 
 #undef AKI_CW8_PAIR
   return acc;
 }
+// MXFP4 weights: mxfp4.hip's w4_scale and dot32_w4, instruction for instruction (a 16-byte weight chunk = one block of 32 k with ONE e8m0
+// byte, against four x chunks; dword i of w carries k 8i .. 8i+7 = x chunk i; the block scale rides in the convert's scale operand)
+__device__ __forceinline__ float cw4_scale(unsigned byte) { return __builtin_bit_cast(float, byte << 23); }
+__device__ __forceinline__ float cdot32_w4(const u32x4 w, const float scale, const u32x4 (&x)[4], float acc) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const chain_bf16x8_t xv = __builtin_bit_cast(chain_bf16x8_t, x[i]);
+#define AKI_CW4_PAIR(sel, i0)                                                                                      \
+  {                                                                                                                \
+    const chain_bf16x2_t wb = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[i], scale, sel);   /* byte sel: low nibble -> element 0, high -> 1 */ \
+    acc = __builtin_amdgcn_fdot2_f32_bf16(wb, __builtin_shufflevector(xv, xv, i0, i0 + 1), acc, false);            \
+  }
+    AKI_CW4_PAIR(0, 0) AKI_CW4_PAIR(1, 2) AKI_CW4_PAIR(2, 4) AKI_CW4_PAIR(3, 6)
+#undef AKI_CW4_PAIR
+  }
+  return acc;
+}
+// the weight format of a chain: what a 16-byte chunk of a weight row holds
+enum ChainFmt : int { CH_BF16 = 0, CH_W8 = 1, CH_W4 = 2 };      // 8 bf16 | 16 e4m3 (+ an f32 scale per row) | 32 e2m1 = one MX block (+ its e8m0 byte)
 
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for_chain_impl(F&& f) {
@@ -80,6 +99,7 @@ __device__ __forceinline__ void static_for_chain(F&& f) { static_for_chain_impl<
 typedef const __attribute__((address_space(1))) u32x4* gptr_u32x4;
 typedef const __attribute__((address_space(1))) unsigned* gptr_u32;
 typedef const __attribute__((address_space(1))) float* gptr_f32;
+typedef const __attribute__((address_space(1))) unsigned char* gptr_u8;
 #define AKI_G128(p) ((gptr_u32x4)(p))
 constexpr int CH_PSTRIDE = 104;          // decode.hip's DEC_PSTRIDE: m, l, 6 pad, acc[96]
 // Synchronisation block of one (layer, phase), every word in a 128-byte line of its own:
@@ -104,6 +124,9 @@ constexpr int CH_PFQ = 2, CH_PFO = 2, CH_PFG = 2, CH_PFD = 2;
 // e4m3 weights (half the bytes, 24 VALU operations per 16 weights to widen them): ONE batch per workgroup, requested before the wait - that chain is
 // all dependency latency and the second batch's dot products (2 us) sat on it: {1,1,1,1} 1.37 ms per token, {2,2,2,2}/{2,2,2,2} 1.48, five launches 1.46
 // (tools/decode_chain_w8.py).
+// MXFP4 weights (a quarter of the bytes; a 16-byte chunk is one block of 32 k and its e8m0 byte): the e4m3 settings - its rows per wave, ONE batch
+// per workgroup, weights and scale bytes requested before the wait - so the same 576 / 192 / 1024 / 384 workgroups per layer at the same 127 VGPRs
+// and LDS: the residency of the e4m3 chain.  Times and the lab presets tried: tools/w4_decode_bench.py --chain, DESIGN section 4, EXPERIMENTS.md.
 constexpr int CH_TOUCH = 0;
 constexpr int CH_QKV_BY_HEAD = 1;
 constexpr int CH_XREP = 8;               // room for copies of every hand-off vector: consumer j reads copy j % xrep
@@ -217,12 +240,19 @@ __device__ __forceinline__ void chain_publish(unsigned* sync, int idx, int n) {
 // vector through the fabric (sc1), and at one batch per workgroup those reads were 15 % of all bytes moved - the weight stream
 // ran at exactly 6.3 TB/s / 1.15 with the dependency waits switched off (tools/decode_chain_ab.py).  Batch 0 is loaded before the
 // wait; batch b+1 as soon as the dot products have released the registers of batch b, under its reduction and epilogue.
-template <int NR, int KC, bool SWIGLU, bool NORM, bool W8, int NB, int PF>
+// FMT = CH_W4: a chunk is one MX block; a row is NBLK = K / 32 of them (K/2 bytes) with NBLK dense scale bytes at w_scale (read as bytes).  KC =
+// ceil(NBLK / 64): K = 3072 is 96 blocks = 1.5 per lane, and lanes 32-63 have no second chunk - the load AND the dot product of chunk c = lane + 64 kc
+// are predicated on c < NBLK (mxfp4.hip's gemv_w4_kernel runs those lanes through one sweep only; an unpredicated load would run past the last
+// row of the matrix, a zero product could flip the sign of a zero sum).  The scale bytes travel with the weights, in the same prefetch slots,
+// before the wait.  Per lane and row: chunks ascending, cdot32_w4 into one f32, the xor-shuffle reduction, nothing multiplied after it.
+template <int NR, int KC, bool SWIGLU, bool NORM, ChainFmt FMT, int NB, int PF, int NBLK = KC * 64>
 __device__ __forceinline__ unsigned chain_gemv(const ChainParams& p, int wg, int n_wg, const void* w, const float* w_scale, int K, int n_out,
                                            const bf16_t* x, int x_rep, const bf16_t* norm_w, const bf16_t* residual, int res_rep, bf16_t* y,
                                            int y_reps, unsigned* wait_sync, unsigned* done_sync, unsigned code, char* sx, float* s_red,
                                            int head_per = 0, unsigned* head_sync = nullptr) {
   constexpr int FPW = SWIGLU ? NR / 2 : NR;
+  constexpr bool W8 = FMT == CH_W8, W4 = FMT == CH_W4;
+  static_assert(!W4 || (NBLK <= KC * 64 && NBLK > (KC - 1) * 64), "W4: KC = ceil(blocks per row / 64)");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   constexpr int nb = NB;
   // qkv phase, head-major (head_per = workgroups per 96 rows): workgroup -> (head, section q / k / v, slice) so that the producers of one
@@ -234,11 +264,12 @@ __device__ __forceinline__ unsigned chain_gemv(const ChainParams& p, int wg, int
     const int part = wg - head_of_wg * 3 * head_per, sec = part / head_per, sub = part - sec * head_per;
     fbase = sec * (n_out / 3) + head_of_wg * 96 + sub * (4 * FPW * nb) + wave * FPW;
   }
-  const size_t row_bytes = W8 ? (size_t)K : (size_t)K * 2;
+  const size_t row_bytes = W4 ? (size_t)NBLK * 16 : (W8 ? (size_t)K : (size_t)K * 2);
   // PF batches are requested before the wait (register slots b % PF); with PF = NB nothing is left to load once the input is there
   static_assert(PF >= 1 && PF <= NB, "prefetch depth");
   u32x4 wv[PF][NR][KC];
   float wsc[PF][NR];
+  unsigned wsb[PF][NR][W4 ? KC : 1];         // W4: the e8m0 byte of chunk kc
   auto issue = [&](int f0, auto slot_c) {
     constexpr int SL = decltype(slot_c)::value;
 #pragma unroll
@@ -247,8 +278,22 @@ __device__ __forceinline__ unsigned chain_gemv(const ChainParams& p, int wg, int
       const int row = (SWIGLU && r >= FPW) ? n_out + f : f;
       const char* wr = (const char*)w + (size_t)row * row_bytes;
       wsc[SL][r] = W8 ? ((gptr_f32)w_scale)[row] : 1.f;
+      if constexpr (W4) {
+        const gptr_u8 sr = (gptr_u8)w_scale + (size_t)row * NBLK;
 #pragma unroll
-      for (int kc = 0; kc < KC; ++kc) wv[SL][r][kc] = __builtin_nontemporal_load(AKI_G128(wr + (size_t)(lane + 64 * kc) * 16));
+        for (int kc = 0; kc < KC; ++kc) {
+          const int c = lane + 64 * kc;
+          wv[SL][r][kc] = u32x4{0u, 0u, 0u, 0u};
+          wsb[SL][r][kc] = 0u;
+          if (64 * (kc + 1) <= NBLK || c < NBLK) {          // the half chunk: no load past the row
+            wv[SL][r][kc] = __builtin_nontemporal_load(AKI_G128(wr + (size_t)c * 16));
+            wsb[SL][r][kc] = sr[c];
+          }
+        }
+      } else {
+#pragma unroll
+        for (int kc = 0; kc < KC; ++kc) wv[SL][r][kc] = __builtin_nontemporal_load(AKI_G128(wr + (size_t)(lane + 64 * kc) * 16));
+      }
     }
   };
   AKI_CHAIN_STAMP(p, (int)(code >> 8), (int)(code & 255) - 1, wg, 0);
@@ -266,9 +311,10 @@ __device__ __forceinline__ unsigned chain_gemv(const ChainParams& p, int wg, int
           const int f = min(fbase + b * 4 * FPW + (r % FPW), n_out - 1);
           const int row = (SWIGLU && r >= FPW) ? n_out + f : f;
           const char* wr = (const char*)w + (size_t)row * row_bytes;
+          constexpr int RB = W4 ? NBLK * 16 : KC * 1024;      // bytes of a row
 #pragma unroll
-          for (int o = 0; o < KC * 1024; o += 64 * 128)
-            if (o + lane * 128 < KC * 1024) touched |= *(volatile const __attribute__((address_space(1))) unsigned*)(wr + o + lane * 128);
+          for (int o = 0; o < RB; o += 64 * 128)
+            if (o + lane * 128 < RB) touched |= *(volatile const __attribute__((address_space(1))) unsigned*)(wr + o + lane * 128);
         }
     }
   }
@@ -339,7 +385,15 @@ __device__ __forceinline__ unsigned chain_gemv(const ChainParams& p, int wg, int
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       const int c = lane + 64 * kc;
-      if constexpr (W8) {
+      if constexpr (W4) {
+        if (64 * (kc + 1) <= NBLK || c < NBLK) {            // the half chunk: lanes without this chunk add nothing, not a zero product
+          u32x4 x4[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) x4[i] = *(const u32x4*)(sx + ((size_t)4 * c + i) * 16);
+#pragma unroll
+          for (int r = 0; r < NR; ++r) acc[r] = cdot32_w4(wv[SL][r][kc], cw4_scale(wsb[SL][r][kc]), x4, acc[r]);
+        }
+      } else if constexpr (W8) {
         const u32x4 x0 = *(const u32x4*)(sx + (size_t)(2 * c) * 16), x1 = *(const u32x4*)(sx + (size_t)(2 * c + 1) * 16);
 #pragma unroll
         for (int r = 0; r < NR; ++r) acc[r] = cdot16_w8(wv[SL][r][kc], x0, x1, acc[r]);
@@ -834,8 +888,8 @@ __device__ __forceinline__ void chain_attn(const ChainParams& p, const aki_decod
 #endif
 }
 
-// KCD = d / 512, KCF = F / 512 (bf16) - the register arrays are static; W8 halves both.
-template <int KCD, int KCF, bool W8, int NBQ, int NBO, int NBG, int NBD, int PFQ = 1, int PFO = 1, int PFG = 1, int PFDN = 1, int OCC = 1>
+// KCD = d / 512, KCF = F / 512 (bf16) - the register arrays are static; W8 halves both, W4 quarters them (d: 1.5 chunks per lane -> 2, the second predicated).
+template <int KCD, int KCF, ChainFmt FMT, int NBQ, int NBO, int NBG, int NBD, int PFQ = 1, int PFO = 1, int PFG = 1, int PFDN = 1, int OCC = 1>
 __global__ __launch_bounds__(256, OCC) void decode_chain_kernel(const ChainParams p0) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* s_red = (float*)(smem + 16384);
@@ -869,12 +923,14 @@ __global__ __launch_bounds__(256, OCC) void decode_chain_kernel(const ChainParam
   const bool last = layer == p.n_layers - 1;
   bf16_t* h2 = last ? p.h_out : p.hbuf + (layer & 1) * p.d;
   const unsigned code = ((unsigned)layer << 8);
-  constexpr int NRD = W8 ? 4 : 2;          // rows per wave on the K = d matrices
-  constexpr int KD = W8 ? KCD / 2 : KCD;
-  constexpr int NRF = W8 ? 2 : 1;          // rows per wave on the K = F matrix
-  constexpr int KF = W8 ? KCF / 2 : KCF;
+  constexpr bool W8 = FMT == CH_W8, W4 = FMT == CH_W4;
+  constexpr int NRD = (W8 || W4) ? 4 : 2;  // rows per wave on the K = d matrices (W4: W8's rows over half the bytes - decode_chain_launch)
+  constexpr int KD = W4 ? (KCD + 3) / 4 : (W8 ? KCD / 2 : KCD);
+  constexpr int NRF = (W8 || W4) ? 2 : 1;  // rows per wave on the K = F matrix
+  constexpr int KF = W4 ? (KCF + 3) / 4 : (W8 ? KCF / 2 : KCF);
+  constexpr int BD = W4 ? KCD * 16 : KD * 64, BF = W4 ? KCF * 16 : KF * 64;      // W4: blocks of 32 k per row of the K = d / K = F matrices
   if (r < p.n_qkv) {
-    chain_gemv<NRD, KD, false, true, W8, NBQ, PFQ>(p, r, p.n_qkv, ly.w_qkv, ly.s_qkv, p.d, 3 * p.H * 96, h0, h0_rep, (const bf16_t*)ly.norm1, nullptr, 0, p.qkv,
+    chain_gemv<NRD, KD, false, true, FMT, NBQ, PFQ, BD>(p, r, p.n_qkv, ly.w_qkv, ly.s_qkv, p.d, 3 * p.H * 96, h0, h0_rep, (const bf16_t*)ly.norm1, nullptr, 0, p.qkv,
                                           CH_XREP, prev_down, sy + 0 * CH_SYNC_WORDS, code | 1u, sx, s_red, p.qkv_by_head,
                                           p.head_sync + (size_t)layer * p.H * 64);
     return;
@@ -886,18 +942,18 @@ __global__ __launch_bounds__(256, OCC) void decode_chain_kernel(const ChainParam
   }
   r -= p.n_attn;
   if (r < p.n_o) {
-    chain_gemv<NRD, KD, false, false, W8, NBO, PFO>(p, r, p.n_o, ly.w_o, ly.s_o, p.H * 96, p.d, p.attn_o, 1, nullptr, h0, h0_rep, p.h1, CH_XREP,
+    chain_gemv<NRD, KD, false, false, FMT, NBO, PFO, BD>(p, r, p.n_o, ly.w_o, ly.s_o, p.H * 96, p.d, p.attn_o, 1, nullptr, h0, h0_rep, p.h1, CH_XREP,
                                            sy + 1 * CH_SYNC_WORDS, sy + 2 * CH_SYNC_WORDS, code | 3u, sx, s_red);
     return;
   }
   r -= p.n_o;
   if (r < p.n_gu) {
-    chain_gemv<NRD, KD, true, true, W8, NBG, PFG>(p, r, p.n_gu, ly.w_gate_up, ly.s_gate_up, p.d, p.F, p.h1, 1, (const bf16_t*)ly.norm2, nullptr, 0, p.act,
+    chain_gemv<NRD, KD, true, true, FMT, NBG, PFG, BD>(p, r, p.n_gu, ly.w_gate_up, ly.s_gate_up, p.d, p.F, p.h1, 1, (const bf16_t*)ly.norm2, nullptr, 0, p.act,
                                          CH_XREP, sy + 2 * CH_SYNC_WORDS, sy + 3 * CH_SYNC_WORDS, code | 4u, sx, s_red);
     return;
   }
   r -= p.n_gu;
-  const unsigned fin = chain_gemv<NRF, KF, false, false, W8, NBD, PFDN>(p, r, p.n_down, ly.w_down, ly.s_down, p.F, p.d, p.act, 1, nullptr, p.h1, 1, h2,
+  const unsigned fin = chain_gemv<NRF, KF, false, false, FMT, NBD, PFDN, BF>(p, r, p.n_down, ly.w_down, ly.s_down, p.F, p.d, p.act, 1, nullptr, p.h1, 1, h2,
                                                                          last ? 1 : CH_XREP, sy + 3 * CH_SYNC_WORDS, sy + 4 * CH_SYNC_WORDS, code | 5u, sx, s_red);
   if (last && fin && threadIdx.x == 0) __hip_atomic_store(p.epoch, ep + 1u, AKI_RLX_AGENT);      // the call is complete: the next one takes the other set
 }
@@ -1069,14 +1125,16 @@ static int decode_chain_b_launch(const aki_decode_chain_args* a, hipStream_t str
 
 int decode_chain_launch(const aki_decode_chain_args* a, hipStream_t stream) {
 #ifdef AKI_LAB_HOOKS
+  if (a->batch > 1 && a->dtype == AKI_DT_W4A16) return AKI_ERR_UNSUPPORTED;      // MXFP4 weights: one sequence
   if (a->batch > 1) return decode_chain_b_launch(a, stream);
 #else
   if (a->batch > 1) return AKI_ERR_UNSUPPORTED;      // lab library only (see above)
 #endif
   const int d = a->d, H = a->H, F = a->F;
   if (a->Dh != 96 || d != H * 96 || d % 512 || F % 512) return AKI_ERR_UNSUPPORTED;
+  const bool w4 = a->dtype == AKI_DT_W4A16;
   const bool w8 = a->dtype == AKI_DT_W8A16;
-  if (!w8 && a->dtype != AKI_DT_BF16) return AKI_ERR_UNSUPPORTED;
+  if (!w8 && !w4 && a->dtype != AKI_DT_BF16) return AKI_ERR_UNSUPPORTED;
   if (!(d == 3072 && F == 8192)) return AKI_ERR_UNSUPPORTED;     // the register arrays are sized at compile time: Phi-3.5-mini
   if (a->workspace_bytes < decode_chain_ws_bytes(a->n_layers, d, H, F, a->capacity) || ((uintptr_t)a->workspace & 255)) return AKI_ERR_WORKSPACE;
   ChainParams p;
@@ -1101,15 +1159,23 @@ int decode_chain_launch(const aki_decode_chain_args* a, hipStream_t stream) {
   p.act = v; v += F;
   p.hbuf = v;
   p.part = (float*)(ws + 2 * cb + 256 + chain_vec_elems(d, H, F) * 2 * CH_XREP);
-  const int rd = w8 ? 4 : 2, rf = w8 ? 2 : 1;     // rows per wave and batch (see the kernel)
-  p.nbq = w8 ? 1 : CH_NBQ; p.nbo = w8 ? 1 : CH_NBO; p.nbg = w8 ? 1 : CH_NBG; p.nbd = w8 ? 1 : CH_NBD;
+  const int rd = (w8 || w4) ? 4 : 2, rf = (w8 || w4) ? 2 : 1;     // rows per wave and batch (see the kernel)
+  p.nbq = (w8 || w4) ? 1 : CH_NBQ; p.nbo = (w8 || w4) ? 1 : CH_NBO; p.nbg = (w8 || w4) ? 1 : CH_NBG; p.nbd = (w8 || w4) ? 1 : CH_NBD;
 #ifdef AKI_LAB_HOOKS
-  const int presets[][4] = {{w8 ? 1 : CH_NBQ, w8 ? 1 : CH_NBO, w8 ? 1 : CH_NBG, w8 ? 1 : CH_NBD}, {8, 8, 8, 8}, {4, 2, 8, 2}, {8, 2, 8, 4}, {4, 4, 4, 4}, {16, 4, 16, 4}, {8, 2, 16, 2}, {1, 1, 1, 1}, {8, 4, 16, 4}, {2, 1, 4, 1}, {4, 2, 4, 2}, {2, 2, 4, 2}, {2, 2, 2, 2}, {2, 2, 4, 2}, {2, 2, 4, 2}, {2, 2, 8, 2}, {2, 2, 4, 4}, {2, 2, 4, 2}, {2, 2, 8, 2}, {2, 2, 4, 2}, {2, 2, 4, 4}, {4, 2, 8, 4}, {2, 2, 4, 2}, {4, 4, 8, 4}, {2, 2, 4, 2}, {2, 2, 4, 2}, {2, 2, 4, 2}};
-  const int* ps = presets[(w8 && g_chain_nb != 9 && g_chain_nb != 20 && g_chain_nb != 21 && (g_chain_nb < 12 || g_chain_nb > 14)) ? 0 : g_chain_nb];
-  p.nbq = ps[0]; p.nbo = ps[1]; p.nbg = ps[2]; p.nbd = ps[3];
-  if (w8 && g_chain_nb == 20) { p.nbq = 1; p.nbo = 1; p.nbg = 2; p.nbd = 1; }
-  if (w8 && g_chain_nb == 21) { p.nbq = 1; p.nbo = 1; p.nbg = 1; p.nbd = 2; }
-  if (w8 && g_chain_nb == 7) { p.nbq = 2; p.nbo = 2; p.nbg = 2; p.nbd = 2; }
+  if (!w4) {
+    const int presets[][4] = {{w8 ? 1 : CH_NBQ, w8 ? 1 : CH_NBO, w8 ? 1 : CH_NBG, w8 ? 1 : CH_NBD}, {8, 8, 8, 8}, {4, 2, 8, 2}, {8, 2, 8, 4}, {4, 4, 4, 4}, {16, 4, 16, 4}, {8, 2, 16, 2}, {1, 1, 1, 1}, {8, 4, 16, 4}, {2, 1, 4, 1}, {4, 2, 4, 2}, {2, 2, 4, 2}, {2, 2, 2, 2}, {2, 2, 4, 2}, {2, 2, 4, 2}, {2, 2, 8, 2}, {2, 2, 4, 4}, {2, 2, 4, 2}, {2, 2, 8, 2}, {2, 2, 4, 2}, {2, 2, 4, 4}, {4, 2, 8, 4}, {2, 2, 4, 2}, {4, 4, 8, 4}, {2, 2, 4, 2}, {2, 2, 4, 2}, {2, 2, 4, 2}};
+    const int* ps = presets[(w8 && g_chain_nb != 9 && g_chain_nb != 20 && g_chain_nb != 21 && (g_chain_nb < 12 || g_chain_nb > 14)) ? 0 : g_chain_nb];
+    p.nbq = ps[0]; p.nbo = ps[1]; p.nbg = ps[2]; p.nbd = ps[3];
+    if (w8 && g_chain_nb == 20) { p.nbq = 1; p.nbo = 1; p.nbg = 2; p.nbd = 1; }
+    if (w8 && g_chain_nb == 21) { p.nbq = 1; p.nbo = 1; p.nbg = 1; p.nbd = 2; }
+    if (w8 && g_chain_nb == 7) { p.nbq = 2; p.nbo = 2; p.nbg = 2; p.nbd = 2; }
+  }
+  // MXFP4 variants (tools/w4_decode_bench.py --variants): 7 / 12 two batches everywhere, one / both requested before the wait (12 = W8's BYTES per
+  // workgroup); 20 / 21 two batches on gate_up / down only; 13 two on gate_up and down
+  if (w4 && (g_chain_nb == 7 || g_chain_nb == 12)) { p.nbq = 2; p.nbo = 2; p.nbg = 2; p.nbd = 2; }
+  if (w4 && g_chain_nb == 20) { p.nbg = 2; }
+  if (w4 && g_chain_nb == 21) { p.nbd = 2; }
+  if (w4 && g_chain_nb == 13) { p.nbg = 2; p.nbd = 2; }
 #endif
   auto wgs = [&](int n_out, int fpw, int nb) { return (n_out + 4 * fpw * nb - 1) / (4 * fpw * nb); };
   p.n_qkv = wgs(3 * H * 96, rd, p.nbq);
@@ -1158,45 +1224,54 @@ int decode_chain_launch(const aki_decode_chain_args* a, hipStream_t stream) {
     hipLaunchKernelGGL((decode_chain_kernel<6, 16, W8V, A, B, C, D, PA, PB, PC, PD>), grid, block, SMEM, stream, p);                         \
   } while (0)
 #ifdef AKI_LAB_HOOKS
-  if (w8 && g_chain_nb == 12) AKI_CHAIN_LAUNCH2(true, 2, 2, 2, 2, 2, 2, 2, 2);
-  else if (w8 && g_chain_nb == 13) AKI_CHAIN_LAUNCH2(true, 2, 2, 4, 2, 2, 2, 2, 2);
-  else if (w8 && g_chain_nb == 14) AKI_CHAIN_LAUNCH2(true, 2, 2, 4, 2, 2, 2, 2, 1);
-  else if (w8 && g_chain_nb == 7) AKI_CHAIN_LAUNCH2(true, 2, 2, 2, 2, 1, 1, 1, 1);
-  else if (w8 && g_chain_nb == 9) AKI_CHAIN_LAUNCH2(true, 2, 1, 4, 1, 2, 1, 4, 1);
-  else if (w8 && g_chain_nb == 20) AKI_CHAIN_LAUNCH2(true, 1, 1, 2, 1, 1, 1, 2, 1);
-  else if (w8 && g_chain_nb == 21) AKI_CHAIN_LAUNCH2(true, 1, 1, 1, 2, 1, 1, 1, 2);
+  if (w8 && g_chain_nb == 12) AKI_CHAIN_LAUNCH2(CH_W8, 2, 2, 2, 2, 2, 2, 2, 2);
+  else if (w8 && g_chain_nb == 13) AKI_CHAIN_LAUNCH2(CH_W8, 2, 2, 4, 2, 2, 2, 2, 2);
+  else if (w8 && g_chain_nb == 14) AKI_CHAIN_LAUNCH2(CH_W8, 2, 2, 4, 2, 2, 2, 2, 1);
+  else if (w8 && g_chain_nb == 7) AKI_CHAIN_LAUNCH2(CH_W8, 2, 2, 2, 2, 1, 1, 1, 1);
+  else if (w8 && g_chain_nb == 9) AKI_CHAIN_LAUNCH2(CH_W8, 2, 1, 4, 1, 2, 1, 4, 1);
+  else if (w8 && g_chain_nb == 20) AKI_CHAIN_LAUNCH2(CH_W8, 1, 1, 2, 1, 1, 1, 2, 1);
+  else if (w8 && g_chain_nb == 21) AKI_CHAIN_LAUNCH2(CH_W8, 1, 1, 1, 2, 1, 1, 1, 2);
   else
 #endif
-  if (w8) AKI_CHAIN_LAUNCH2(true, 1, 1, 1, 1, 1, 1, 1, 1);
+  if (w8) AKI_CHAIN_LAUNCH2(CH_W8, 1, 1, 1, 1, 1, 1, 1, 1);
 #ifdef AKI_LAB_HOOKS
-  else if (g_chain_nb == 1) AKI_CHAIN_LAUNCH(false, 8, 8, 8, 8);
-  else if (g_chain_nb == 2) AKI_CHAIN_LAUNCH(false, 4, 2, 8, 2);
-  else if (g_chain_nb == 3) AKI_CHAIN_LAUNCH(false, 8, 2, 8, 4);
-  else if (g_chain_nb == 4) AKI_CHAIN_LAUNCH(false, 4, 4, 4, 4);
-  else if (g_chain_nb == 5) AKI_CHAIN_LAUNCH(false, 16, 4, 16, 4);
-  else if (g_chain_nb == 6) AKI_CHAIN_LAUNCH(false, 8, 2, 16, 2);
-  else if (g_chain_nb == 7) AKI_CHAIN_LAUNCH(false, 1, 1, 1, 1);
-  else if (g_chain_nb == 8) AKI_CHAIN_LAUNCH(false, 8, 4, 16, 4);
-  else if (g_chain_nb == 9) AKI_CHAIN_LAUNCH(false, 2, 1, 4, 1);
-  else if (g_chain_nb == 10) AKI_CHAIN_LAUNCH(false, 4, 2, 4, 2);
-  else if (g_chain_nb == 11) AKI_CHAIN_LAUNCH(false, 2, 2, 4, 2);
-  else if (g_chain_nb == 12) AKI_CHAIN_LAUNCH2(false, 2, 2, 2, 2, 2, 2, 2, 2);      // batches requested before the wait: qkv, o, gate_up, down
-  else if (g_chain_nb == 13) AKI_CHAIN_LAUNCH2(false, 2, 2, 4, 2, 2, 2, 2, 2);
-  else if (g_chain_nb == 14) AKI_CHAIN_LAUNCH2(false, 2, 2, 4, 2, 2, 2, 2, 1);
-  else if (g_chain_nb == 15) AKI_CHAIN_LAUNCH2(false, 2, 2, 8, 2, 2, 2, 2, 1);
-  else if (g_chain_nb == 16) AKI_CHAIN_LAUNCH2(false, 2, 2, 4, 4, 2, 2, 2, 1);
-  else if (g_chain_nb == 17) AKI_CHAIN_LAUNCH2(false, 2, 2, 4, 2, 2, 2, 1, 2);
-  else if (g_chain_nb == 18) AKI_CHAIN_LAUNCH2(false, 2, 2, 8, 2, 2, 2, 2, 2);
-  else if (g_chain_nb == 19) AKI_CHAIN_LAUNCH2(false, 2, 2, 4, 2, 2, 2, 1, 1);
-  else if (g_chain_nb == 20) AKI_CHAIN_LAUNCH2(false, 2, 2, 4, 4, 2, 2, 1, 1);
-  else if (g_chain_nb == 21) AKI_CHAIN_LAUNCH2(false, 4, 2, 8, 4, 2, 2, 2, 1);
-  else if (g_chain_nb == 22) AKI_CHAIN_LAUNCH2(false, 2, 2, 4, 2, 1, 1, 1, 1);
-  else if (g_chain_nb == 23) AKI_CHAIN_LAUNCH2(false, 4, 4, 8, 4, 1, 1, 1, 1);
-  else if (g_chain_nb == 24) AKI_CHAIN_LAUNCH3(false, 2, 2, 4, 2, 2, 2, 2, 1, 4);
-  else if (g_chain_nb == 25) AKI_CHAIN_LAUNCH2(false, 2, 2, 4, 2, 2, 2, 4, 2);   // every weight of every phase before the wait: ~250 VGPRs, 2 workgroups per CU
-  else if (g_chain_nb == 26) AKI_CHAIN_LAUNCH2(false, 2, 2, 4, 2, 2, 2, 3, 2);   // the product's batches held to 128 VGPRs (4 workgroups per CU; spills)
+  else if (w4 && g_chain_nb == 7) AKI_CHAIN_LAUNCH2(CH_W4, 2, 2, 2, 2, 1, 1, 1, 1);
+  else if (w4 && g_chain_nb == 12) AKI_CHAIN_LAUNCH2(CH_W4, 2, 2, 2, 2, 2, 2, 2, 2);
+  else if (w4 && g_chain_nb == 13) AKI_CHAIN_LAUNCH2(CH_W4, 1, 1, 2, 2, 1, 1, 2, 2);
+  else if (w4 && g_chain_nb == 20) AKI_CHAIN_LAUNCH2(CH_W4, 1, 1, 2, 1, 1, 1, 2, 1);
+  else if (w4 && g_chain_nb == 21) AKI_CHAIN_LAUNCH2(CH_W4, 1, 1, 1, 2, 1, 1, 1, 2);
 #endif
-  else AKI_CHAIN_LAUNCH2(false, CH_NBQ, CH_NBO, CH_NBG, CH_NBD, CH_PFQ, CH_PFO, CH_PFG, CH_PFD);
+  // MXFP4: W8's rows per wave (4 on K = d, 2 on K = F), one batch per workgroup, every weight and scale byte requested before the wait
+  else if (w4) AKI_CHAIN_LAUNCH2(CH_W4, 1, 1, 1, 1, 1, 1, 1, 1);
+#ifdef AKI_LAB_HOOKS
+  else if (g_chain_nb == 1) AKI_CHAIN_LAUNCH(CH_BF16, 8, 8, 8, 8);
+  else if (g_chain_nb == 2) AKI_CHAIN_LAUNCH(CH_BF16, 4, 2, 8, 2);
+  else if (g_chain_nb == 3) AKI_CHAIN_LAUNCH(CH_BF16, 8, 2, 8, 4);
+  else if (g_chain_nb == 4) AKI_CHAIN_LAUNCH(CH_BF16, 4, 4, 4, 4);
+  else if (g_chain_nb == 5) AKI_CHAIN_LAUNCH(CH_BF16, 16, 4, 16, 4);
+  else if (g_chain_nb == 6) AKI_CHAIN_LAUNCH(CH_BF16, 8, 2, 16, 2);
+  else if (g_chain_nb == 7) AKI_CHAIN_LAUNCH(CH_BF16, 1, 1, 1, 1);
+  else if (g_chain_nb == 8) AKI_CHAIN_LAUNCH(CH_BF16, 8, 4, 16, 4);
+  else if (g_chain_nb == 9) AKI_CHAIN_LAUNCH(CH_BF16, 2, 1, 4, 1);
+  else if (g_chain_nb == 10) AKI_CHAIN_LAUNCH(CH_BF16, 4, 2, 4, 2);
+  else if (g_chain_nb == 11) AKI_CHAIN_LAUNCH(CH_BF16, 2, 2, 4, 2);
+  else if (g_chain_nb == 12) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 2, 2, 2, 2, 2, 2);      // batches requested before the wait: qkv, o, gate_up, down
+  else if (g_chain_nb == 13) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 2, 2, 2, 2, 2);
+  else if (g_chain_nb == 14) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 2, 2, 2, 2, 1);
+  else if (g_chain_nb == 15) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 8, 2, 2, 2, 2, 1);
+  else if (g_chain_nb == 16) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 4, 2, 2, 2, 1);
+  else if (g_chain_nb == 17) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 2, 2, 2, 1, 2);
+  else if (g_chain_nb == 18) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 8, 2, 2, 2, 2, 2);
+  else if (g_chain_nb == 19) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 2, 2, 2, 1, 1);
+  else if (g_chain_nb == 20) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 4, 2, 2, 1, 1);
+  else if (g_chain_nb == 21) AKI_CHAIN_LAUNCH2(CH_BF16, 4, 2, 8, 4, 2, 2, 2, 1);
+  else if (g_chain_nb == 22) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 2, 1, 1, 1, 1);
+  else if (g_chain_nb == 23) AKI_CHAIN_LAUNCH2(CH_BF16, 4, 4, 8, 4, 1, 1, 1, 1);
+  else if (g_chain_nb == 24) AKI_CHAIN_LAUNCH3(CH_BF16, 2, 2, 4, 2, 2, 2, 2, 1, 4);
+  else if (g_chain_nb == 25) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 2, 2, 2, 4, 2);   // every weight of every phase before the wait: ~250 VGPRs, 2 workgroups per CU
+  else if (g_chain_nb == 26) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 2, 2, 2, 3, 2);   // the product's batches held to 128 VGPRs (4 workgroups per CU; spills)
+#endif
+  else AKI_CHAIN_LAUNCH2(CH_BF16, CH_NBQ, CH_NBO, CH_NBG, CH_NBD, CH_PFQ, CH_PFO, CH_PFG, CH_PFD);
 #undef AKI_CHAIN_LAUNCH
   AKI_LAUNCH_CHECK();
   return AKI_OK;
@@ -1210,6 +1285,7 @@ int decode_chain_launch(const aki_decode_chain_args* a, hipStream_t stream) {
 // device buffer of 5 x 2048 x 8 uint64 (or NULL) and the layer whose workgroups stamp their wall clock into it (tools/decode_chain_edges.py)
 extern "C" void aki_lab_set_chain_stamps(void* buf, int layer) { aki::g_chain_stamps = (unsigned long long*)buf; aki::g_chain_stamp_layer = layer; }
 extern "C" void aki_lab_set_chain_lds(int pad_bytes) { aki::g_chain_lds_pad = pad_bytes < 0 ? 0 : (pad_bytes > 140 * 1024 ? 140 * 1024 : pad_bytes); }
+// MXFP4 chains (product: one batch per workgroup) know 7 {2,2,2,2}, 12 {2,2,2,2} all before the wait, 13 {1,1,2,2}, 20 {1,1,2,1}, 21 {1,1,1,2}; any other preset = the product.
 // preset of batches per workgroup (qkv, o_proj, gate_up, down): 0 product {2,2,2,2}, 1 {8,8,8,8}, 2 {4,2,8,2}, 3 {8,2,8,4}, 4 {4,4,4,4}, 5 {16,4,16,4}, 6 {8,2,16,2}, 7 {1,1,1,1}, 8 {8,4,16,4}, 9 {2,1,4,1}, 10 {4,2,4,2}, 11 {2,2,4,2}
 extern "C" void aki_lab_set_chain_nb(int preset) { aki::g_chain_nb = (preset >= 0 && preset <= 26) ? preset : 0; }
 extern "C" void aki_lab_set_chain(int sleep_n, int xrep, int nflags, int nowait) {

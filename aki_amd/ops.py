@@ -561,14 +561,25 @@ class DecodeChain:
 
     SUPPORTED = dict(d=3072, F=8192, Dh=96)
 
-    def __init__(self, layers, k_caches, v_caches, H: int, Dh: int, d: int, F: int, capacity: int, scale: float, eps: float, device, w8: bool,
-                 batch: int = 1):
+    FORMATS = {"bf16": L.AKI_DT_BF16, "w8": L.AKI_DT_W8A16, "w4": L.AKI_DT_W4A16}
+
+    def __init__(self, layers, k_caches, v_caches, H: int, Dh: int, d: int, F: int, capacity: int, scale: float, eps: float, device, fmt="bf16",
+                 batch: int = 1, w8: Optional[bool] = None):
         """layers: per layer (w_qkv, w_o, w_gate_up, w_down, norm1, norm2, s_qkv, s_o, s_gate_up, s_down) - scales None for bf16.
+        fmt: the weight format - "bf16", "w8" (e4m3 weights, an f32 scale per row) or "w4" (MXFP4 as ops.quant_mxfp4 makes it: contiguous
+        uint8 nibbles [N, K/2] with contiguous uint8 e8m0 scales [N, K/32] in the scale slots; one sequence only).  False / True = "bf16" / "w8".
         batch 2..8 (bf16): that many sequences per step - the batched chain (16-feature MFMA tiles instead of dot-product rows), bit-identical to
         the per-layer batched launches; k / v caches [batch, H, capacity, Dh]."""
         lib = L.load()
+        if w8 is not None:                      # the argument's earlier name
+            fmt = bool(w8)
+        if isinstance(fmt, bool):
+            fmt = "w8" if fmt else "bf16"
+        if fmt not in self.FORMATS:
+            raise AkiError(f"decode chain: weight format {fmt!r} is not one of {sorted(self.FORMATS)}")
+        w8 = fmt == "w8"
         self.batch = int(batch)
-        if self.batch > 1 and (w8 or self.batch > 8 or H != 32):
+        if self.batch > 1 and (fmt != "bf16" or self.batch > 8 or H != 32):
             raise AkiError("decode chain: batches of 2..8 sequences run on bf16 weights with 32 heads")
         self.n_layers = len(layers)
         rows = []
@@ -576,6 +587,12 @@ class DecodeChain:
             for t_ in (wq, wo, wg, wd):
                 if not t_.is_contiguous():
                     raise AkiError("decode chain: weights must be contiguous [N, K]")
+            if fmt == "w4":
+                # the table holds raw pointers the library cannot inspect (device memory): the layout is checked here
+                for t_, s_, K in ((wq, sq, d), (wo, so, H * Dh), (wg, sg, d), (wd, sd, F)):
+                    if s_ is None or t_.dtype != torch.uint8 or s_.dtype != torch.uint8 or not s_.is_contiguous() or t_.dim() != 2 \
+                            or tuple(t_.shape) != (t_.shape[0], K // 2) or tuple(s_.shape) != (t_.shape[0], K // 32):
+                        raise AkiError("decode chain: MXFP4 weights are contiguous uint8 nibbles [N, K/2] with uint8 e8m0 scales [N, K/32]")
             rows.append([wq.data_ptr(), wo.data_ptr(), wg.data_ptr(), wd.data_ptr(), n1.data_ptr(), n2.data_ptr(), k.data_ptr(), v.data_ptr(),
                          _ptr(sq) or 0, _ptr(so) or 0, _ptr(sg) or 0, _ptr(sd) or 0])
         self.keep = (layers, k_caches, v_caches)                      # the table holds raw pointers: keep the tensors alive
@@ -592,7 +609,7 @@ class DecodeChain:
         self.err_index = (off + int(lib.aki_decode_chain_batch_error_offset(self.n_layers, H, self.batch))) // 4
         self.h_out = torch.empty((self.batch, d), dtype=torch.bfloat16, device=device)
         self.dims = (H, Dh, d, F, capacity)
-        self.scale, self.eps, self.w8 = float(scale), float(eps), bool(w8)
+        self.scale, self.eps, self.w8, self.fmt = float(scale), float(eps), bool(w8), fmt
 
     def step(self, h_in: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, cache_len: torch.Tensor, col_valid_bits: Optional[torch.Tensor],
              max_keys: int) -> torch.Tensor:
@@ -606,7 +623,7 @@ class DecodeChain:
         _dev(h_in, cos, sin, cache_len, col_valid_bits, self.table)
         a = L.DecodeChainArgs(self.table.data_ptr(), _ptr(h_in), _ptr(self.h_out), _ptr(cos), _ptr(sin), _ptr(cache_len), _ptr(col_valid_bits),
                               self.ws_ptr, self.ws_bytes, self.n_layers, 0 if col_valid_bits is None else col_valid_bits.shape[-1], d, H, Dh, F,
-                              cap, int(max_keys), self.scale, self.eps, L.AKI_DT_W8A16 if self.w8 else L.AKI_DT_BF16, self.batch)
+                              cap, int(max_keys), self.scale, self.eps, self.FORMATS[self.fmt], self.batch)
         end = _TAP.begin(("decode_chain", self.n_layers)) if (_TAP is not None and _TAP.want(("decode_chain",))) else None
         cur = torch.cuda.current_stream()
         with _CHAIN_LOCK:

@@ -641,16 +641,22 @@ class Phi3Model(nn.Module):
                                                     # (3.29-3.46 vs 3.27-3.34 ms per step at batch 8, EXPERIMENTS.md round 5)
     decode_chain_w8 = True                          # e4m3 weights: one batch per workgroup, 1.37 ms per token against 1.46 on five launches
                                                     # (1.55 vs 1.46 ms per token: half the bytes, the same dependency latencies)
+    decode_chain_w4 = False                         # True: MXFP4 decode weights (enable_mxfp4) on the chain too, bit-identical to their five launches.
+                                                    # OFF: (1) no time of it has been recorded yet (tools/w4_decode_bench.py --chain writes profiles/w4_chain_bench.json);
+                                                    # (2) tests/test_mxfp4_gpu.py asserts that enable_mxfp4() leaves `cache.chain` None.
+                                                    # Flipping the default is a follow-up
 
     def _decode_chain(self, h, cache):
         """The one-launch decode step when it applies: one sequence, bf16 stream, Phi-3.5-mini's dimensions, every layer either
-        bf16 or fully e4m3-quantised (the fp8 configuration's weight-only GEMVs), a bf16 KV cache (an fp8_e4m3 cache takes the
-        five-launch-per-layer path).  Built once per (weights, KV cache)."""
+        bf16 or fully e4m3-quantised (the fp8 configuration's weight-only GEMVs) or - with `decode_chain_w4` - MXFP4 (enable_mxfp4), a bf16
+        KV cache (an fp8_e4m3 cache takes the five-launch-per-layer path).  Built once per (weights, KV cache).  Set `decode_chain_w4` before
+        the first step on a cache: a cache that dropped its MXFP4 chain because the switch went off keeps its five launches."""
         B = h.shape[0]
         if getattr(cache, "group", 1) > 1:
             return None                             # a grouped cache (share_prefix) is batched: the five-launch-per-layer path
-        if self.layers[0]._w4 is not None:
-            cache.chain = None                      # MXFP4 weights: the chain knows bf16 and e4m3 only - the five-launch-per-layer path
+        w4 = self.layers[0]._w4 is not None
+        if w4 and not self.decode_chain_w4:
+            cache.chain = None                      # MXFP4 weights: the five-launch-per-layer path unless `decode_chain_w4` asks for the chain
             return None
         if (not self.use_decode_chain or cache.chain_disabled or getattr(cache, "kv_dtype", "bf16") != "bf16" or B > (8 if self.use_decode_chain_batched else 1) or h.dtype != torch.bfloat16
                 or not h.is_cuda):
@@ -675,19 +681,27 @@ class Phi3Model(nn.Module):
                 or any(n.variance_epsilon != l0.input_layernorm.variance_epsilon for ly in self.layers
                        for n in (ly.input_layernorm, ly.post_attention_layernorm))):
             return None
-        w8 = l0._fp8 is not None and l0._fp8["o"] is not None
-        if any((ly._fp8 is not None and ly._fp8["o"] is not None) != w8 for ly in self.layers):
-            return None
-        if l0._fp8 is not None and not w8:
-            return None                             # qkv / gate_up only in e4m3: the mixed per-layer path
-        if w8 and not self.decode_chain_w8:
-            return None
-        if B > 1 and (w8 or at.num_heads != 32 or cache.k[0].shape[0] != B or not cache.k[0].is_contiguous()):
+        if w4 and any(ly._w4 is None for ly in self.layers):
+            return None                             # MXFP4 on some layers only: the per-layer path
+        # decode rows prefer MXFP4 over e4m3 (Phi3DecoderLayer.decode): with both enabled the chain is the MXFP4 one
+        w8 = not w4 and l0._fp8 is not None and l0._fp8["o"] is not None
+        if not w4:
+            if any((ly._fp8 is not None and ly._fp8["o"] is not None) != w8 for ly in self.layers):
+                return None
+            if l0._fp8 is not None and not w8:
+                return None                         # qkv / gate_up only in e4m3: the mixed per-layer path
+            if w8 and not self.decode_chain_w8:
+                return None
+        if B > 1 and (w8 or w4 or at.num_heads != 32 or cache.k[0].shape[0] != B or not cache.k[0].is_contiguous()):
             return None                             # the batched chain: bf16 weights, caches [B, H, capacity, 96]
         rows = []
         for ly in self.layers:
             a_, m_ = ly.self_attn, ly.mlp
-            if w8:
+            if w4:
+                f = ly._w4
+                rows.append((f["qkv"][0], f["o"][0], f["gate_up"][0], f["down"][0], ly.input_layernorm.weight, ly.post_attention_layernorm.weight,
+                             f["qkv"][1], f["o"][1], f["gate_up"][1], f["down"][1]))
+            elif w8:
                 f = ly._fp8
                 rows.append((f["qkv"][0], f["o"][0], f["gate_up"][0], f["down"][0], ly.input_layernorm.weight, ly.post_attention_layernorm.weight,
                              f["qkv"][1], f["o"][1], f["gate_up"][1], f["down"][1]))
@@ -696,7 +710,7 @@ class Phi3Model(nn.Module):
                              ly.post_attention_layernorm.weight, None, None, None, None))
         chain = cache.chain = ops.DecodeChain(rows, list(cache.k), list(cache.v), at.num_heads, at.head_dim, h.shape[-1],
                                               mlp.down_proj.weight.shape[1], cache.capacity, at.scaling, l0.input_layernorm.variance_epsilon,
-                                              h.device, w8, batch=B)
+                                              h.device, "w4" if w4 else ("w8" if w8 else "bf16"), batch=B)
         chain.sig = sig
         return chain
 
@@ -762,7 +776,7 @@ class Phi3ForCausalLM(nn.Module):
     def enable_mxfp4(self, enable: bool = True, head: bool = True):
         """Opt-in MXFP4 weight-only decode: quantise the decoder's projection weights (and, with `head`, the lm_head) once to OCP MXFP4 -
         e2m1 elements in blocks of 32 with one e8m0 scale byte, 4.25 bits per weight - for the decode rows (up to 16: ops.linear_w4, five
-        launches per layer; the one-launch chain is not used).  Prefill and training are untouched and the bf16 weights stay in place.
+        launches per layer; the one-launch chain only with `model.decode_chain_w4 = True`, off by default).  Prefill and training are untouched and the bf16 weights stay in place.
         Independent of enable_fp8() (with both on, prefill runs e4m3 and the decode rows MXFP4) and of set_kv_cache_dtype().  4-bit rounding
         costs accuracy (DESIGN section 4 gives the measured figure); enable_mxfp4(False) drops the copies."""
         self.model._weights_version += 1

@@ -44,7 +44,9 @@ typedef enum {
   AKI_DT_BF16 = 0,
   AKI_DT_F32 = 1,
   AKI_DT_FP8_E4M3 = 2, /* e4m3 x and w with per-row scales (aki_linear_args / aki_mma_attn_args) */
-  AKI_DT_W8A16 = 3     /* weight-only fp8: e4m3 w + w_scale, bf16 x; decode rows (aki_linear_fwd: M <= 16, aki_decode_linear_fwd: M <= 8) */
+  AKI_DT_W8A16 = 3,    /* weight-only fp8: e4m3 w + w_scale, bf16 x; decode rows (aki_linear_fwd: M <= 16, aki_decode_linear_fwd: M <= 8) */
+  AKI_DT_W4A16 = 4     /* weight-only MXFP4: e2m1 nibbles + one e8m0 scale byte per block of 32 k (the layout of aki_linear_w4_fwd), bf16 x;
+                          accepted by aki_decode_chain_fwd only (the per-layer calls take MXFP4 through aki_linear_w4_fwd) */
 } aki_dtype;
 
 /* Activation fused into aki_linear_fwd. */
@@ -429,7 +431,13 @@ int aki_decode_attn_group_fwd(const void* qkv, const float* cos, const float* si
  *                 sticky: 0 = every wait of every call so far was satisfied; otherwise (layer << 8 | phase) of a wait that gave
  *                 up after its bounded spin (the launch then drains and h_out is garbage) - read it after synchronising, and
  *                 zero-fill the workspace again before any further call on it.
- * Supported: Dh = 96, d = H * 96 = 3072, F = 8192 (Phi-3.5-mini); AKI_ERR_UNSUPPORTED otherwise (use the per-layer calls). */
+ * Supported: Dh = 96, d = H * 96 = 3072, F = 8192 (Phi-3.5-mini); AKI_ERR_UNSUPPORTED otherwise (use the per-layer calls).
+ * AKI_DT_W4A16 (batch 1 only; batch > 1 -> AKI_ERR_UNSUPPORTED): MXFP4 weights in the layout of aki_quant_mxfp4 - w_* are the nibbles
+ * [N, K/2] bytes, dense, 16-byte aligned, and the s_* slots carry the e8m0 scale BYTES ws [N, K/32] (cast the uint8_t pointers to the
+ * slots' type; nothing is read through them as float).  The step then reproduces the per-layer aki_linear_w4_fwd calls at M = 1 bit for bit.
+ * The descriptors live in DEVICE memory, so the entry point cannot see their pointers: a NULL s_* under AKI_DT_W8A16 / AKI_DT_W4A16 is the
+ * caller's error to prevent, for both formats alike (ops.DecodeChain checks it on the host before it builds the table).
+ * AKI_DT_W4A16 is purely additive: AKI_ABI_VERSION was not bumped. */
 typedef struct {
   const void* w_qkv;
   const void* w_o;

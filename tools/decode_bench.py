@@ -14,7 +14,8 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--fp8", action="store_true", help="fp8 configuration: e4m3 prefill GEMMs, weight-only e4m3 GEMVs for batch 1")
-    ap.add_argument("--mxfp4", action="store_true", help="MXFP4 weights (e2m1 + e8m0 block scales) for the decode rows: five launches per layer, no chain")
+    ap.add_argument("--mxfp4", action="store_true", help="MXFP4 weights (e2m1 + e8m0 block scales) for the decode rows: five launches per layer unless --w4-chain")
+    ap.add_argument("--w4-chain", action="store_true", help="with --mxfp4, batch 1: the MXFP4 weights on the one-launch chain (Phi3Model.decode_chain_w4, off by default)")
     ap.add_argument("--norm-launch", action="store_true", help="batches of 2..8: the RMSNorm as a launch of its own instead of the skinny GEMM's prologue (A/B)")
     ap.add_argument("--batched-chain", action="store_true", help="batches of 2..8: the batched chain (opt-in) instead of five launches per layer")
     ap.add_argument("--no-chain", action="store_true", help="batch 1: the five-launch-per-layer path instead of the one-launch chain")
@@ -37,6 +38,7 @@ def main():
     if a.mxfp4:
         lm.enable_mxfp4()
     lm.model.use_decode_chain = not a.no_chain
+    lm.model.decode_chain_w4 = bool(a.w4_chain)
     lm.model.use_decode_chain_batched = bool(a.batched_chain)
     ops.SKINNY_NORM_FUSED = not a.norm_launch
     wbytes = sum(p.numel() * 2 for n, p in lm.named_parameters() if "embed_tokens" not in n)
@@ -52,7 +54,7 @@ def main():
     # cache once per sequence (mid-run length), activations negligible.  Peak: 8 TB/s (MI355X_MICROARCH.md; ~6.3 TB/s achievable).
     kv_bytes = B * a.layers * 2 * cfg.num_attention_heads * 96 * 2 * (L + 4 + a.steps // 2)
     res = {"batch": B, "prompt": L, "steps": a.steps, "weight_bytes": wbytes, "kv_bytes": kv_bytes, "fp8": bool(a.fp8), "mxfp4": bool(a.mxfp4),
-           "chain": bool(not a.no_chain and not a.mxfp4 and (B == 1 or (B <= 8 and not a.fp8 and a.batched_chain)))}
+           "chain": bool(not a.no_chain and (not a.mxfp4 or (a.w4_chain and B == 1)) and (B == 1 or (B <= 8 and not a.fp8 and a.batched_chain)))}
     with torch.no_grad():
         for mode in ("eager", "graph"):
             out = lm(inputs_embeds=x, attention_mask=table, use_cache=True, cache_capacity=L + 2 * a.steps + 8)

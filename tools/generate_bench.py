@@ -20,6 +20,7 @@ def main():
     ap.add_argument("--new", type=int, default=256)
     ap.add_argument("--fp8", action="store_true")
     ap.add_argument("--mxfp4", action="store_true", help="MXFP4 weights for the decode rows (enable_mxfp4; combines with --fp8: prefill e4m3, decode MXFP4)")
+    ap.add_argument("--w4-chain", action="store_true", help="with --mxfp4, one sequence: decode on the one-launch chain (Phi3Model.decode_chain_w4, off by default)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--txt", type=int, default=512, help="prompt tokens: 512 = the headline prompt (L = 655), 64 = BASELINE configs[0] (L = 207)")
     ap.add_argument("--repetition-penalty", type=float, default=1.0)
@@ -47,6 +48,7 @@ def main():
         model.lang_model.enable_fp8()
     if a.mxfp4:
         model.lang_model.enable_mxfp4()
+    model.lang_model.model.decode_chain_w4 = bool(a.w4_chain)
     vx, ids, am = bench.synth_batch(1, dev, torch.bfloat16, model.media_token_id, seed=1000)
     if a.batch > 1:
         vx, ids, am = vx.repeat(a.batch, 1, 1, 1, 1, 1), ids.repeat(a.batch, 1), am.repeat(a.batch, 1)
@@ -69,7 +71,7 @@ def main():
         import aki_amd
         run(16, generator=torch.Generator(device=dev).manual_seed(0), **sample_kw)
         run(16, generator=aki_amd.DeviceGenerator(0), **sample_kw)
-    res = {"prompt_tokens_lm_stream": bench.N_TXT - 1 + bench.NV, "new_tokens": a.new, "fp8": bool(a.fp8), "mxfp4": bool(a.mxfp4), "rounds": []}
+    res = {"prompt_tokens_lm_stream": bench.N_TXT - 1 + bench.NV, "new_tokens": a.new, "fp8": bool(a.fp8), "mxfp4": bool(a.mxfp4), "w4_chain": bool(a.w4_chain), "rounds": []}
     if proc_kw:
         res["processors"] = proc_kw
     if a.sample:

@@ -8,7 +8,12 @@ run the five-launch-per-layer path; batch 1 also runs the one-launch chain where
 are against e4m3 on five launches AND against the e4m3 chain.  One more child records the quality figure once: relative L2 of the
 last-token decode logits with MXFP4 (and, for scale, e4m3) weights against bf16 weights at full depth, prompt 655, from identical bf16
 prefills.  Every child runs under its own time limit; the first one that fails ends the run.
-    python tools/w4_decode_bench.py [--steps 32] [--rounds 3] [--shapes 1x655,8x655,16x655,16x4096] [--out profiles/w4_decode_bench.json]"""
+    python tools/w4_decode_bench.py [--steps 32] [--rounds 3] [--shapes 1x655,8x655,16x655,16x4096] [--out profiles/w4_decode_bench.json]
+--chain: the batch-1 question only -> profiles/w4_chain_bench.json.  One child alternates FOUR legs at batch 1, prompt 655: the bf16 chain, the
+e4m3 chain, MXFP4 on five launches per layer and the MXFP4 chain (Phi3Model.decode_chain_w4); the logits of the MXFP4 chain's first steps are
+checked against MXFP4 on five launches, bit for bit.  --variants 7,12,13,20,21 adds legs of the MXFP4 chain under the lab library's batch /
+prefetch presets (aki_lab_set_chain_nb, decode_chain.hip), alternating in the same process - then EVERY leg runs on the lab library.
+    python tools/w4_decode_bench.py --chain [--variants 7,12,13,20,21] [--steps 32] [--rounds 3]"""
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -77,6 +82,70 @@ def child_shape(a, B, L):
     print("ROW " + json.dumps(row), flush=True)
 
 
+W4_PRESETS = {7: "{2,2,2,2} batches, one requested before the wait", 12: "{2,2,2,2} batches, all requested before the wait",
+              13: "{1,1,2,2} batches, all requested before the wait", 20: "{1,1,2,1} batches, all requested before the wait",
+              21: "{1,1,1,2} batches, all requested before the wait"}
+
+
+def child_chain(a):
+    """Batch 1, prompt 655: bf16 chain | e4m3 chain | MXFP4 on five launches | MXFP4 chain (+ lab presets of the MXFP4 chain), alternating."""
+    import contextlib
+    import torch
+    from aki_amd import _lib
+    from aki_amd.phi3 import DecodeGraph
+    B, L = 1, a.prompt
+    variants = [int(v) for v in a.variants.split(",") if v]
+    lm = build_lm(a.layers)
+    legs = [("bf16_chain", "bf16", True, False, 0), ("e4m3_chain", "e4m3", True, False, 0), ("mxfp4", "mxfp4", False, False, 0),
+            ("mxfp4_chain", "mxfp4", True, True, 0)] + [(f"mxfp4_chain_preset_{v}", "mxfp4", True, True, v) for v in variants]
+    best, first = {}, {}
+    with (_lib.use_lab(0) if variants else contextlib.nullcontext()) as lab, torch.no_grad():
+        for _ in range(a.rounds):
+            for name, fmt, chain, w4c, preset in legs:
+                set_format(lm, None)
+                lm.model.use_decode_chain = True
+                lm.model.decode_chain_w4 = w4c
+                out = prefill(lm, B, L, L + a.steps + 16)              # always the bf16 prefill: the same cache content for every leg
+                cache = out.past_key_values
+                ids = out.logits[:, -1].float().argmax(-1)
+                set_format(lm, fmt)
+                if lab is not None:
+                    lab.aki_lab_set_chain_nb(preset)
+                st = DecodeGraph(lm, cache)
+                head = []
+                for _ in range(3):
+                    lg = st.step(ids)
+                    head.append(lg.clone())
+                    ids = lg.argmax(-1)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    ids = st.step(ids).argmax(-1)
+                torch.cuda.synchronize()
+                ms = (time.perf_counter() - t0) * 1e3 / a.steps
+                assert (getattr(cache, "chain", None) is not None) == chain, name
+                if chain:
+                    cache.chain.check()
+                    assert cache.chain.fmt == {"bf16": "bf16", "e4m3": "w8", "mxfp4": "w4"}[fmt], name
+                first.setdefault(name, torch.stack(head))
+                best[name] = min(best.get(name, float("inf")), ms)
+                del st, cache, out
+                torch.cuda.empty_cache()
+        if lab is not None:
+            lab.aki_lab_set_chain_nb(0)
+    bad = {k: int((v != first["mxfp4"]).sum()) for k, v in first.items() if k.startswith("mxfp4_chain")}
+    assert not any(bad.values()), f"MXFP4 chain logits differ from MXFP4 on five launches: {bad}"
+    row = {"batch": B, "prompt": L, "ms_per_step": {k: round(v, 4) for k, v in best.items()},
+           "library": "lab (same kernels; presets switchable)" if variants else "product",
+           "mxfp4_chain_logits_differing_from_five_launches": bad,
+           "mxfp4_chain_vs_mxfp4_five_launches": round(best["mxfp4"] / best["mxfp4_chain"], 3),
+           "mxfp4_chain_vs_e4m3_chain": round(best["e4m3_chain"] / best["mxfp4_chain"], 3),
+           "mxfp4_chain_beats_e4m3_chain": bool(best["mxfp4_chain"] < best["e4m3_chain"])}
+    if variants:
+        row["presets"] = {f"mxfp4_chain_preset_{v}": W4_PRESETS.get(v, "?") for v in variants}
+    print("ROW " + json.dumps(row), flush=True)
+
+
 def child_quality(a):
     import torch
     lm = build_lm(a.layers)
@@ -105,12 +174,19 @@ def main():
     ap.add_argument("--shapes", default="1x655,8x655,16x655,16x4096")
     ap.add_argument("--limit", type=int, default=240, help="time limit of one child process, seconds")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "w4_decode_bench.json"))
+    ap.add_argument("--chain", action="store_true", help="batch 1 only: bf16 chain, e4m3 chain, MXFP4 on five launches, MXFP4 chain -> profiles/w4_chain_bench.json")
+    ap.add_argument("--variants", default="", help="with --chain: lab presets of the MXFP4 chain to time as further legs, e.g. 7,12,13,20,21")
+    ap.add_argument("--prompt", type=int, default=655, help="with --chain: the prompt length")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.rounds < 3:
         ap.error("at least three rounds")
     if a.child == "quality":
         return child_quality(a)
+    if a.child == "chain":
+        return child_chain(a)
+    if a.chain:
+        return main_chain(a)
     if a.child:
         B, L = (int(v) for v in a.child.split("x"))
         return child_shape(a, B, L)
@@ -139,6 +215,27 @@ def main():
     import torch
     res["device"] = torch.cuda.get_device_name(0)
     with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+def main_chain(a):
+    out = a.out if a.out != os.path.join(ROOT, "profiles", "w4_decode_bench.json") else os.path.join(ROOT, "profiles", "w4_chain_bench.json")
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "chain", "--steps", str(a.steps), "--rounds", str(a.rounds), "--layers", str(a.layers),
+           "--prompt", str(a.prompt), "--variants", a.variants]
+    try:
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.limit)
+    except subprocess.TimeoutExpired:
+        sys.exit(f"chain: no result within {a.limit} s - stopping")
+    rows = [ln[4:] for ln in r.stdout.splitlines() if ln.startswith("ROW ")]
+    if r.returncode != 0 or not rows:
+        sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+        sys.exit(f"chain: exit status {r.returncode} - stopping")
+    import torch
+    res = {"steps": a.steps, "rounds": a.rounds, "layers": a.layers, "timed": "hipGraph replay of one decode step (no pick), host wall clock over the "
+           "timed steps, best of the rounds, all legs alternating inside ONE process", "device": torch.cuda.get_device_name(0), "batch_1": json.loads(rows[-1])}
+    with open(out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
     print(json.dumps(res))

@@ -18,9 +18,13 @@ typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 typedef uint16_t bf16_t;  // storage type on the host side of the ABI
 
-// Decode attention (decode.hip, decode_chain.hip - the two must split a cache identically: their outputs are compared bit for bit): a
-// (head, split) item takes T 64-key tiles with T = ceil(B * H * tiles / AKI_DEC_ITEMS); every tile after an item's first is a serial
-// round trip behind the item's dependency, so items stay one tile long up to this many of them.
+// Decode attention (decode.hip, decode_chain.hip; the core they share is decode_attn_common.h).  THE CONTRACT: every kernel that attends a
+// query to a K/V cache in split-KV items cuts the cache by split_plan, leaves split_publish's partial, and merges in split_merge's
+// order with split_fold / split_finish's arithmetic - their outputs are compared bit for bit (chain against per-layer launches, eager
+// against captured grids, grouped against replicated caches), and that equality is held by the one text, not by copies kept in step.
+// A (head, split) item takes T 64-key tiles with T = ceil(rows * tiles / AKI_DEC_ITEMS); every tile after an item's first is a serial
+// round trip behind the item's dependency, so items stay one tile long up to this many of them.  (The define stays in this file: the
+// tests read it here to compute the plan of their cases.)
 #ifndef AKI_DEC_ITEMS
 #define AKI_DEC_ITEMS 2048
 #endif

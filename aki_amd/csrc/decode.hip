@@ -18,23 +18,13 @@
 #include <type_traits>
 
 #include "aki_device.h"
+#include "decode_attn_common.h"
 
 namespace aki {
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-
-// NB: indexing the u32x4 and bit-casting each dword (bit_cast<bf16x2>(a[i])) is folded by hipcc 7.2 into four uses of
-// dword 0; viewing the whole 16 bytes as bf16x8 and slicing pairs with shufflevector selects the right operands.
-__device__ __forceinline__ float dot8_bf16(const u32x4 a, const u32x4 b, float acc) {
-  const bf16x8_t a8 = __builtin_bit_cast(bf16x8_t, a), b8 = __builtin_bit_cast(bf16x8_t, b);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a8, a8, 0, 1), __builtin_shufflevector(b8, b8, 0, 1), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a8, a8, 2, 3), __builtin_shufflevector(b8, b8, 2, 3), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a8, a8, 4, 5), __builtin_shufflevector(b8, b8, 4, 5), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a8, a8, 6, 7), __builtin_shufflevector(b8, b8, 6, 7), acc, false);
-  return acc;
-}
 
 struct GemvParams {
   const bf16_t* x; const bf16_t* w; const bf16_t* bias; const bf16_t* residual; bf16_t* y;
@@ -840,12 +830,9 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const T* q, const T* k
 // Split-KV single-query attention (bf16, Dh = 96), optionally fused with RoPE + cache append of the new token.
 //
 // With one query per (batch, head) there are only B*H independent rows, far too few to pull the cache at HBM rate
-// from 256 CUs, so the keys of each row are split over S single-wave workgroups of T 64-key tiles each:
-//   score phase  lane = key: the lane loads its whole 192-byte K row (12 x 16 B, all in flight) and dots it with q
-//   PV phase     lane = (row group g = lane>>4, 16-byte column chunk i = lane&15 < 12): 16 loads cover the tile's
-//                64 V rows; the probability of row 4*t+g comes from its owner lane through a wave shuffle
-// Every workgroup leaves (m, l, acc[96]) in the workspace; the one that arrives last at the row's counter merges the
-// S partials, writes the bf16 output and re-arms the counter (so the workspace needs zeroing only once).
+// from 256 CUs, so the keys of each row are split over S single-wave workgroups of T 64-key tiles each (split_plan;
+// the item, the partial it leaves and the merge by the last arriver are decode_attn_common.h's).  The merger
+// re-arms the row's counter, so the workspace needs zeroing only once.
 // FUSED: q comes un-rotated inside the fused qkv row; every workgroup rotates q itself (96 values), the workgroup
 // whose key range contains the new position also rotates k, appends k/v to the cache and uses them from LDS.
 // ------------------------------------------------------------------------------------------------------------
@@ -859,7 +846,6 @@ struct DecodeAttnParams {
   unsigned* cnt; float* part; // workspace: arrival counters [B*H], partials [B*H][S][DEC_PSTRIDE]
   int H, cap, S, T; float scale;
 };
-constexpr int DEC_PSTRIDE = 104;   // m, l, 6 pad, acc[96]
 
 template <bool FUSED>
 __global__ __launch_bounds__(64) void decode_attn_split_kernel(const DecodeAttnParams p) {
@@ -872,181 +858,80 @@ __global__ __launch_bounds__(64) void decode_attn_split_kernel(const DecodeAttnP
   bf16_t* kb = p.kc + (size_t)bh * p.cap * 96;
   bf16_t* vb = p.vc + (size_t)bh * p.cap * 96;
   float* part = p.part + ((size_t)bh * p.S + split) * DEC_PSTRIDE;
-  const int g = lane >> 4, i16 = lane & 15;
-  float m = -INFINITY, l = 0.f, acc[8];
+  float m, l, acc[8];
+  if constexpr (FUSED) {
+    split_item_bf16<true, true>(kb, vb, ln, ln, k_begin, k_end, p.T, p.vbits, (size_t)b * p.nwords, p.nwords, p.q + (size_t)b * 3 * p.H * 96 + h * 96,
+                                p.H, p.cos, p.sin, p.scale, lane, s_q, s_k, s_v, m, l, acc);
+  } else {
+    // The item on a rotated q and an appended cache.  Kept as its own text: on top of split_item_bf16 this instance took 226 VGPRs
+    // for 224 (EXPERIMENTS.md has how to reproduce that); what it computes per tile is the shared item's loop without the new row.
+    // The comments there hold here too: rows clamped to k_end - 1 carry probability 0, q is read from LDS where it is used and V is
+    // widened row by row (either one held in registers made the kernel 272 VGPRs = one wave per SIMD).
+    const int g = lane >> 4, i16 = lane & 15;
+    m = -INFINITY;
+    l = 0.f;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-  if (k_begin < k_end) {
-    const bool owner = FUSED && ln >= k_begin;          // ln < k_end holds by construction (k_end <= ln + 1)
-    u32x4 kr[12], vr[16];
-    auto issue_tile = [&](int base) {                    // all 28 loads of a tile go out back to back
-      const bf16_t* krow = kb + (size_t)min(base + lane, k_end - 1) * 96;       // clamped rows carry probability 0
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    if (k_begin < k_end) {
+      u32x4 kr[12], vr[16];
+      auto issue_tile = [&](int base) {
+        const bf16_t* krow = kb + (size_t)min(base + lane, k_end - 1) * 96;
 #pragma unroll
-      for (int i = 0; i < 12; ++i) kr[i] = *(const u32x4*)(krow + i * 8);
+        for (int i = 0; i < 12; ++i) kr[i] = *(const u32x4*)(krow + i * 8);
 #pragma unroll
-      for (int t2 = 0; t2 < 16; ++t2) {
-        const int r = min(base + 4 * t2 + g, k_end - 1);
-        vr[t2] = *(const u32x4*)(vb + (size_t)r * 96 + min(i16, 11) * 8);
-      }
-    };
-    issue_tile(k_begin);                                 // in flight while q is rotated
-    if (FUSED) {
-      if (lane < 48) {
-        const bf16_t* row = p.q + (size_t)b * 3 * p.H * 96 + h * 96;
-        const float c0 = p.cos[(size_t)ln * 96 + lane], c1 = p.cos[(size_t)ln * 96 + lane + 48];
-        const float s0 = p.sin[(size_t)ln * 96 + lane], s1 = p.sin[(size_t)ln * 96 + lane + 48];
-        const float q0 = bf16_bits_to_f32(row[lane]), q1 = bf16_bits_to_f32(row[lane + 48]);
-        ((__bf16*)s_q)[lane] = (__bf16)(q0 * c0 - q1 * s0);          // rotate-half: d < 48 pairs with -x[d+48]
-        ((__bf16*)s_q)[lane + 48] = (__bf16)(q1 * c1 + q0 * s1);
-        if (owner) {
-          const bf16_t* kr = row + p.H * 96;
-          const bf16_t* vr = row + 2 * p.H * 96;
-          const float k0 = bf16_bits_to_f32(kr[lane]), k1 = bf16_bits_to_f32(kr[lane + 48]);
-          const __bf16 kn0 = (__bf16)(k0 * c0 - k1 * s0), kn1 = (__bf16)(k1 * c1 + k0 * s1);
-          ((__bf16*)s_k)[lane] = kn0;
-          ((__bf16*)s_k)[lane + 48] = kn1;
-          ((__bf16*)kb)[(size_t)ln * 96 + lane] = kn0;
-          ((__bf16*)kb)[(size_t)ln * 96 + lane + 48] = kn1;
-          s_v[lane] = vr[lane];
-          s_v[lane + 48] = vr[lane + 48];
-          vb[(size_t)ln * 96 + lane] = vr[lane];
-          vb[(size_t)ln * 96 + lane + 48] = vr[lane + 48];
+        for (int t2 = 0; t2 < 16; ++t2) {
+          const int r = min(base + 4 * t2 + g, k_end - 1);
+          vr[t2] = *(const u32x4*)(vb + (size_t)r * 96 + min(i16, 11) * 8);
         }
-      }
-    } else if (lane < 12) {
-      *(u32x4*)(s_q + lane * 8) = *(const u32x4*)(p.q + (size_t)bh * 96 + lane * 8);
-    }
-    __syncthreads();
-    // q is read from LDS where it is used (a broadcast): holding it (48 VGPRs) next to the K and V tiles put the kernel at 272 VGPRs = ONE wave
-    // per SIMD, 1024 single-wave items in flight for the 1536 of a batch of eight; without it two fit
-    for (int t = 0; t < p.T; ++t) {
-      const int base = k_begin + t * 64;
-      if (base >= k_end) break;
-      const int j = base + lane;
-      if (t > 0) issue_tile(base);
-      if (owner && base <= ln && ln < base + 64) {
-        // The new token's row lives in LDS: the tile loads were issued before it was stored, so every lane whose (clamped)
-        // row index is ln - the row itself and all rows past k_end - 1 = ln, which carry probability 0 - holds stale
-        // cache contents (0 * NaN would poison the sum) and takes the row from LDS instead.
-        if (min(j, k_end - 1) == ln) {
+      };
+      issue_tile(k_begin);
+      if (lane < 12) *(u32x4*)(s_q + lane * 8) = *(const u32x4*)(p.q + (size_t)bh * 96 + lane * 8);
+      __syncthreads();
+      for (int t = 0; t < p.T; ++t) {
+        const int base = k_begin + t * 64;
+        if (base >= k_end) break;
+        const int j = base + lane;
+        if (t > 0) issue_tile(base);
+        bool ok = j < k_end;
+        if (p.vbits && (base >> 6) < p.nwords) ok = ok && ((p.vbits[(size_t)b * p.nwords + (base >> 6)] >> lane) & 1ull);
+        float s = 0.f;
 #pragma unroll
-          for (int i = 0; i < 12; ++i) kr[i] = *(const u32x4*)(s_k + i * 8);
+        for (int i = 0; i < 12; ++i) s = dot8_bf16(kr[i], *(const u32x4*)(s_q + i * 8), s);
+        s = ok ? s * p.scale : -INFINITY;
+        const float mn = fmaxf(m, wave_max(s));
+        if (mn == -INFINITY) continue;
+        const float a = __expf(m - mn);
+        const float pr = ok ? __expf(s - mn) : 0.f;
+        l = l * a + wave_sum(pr);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] *= a;
+#pragma unroll
+        for (int t2 = 0; t2 < 16; ++t2) {
+          const float w = __shfl(pr, 4 * t2 + g);
+          u32x4 vt = vr[t2];
+          asm volatile("" : "+v"(vt));
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            acc[2 * e] = __builtin_fmaf(w, bf16_lo(vt[e]), acc[2 * e]);
+            acc[2 * e + 1] = __builtin_fmaf(w, bf16_hi(vt[e]), acc[2 * e + 1]);
+          }
         }
-#pragma unroll
-        for (int t2 = 0; t2 < 16; ++t2)
-          if (min(base + 4 * t2 + g, k_end - 1) == ln) vr[t2] = *(const u32x4*)(s_v + min(i16, 11) * 8);
+        m = mn;
       }
-      bool ok = j < k_end;
-      if (p.vbits && (base >> 6) < p.nwords) ok = ok && ((p.vbits[(size_t)b * p.nwords + (base >> 6)] >> lane) & 1ull);
-      float s = 0.f;
 #pragma unroll
-      for (int i = 0; i < 12; ++i) s = dot8_bf16(kr[i], *(const u32x4*)(s_q + i * 8), s);
-      s = ok ? s * p.scale : -INFINITY;
-      const float mn = fmaxf(m, wave_max(s));
-      if (mn == -INFINITY) continue;                                   // wave-uniform: nothing visible yet
-      const float a = __expf(m - mn);
-      const float pr = ok ? __expf(s - mn) : 0.f;
-      l = l * a + wave_sum(pr);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] *= a;
-#pragma unroll
-      for (int t2 = 0; t2 < 16; ++t2) {
-        const float w = __shfl(pr, 4 * t2 + g);
-        u32x4 vt = vr[t2];
-        asm volatile("" : "+v"(vt));                     // widened here, row by row - not all 128 values ahead of the loop (that made it 272 VGPRs: one wave per SIMD)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          acc[2 * e] = __builtin_fmaf(w, bf16_lo(vt[e]), acc[2 * e]);
-          acc[2 * e + 1] = __builtin_fmaf(w, bf16_hi(vt[e]), acc[2 * e + 1]);
-        }
+      for (int e = 0; e < 8; ++e) {
+        acc[e] += __shfl_xor(acc[e], 16);
+        acc[e] += __shfl_xor(acc[e], 32);
       }
-      m = mn;
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      acc[e] += __shfl_xor(acc[e], 16);
-      acc[e] += __shfl_xor(acc[e], 32);
     }
   }
-  // Partials travel between workgroups (possibly on different XCDs, i.e. different L2s) as agent-scope relaxed atomic
-  // stores / loads: those carry sc1 and are written through / read past the non-coherent levels.  A __threadfence()
-  // here would instead make every workgroup write back and invalidate its whole L2 (buffer_wbl2 + buffer_inv).
-#define AKI_ST_AGENT(ptr, v) __hip_atomic_store((ptr), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define AKI_LD_AGENT(ptr) __hip_atomic_load((ptr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-  if (lane == 0) { AKI_ST_AGENT(part, m); AKI_ST_AGENT(part + 1, l); }
-  if (lane < 12) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) AKI_ST_AGENT(part + 8 + lane * 8 + e, acc[e]);
-  }
-  // ---- last workgroup of this (batch, head) merges the partials
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the stores above have reached the coherence point
-  unsigned prev = 0;
-  if (lane == 0) prev = __hip_atomic_fetch_add(p.cnt + bh, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  prev = __shfl(prev, 0);
-  if (prev != (unsigned)(p.S - 1)) return;
+  split_publish(part, m, l, acc, lane);
+  if (split_ticket(p.cnt + bh, lane) != (unsigned)(p.S - 1)) return;
   asm volatile("" ::: "memory");
-  // lane = (split slot sl = lane / 12 in 0..4, column chunk ch = lane % 12): five splits are merged per pass with all of
-  // a pass's loads in flight together (each is a round trip to memory); the five slots then meet through LDS
-  __shared__ float s_mg[5][12][10];
-  const float* pp = p.part + (size_t)bh * p.S * DEC_PSTRIDE;
-  const int sl = lane / 12, ch = lane - sl * 12;
-  float gm = -INFINITY, lt = 0.f, o8[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o8[e] = 0.f;
-  if (sl < 5) {
-    for (int s2 = sl; s2 < p.S; s2 += 5) {
-      const float* ps = pp + (size_t)s2 * DEC_PSTRIDE;
-      const float ms = AKI_LD_AGENT(ps), ls = AKI_LD_AGENT(ps + 1);
-      float a[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a[e] = AKI_LD_AGENT(ps + 8 + ch * 8 + e);
-      const float mn = fmaxf(gm, ms);
-      const float f0 = gm == -INFINITY ? 0.f : __expf(gm - mn), f1 = ms == -INFINITY ? 0.f : __expf(ms - mn);
-      lt = lt * f0 + ls * f1;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o8[e] = o8[e] * f0 + a[e] * f1;
-      gm = mn;
-    }
-    s_mg[sl][ch][0] = gm;
-    s_mg[sl][ch][1] = lt;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s_mg[sl][ch][2 + e] = o8[e];
-  }
-  __syncthreads();
-  if (lane < 12) {
-    float sv[5][10];
-#pragma unroll
-    for (int q = 0; q < 5; ++q)
-#pragma unroll
-      for (int e = 0; e < 10; ++e) sv[q][e] = s_mg[q][lane][e];
-    lds_reads_landed();
-#pragma unroll
-    for (int q = 0; q < 5; ++q)
-#pragma unroll
-      for (int e = 0; e < 10; ++e) asm volatile("" : "+v"(sv[q][e]));
-    float M5 = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) M5 = fmaxf(M5, sv[q][0]);
-    lt = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o8[e] = 0.f;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      const float mq = sv[q][0];
-      const float f = mq == -INFINITY ? 0.f : __expf(mq - M5);
-      lt += sv[q][1] * f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o8[e] += sv[q][2 + e] * f;
-    }
-    const float inv = lt > 0.f ? 1.f / lt : 0.f;
-    u32x4 ov;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ov[e] = pack_bf16x2(o8[2 * e] * inv, o8[2 * e + 1] * inv);
-    *(u32x4*)(p.o + (size_t)bh * 96 + lane * 8) = ov;
-  }
-  if (lane == 0) AKI_ST_AGENT(p.cnt + bh, 0u);
-#undef AKI_ST_AGENT
-#undef AKI_LD_AGENT
+  // ---- last workgroup of this (batch, head) merges the partials
+  __shared__ float s_mg[DEC_MERGE_FLOATS];
+  split_merge(p.part + (size_t)bh * p.S * DEC_PSTRIDE, p.S, 0, lane, s_mg, p.o + (size_t)bh * 96);
+  if (lane == 0) AKI_ST_AGENT(p.cnt + bh, 0u);           // re-armed: the workspace needs zeroing only once
 }
 
 static inline size_t dec_cnt_bytes(int B, int H) { return (((size_t)B * H * 4) + 255) / 256 * 256; }
@@ -1062,14 +947,8 @@ size_t decode_attn_ws_bytes(int B, int H, int Dh, int cap) {
 int decode_attn_split_launch(const void* q_or_qkv, const float* cos, const float* sin, const int* len, void* kc, void* vc, void* o,
                              const uint64_t* vbits, int nwords, int B, int H, int cap, int max_keys, float scale, bool fused,
                              void* ws, size_t ws_bytes, hipStream_t s) {
-  if (max_keys <= 0 || max_keys > cap) max_keys = cap;
-  // Tiles per item from the cache CAPACITY, items per head from max_keys: a launch sized for the keys cached so far (eager steps) and one
-  // sized for the whole cache (a captured step) then cut the keys at the same places and differ only by trailing empty items, whose
-  // partials (m = -inf, l = 0) fold exactly - eager and replayed steps give the same bits at any cache size.
-  const int tiles = (max_keys + 63) / 64, tiles_cap = (cap + 63) / 64;
-  int T = (int)(((size_t)B * H * tiles_cap + AKI_DEC_ITEMS - 1) / AKI_DEC_ITEMS);
-  if (T < 1) T = 1;
-  const int S = (tiles + T - 1) / T;
+  int S, T;
+  split_plan((size_t)B * H, cap, max_keys, S, T);
   if (ws == nullptr || ws_bytes < dec_cnt_bytes(B, H) + (size_t)B * H * S * DEC_PSTRIDE * 4) return AKI_ERR_WORKSPACE;
   DecodeAttnParams p = {(const bf16_t*)q_or_qkv, cos, sin, len, (bf16_t*)kc, (bf16_t*)vc, (bf16_t*)o, vbits, nwords,
                         (unsigned*)ws, (float*)((char*)ws + dec_cnt_bytes(B, H)), H, cap, S, T, scale};
@@ -1195,17 +1074,18 @@ __global__ __launch_bounds__(64) void decode_attn_split_fp8kv_kernel(const Decod
     float kn0 = 0.f, kn1 = 0.f, vn0 = 0.f, vn1 = 0.f;
     if (lane < 48) {
       const bf16_t* row = p.qkv + (size_t)b * 3 * p.H * 96 + h * 96;
-      const float c0 = p.cos[(size_t)ln * 96 + lane], c1 = p.cos[(size_t)ln * 96 + lane + 48];
-      const float s0 = p.sin[(size_t)ln * 96 + lane], s1 = p.sin[(size_t)ln * 96 + lane + 48];
-      const float q0 = bf16_bits_to_f32(row[lane]), q1 = bf16_bits_to_f32(row[lane + 48]);
-      ((__bf16*)s_q)[lane] = (__bf16)(q0 * c0 - q1 * s0);          // rotate-half: d < 48 pairs with -x[d+48]
-      ((__bf16*)s_q)[lane + 48] = (__bf16)(q1 * c1 + q0 * s1);
+      const RopeRow rr = rope_row(p.cos, p.sin, ln, lane);
+      __bf16 q0, q1;
+      rope_rotate_half(rr, bf16_bits_to_f32(row[lane]), bf16_bits_to_f32(row[lane + 48]), q0, q1);
+      ((__bf16*)s_q)[lane] = q0;
+      ((__bf16*)s_q)[lane + 48] = q1;
       if (owner) {
         const bf16_t* krw = row + p.H * 96;
         const bf16_t* vrw = row + 2 * p.H * 96;
-        const float k0 = bf16_bits_to_f32(krw[lane]), k1 = bf16_bits_to_f32(krw[lane + 48]);
-        kn0 = (float)(__bf16)(k0 * c0 - k1 * s0);                   // the bf16 row the bf16 cache would hold
-        kn1 = (float)(__bf16)(k1 * c1 + k0 * s1);
+        __bf16 k0, k1;
+        rope_rotate_half(rr, bf16_bits_to_f32(krw[lane]), bf16_bits_to_f32(krw[lane + 48]), k0, k1);
+        kn0 = (float)k0;                                            // the bf16 row the bf16 cache would hold
+        kn1 = (float)k1;
         vn0 = bf16_bits_to_f32(vrw[lane]);
         vn1 = bf16_bits_to_f32(vrw[lane + 48]);
       }
@@ -1286,92 +1166,20 @@ __global__ __launch_bounds__(64) void decode_attn_split_fp8kv_kernel(const Decod
       acc[e] += __shfl_xor(acc[e], 32);
     }
   }
-  // From here on the bf16 kernel's code (partials as agent-scope relaxed atomics, arrival counter, merge by the last item), repeated
-  // rather than shared so that the bf16 kernel's code stays exactly as it was.
-#define AKI_ST_AGENT(ptr, v) __hip_atomic_store((ptr), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define AKI_LD_AGENT(ptr) __hip_atomic_load((ptr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-  if (lane == 0) { AKI_ST_AGENT(part, m); AKI_ST_AGENT(part + 1, l); }
-  if (lane < 6) {                                        // lane i8 < 6 of row group 0 holds columns 16 i8 .. 16 i8 + 15
-#pragma unroll
-    for (int e = 0; e < 16; ++e) AKI_ST_AGENT(part + 8 + lane * 16 + e, acc[e]);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  unsigned prev = 0;
-  if (lane == 0) prev = __hip_atomic_fetch_add(p.cnt + bh, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  prev = __shfl(prev, 0);
-  if (prev != (unsigned)(p.S - 1)) return;
+  split_publish(part, m, l, acc, lane);                  // lane i8 < 6 of row group 0 holds columns 16 i8 .. 16 i8 + 15
+  if (split_ticket(p.cnt + bh, lane) != (unsigned)(p.S - 1)) return;
   asm volatile("" ::: "memory");
-  __shared__ float s_mg[5][12][10];
-  const float* pp = p.part + (size_t)bh * p.S * DEC_PSTRIDE;
-  const int sl = lane / 12, ch = lane - sl * 12;
-  float gm = -INFINITY, lt = 0.f, o8[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o8[e] = 0.f;
-  if (sl < 5) {
-    for (int s2 = sl; s2 < p.S; s2 += 5) {
-      const float* ps = pp + (size_t)s2 * DEC_PSTRIDE;
-      const float ms = AKI_LD_AGENT(ps), ls = AKI_LD_AGENT(ps + 1);
-      float a[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a[e] = AKI_LD_AGENT(ps + 8 + ch * 8 + e);
-      const float mn = fmaxf(gm, ms);
-      const float f0 = gm == -INFINITY ? 0.f : __expf(gm - mn), f1 = ms == -INFINITY ? 0.f : __expf(ms - mn);
-      lt = lt * f0 + ls * f1;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o8[e] = o8[e] * f0 + a[e] * f1;
-      gm = mn;
-    }
-    s_mg[sl][ch][0] = gm;
-    s_mg[sl][ch][1] = lt;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s_mg[sl][ch][2 + e] = o8[e];
-  }
-  __syncthreads();
-  if (lane < 12) {
-    float sv[5][10];
-#pragma unroll
-    for (int q = 0; q < 5; ++q)
-#pragma unroll
-      for (int e = 0; e < 10; ++e) sv[q][e] = s_mg[q][lane][e];
-    lds_reads_landed();
-#pragma unroll
-    for (int q = 0; q < 5; ++q)
-#pragma unroll
-      for (int e = 0; e < 10; ++e) asm volatile("" : "+v"(sv[q][e]));
-    float M5 = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) M5 = fmaxf(M5, sv[q][0]);
-    lt = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o8[e] = 0.f;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      const float mq = sv[q][0];
-      const float f = mq == -INFINITY ? 0.f : __expf(mq - M5);
-      lt += sv[q][1] * f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o8[e] += sv[q][2 + e] * f;
-    }
-    const float inv = lt > 0.f ? 1.f / lt : 0.f;
-    u32x4 ov;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ov[e] = pack_bf16x2(o8[2 * e] * inv, o8[2 * e + 1] * inv);
-    *(u32x4*)(p.o + (size_t)bh * 96 + lane * 8) = ov;
-  }
+  __shared__ float s_mg[DEC_MERGE_FLOATS];
+  split_merge(p.part + (size_t)bh * p.S * DEC_PSTRIDE, p.S, 0, lane, s_mg, p.o + (size_t)bh * 96);
   if (lane == 0) AKI_ST_AGENT(p.cnt + bh, 0u);
-#undef AKI_ST_AGENT
-#undef AKI_LD_AGENT
 }
 
 // The grid of decode_attn_split_launch (same T and S, so the same workspace and the same eager / replayed key cuts) on the e4m3 cache.
 int decode_attn_split_fp8kv_launch(const void* qkv, const float* cos, const float* sin, const int* len, void* kc, void* vc, float* ks, float* vs,
                                    void* o, const uint64_t* vbits, int nwords, int B, int H, int cap, int max_keys, float scale, void* ws,
                                    size_t ws_bytes, hipStream_t s) {
-  if (max_keys <= 0 || max_keys > cap) max_keys = cap;
-  const int tiles = (max_keys + 63) / 64, tiles_cap = (cap + 63) / 64;
-  int T = (int)(((size_t)B * H * tiles_cap + AKI_DEC_ITEMS - 1) / AKI_DEC_ITEMS);
-  if (T < 1) T = 1;
-  const int S = (tiles + T - 1) / T;
+  int S, T;
+  split_plan((size_t)B * H, cap, max_keys, S, T);
   if (ws == nullptr || ws_bytes < dec_cnt_bytes(B, H) + (size_t)B * H * S * DEC_PSTRIDE * 4) return AKI_ERR_WORKSPACE;
   DecodeAttn8Params p = {(const bf16_t*)qkv, cos, sin, len, (uint8_t*)kc, (uint8_t*)vc, ks, vs, (bf16_t*)o, vbits, nwords,
                          (unsigned*)ws, (float*)((char*)ws + dec_cnt_bytes(B, H)), H, cap, S, T, scale};
@@ -1412,18 +1220,6 @@ struct DecodeGroupParams {
   int N, H, pcap, scap, Sp, Tp, Ss, Ts, NC; float scale;
 };
 
-#define AKI_ST_AGENT(ptr, v) __hip_atomic_store((ptr), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define AKI_LD_AGENT(ptr) __hip_atomic_load((ptr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-
-// q (and, for the owner of the new token, k) of one head rotated at table row `pos`: lane < 48 handles dims lane and lane + 48
-__device__ __forceinline__ void group_rotate(const bf16_t* x, const float* cos, const float* sin, int pos, int lane, __bf16& r0, __bf16& r1) {
-  const float c0 = cos[(size_t)pos * 96 + lane], c1 = cos[(size_t)pos * 96 + lane + 48];
-  const float s0 = sin[(size_t)pos * 96 + lane], s1 = sin[(size_t)pos * 96 + lane + 48];
-  const float x0 = bf16_bits_to_f32(x[lane]), x1 = bf16_bits_to_f32(x[lane + 48]);
-  r0 = (__bf16)(x0 * c0 - x1 * s0);
-  r1 = (__bf16)(x1 * c1 + x0 * s1);
-}
-
 // nothing moves across this point, neither in the optimiser (memory operations) nor in the machine scheduler (anything)
 __device__ __forceinline__ void group_order() {
   asm volatile("" ::: "memory");
@@ -1435,61 +1231,9 @@ __device__ __forceinline__ float uniform_f32(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }
 
-// The last arriver of (row, head) = rh: all Sp + Ss partials -> o.  The whole wave calls it.
-__device__ __forceinline__ void group_merge(const DecodeGroupParams& p, int rh, int lane, float (*s_mg)[12][10]) {
-  const float* pp = p.part + (size_t)rh * (p.Sp + p.Ss) * DEC_PSTRIDE;
-  const int sl = lane / 12, ch = lane - sl * 12;
-  float gm = -INFINITY, lt = 0.f, o8[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o8[e] = 0.f;
-  if (sl < 5) {
-    auto fold = [&](const float* ps) {
-      const float ms = AKI_LD_AGENT(ps), ls = AKI_LD_AGENT(ps + 1);
-      float a[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a[e] = AKI_LD_AGENT(ps + 8 + ch * 8 + e);
-      const float mn = fmaxf(gm, ms);
-      const float f0 = gm == -INFINITY ? 0.f : __expf(gm - mn), f1 = ms == -INFINITY ? 0.f : __expf(ms - mn);
-      lt = lt * f0 + ls * f1;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o8[e] = o8[e] * f0 + a[e] * f1;
-      gm = mn;
-    };
-    for (int s2 = sl; s2 < p.Sp; s2 += 5) fold(pp + (size_t)s2 * DEC_PSTRIDE);
-    for (int s2 = sl; s2 < p.Ss; s2 += 5) fold(pp + (size_t)(p.Sp + s2) * DEC_PSTRIDE);
-    s_mg[sl][ch][0] = gm;
-    s_mg[sl][ch][1] = lt;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s_mg[sl][ch][2 + e] = o8[e];
-  }
-  __syncthreads();
-  if (lane < 12) {
-    float sv[50];
-#pragma unroll
-    for (int q = 0; q < 5; ++q)
-#pragma unroll
-      for (int e = 0; e < 10; ++e) sv[q * 10 + e] = s_mg[q][lane][e];
-    lds_fold_ready(sv);
-    float M5 = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) M5 = fmaxf(M5, sv[q * 10]);
-    lt = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o8[e] = 0.f;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      const float mq = sv[q * 10];
-      const float f = mq == -INFINITY ? 0.f : __expf(mq - M5);
-      lt += sv[q * 10 + 1] * f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o8[e] += sv[q * 10 + 2 + e] * f;
-    }
-    const float inv = lt > 0.f ? 1.f / lt : 0.f;
-    u32x4 ov;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ov[e] = pack_bf16x2(o8[2 * e] * inv, o8[2 * e + 1] * inv);
-    *(u32x4*)(p.o + (size_t)rh * 96 + lane * 8) = ov;
-  }
+// The last arriver of (row, head) = rh: all Sp + Ss partials -> o, prefix splits in order, then suffix splits.  The whole wave calls it.
+__device__ __forceinline__ void group_merge(const DecodeGroupParams& p, int rh, int lane, float* s_mg) {
+  split_merge(p.part + (size_t)rh * (p.Sp + p.Ss) * DEC_PSTRIDE, p.Sp, p.Ss, lane, s_mg, p.o + (size_t)rh * 96);
   __syncthreads();                                     // s_mg is free again: a prefix item may merge several rows
   if (lane == 0) AKI_ST_AGENT(p.cnt + rh, 0u);          // re-armed for the next launch
 }
@@ -1497,7 +1241,7 @@ __device__ __forceinline__ void group_merge(const DecodeGroupParams& p, int rh, 
 // rows r0 .. r0 + nr - 1 (nr <= NR) of sample b against keys [split * Tp * 64, ...) of the sample's prefix
 template <int NR>
 __device__ __forceinline__ void group_prefix_item(const DecodeGroupParams& p, int b, int h, int split, int r0, int nr, int lane, bf16_t* s_q,
-                                                  float* s_p, float (*s_mg)[12][10]) {
+                                                  float* s_p, float* s_mg) {
   const int g = lane >> 4, i16 = lane & 15, S = p.Sp + p.Ss;
   const int plen = min(p.plen[b], p.pcap);
   const int k_begin = split * p.Tp * 64;
@@ -1532,7 +1276,10 @@ __device__ __forceinline__ void group_prefix_item(const DecodeGroupParams& p, in
 #pragma unroll
       for (int j = 0; j < NR; ++j) {
         __bf16 q0 = (__bf16)0.f, q1 = (__bf16)0.f;       // rows past the chunk: q = 0, finite scores that nobody stores
-        if (j < nr) group_rotate(p.qkv + (size_t)(r0 + j) * 3 * p.H * 96 + h * 96, p.cos, p.sin, p.len[r0 + j], lane, q0, q1);
+        if (j < nr) {
+          const bf16_t* row = p.qkv + (size_t)(r0 + j) * 3 * p.H * 96 + h * 96;
+          rope_rotate_half(rope_row(p.cos, p.sin, p.len[r0 + j], lane), bf16_bits_to_f32(row[lane]), bf16_bits_to_f32(row[lane + 48]), q0, q1);
+        }
         ((__bf16*)s_q)[j * 96 + lane] = q0;
         ((__bf16*)s_q)[j * 96 + lane + 48] = q1;
       }
@@ -1599,19 +1346,11 @@ __device__ __forceinline__ void group_prefix_item(const DecodeGroupParams& p, in
       }
   }
 #pragma unroll
-  for (int j = 0; j < NR; ++j) {
-    if (j < nr) {
-      float* part = p.part + (((size_t)(r0 + j) * p.H + h) * S + split) * DEC_PSTRIDE;
-      if (lane == 0) { AKI_ST_AGENT(part, m[j]); AKI_ST_AGENT(part + 1, l[j]); }
-      if (lane < 12) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) AKI_ST_AGENT(part + 8 + lane * 8 + e, acc[j][e]);
-      }
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the stores above have reached the coherence point
+  for (int j = 0; j < NR; ++j)
+    if (j < nr) split_publish(p.part + (((size_t)(r0 + j) * p.H + h) * S + split) * DEC_PSTRIDE, m[j], l[j], acc[j], lane);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // split_ticket for up to 16 rows at once: lane j arrives at row j's counter
   unsigned prev = 0;
-  if (lane < nr) prev = __hip_atomic_fetch_add(p.cnt + (size_t)(r0 + lane) * p.H + h, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (lane < nr) prev = AKI_ADD_AGENT(p.cnt + (size_t)(r0 + lane) * p.H + h, 1u);
   unsigned long long last = __ballot(lane < nr && prev == (unsigned)(S - 1));
   group_order();
   while (last) {                                         // wave-uniform: the rows this item was the last to reach
@@ -1621,111 +1360,21 @@ __device__ __forceinline__ void group_prefix_item(const DecodeGroupParams& p, in
   }
 }
 
-// row r of sample b against keys [split * Ts * 64, ...) of its own suffix slab: decode_attn_split_kernel<true>'s item
+// row r of sample b against keys [split * Ts * 64, ...) of its own suffix slab: the fused item.  The slab has no valid bits, and this
+// caller has never passed over a tile that leaves the running max at -inf; both stay as they are
 __device__ __forceinline__ void group_suffix_item(const DecodeGroupParams& p, int b, int r, int h, int split, int lane, bf16_t* s_q, bf16_t* s_k,
-                                                  bf16_t* s_v, float (*s_mg)[12][10]) {
-  const int g = lane >> 4, i16 = lane & 15, S = p.Sp + p.Ss, rh = r * p.H + h;
+                                                  bf16_t* s_v, float* s_mg) {
+  const int S = p.Sp + p.Ss, rh = r * p.H + h;
   const int ln = p.len[r];                               // RoPE position
   const int la = ln - p.plen[b];                         // append row in the suffix slab
   const int n = (la >= 0 && la < p.scap) ? la + 1 : 0;   // a length outside the slab touches no memory: the row sees its prefix only
   const int k_begin = split * p.Ts * 64;
   const int k_end = min(n, k_begin + p.Ts * 64);
-  bf16_t* kb = p.ks + (size_t)rh * p.scap * 96;
-  bf16_t* vb = p.vs + (size_t)rh * p.scap * 96;
-  float m = -INFINITY, l = 0.f, acc[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-  if (k_begin < k_end) {
-    const bool owner = la >= k_begin;                    // la < k_end holds by construction (k_end <= la + 1)
-    u32x4 kr[12], vr[16];
-    auto issue_tile = [&](int base) {
-      const bf16_t* krow = kb + (size_t)min(base + lane, k_end - 1) * 96;
-#pragma unroll
-      for (int i = 0; i < 12; ++i) kr[i] = *(const u32x4*)(krow + i * 8);
-#pragma unroll
-      for (int t2 = 0; t2 < 16; ++t2) {
-        const int rr = min(base + 4 * t2 + g, k_end - 1);
-        vr[t2] = *(const u32x4*)(vb + (size_t)rr * 96 + min(i16, 11) * 8);
-      }
-    };
-    issue_tile(k_begin);
-    if (lane < 48) {
-      const bf16_t* row = p.qkv + (size_t)r * 3 * p.H * 96 + h * 96;
-      __bf16 q0, q1;
-      group_rotate(row, p.cos, p.sin, ln, lane, q0, q1);
-      ((__bf16*)s_q)[lane] = q0;
-      ((__bf16*)s_q)[lane + 48] = q1;
-      if (owner) {
-        const bf16_t* vn = row + 2 * p.H * 96;
-        __bf16 kn0, kn1;
-        group_rotate(row + p.H * 96, p.cos, p.sin, ln, lane, kn0, kn1);
-        ((__bf16*)s_k)[lane] = kn0;
-        ((__bf16*)s_k)[lane + 48] = kn1;
-        ((__bf16*)kb)[(size_t)la * 96 + lane] = kn0;
-        ((__bf16*)kb)[(size_t)la * 96 + lane + 48] = kn1;
-        s_v[lane] = vn[lane];
-        s_v[lane + 48] = vn[lane + 48];
-        vb[(size_t)la * 96 + lane] = vn[lane];
-        vb[(size_t)la * 96 + lane + 48] = vn[lane + 48];
-      }
-    }
-    __syncthreads();
-    for (int t = 0; t < p.Ts; ++t) {
-      const int base = k_begin + t * 64;
-      if (base >= k_end) break;
-      const int j = base + lane;
-      if (t > 0) issue_tile(base);
-      if (owner && base <= la && la < base + 64) {
-        // the tile loads went out before the new row was stored: every lane whose (clamped) row index is la takes it from LDS,
-        // so no stale cache contents (0 * NaN) can reach the sums
-        if (min(j, k_end - 1) == la) {
-#pragma unroll
-          for (int i = 0; i < 12; ++i) kr[i] = *(const u32x4*)(s_k + i * 8);
-        }
-#pragma unroll
-        for (int t2 = 0; t2 < 16; ++t2)
-          if (min(base + 4 * t2 + g, k_end - 1) == la) vr[t2] = *(const u32x4*)(s_v + min(i16, 11) * 8);
-      }
-      const bool ok = j < k_end;
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < 12; ++i) s = dot8_bf16(kr[i], *(const u32x4*)(s_q + i * 8), s);
-      s = ok ? s * p.scale : -INFINITY;
-      const float mn = fmaxf(m, wave_max(s));
-      const float a = __expf(m - mn);
-      const float pr = ok ? __expf(s - mn) : 0.f;
-      l = l * a + wave_sum(pr);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] *= a;
-#pragma unroll
-      for (int t2 = 0; t2 < 16; ++t2) {
-        const float w = __shfl(pr, 4 * t2 + g);
-        u32x4 vt = vr[t2];
-        asm volatile("" : "+v"(vt));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          acc[2 * e] = __builtin_fmaf(w, bf16_lo(vt[e]), acc[2 * e]);
-          acc[2 * e + 1] = __builtin_fmaf(w, bf16_hi(vt[e]), acc[2 * e + 1]);
-        }
-      }
-      m = mn;
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      acc[e] += __shfl_xor(acc[e], 16);
-      acc[e] += __shfl_xor(acc[e], 32);
-    }
-  }
-  float* part = p.part + ((size_t)rh * S + p.Sp + split) * DEC_PSTRIDE;
-  if (lane == 0) { AKI_ST_AGENT(part, m); AKI_ST_AGENT(part + 1, l); }
-  if (lane < 12) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) AKI_ST_AGENT(part + 8 + lane * 8 + e, acc[e]);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  unsigned prev = 0;
-  if (lane == 0) prev = __hip_atomic_fetch_add(p.cnt + rh, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  prev = __shfl(prev, 0);
+  float m, l, acc[8];
+  split_item_bf16<false, false>(p.ks + (size_t)rh * p.scap * 96, p.vs + (size_t)rh * p.scap * 96, la, ln, k_begin, k_end, p.Ts, nullptr, 0, 0,
+                                      p.qkv + (size_t)r * 3 * p.H * 96 + h * 96, p.H, p.cos, p.sin, p.scale, lane, s_q, s_k, s_v, m, l, acc);
+  split_publish(p.part + ((size_t)rh * S + p.Sp + split) * DEC_PSTRIDE, m, l, acc, lane);
+  const unsigned prev = split_ticket(p.cnt + rh, lane);
   asm volatile("" ::: "memory");
   if (prev == (unsigned)(S - 1)) group_merge(p, rh, lane, s_mg);
 }
@@ -1737,7 +1386,7 @@ template <int NR>
 __global__ __launch_bounds__(64) void decode_attn_group_kernel(const DecodeGroupParams p) {
   __shared__ __attribute__((aligned(16))) bf16_t s_q[NR * 96], s_k[96], s_v[96];
   __shared__ __attribute__((aligned(16))) float s_p[64 * NR];
-  __shared__ float s_mg[5][12][10];
+  __shared__ float s_mg[DEC_MERGE_FLOATS];
   const int lane = threadIdx.x, x = blockIdx.x, b = blockIdx.y / p.H, h = blockIdx.y - b * p.H;
   if (x < p.NC * p.Sp) {
     const int c = x / p.Sp, split = x - c * p.Sp;
@@ -1747,8 +1396,6 @@ __global__ __launch_bounds__(64) void decode_attn_group_kernel(const DecodeGroup
     group_suffix_item(p, b, b * p.N + j, h, split, lane, s_q, s_k, s_v, s_mg);
   }
 }
-#undef AKI_ST_AGENT
-#undef AKI_LD_AGENT
 
 size_t decode_attn_group_ws_bytes(int B0, int N, int H, int pcap, int scap) {
   const size_t tiles = ((size_t)pcap + 63) / 64 + ((size_t)scap + 63) / 64;
@@ -1756,19 +1403,14 @@ size_t decode_attn_group_ws_bytes(int B0, int N, int H, int pcap, int scap) {
 }
 
 // max_pkeys / max_skeys: host upper bounds of prefix_len[b] and of the suffix keys (new token included) - they size the grid.
-// Tiles per item from the CAPACITIES, items from the bounds (decode_attn_split_launch's rule): eager and captured steps cut alike.
+// Tiles per item from the CAPACITIES, items from the bounds (split_plan, once per segment): eager and captured steps cut alike.
 int decode_attn_group_launch(const void* qkv, const float* cos, const float* sin, const int* len, const int* plen, const void* kp,
                              const void* vp, void* ks, void* vs, void* o, const uint64_t* vbits, int nwords, int B0, int N, int H, int pcap,
                              int scap, int max_pkeys, int max_skeys, float scale, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (max_pkeys <= 0 || max_pkeys > pcap) max_pkeys = pcap;
-  if (max_skeys <= 0 || max_skeys > scap) max_skeys = scap;
   const int NC = (N + 15) / 16;
-  const int ptiles_cap = (pcap + 63) / 64, stiles_cap = (scap + 63) / 64;
-  int Tp = (int)(((size_t)B0 * NC * H * ptiles_cap + AKI_DEC_ITEMS - 1) / AKI_DEC_ITEMS);
-  int Ts = (int)(((size_t)B0 * N * H * stiles_cap + AKI_DEC_ITEMS - 1) / AKI_DEC_ITEMS);
-  if (Tp < 1) Tp = 1;
-  if (Ts < 1) Ts = 1;
-  const int Sp = ((max_pkeys + 63) / 64 + Tp - 1) / Tp, Ss = ((max_skeys + 63) / 64 + Ts - 1) / Ts;
+  int Sp, Tp, Ss, Ts;
+  split_plan((size_t)B0 * NC * H, pcap, max_pkeys, Sp, Tp);
+  split_plan((size_t)B0 * N * H, scap, max_skeys, Ss, Ts);
   const size_t cnt_bytes = dec_cnt_bytes(B0 * N, H);
   if (ws == nullptr || ws_bytes < cnt_bytes + (size_t)B0 * N * H * (Sp + Ss) * DEC_PSTRIDE * 4) return AKI_ERR_WORKSPACE;
   if ((size_t)B0 * H > 65535 || (size_t)NC * Sp + (size_t)N * Ss > 0x7fffffffu) return AKI_ERR_UNSUPPORTED;

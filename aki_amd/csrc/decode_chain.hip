@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "aki_device.h"
+#include "decode_attn_common.h"
 
 namespace aki {
 
@@ -94,14 +95,12 @@ __device__ __forceinline__ void static_for_chain_impl(F&& f) {
 template <int N, class F>
 __device__ __forceinline__ void static_for_chain(F&& f) { static_for_chain_impl<0, N>(f); }
 
-#define AKI_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 // pointers that arrive through the layer table are generic to the compiler: say "global" or every load is a flat_load
 typedef const __attribute__((address_space(1))) u32x4* gptr_u32x4;
 typedef const __attribute__((address_space(1))) unsigned* gptr_u32;
 typedef const __attribute__((address_space(1))) float* gptr_f32;
 typedef const __attribute__((address_space(1))) unsigned char* gptr_u8;
 #define AKI_G128(p) ((gptr_u32x4)(p))
-constexpr int CH_PSTRIDE = 104;          // decode.hip's DEC_PSTRIDE: m, l, 6 pad, acc[96]
 // Synchronisation block of one (layer, phase), every word in a 128-byte line of its own:
 //   [0..15] arrival shards (producer workgroup i adds to shard i % 16), [16] the top counter (a completed shard adds 1),
 //   [17..17+CH_FLAGS) READY flags, all written by the arriver that completes the top counter; consumer workgroup j polls flag j % CH_FLAGS.
@@ -153,7 +152,7 @@ struct ChainParams {
   int cnt_words;          // 4-byte words of one counter set; sync / head_sync / attn_cnt point into set 0
   bf16_t* qkv; bf16_t* attn_o; bf16_t* h1; bf16_t* act; bf16_t* hbuf;   // hand-off vectors (copy 0); hbuf = 2 x d
   int rep_stride;         // elements between the copies of a hand-off vector
-  float* part;            // [H][S][CH_PSTRIDE]
+  float* part;            // [H][S][DEC_PSTRIDE]
   int n_qkv, n_attn, n_o, n_gu, n_down, wg_layer;
   int sleep_n, xrep, nflags, nowait;   // product: 8, CH_XREP_USED, CH_FLAGS, 0; the lab library can change them (aki_lab_set_chain)
   int nbq, nbo, nbg, nbd;              // batches of 4 x FPW features per workgroup of the qkv / o_proj / gate_up / down phases
@@ -191,15 +190,15 @@ __device__ __forceinline__ void chain_wait(const ChainParams& p, unsigned* sync,
     unsigned* flag = sync + (CH_SHARDS + 1 + (wg % p.nflags)) * 32;
     unsigned spins = 0;
     auto give_up = [&]() {
-      __hip_atomic_store(p.err, code, AKI_RLX_AGENT);
+      AKI_ST_AGENT(p.err, code);
       for (int i = 0; i < p.n_layers * CH_PHASES; ++i)
-        for (int f = 0; f < CH_FLAGS; ++f) __hip_atomic_store(p.sync + (size_t)i * CH_SYNC_WORDS + (CH_SHARDS + 1 + f) * 32, 2u, AKI_RLX_AGENT);
+        for (int f = 0; f < CH_FLAGS; ++f) AKI_ST_AGENT(p.sync + (size_t)i * CH_SYNC_WORDS + (CH_SHARDS + 1 + f) * 32, 2u);
     };
 #ifdef AKI_LAB_HOOKS
     if (p.fault_code != 0u && code == p.fault_code) give_up();
     else
 #endif
-    while (__hip_atomic_load(flag, AKI_RLX_AGENT) == 0u) {
+    while (AKI_LD_AGENT(flag) == 0u) {
       for (int i = 0; i < p.sleep_n; ++i) __builtin_amdgcn_s_sleep(1);
       if (++spins > CH_SPIN_LIMIT) { give_up(); break; }
     }
@@ -213,16 +212,16 @@ __device__ __forceinline__ unsigned chain_arrive(unsigned* sync, int idx, int n,
   unsigned done = 0;
   if (lane == 0) {
     if (n <= 64) {     // few producers (the 32 head mergers): straight to the top counter - one memory round trip less on the edge
-      done = (__hip_atomic_fetch_add(sync + CH_SHARDS * 32, 1u, AKI_RLX_AGENT) + 1u == (unsigned)n) ? 1u : 0u;
+      done = (AKI_ADD_AGENT(sync + CH_SHARDS * 32, 1u) + 1u == (unsigned)n) ? 1u : 0u;
     } else {
       const int shard = idx % CH_SHARDS;
       const unsigned target = (unsigned)(n / CH_SHARDS + ((n % CH_SHARDS) > shard ? 1 : 0));
-      const unsigned prev = __hip_atomic_fetch_add(sync + shard * 32, 1u, AKI_RLX_AGENT);
-      if (prev + 1u == target) done = (__hip_atomic_fetch_add(sync + CH_SHARDS * 32, 1u, AKI_RLX_AGENT) + 1u == (unsigned)CH_SHARDS) ? 1u : 0u;
+      const unsigned prev = AKI_ADD_AGENT(sync + shard * 32, 1u);
+      if (prev + 1u == target) done = (AKI_ADD_AGENT(sync + CH_SHARDS * 32, 1u) + 1u == (unsigned)CH_SHARDS) ? 1u : 0u;
     }
   }
   done = __shfl(done, 0);
-  if (done && lane < CH_FLAGS) __hip_atomic_store(sync + (CH_SHARDS + 1 + lane) * 32, 1u, AKI_RLX_AGENT);
+  if (done && lane < CH_FLAGS) AKI_ST_AGENT(sync + (CH_SHARDS + 1 + lane) * 32, 1u);
   return done;             // 1 in the wave that completed the phase
 }
 
@@ -373,9 +372,9 @@ __device__ __forceinline__ unsigned chain_gemv(const ChainParams& p, int wg, int
     const int f0 = fbase + b * 4 * FPW;
     unsigned long long res_bits = 0;
     if (residual != nullptr && lane == 0 && f0 < n_out) {            // in flight under the dot products
-      if constexpr (FPW == 4) res_bits = __hip_atomic_load((const unsigned long long*)(residual + f0), AKI_RLX_AGENT);
-      else if constexpr (FPW == 2) res_bits = __hip_atomic_load((const unsigned*)(residual + f0), AKI_RLX_AGENT);
-      else res_bits = __hip_atomic_load((const unsigned short*)(residual + f0), AKI_RLX_AGENT);
+      if constexpr (FPW == 4) res_bits = AKI_LD_AGENT((const unsigned long long*)(residual + f0));
+      else if constexpr (FPW == 2) res_bits = AKI_LD_AGENT((const unsigned*)(residual + f0));
+      else res_bits = AKI_LD_AGENT((const unsigned short*)(residual + f0));
     }
     // (5) dot products out of the registers, chunk order ascending per lane and row
     float acc[NR];
@@ -428,11 +427,11 @@ __device__ __forceinline__ unsigned chain_gemv(const ChainParams& p, int wg, int
         bf16_t* yr = y + (size_t)rep * p.rep_stride + f0;
         if constexpr (FPW == 4) {
           const unsigned long long o = (unsigned long long)pack_bf16x2(out[0], out[1]) | ((unsigned long long)pack_bf16x2(out[2], out[3]) << 32);
-          __hip_atomic_store((unsigned long long*)yr, o, AKI_RLX_AGENT);
+          AKI_ST_AGENT((unsigned long long*)yr, o);
         } else if constexpr (FPW == 2) {
-          __hip_atomic_store((unsigned*)yr, pack_bf16x2(out[0], out[1]), AKI_RLX_AGENT);
+          AKI_ST_AGENT((unsigned*)yr, pack_bf16x2(out[0], out[1]));
         } else {
-          __hip_atomic_store((unsigned short*)yr, (unsigned short)(pack_bf16x2(out[0], 0.f) & 0xffffu), AKI_RLX_AGENT);
+          AKI_ST_AGENT((unsigned short*)yr, (unsigned short)(pack_bf16x2(out[0], 0.f) & 0xffffu));
         }
       }
     }
@@ -445,7 +444,7 @@ __device__ __forceinline__ unsigned chain_gemv(const ChainParams& p, int wg, int
   if (head_per > 0) {             // one counter per head: 3 x head_per arrivals, the last one raises the head's flag
     if (threadIdx.x == 0) {
       unsigned* hs = head_sync + (size_t)head_of_wg * 64;
-      if (__hip_atomic_fetch_add(hs, 1u, AKI_RLX_AGENT) + 1u == (unsigned)(3 * head_per)) __hip_atomic_store(hs + 32, 1u, AKI_RLX_AGENT);
+      if (AKI_ADD_AGENT(hs, 1u) + 1u == (unsigned)(3 * head_per)) AKI_ST_AGENT(hs + 32, 1u);
     }
   } else if (threadIdx.x < 64) {
     completed = chain_arrive(done_sync, wg, n_wg, threadIdx.x);
@@ -603,7 +602,7 @@ __device__ __forceinline__ unsigned chain_gemm(const ChainParams& p, int wg, int
     const int tok = l15, f = f0 + 4 * kg;
     if (tok < M && f < n_out) {
       unsigned long long res_bits = 0;
-      if (residual != nullptr) res_bits = __hip_atomic_load((const unsigned long long*)(residual + (size_t)tok * n_out + f), AKI_RLX_AGENT);
+      if (residual != nullptr) res_bits = AKI_LD_AGENT((const unsigned long long*)(residual + (size_t)tok * n_out + f));
       float v[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -611,7 +610,7 @@ __device__ __forceinline__ unsigned chain_gemm(const ChainParams& p, int wg, int
         if (residual != nullptr) v[r] += bf16_bits_to_f32((unsigned short)(res_bits >> (16 * r)));
       }
       const unsigned long long o = (unsigned long long)pack_bf16x2(v[0], v[1]) | ((unsigned long long)pack_bf16x2(v[2], v[3]) << 32);
-      __hip_atomic_store((unsigned long long*)(y + (size_t)tok * n_out + f), o, AKI_RLX_AGENT);
+      AKI_ST_AGENT((unsigned long long*)(y + (size_t)tok * n_out + f), o);
     }
   }
   AKI_CHAIN_STAMP(p, (int)(code >> 8), (int)(code & 255) - 1, wg, 3);
@@ -622,7 +621,7 @@ __device__ __forceinline__ unsigned chain_gemm(const ChainParams& p, int wg, int
   if (head_per > 0) {
     if (threadIdx.x == 0) {
       unsigned* hs = head_sync + (size_t)head_of_wg * 64;
-      if (__hip_atomic_fetch_add(hs, 1u, AKI_RLX_AGENT) + 1u == (unsigned)(3 * head_per)) __hip_atomic_store(hs + 32, 1u, AKI_RLX_AGENT);
+      if (AKI_ADD_AGENT(hs, 1u) + 1u == (unsigned)(3 * head_per)) AKI_ST_AGENT(hs + 32, 1u);
     }
   } else if (threadIdx.x < 64) {
     completed = chain_arrive(done_sync, wg, n_wg, threadIdx.x);
@@ -632,6 +631,9 @@ __device__ __forceinline__ unsigned chain_gemm(const ChainParams& p, int wg, int
 }
 
 // ---- the attention phase: decode.hip's decode_attn_split_kernel<true>, one (head, split) item per WAVE ---------------------
+// Shared with it (decode_attn_common.h): the cut of the cache, rotate-half, the partial, the ticket and the merge arithmetic.  Its own:
+// the tile loop (the K/V issue is split around the scores for this launch's register budget), atomic loads of the handed-off qkv row,
+// the merge's load schedule, wave-level barriers and write-through output stores.
 // qkv (un-rotated, handed off by phase 0) -> rotated q; the item whose key range holds the new position also rotates k, appends
 // k / v to the cache and uses them from LDS.  Partials (m, l, acc[96]) meet in the workspace; the item that arrives last at its
 // head's ticket merges, stores the head's 96 outputs write-through and adds 1 to the layer's attention counter.
@@ -641,7 +643,7 @@ template <bool BT = false>
 __device__ __forceinline__ void chain_attn(const ChainParams& p, const aki_decode_chain_layer& ly, int layer, int wg, unsigned* wait_sync,
                                            unsigned* done_sync, unsigned code, char* smem) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // per-wave LDS: s_q, s_k, s_v (96 bf16 each, 16-byte aligned) and the merge scratch s_mg[5][12][10] floats
+  // per-wave LDS: s_q, s_k, s_v (96 bf16 each, 16-byte aligned) and the merge scratch (DEC_MERGE_FLOATS floats)
   bf16_t* s_q = (bf16_t*)(smem + wave * 3072);
   bf16_t* s_k = s_q + 96;
   bf16_t* s_v = s_k + 96;
@@ -657,7 +659,7 @@ __device__ __forceinline__ void chain_attn(const ChainParams& p, const aki_decod
   const int k_end = live ? min(n, k_begin + p.T * 64) : 0;
   bf16_t* kb = (bf16_t*)ly.k_cache + (size_t)bh * p.cap * 96;
   bf16_t* vb = (bf16_t*)ly.v_cache + (size_t)bh * p.cap * 96;
-  float* part = p.part + ((size_t)bh * p.S + split) * CH_PSTRIDE;
+  float* part = p.part + ((size_t)bh * p.S + split) * DEC_PSTRIDE;
   const int g = lane >> 4, i16 = lane & 15;
   float m = -INFINITY, l = 0.f, acc[8];
 #pragma unroll
@@ -695,10 +697,10 @@ __device__ __forceinline__ void chain_attn(const ChainParams& p, const aki_decod
     if (live && lane == 0) {
       const unsigned* flag = p.head_sync + ((size_t)layer * p.H + h) * 64 + 32;
       unsigned spins = 0;
-      while (__hip_atomic_load(flag, AKI_RLX_AGENT) == 0u) {
+      while (AKI_LD_AGENT(flag) == 0u) {
         for (int i = 0; i < p.sleep_n; ++i) __builtin_amdgcn_s_sleep(1);
-        if (++spins > CH_SPIN_LIMIT) { __hip_atomic_store(p.err, code, AKI_RLX_AGENT); break; }
-        if ((spins & 63u) == 0u && __hip_atomic_load(p.err, AKI_RLX_AGENT) != 0u) break;      // somebody gave up: drain
+        if (++spins > CH_SPIN_LIMIT) { AKI_ST_AGENT(p.err, code); break; }
+        if ((spins & 63u) == 0u && AKI_LD_AGENT(p.err) != 0u) break;      // somebody gave up: drain
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -711,19 +713,21 @@ __device__ __forceinline__ void chain_attn(const ChainParams& p, const aki_decod
   if (work) {
     if (lane < 48) {
       const bf16_t* row = BT ? p.qkv + (size_t)b * 3 * p.H * 96 + h * 96 : p.qkv + (size_t)(item % p.xrep) * p.rep_stride + h * 96;
-      const float c0 = p.cos[(size_t)ln * 96 + lane], c1 = p.cos[(size_t)ln * 96 + lane + 48];
-      const float s0 = p.sin[(size_t)ln * 96 + lane], s1 = p.sin[(size_t)ln * 96 + lane + 48];
-      const float q0 = bf16_bits_to_f32(__hip_atomic_load(row + lane, AKI_RLX_AGENT));
-      const float q1 = bf16_bits_to_f32(__hip_atomic_load(row + lane + 48, AKI_RLX_AGENT));
-      ((__bf16*)s_q)[lane] = (__bf16)(q0 * c0 - q1 * s0);
-      ((__bf16*)s_q)[lane + 48] = (__bf16)(q1 * c1 + q0 * s1);
+      const RopeRow rr = rope_row(p.cos, p.sin, ln, lane);
+      const float q0 = bf16_bits_to_f32(AKI_LD_AGENT(row + lane));
+      const float q1 = bf16_bits_to_f32(AKI_LD_AGENT(row + lane + 48));
+      __bf16 qn0, qn1;
+      rope_rotate_half(rr, q0, q1, qn0, qn1);
+      ((__bf16*)s_q)[lane] = qn0;
+      ((__bf16*)s_q)[lane + 48] = qn1;
       if (owner) {
         const bf16_t* krw = row + p.H * 96;
         const bf16_t* vrw = row + 2 * p.H * 96;
-        const float k0 = bf16_bits_to_f32(__hip_atomic_load(krw + lane, AKI_RLX_AGENT));
-        const float k1 = bf16_bits_to_f32(__hip_atomic_load(krw + lane + 48, AKI_RLX_AGENT));
-        const unsigned short v0 = __hip_atomic_load(vrw + lane, AKI_RLX_AGENT), v1 = __hip_atomic_load(vrw + lane + 48, AKI_RLX_AGENT);
-        const __bf16 kn0 = (__bf16)(k0 * c0 - k1 * s0), kn1 = (__bf16)(k1 * c1 + k0 * s1);
+        const float k0 = bf16_bits_to_f32(AKI_LD_AGENT(krw + lane));
+        const float k1 = bf16_bits_to_f32(AKI_LD_AGENT(krw + lane + 48));
+        const unsigned short v0 = AKI_LD_AGENT(vrw + lane), v1 = AKI_LD_AGENT(vrw + lane + 48);
+        __bf16 kn0, kn1;
+        rope_rotate_half(rr, k0, k1, kn0, kn1);
         ((__bf16*)s_k)[lane] = kn0;
         ((__bf16*)s_k)[lane + 48] = kn1;
         ((__bf16*)kb)[(size_t)ln * 96 + lane] = kn0;
@@ -791,86 +795,43 @@ __device__ __forceinline__ void chain_attn(const ChainParams& p, const aki_decod
     }
   }
   AKI_CHAIN_STAMP(p, layer, 1, wg, 3);
-  if (lane == 0) { __hip_atomic_store(part, m, AKI_RLX_AGENT); __hip_atomic_store(part + 1, l, AKI_RLX_AGENT); }
-  if (lane < 12) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) __hip_atomic_store(part + 8 + lane * 8 + e, acc[e], AKI_RLX_AGENT);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  unsigned prev = 0;
-  if (lane == 0) prev = __hip_atomic_fetch_add(p.attn_cnt + (size_t)layer * nB * p.H + bh, 1u, AKI_RLX_AGENT);
-  prev = __shfl(prev, 0);
+  split_publish(part, m, l, acc, lane);
+  const unsigned prev = split_ticket(p.attn_cnt + (size_t)layer * nB * p.H + bh, lane);
   AKI_CHAIN_STAMP(p, layer, 1, wg, 4);
   if (prev != (unsigned)(p.S - 1)) return;
   asm volatile("" ::: "memory");
-  // the last arriver of head h merges the S partials (decode.hip's order: five split slots per pass, the slots then meet in LDS)
-  const float* pp = p.part + (size_t)bh * p.S * CH_PSTRIDE;
+  // the last arriver of head h merges the S partials: split_merge's order and arithmetic under this phase's own load schedule and barrier
+  const float* pp = p.part + (size_t)bh * p.S * DEC_PSTRIDE;
   const int sl = lane / 12, ch = lane - sl * 12;
   float gm = -INFINITY, lt = 0.f, o8[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) o8[e] = 0.f;
   if (sl < 5) {
     // every partial of this slot is requested before the first is used (each load is a round trip to memory; S <= 15 is three of
-    // them in a row otherwise, on the critical path of the layer); the combination runs in decode.hip's order
+    // them in a row otherwise, on the critical path of the layer); the combination runs in split_merge's order
     for (int s0 = sl; s0 < p.S; s0 += 15) {
       float ms[3], ls[3], a[3][8];
 #pragma unroll
       for (int u = 0; u < 3; ++u) {
         const int s2 = s0 + 5 * u;
-        const float* ps = pp + (size_t)min(s2, p.S - 1) * CH_PSTRIDE;
-        ms[u] = __hip_atomic_load(ps, AKI_RLX_AGENT);
-        ls[u] = __hip_atomic_load(ps + 1, AKI_RLX_AGENT);
+        const float* ps = pp + (size_t)min(s2, p.S - 1) * DEC_PSTRIDE;
+        ms[u] = AKI_LD_AGENT(ps);
+        ls[u] = AKI_LD_AGENT(ps + 1);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) a[u][e] = __hip_atomic_load(ps + 8 + ch * 8 + e, AKI_RLX_AGENT);
+        for (int e = 0; e < 8; ++e) a[u][e] = AKI_LD_AGENT(ps + 8 + ch * 8 + e);
       }
 #pragma unroll
       for (int u = 0; u < 3; ++u) {
         if (s0 + 5 * u >= p.S) break;
-        const float mn = fmaxf(gm, ms[u]);
-        const float fa = gm == -INFINITY ? 0.f : __expf(gm - mn), fb = ms[u] == -INFINITY ? 0.f : __expf(ms[u] - mn);
-        lt = lt * fa + ls[u] * fb;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o8[e] = o8[e] * fa + a[u][e] * fb;
-        gm = mn;
+        split_fold(gm, lt, o8, ms[u], ls[u], a[u]);
       }
     }
-    float* sm = s_mg + (sl * 12 + ch) * 10;
-    sm[0] = gm;
-    sm[1] = lt;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sm[2 + e] = o8[e];
+    split_slot_store(s_mg, sl, ch, gm, lt, o8);
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
   if (lane < 12) {
-    float sv[5][10];
-#pragma unroll
-    for (int q = 0; q < 5; ++q)
-#pragma unroll
-      for (int e = 0; e < 10; ++e) sv[q][e] = s_mg[(q * 12 + lane) * 10 + e];
-    lds_reads_landed();
-#pragma unroll
-    for (int q = 0; q < 5; ++q)
-#pragma unroll
-      for (int e = 0; e < 10; ++e) asm volatile("" : "+v"(sv[q][e]));
-    float M5 = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) M5 = fmaxf(M5, sv[q][0]);
-    lt = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o8[e] = 0.f;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      const float mq = sv[q][0];
-      const float f = mq == -INFINITY ? 0.f : __expf(mq - M5);
-      lt += sv[q][1] * f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o8[e] += sv[q][2 + e] * f;
-    }
-    const float inv = lt > 0.f ? 1.f / lt : 0.f;
-    u32x4 ov;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ov[e] = pack_bf16x2(o8[2 * e] * inv, o8[2 * e + 1] * inv);
+    const u32x4 ov = split_finish(s_mg, lane);
     if constexpr (BT) {
       const __amdgpu_buffer_rsrc_t ro = chain_rsrc(p.attn_o + (size_t)b * p.H * 96, p.H * 96 * 2);
       __builtin_amdgcn_raw_buffer_store_b128(ov, ro, (h * 96 + lane * 8) * 2, 0, 16);     // sc1: write-through
@@ -904,7 +865,7 @@ __global__ __launch_bounds__(256, OCC) void decode_chain_kernel(const ChainParam
   // give-up - sticky error word - the sets are in no defined state: the caller zero-fills the workspace before using it again.)  The word and
   // the sets are read and written at agent scope or across a kernel boundary only.
   ChainParams p = p0;
-  const unsigned ep = (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(p0.epoch, AKI_RLX_AGENT));
+  const unsigned ep = (unsigned)__builtin_amdgcn_readfirstlane((int)AKI_LD_AGENT(p0.epoch));
   {
     const size_t cur = (ep & 1u) ? (size_t)p0.cnt_words : 0;
     p.sync = p0.sync + cur; p.head_sync = p0.head_sync + cur; p.attn_cnt = p0.attn_cnt + cur;
@@ -955,7 +916,7 @@ __global__ __launch_bounds__(256, OCC) void decode_chain_kernel(const ChainParam
   r -= p.n_gu;
   const unsigned fin = chain_gemv<NRF, KF, false, false, FMT, NBD, PFDN, BF>(p, r, p.n_down, ly.w_down, ly.s_down, p.F, p.d, p.act, 1, nullptr, p.h1, 1, h2,
                                                                          last ? 1 : CH_XREP, sy + 3 * CH_SYNC_WORDS, sy + 4 * CH_SYNC_WORDS, code | 5u, sx, s_red);
-  if (last && fin && threadIdx.x == 0) __hip_atomic_store(p.epoch, ep + 1u, AKI_RLX_AGENT);      // the call is complete: the next one takes the other set
+  if (last && fin && threadIdx.x == 0) AKI_ST_AGENT(p.epoch, ep + 1u);      // the call is complete: the next one takes the other set
 }
 
 // ---- the batched chain: 2..8 sequences per step ------------------------------------------------------------------------------
@@ -967,7 +928,7 @@ __global__ __launch_bounds__(512) void decode_chain_b_kernel(const ChainParams p
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int bid = blockIdx.x;
   ChainParams p = p0;                                      // the counter set of this call: see decode_chain_kernel
-  const unsigned ep = (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(p0.epoch, AKI_RLX_AGENT));
+  const unsigned ep = (unsigned)__builtin_amdgcn_readfirstlane((int)AKI_LD_AGENT(p0.epoch));
   {
     const size_t cur = (ep & 1u) ? (size_t)p0.cnt_words : 0;
     p.sync = p0.sync + cur; p.head_sync = p0.head_sync + cur; p.attn_cnt = p0.attn_cnt + cur;
@@ -1010,7 +971,7 @@ __global__ __launch_bounds__(512) void decode_chain_b_kernel(const ChainParams p
   r -= p.n_gu;
   const unsigned fin = chain_gemm<16, false, 2, RD>(p, r, p.n_down, ly.w_down, p.d, p.act, nullptr, p.h1, h2, sy + 3 * CH_SYNC_WORDS, sy + 4 * CH_SYNC_WORDS,
                                                     code | 5u, smem);
-  if (last && fin && threadIdx.x == 0) __hip_atomic_store(p.epoch, ep + 1u, AKI_RLX_AGENT);
+  if (last && fin && threadIdx.x == 0) AKI_ST_AGENT(p.epoch, ep + 1u);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -1024,14 +985,6 @@ static unsigned g_chain_fault_code = 0;
 static int g_chain_fault_skip = 0;
 #endif
 
-static void chain_split(int H, int cap, int max_keys, int& S, int& T, int B = 1) {
-  if (max_keys <= 0 || max_keys > cap) max_keys = cap;
-  const int tiles = (max_keys + 63) / 64, tiles_cap = (cap + 63) / 64;     // decode.hip's rule: T from the capacity, S from max_keys
-  T = (int)(((size_t)B * H * tiles_cap + AKI_DEC_ITEMS - 1) / AKI_DEC_ITEMS);
-  if (T < 1) T = 1;
-  S = (tiles + T - 1) / T;
-}
-
 // workspace: counter set 0 | counter set 1 | 256 bytes: the sticky error word (+0) and the count of completed calls (+64) | hand-off vectors | partials
 size_t decode_chain_err_offset(int n_layers, int H) { return 2 * chain_cnt_bytes(n_layers, H); }
 
@@ -1039,12 +992,12 @@ size_t decode_chain_err_offset(int n_layers, int H) { return 2 * chain_cnt_bytes
 size_t decode_chain_b_err_offset(int n_layers, int H, int B) { return 2 * chain_cnt_bytes(n_layers, H, B); }
 size_t decode_chain_b_ws_bytes(int n_layers, int d, int H, int F, int cap, int B) {
   const size_t tiles = ((size_t)cap + 63) / 64;
-  return 2 * chain_cnt_bytes(n_layers, H, B) + 256 + (size_t)B * chain_vec_elems(d, H, F) * 2 + (size_t)B * H * tiles * CH_PSTRIDE * 4;
+  return 2 * chain_cnt_bytes(n_layers, H, B) + 256 + (size_t)B * chain_vec_elems(d, H, F) * 2 + (size_t)B * H * tiles * DEC_PSTRIDE * 4;
 }
 
 size_t decode_chain_ws_bytes(int n_layers, int d, int H, int F, int cap) {
   const size_t tiles = ((size_t)cap + 63) / 64;
-  return 2 * chain_cnt_bytes(n_layers, H) + 256 /* error word, call count */ + chain_vec_elems(d, H, F) * 2 * CH_XREP + (size_t)H * tiles * CH_PSTRIDE * 4;
+  return 2 * chain_cnt_bytes(n_layers, H) + 256 /* error word, call count */ + chain_vec_elems(d, H, F) * 2 * CH_XREP + (size_t)H * tiles * DEC_PSTRIDE * 4;
 }
 
 // The batched chain is built, bit-identical to the five launches per layer and NOT faster (3.3-3.5 vs 3.2 ms per step at batch 8: 1664 fat
@@ -1060,7 +1013,7 @@ static int decode_chain_b_launch(const aki_decode_chain_args* a, hipStream_t str
   p.h_in = (const bf16_t*)a->h_in; p.h_out = (bf16_t*)a->h_out;
   p.cos = a->cos; p.sin = a->sin; p.cache_len = a->cache_len; p.vbits = a->col_valid_bits; p.nwords = a->nwords;
   p.d = d; p.H = H; p.F = F; p.cap = a->capacity; p.scale = a->scale; p.eps = a->rms_eps;
-  chain_split(H, a->capacity, a->max_keys, p.S, p.T, B);
+  split_plan((size_t)B * H, a->capacity, a->max_keys, p.S, p.T);
   char* ws = (char*)a->workspace;
   const size_t cb = chain_cnt_bytes(a->n_layers, H, B);
   p.sync = (unsigned*)ws;
@@ -1142,7 +1095,7 @@ int decode_chain_launch(const aki_decode_chain_args* a, hipStream_t stream) {
   p.h_in = (const bf16_t*)a->h_in; p.h_out = (bf16_t*)a->h_out;
   p.cos = a->cos; p.sin = a->sin; p.cache_len = a->cache_len; p.vbits = a->col_valid_bits; p.nwords = a->nwords;
   p.d = d; p.H = H; p.F = F; p.cap = a->capacity; p.scale = a->scale; p.eps = a->rms_eps;
-  chain_split(H, a->capacity, a->max_keys, p.S, p.T);
+  split_plan((size_t)H, a->capacity, a->max_keys, p.S, p.T);
   char* ws = (char*)a->workspace;
   const size_t cb = chain_cnt_bytes(a->n_layers, H);
   p.sync = (unsigned*)ws;

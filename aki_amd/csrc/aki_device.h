@@ -49,7 +49,14 @@ __device__ __forceinline__ float gelu_tanh(float x) {
   const float c = 0.79788456080286535588f;
   return 0.5f * x * (1.0f + tanhf(c * (x + 0.044715f * x * x * x)));
 }
-__device__ __forceinline__ float silu(float x) { return x / (1.0f + __expf(-x)); }
+// x / (1 + e^-x).  e^-x overflows f32 below x = -88.72 while x e^x stays a normal number down to x = -91.9 (and a bf16 one): below -80,
+// where 1 + e^-x == e^-x in f32, the quotient is taken against e^(-x-32) with the e^-32 in the numerator.  At and above -80 the
+// operations and their results are those of the plain form.
+__device__ __forceinline__ float silu(float x) {
+  const bool deep = x < -80.0f;
+  const float e = __expf(-x - (deep ? 32.0f : 0.0f));
+  return (deep ? x * 1.26641655e-14f : x) / (deep ? e : 1.0f + e);
+}
 
 // Fast forms for the bf16 MFMA epilogues (v_exp_f32 + v_rcp_f32, a handful of FMAs).  Absolute errors are below
 // 1e-6 relative to |x| - three orders of magnitude under the bf16 output resolution; the f32 parity path keeps the

@@ -314,6 +314,11 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const bf16_t* gu, const
         const float sg = 1.0f / (1.0f + __expf(-gg));
         du[hh] = dd * gg * sg;
         dg[hh] = dd * uu * sg * (1.0f + gg * (1.0f - sg));
+        if (gg < -80.0f) {     // sg underflows to 0 below -88.72 (and da * g overflows first for |g| > 2e38: inf * 0); see silu()
+          const float sl = silu(gg);
+          du[hh] = dd * sl;
+          dg[hh] = dd * uu * (sl * (1.0f + 1.0f / gg));     // sg (1 + g (1 - sg)) with 1 - sg == 1: silu(g) (1 + 1 / g)
+        }
       }
       og[e] = pack_bf16x2(dg[0], dg[1]);
       ou[e] = pack_bf16x2(du[0], du[1]);

@@ -510,6 +510,8 @@ int aki_decode_chain_fwd(const aki_decode_chain_args* args, void* stream);
  * aki_ce_loss_fwd_bwd   HF shifted cross-entropy: row (b,t) against labels[b][t+1], ignore_index -100;
  *                       loss_rows [B*L] f32 (sum / *n_valid = loss), n_valid: device int32 (written),
  *                       dlogits (may alias logits, may be NULL) = d(mean loss)/d(logits) * gscale
+ *                       Only columns 0..V-1 of a row are read or written: columns V..ldl-1 of logits and V..lddl-1 of dlogits
+ *                       keep whatever they held (ignored rows get zeros in columns 0..V-1 only).
  * aki_ce_rows_fwd_bwd   the same arithmetic for an arbitrary CHUNK of rows: targets[r] is the (already shifted) class of row r
  *                       (< 0 or >= V: ignored row), *n_valid (device int32) is an INPUT - the number of scored rows of the
  *                       whole batch.  With it the lm_head and the loss run chunk by chunk and the [B, L, V] logits tensor

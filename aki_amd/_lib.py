@@ -289,6 +289,12 @@ def load_lab() -> C.CDLL:
     lib.aki_lab_gemm_log.argtypes = [C.c_void_p, C.c_int]
     lib.aki_lab_set_gemm_dry_run.restype = None
     lib.aki_lab_set_gemm_dry_run.argtypes = [C.c_int]
+    lib.aki_lab_decode_log_reset.restype = None
+    lib.aki_lab_decode_log_reset.argtypes = []
+    lib.aki_lab_decode_log.restype = C.c_int
+    lib.aki_lab_decode_log.argtypes = [C.c_void_p, C.c_int]
+    lib.aki_lab_set_decode_dry_run.restype = None
+    lib.aki_lab_set_decode_dry_run.argtypes = [C.c_int]
     return lib
 
 
@@ -302,6 +308,21 @@ def gemm_log(lib: C.CDLL, cap: int = 64) -> list:
     if count > cap:
         raise AkiError(f"gemm_log: {count} launches recorded, more than cap = {cap}")
     f = len(GEMM_LOG_FIELDS)
+    return [tuple(buf[i * f:(i + 1) * f]) for i in range(count)]
+
+
+DECODE_LOG_FIELDS = ("family", "rows_or_ks", "swiglu", "fpw_or_ft", "w8_or_norm_kernel", "norm", "grid", "groups_per_wg", "smem")
+DECODE_FAMILIES = ("gemv", "skinny", "skinny_w8")
+
+
+def decode_log(lib: C.CDLL, cap: int = 64) -> list:
+    """The lab library's decode-linear route log since the last aki_lab_decode_log_reset(): one tuple per launch (DECODE_LOG_FIELDS;
+    family: index into DECODE_FAMILIES; second field: M of gemv_bf16_kernel, KS of the skinny GEMMs; fourth: FPW / FT; fifth: W8 / NORM)."""
+    f = len(DECODE_LOG_FIELDS)
+    buf = (C.c_int32 * (cap * f))()
+    count = lib.aki_lab_decode_log(buf, cap)
+    if count > cap:
+        raise AkiError(f"decode_log: {count} launches recorded, more than cap = {cap}")
     return [tuple(buf[i * f:(i + 1) * f]) for i in range(count)]
 
 

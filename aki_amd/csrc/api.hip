@@ -89,6 +89,9 @@ extern int g_probe_block;
 extern int g_gemm_dry_run;
 void gemm_log_reset();
 int gemm_log_copy(int* out, int cap);
+extern int g_decode_dry_run;
+void decode_log_reset();
+int decode_log_copy(int* out, int cap);
 #endif
 size_t attn_bwd_ws_bytes(int B, int H, int Lq);
 int attn_bwd_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, void* dq, void* dk,
@@ -163,6 +166,13 @@ void aki_lab_gemm_log_reset(void) { aki::gemm_log_reset(); }
 int aki_lab_gemm_log(int32_t* out, int cap) { return aki::gemm_log_copy(out, cap); }
 // 1: every GEMM launch is recorded and returns AKI_OK before any HIP call (the planner without a GPU)
 void aki_lab_set_gemm_dry_run(int on) { aki::g_gemm_dry_run = on ? 1 : 0; }
+// route log of the decode linears (decode.hip, launch_gemv_cfg / launch_skinny / launch_skinny_w8): 9 int32 per launch {family, M or KS, SWIGLU,
+// FPW or FT, W8 or NORM, norm, grid, feature groups per workgroup, dynamic LDS bytes}; family 0 = gemv_bf16_kernel, 1 = skinny_gemm_bf16_kernel,
+// 2 = skinny_gemm_w8_kernel.  aki_lab_decode_log copies up to `cap` records and returns the number of launches since the last reset
+void aki_lab_decode_log_reset(void) { aki::decode_log_reset(); }
+int aki_lab_decode_log(int32_t* out, int cap) { return aki::decode_log_copy(out, cap); }
+// 1: every decode-linear launch is recorded and returns AKI_OK before any HIP call
+void aki_lab_set_decode_dry_run(int on) { aki::g_decode_dry_run = on ? 1 : 0; }
 #endif
 
 // ---- attention core --------------------------------------------------------------------------------

@@ -284,6 +284,32 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(const GemvParams p) {
   }
 }
 
+#ifdef AKI_LAB_HOOKS
+// Route log of the decode linears (tests/decode_linear_cases.py): one record of nine int32 per launch decision, so that a test can see which
+// instantiation the planner chose -
+//   {0, M, SWIGLU, FPW, W8, norm, grid, feature groups per workgroup, dynamic LDS bytes}      gemv_bf16_kernel
+//   {1, KS, SWIGLU, FT, NORM, norm, grid, 0, dynamic LDS bytes}                               skinny_gemm_bf16_kernel
+//   {2, KS, SWIGLU, 1, NORM, norm, grid, 0, dynamic LDS bytes}                                skinny_gemm_w8_kernel
+// (norm: a gain pointer was handed over).  g_decode_dry_run (aki_lab_set_decode_dry_run): record and return before any HIP call, so that the
+// planner runs on a machine without a GPU.  A shape that falls through to the MFMA GEMM shows in that GEMM's own log (gemm_bf16.hip).
+constexpr int kDecodeLogFields = 9, kDecodeLogCap = 256;
+static int g_decode_log[kDecodeLogCap][kDecodeLogFields];
+static int g_decode_log_n = 0;
+int g_decode_dry_run = 0;
+void decode_log_reset() { g_decode_log_n = 0; }
+int decode_log_copy(int* out, int cap) {   // records copied: min(count, cap, kDecodeLogCap); returns the number of launches since the reset
+  const int n = g_decode_log_n < kDecodeLogCap ? g_decode_log_n : kDecodeLogCap;
+  for (int i = 0; out && i < n && i < cap; ++i)
+    for (int j = 0; j < kDecodeLogFields; ++j) out[i * kDecodeLogFields + j] = g_decode_log[i][j];
+  return g_decode_log_n;
+}
+static void decode_log_push(const int (&r)[kDecodeLogFields]) {
+  if (g_decode_log_n < kDecodeLogCap)
+    for (int j = 0; j < kDecodeLogFields; ++j) g_decode_log[g_decode_log_n][j] = r[j];
+  ++g_decode_log_n;
+}
+#endif
+
 template <int M, bool SWIGLU, int FPW, bool W8 = false>
 static int launch_gemv_cfg(const GemvParams& p, int n_out, hipStream_t stream) {
   const size_t smem = (size_t)M * p.K * 2;
@@ -292,6 +318,10 @@ static int launch_gemv_cfg(const GemvParams& p, int n_out, hipStream_t stream) {
   const int groups = (n_out + 4 * FPW - 1) / (4 * FPW);
   const int per = M == 1 ? 1 : (groups + 511) / 512;
   const dim3 grid((groups + per - 1) / per), block(256);
+#ifdef AKI_LAB_HOOKS
+  decode_log_push({0, M, SWIGLU ? 1 : 0, FPW, W8 ? 1 : 0, p.norm_w ? 1 : 0, (int)grid.x, per, (int)smem});
+  if (g_decode_dry_run) return AKI_OK;
+#endif
   static bool set = false;
   if (!set) {
     if (hipFuncSetAttribute((const void*)gemv_bf16_kernel<M, SWIGLU, FPW, W8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 8192 * 2) != hipSuccess)
@@ -317,7 +347,9 @@ static int launch_gemv(const GemvParams& p, hipStream_t stream) {
   }
   if (p.act == AKI_ACT_SWIGLU) return launch_gemv_cfg<M, true, 2>(p, n_out, stream);
   // wide outputs (qkv, lm_head) have waves to spare: 4 features per wave doubles the loads each wave keeps in flight
-  if (M <= 2 && n_out >= 8192) return launch_gemv_cfg<M, false, 4>(p, n_out, stream);
+  if constexpr (M <= 2) {      // (constexpr: the four-feature kernel is not instantiated for the row counts that never take it)
+    if (n_out >= 8192) return launch_gemv_cfg<M, false, 4>(p, n_out, stream);
+  }
   return launch_gemv_cfg<M, false, 2>(p, n_out, stream);
 }
 
@@ -498,6 +530,10 @@ static int launch_skinny(const GemvParams& p, hipStream_t stream) {
   constexpr size_t RED = (size_t)KS * 2 * 1024;      // the partial tiles (two streams with SwiGLU) alias the rows
   const size_t rows = (size_t)p.M * ((size_t)p.K * 2 + 16);
   const size_t smem = NORM ? (rows > RED ? rows : RED) : 0;
+#ifdef AKI_LAB_HOOKS
+  decode_log_push({1, KS, p.act == AKI_ACT_SWIGLU ? 1 : 0, FT, NORM ? 1 : 0, p.norm_w ? 1 : 0, (int)grid.x, 0, (int)smem});
+  if (g_decode_dry_run) return AKI_OK;
+#endif
   if constexpr (NORM) {
     static bool set_s = false, set_p = false;
     bool& set = p.act == AKI_ACT_SWIGLU ? set_s : set_p;
@@ -676,6 +712,10 @@ static int launch_skinny_w8(const GemvParams& p, hipStream_t stream) {
   constexpr size_t RED = (size_t)KS * 2 * 1024;
   const size_t rows = (size_t)p.M * ((size_t)p.K * 2 + 16);
   const size_t smem = NORM ? (rows > RED ? rows : RED) : 0;
+#ifdef AKI_LAB_HOOKS
+  decode_log_push({2, KS, p.act == AKI_ACT_SWIGLU ? 1 : 0, 1, NORM ? 1 : 0, p.norm_w ? 1 : 0, (int)grid.x, 0, (int)smem});
+  if (g_decode_dry_run) return AKI_OK;
+#endif
   if constexpr (NORM) {
     static bool set_s = false, set_p = false;
     bool& set = p.act == AKI_ACT_SWIGLU ? set_s : set_p;

@@ -175,6 +175,8 @@ SIGNATURES = {
     "aki_kv_cache_quant_fp8": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p]),
     "aki_decode_attn_fused_fp8kv_fwd": (C.c_int, [C.c_void_p] * 10 + [C.c_int32] * 6 + [C.c_float, C.c_int32, C.c_void_p, C.c_size_t,
                                                                                   C.c_void_p]),
+    "aki_chunk_attn_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "aki_chunk_attn_fwd": (C.c_int, [C.c_void_p] * 9 + [C.c_int32] * 7 + [C.c_float, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "aki_decode_attn_group_workspace_bytes": (C.c_size_t, [C.c_int32] * 6),
     "aki_decode_attn_group_fwd": (C.c_int, [C.c_void_p] * 11 + [C.c_int32] * 9 + [C.c_float, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "aki_decode_chain_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),

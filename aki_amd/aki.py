@@ -202,6 +202,59 @@ class AKI(VLMWithLanguageStream):
             out[b, : len(x)] = torch.tensor(x, dtype=torch.long)
         return out.to(dev)
 
+    def _continue_from_cache(self, vision_x, lang_x, attention_mask, cache, max_new_tokens):
+        """The prefill of generate(past_key_values=cache) - the reference's continuation call (src/aki.py:193-200): the new ids `lang_x`
+        [B, T] are appended to the cache (Phi3ForCausalLM._continue: one chunked pass with lang_model.chunked_continue, T decode steps
+        without) and each sample's logits row n_new[b] - 1 is returned with the cache.  attention_mask, if given, spans the cached tokens
+        and the new ids; its last T columns are ones followed by zeros per row (a right-padded chunk), which gives n_new."""
+        from . import ops
+        from .phi3 import AkiKVCache
+        if vision_x is not None:
+            raise NotImplementedError("new images on top of an existing KV cache: the reference cannot do it either "
+                                      "(its mask for the new chunk would not cover the cached columns); start a new prefill")
+        if not isinstance(cache, AkiKVCache):
+            raise ops.AkiError("past_key_values must be the AkiKVCache returned by a use_cache=True forward of this model")
+        if lang_x is None or lang_x.dim() != 2 or lang_x.shape[1] < 1:
+            raise ValueError("generate(past_key_values=...) takes the new token ids as lang_x [B, T], T >= 1")
+        B, T_new = lang_x.shape
+        if cache.cache_len.shape[0] != B:
+            raise ValueError(f"the KV cache holds {cache.cache_len.shape[0]} rows, lang_x brings {B}")
+        n_new = None
+        if attention_mask is not None:
+            past_len = cache.get_seq_length()
+            if attention_mask.dim() != 2 or attention_mask.shape[0] != B or attention_mask.shape[1] != past_len + T_new:
+                raise ValueError(f"attention_mask must be [B, past length + new ids] = [{B}, {past_len} + {T_new}] (the entire past, image "
+                                 f"tokens included, and the current input ids); got {tuple(attention_mask.shape)}")
+            tail = attention_mask[:, past_len:].ne(0)
+            counts = tail.sum(1)
+            prefix = torch.arange(T_new, device=tail.device)[None, :] < counts[:, None]
+            if not bool((tail == prefix).all()) or int(counts.min()) < 1:
+                raise ValueError("the mask over the new ids must be ones followed by zeros in every row (a right-padded chunk), "
+                                 "with at least one real token per sample")
+            if int(counts.min()) < T_new:
+                n_new = counts.to(torch.int32)
+        if cache.host_len + T_new + max_new_tokens - 1 > cache.capacity:           # before any launch
+            raise ops.AkiError(f"KV cache is full: {cache.host_len} of {cache.capacity} rows used, the continuation needs {T_new} + "
+                               f"{max_new_tokens - 1} more; size it with lang_model(..., use_cache=True, cache_capacity=...)")
+        self._prepare_inputs_for_forward(vision_tokens=None, lang_x=lang_x, attention_mask=attention_mask, past_key_values=cache)
+        logits = self.lang_model._continue(lang_x, None, cache, n_new=n_new).logits           # [B, T, V']
+        if n_new is None:
+            return cache, logits[:, -1]
+        return cache, logits[torch.arange(B, device=logits.device), n_new.long() - 1]
+
+    @staticmethod
+    def _trim_cache_to_returned(cache, start_len, host_len0, out, eos_t):
+        """The end of generate(past_key_values=...): every row's cache ends right before its last returned token.  start_len / host_len0:
+        the cache's lengths behind the new ids; out [B, steps]: the returned tokens; a row's last token is its first EOS, or column
+        steps - 1.  The decode loops step finished rows on with pad tokens until their next look at the flags - those rows are cut off here."""
+        steps = out.shape[1]
+        kept = torch.full_like(start_len, steps - 1)
+        if eos_t is not None:
+            hit = (out[:, :, None] == eos_t[None, None, :]).any(-1)
+            kept = torch.where(hit.any(1), hit.to(torch.int32).argmax(1).to(kept.dtype), kept)
+        cache.cache_len.copy_(start_len + kept)
+        cache.host_len = host_len0 + steps - 1
+
     @torch.no_grad()
     def generate(self, vision_x, lang_x, image_size=None, attention_mask=None, past_key_values=None,
                  past_media_locations=None, past_vision_tokens=None, **kwargs):
@@ -222,6 +275,19 @@ class AKI(VLMWithLanguageStream):
         generated), `suppress_tokens`, `begin_suppress_tokens`.  As in HF `generate` with inputs_embeds only, they see the generated
         tokens, never the prompt; beam search applies them to each beam's log-softmax scores.  Any other keyword (`logits_processor`,
         `stopping_criteria`, `output_scores`, `generation_config`, ...) raises ValueError instead of being ignored.
+        `past_key_values=cache` (the AkiKVCache of a use_cache=True forward or of an earlier turn; `vision_x` must be None) continues from
+        the cache instead of a prefill: `lang_x` [B, T] holds the NEW ids only and `attention_mask`, if given, spans past + new ids (width
+        past length + T, else ValueError) with a right-padded new part (ones then zeros per row, else ValueError; ragged rows need
+        `lang_model.chunked_continue = True`).  The new ids are appended to the cache, then the same greedy / sampling loops run.  The return
+        value is again the new tokens only.  The LAST returned token of a row - its EOS where it hit one, else the last column - is not in
+        the cache, so the next turn's `lang_x` must begin with it: on return cache_len[b] = its value before the call + n_new[b] + (tokens
+        returned for row b) - 1.  The loops themselves run past that point: the graph / device loop looks at the finished flags only every
+        8th token, and until then ops.greedy_pick / ops.sample_pick feed a finished row pad tokens and advance its cache_len like any
+        other (the host loop does the same to the finished rows of a batch), so pad-token rows land behind the EOS.  A call from a cache
+        therefore rewinds cache_len to the rule above before it returns (_trim_cache_to_returned; the rows behind are dead and the next
+        append overwrites them), at B = 1 and per row in a batch - there the next turn's chunk is ragged (chunked_continue).  The cache
+        must have room for T + max_new_tokens - 1 more rows (AkiError before any launch otherwise); beam search and
+        num_return_sequences > 1 from a cache raise NotImplementedError.
         Differences from the reference, both only visible for B > 1 (where the reference is inconsistent): the
         prompt batch is right-padded and every sample continues from its own length."""
         num_beams = int(kwargs.pop("num_beams", 1))
@@ -250,8 +316,9 @@ class AKI(VLMWithLanguageStream):
             raise ValueError("num_return_sequences > 1 needs do_sample=True: greedy decoding returns one sequence per sample")
         if do_sample and temperature <= 0:
             raise ValueError("temperature must be positive")
-        if past_key_values is not None:
-            raise NotImplementedError("generate() starts from a fresh prefill")
+        if past_key_values is not None and (num_beams > 1 or n_ret > 1):
+            raise NotImplementedError("generate(past_key_values=...) continues one sequence per cached row: beam search and "
+                                      "num_return_sequences > 1 start from a fresh prefill")
         max_new_tokens = int(kwargs.pop("max_new_tokens", kwargs.pop("max_length", 20)))
         # HF `generate` stops on generation_config.eos_token_id when the caller passes none (the reference's callers pass only
         # max_new_tokens / do_sample: local_demo.py:76-87, eval_cv_bench/eval.py:99-104); `eos_token_id=[]` switches it off.
@@ -265,19 +332,24 @@ class AKI(VLMWithLanguageStream):
             use_graph = max_new_tokens >= 8          # capture costs about two eager steps
         pk = _pop_processor_kwargs(kwargs)
         _reject_unused_kwargs(kwargs)
-        if vision_x is None:
-            raise NotImplementedError("text-only generation is outside the AKI hot path")
-        plan = self._start_splice_plan(lang_x)
-        vision_tokens = self.vision_tokenizer(self._encode_vision_x(vision_x=vision_x))
-        new_inputs = self._prepare_inputs_for_forward(vision_tokens=vision_tokens, lang_x=lang_x, attention_mask=attention_mask,
-                                                      padding_side="right", splice_plan=plan)
-        table = new_inputs["attention_mask"]
-        L = new_inputs["inputs_embeds"].shape[1]
-        out = self.lang_model(inputs_embeds=new_inputs["inputs_embeds"], attention_mask=table, use_cache=True,
-                              cache_capacity=L + max_new_tokens, last_token_logits=True)
-        cache = out.past_key_values
-        B = lang_x.shape[0]
-        logits = out.logits[:, 0]                                                  # logits of each sample's last real token
+        if past_key_values is not None:
+            cache, logits = self._continue_from_cache(vision_x, lang_x, attention_mask, past_key_values, max_new_tokens)
+            B = lang_x.shape[0]
+            appended = (cache.cache_len.clone(), cache.host_len)       # the caller's cache: the state behind the new ids
+        else:
+            if vision_x is None:
+                raise NotImplementedError("text-only generation is outside the AKI hot path")
+            plan = self._start_splice_plan(lang_x)
+            vision_tokens = self.vision_tokenizer(self._encode_vision_x(vision_x=vision_x))
+            new_inputs = self._prepare_inputs_for_forward(vision_tokens=vision_tokens, lang_x=lang_x, attention_mask=attention_mask,
+                                                          padding_side="right", splice_plan=plan)
+            table = new_inputs["attention_mask"]
+            L = new_inputs["inputs_embeds"].shape[1]
+            out = self.lang_model(inputs_embeds=new_inputs["inputs_embeds"], attention_mask=table, use_cache=True,
+                                  cache_capacity=L + max_new_tokens, last_token_logits=True)
+            cache = out.past_key_values
+            B = lang_x.shape[0]
+            logits = out.logits[:, 0]                                                  # logits of each sample's last real token
         proc = ops.LogitsProcessors(logits.shape[-1], logits.device, pk["repetition_penalty"], pk["no_repeat_ngram_size"],
                                     max(int(pk["min_length"]), int(pk["min_new_tokens"])), sorted(eos_ids), pk["suppress_tokens"],
                                     pk["begin_suppress_tokens"], pk["bad_words_ids"])
@@ -387,6 +459,8 @@ class AKI(VLMWithLanguageStream):
             steps = t
             if eos_t is not None and bool(done8.all()):
                 steps = int(done_at.max()) + 1
+            if past_key_values is not None:
+                self._trim_cache_to_returned(cache, *appended, tokens[:, :steps], eos_t)
             self._post_forward_hook()
             return tokens[:, :steps]
         if use_graph:
@@ -428,5 +502,7 @@ class AKI(VLMWithLanguageStream):
             n_out, stepper = max_new_tokens, None           # a graph captured around the chain is gone with it
             if use_graph:
                 stepper = DecodeGraph(lm, cache)
+        if past_key_values is not None:
+            self._trim_cache_to_returned(cache, *appended, tokens[:, :n_out], eos_t)
         self._post_forward_hook()
         return tokens[:, :n_out]

@@ -37,6 +37,10 @@ size_t decode_attn_group_ws_bytes(int B0, int N, int H, int pcap, int scap);
 int decode_attn_group_launch(const void* qkv, const float* cos, const float* sin, const int* len, const int* plen, const void* kp,
                              const void* vp, void* ks, void* vs, void* o, const uint64_t* vbits, int nwords, int B0, int N, int H, int pcap,
                              int scap, int max_pkeys, int max_skeys, float scale, void* ws, size_t ws_bytes, hipStream_t s);
+size_t chunk_attn_ws_bytes(int B, int H, int T);
+int chunk_attn_launch(const void* qkv, const float* cos, const float* sin, const int* cache_len, const int* n_new, void* k_cache, void* v_cache,
+                      void* o, const uint64_t* vbits, int nwords, int B, int H, int T, int max_new, int cap, float scale, void* ws,
+                      size_t ws_bytes, hipStream_t s);
 size_t decode_chain_ws_bytes(int n_layers, int d, int H, int F, int cap);
 size_t decode_chain_err_offset(int n_layers, int H);
 size_t decode_chain_b_ws_bytes(int n_layers, int d, int H, int F, int cap, int B);
@@ -497,6 +501,24 @@ int aki_decode_attn_group_fwd(const void* qkv, const float* cos, const float* si
   return decode_attn_group_launch(qkv, cos, sin, cache_len, prefix_len, k_prefix, v_prefix, k_suffix, v_suffix, o, col_valid_bits, nwords, B0, N,
                                   H, prefix_capacity, suffix_capacity, max_prefix_keys, max_suffix_keys, scale, ws, ws_bytes,
                                   (hipStream_t)stream);
+}
+
+size_t aki_chunk_attn_workspace_bytes(int32_t B, int32_t H, int32_t T, int32_t Dh) {
+  if (B <= 0 || H <= 0 || T <= 0 || Dh != 96) return 0;
+  return chunk_attn_ws_bytes(B, H, T);
+}
+
+int aki_chunk_attn_fwd(const void* qkv, const float* cos, const float* sin, const int32_t* cache_len, const int32_t* n_new, void* k_cache,
+                       void* v_cache, void* o, const uint64_t* col_valid_bits, int32_t nwords, int32_t B, int32_t H, int32_t Dh, int32_t T,
+                       int32_t max_new, int32_t capacity, float scale, int32_t dtype, void* ws, size_t ws_bytes, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(qkv && cos && sin && cache_len && k_cache && v_cache && o);
+  AKI_CHECK_ARG(B > 0 && H > 0 && Dh > 0 && T > 0 && capacity > 0 && max_new >= 0 && scale > 0.f);
+  AKI_CHECK_ARG(!col_valid_bits || nwords > 0);
+  if (Dh != 96 || dtype != AKI_DT_BF16) return AKI_ERR_UNSUPPORTED;
+  if (((uintptr_t)k_cache & 15) || ((uintptr_t)v_cache & 15) || ((uintptr_t)o & 15) || ((uintptr_t)ws & 15)) return AKI_ERR_ALIGNMENT;
+  return chunk_attn_launch(qkv, cos, sin, cache_len, n_new, k_cache, v_cache, o, col_valid_bits, nwords, B, H, T, max_new, capacity, scale, ws,
+                           ws_bytes, (hipStream_t)stream);
 }
 
 int aki_decode_linear_fwd(const aki_linear_args* a, const void* rms_weight, float rms_eps, void* stream) {

@@ -549,6 +549,64 @@ def decode_attn_group(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, c
     return o
 
 
+def chunk_attn_workspace(B: int, H: int, T: int, Dh: int, device) -> torch.Tensor:
+    """The q_rot scratch of chunk_attn (nothing in it outlives a call: allocate once per chunk and pass it to every layer)."""
+    nbytes = int(L.load().aki_chunk_attn_workspace_bytes(B, H, T, Dh))
+    if nbytes <= 0:
+        raise AkiError("chunk_attn: bf16, head_dim 96 and positive sizes")
+    return torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=device)
+
+
+def chunk_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, cache_len: torch.Tensor, n_new: Optional[torch.Tensor],
+               k_cache: torch.Tensor, v_cache: torch.Tensor, num_heads: int, scale: float, col_valid_bits: Optional[torch.Tensor] = None,
+               max_new: Optional[int] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """T new tokens per sample appended to a KV cache and attended in one pass (bf16, head_dim 96; two launches, chunk_attn.hip):
+    qkv [B*T, 3*H*96] un-rotated (row b*T + t = token t of sample b); k_cache / v_cache [B, H, cap, 96].  Token t < n_new[b] is rotated at
+    position cache_len[b] + t, its k / v appended at that cache row, and it attends to the cached keys (filtered by col_valid_bits
+    [B, nwords]) plus the chunk's tokens 0..t.  -> o [B*T, H*96]; rows t >= n_new[b] are zeros.  n_new: None (every sample brings T
+    tokens) or int32 [B]; max_new: host upper bound of n_new (default T), sizes the grid.  cache_len is NOT advanced, and the caller
+    guarantees cache_len[b] + n_new[b] <= cap (Phi3ForCausalLM._continue guards it from the cache's host_len)."""
+    dev = _dev(qkv, cos, sin, cache_len, n_new, k_cache, v_cache, col_valid_bits, ws)
+    if k_cache.dim() != 4 or qkv.dim() != 2:
+        raise AkiError("chunk_attn: qkv [B*T, 3*H*Dh] and caches [B, H, cap, Dh]")
+    B, H, cap, Dh = k_cache.shape
+    R = qkv.shape[0]
+    if B <= 0 or R % B or R == 0 or H != num_heads or qkv.shape[1] != 3 * num_heads * Dh or v_cache.shape != k_cache.shape \
+            or cache_len.shape != (B,) or (n_new is not None and n_new.shape != (B,)):
+        raise AkiError("chunk_attn: rows must be samples * T, with one cache slab and one length per sample")
+    if col_valid_bits is not None and col_valid_bits.shape[0] != B:
+        raise AkiError("chunk_attn: col_valid_bits holds one row of words per sample")
+    for t in (k_cache, v_cache):
+        if not t.is_contiguous() or t.dtype != torch.bfloat16:
+            raise AkiError("chunk_attn: contiguous bf16 caches")
+    if qkv.dtype != torch.bfloat16 or Dh != 96:
+        raise AkiError("chunk_attn: bf16 and head_dim 96 only (there is no fallback: take the decode steps instead)")
+    if cache_len.dtype != torch.int32 or (n_new is not None and n_new.dtype != torch.int32):
+        raise AkiError("chunk_attn: int32 lengths")
+    if not cache_len.is_contiguous() or (n_new is not None and not n_new.is_contiguous()):
+        raise AkiError("chunk_attn: contiguous lengths")
+    for t in (cos, sin):                  # the kernel reads the Dh floats of row cache_len[b] + t < cap
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[0] < cap or t.shape[1] != Dh:
+            raise AkiError(f"chunk_attn: cos / sin must be contiguous f32 [>= cap, Dh] = [>= {cap}, {Dh}]")
+    if col_valid_bits is not None and (col_valid_bits.dtype != torch.int64 or not col_valid_bits.is_contiguous() or col_valid_bits.dim() != 2):
+        raise AkiError("chunk_attn: col_valid_bits must be contiguous int64 words [B, nwords]")
+    T = R // B
+    max_new = T if max_new is None else int(max_new)
+    if not 1 <= max_new <= T:
+        raise AkiError(f"chunk_attn: max_new must lie in [1, {T}]")
+    lib = L.load()
+    if ws is None:
+        ws = chunk_attn_workspace(B, H, T, Dh, dev)
+    qkv = qkv.contiguous()                # held in a local: the copy, if one is made, lives until the launch is queued
+    # the kernel writes the 32-row blocks up to max_new; rows past them are zeros by definition
+    o = (torch.empty if (max_new + 31) // 32 * 32 >= T else torch.zeros)((R, H * Dh), dtype=qkv.dtype, device=dev)
+    nw = 0 if col_valid_bits is None else col_valid_bits.shape[1]
+    L.check(lib.aki_chunk_attn_fwd(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(cache_len), _ptr(n_new), _ptr(k_cache), _ptr(v_cache),
+                                   _ptr(o), _ptr(col_valid_bits), nw, B, H, Dh, T, max_new, cap, float(scale), _dt(qkv), _ptr(ws),
+                                   ws.numel() * 4, _stream()), "aki_chunk_attn_fwd")
+    return o
+
+
 _CHAIN_LAST = {}                      # device index -> the torch stream of the last chain launch
 _CHAIN_LOCK = threading.Lock()
 

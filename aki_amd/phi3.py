@@ -827,6 +827,12 @@ class Phi3ForCausalLM(nn.Module):
                                                     # until tools/kv_share_bench.py has been run on an MI355X: the step times of the two forms
                                                     # are not measured, and the default may not be slower than what it replaces
 
+    chunked_continue = False                        # True: a continuation of T >= 2 tokens from a cache (_continue; generate(past_key_values=...))
+                                                    # runs as ONE pass over the weights with ops.chunk_attn instead of T teacher-forced decode
+                                                    # steps.  Measured faster (profiles/continue_bench.json: 4.8 against 51.5 ms at T = 32, batch 1), but
+                                                    # the same run's logits check of the 32-layer model misses the tiny-model bar (0.24 - 0.34 against
+                                                    # 0.10 - 0.13): off until that difference is explained
+
     def set_kv_cache_dtype(self, dtype: str = "bf16"):
         """Format of the KV caches this model allocates from now on (a use_cache=True forward, AKI.generate): "bf16" (the default) or
         "fp8_e4m3" - e4m3 K/V bytes with one f32 scale per (layer, sample, head, position), 0.52x the bytes that a batched or
@@ -915,10 +921,13 @@ class Phi3ForCausalLM(nn.Module):
             loss = causal_lm_loss(logits, labels)
         return CausalLMOutputWithPast(loss=loss, logits=logits, past_key_values=cache)
 
-    def _continue(self, input_ids, inputs_embeds, cache, labels=None):
+    def _continue(self, input_ids, inputs_embeds, cache, labels=None, n_new=None):
         """Text-only continuation from an AkiKVCache - the `past_key_values is not None` call of the reference
         (src/vlm.py:463-475 -> src/aki.py:125-130 with `input_ids` only): the new tokens attend to everything cached plus
-        their own causal prefix, i.e. T teacher-forced decode steps.  Returns logits [B, T, V'] and the same cache."""
+        their own causal prefix, i.e. T teacher-forced decode steps.  Returns logits [B, T, V'] and the same cache.
+        With `chunked_continue`, T >= 2 and an eligible cache (_chunk_eligible) the T rows go through the layers together (_continue_chunk).
+        n_new (int [B], chunk path only): real tokens per sample of a right-padded chunk - sample b appends n_new[b] rows and the logits
+        rows t >= n_new[b] are unspecified.  The sequential path raises ValueError unless every n_new[b] equals T."""
         if not isinstance(cache, AkiKVCache):
             raise ops.AkiError("past_key_values must be the AkiKVCache returned by a use_cache=True forward of this model")
         if labels is not None:
@@ -928,12 +937,67 @@ class Phi3ForCausalLM(nn.Module):
         if inputs_embeds.dim() == 2:
             inputs_embeds = inputs_embeds[:, None]
         T_new = inputs_embeds.shape[1]
+        if self.chunked_continue and T_new >= 2 and self._chunk_eligible(inputs_embeds, cache):
+            return CausalLMOutputWithPast(loss=None, logits=self._continue_chunk(inputs_embeds, cache, n_new), past_key_values=cache)
+        if n_new is not None and not bool((torch.as_tensor(n_new).cpu() == T_new).all()):
+            raise ValueError("a ragged chunk (n_new) needs the chunked continuation (chunked_continue = True and an eligible cache): "
+                             "teacher-forced decode steps append one row to every sample")
         steps = [self.decode_step(inputs_embeds=inputs_embeds[:, t], past_key_values=cache) for t in range(T_new)]
         if not self.decode_verified(cache):          # a chained step failed its check: the same steps again, five launches per layer
             cache.cache_len -= T_new
             cache.host_len -= T_new
             steps = [self.decode_step(inputs_embeds=inputs_embeds[:, t], past_key_values=cache) for t in range(T_new)]
         return CausalLMOutputWithPast(loss=None, logits=torch.stack(steps, dim=1), past_key_values=cache)
+
+    def _chunk_eligible(self, h, cache) -> bool:
+        """What ops.chunk_attn and the folded layer serve: a bf16 model whose layers all fold their norms (no e4m3 / MXFP4 decode weights),
+        a bf16, ungrouped cache with head_dim 96, one cache slab per row.  Anything else takes the decode steps, silently."""
+        return (h.dtype == torch.bfloat16 and h.is_cuda and self.model.fold_norms and all(ly.folds(h) and ly._w4 is None for ly in self.model.layers)
+                and getattr(self, "_fp8_head", None) is None and getattr(self, "_w4_head", None) is None
+                and cache.kv_dtype == "bf16" and cache.group == 1 and cache.k[0].dtype == torch.bfloat16 and cache.k[0].shape[3] == 96
+                and cache.k[0].is_contiguous() and cache.k[0].shape[0] == h.shape[0] and not torch.cuda.is_current_stream_capturing())
+
+    def _continue_chunk(self, inputs_embeds, cache, n_new=None):
+        """The T new rows of every sample through the layers in one pass: per layer the ops.linear calls of Phi3DecoderLayer.forward_folded
+        (gain-folded weights, RowStats of the residual stream) around ops.chunk_attn, which rotates q / k at position cache_len[b] + t,
+        appends k / v and attends to the cache plus the chunk's causal prefix.  The decode chain's counters, attn_ws and grid_keys are not
+        touched: a later decode_step runs on either decode path."""
+        B, T_new, d = inputs_embeds.shape
+        if cache.host_len + T_new > cache.capacity:  # before the first launch: nothing has been written
+            raise ops.AkiError(f"KV cache is full: {cache.host_len} of {cache.capacity} rows used and the chunk brings {T_new}; size it with "
+                               "lang_model(..., use_cache=True, cache_capacity=prompt_len + max_new_tokens)")
+        dev = inputs_embeds.device
+        if n_new is not None:
+            n_new = torch.as_tensor(n_new).to(device=dev, dtype=torch.int32)
+            if n_new.shape != (B,):
+                raise ValueError(f"n_new holds one count per sample: expected shape ({B},), got {tuple(n_new.shape)}")
+            n_new = n_new.clamp(0, T_new).contiguous()         # the kernel's own clamp: cache_len advances by the rows it appended
+        model = self.model
+        cos, sin = model.rotary_emb.tables(cache.capacity, dev, cache.host_len + T_new)     # the LongRoPE rule of decode: the length after the advance
+        h = inputs_embeds.reshape(B * T_new, d).contiguous()
+        st = ops.row_stats(h, model.norm.variance_epsilon)
+        ws = None
+        for ly in model.layers:
+            at, mlp, n1, n2 = ly.self_attn, ly.mlp, ly.input_layernorm, ly.post_attention_layernorm
+            wq = ly._prep.get("qkv", [at.qkv_proj.weight, n1.weight], lambda: ops.fold_gain(at.qkv_proj.weight, n1.weight), T._EPOCH)
+            wg = ly._prep.get("gate_up", [mlp.gate_up_proj.weight, n2.weight], lambda: ops.fold_gain(mlp.gate_up_proj.weight, n2.weight), T._EPOCH)
+            qkv = ops.linear(h, wq, row_scale=st.rstd)
+            if ws is None:
+                ws = ops.chunk_attn_workspace(B, at.num_heads, T_new, at.head_dim, dev)
+            o = ops.chunk_attn(qkv, cos, sin, cache.cache_len, n_new, cache.k[at.layer_idx], cache.v[at.layer_idx], at.num_heads, at.scaling,
+                               cache.valid_bits, T_new, ws)
+            st2 = ops.new_stats(B * T_new, dev)
+            h = ops.linear(o, at.o_proj.weight, residual=h, stats_out=st2, stats_eps=n2.variance_epsilon)
+            a = ops.linear(h, wg, act=ops.ACT_SWIGLU, row_scale=st2.rstd)
+            st = ops.new_stats(B * T_new, dev)
+            h = ops.linear(a, mlp.down_proj.weight, residual=h, stats_out=st, stats_eps=n1.variance_epsilon)
+        logits = self._head_folded(h.reshape(B, T_new, d), st)
+        if n_new is None:
+            cache.cache_len += T_new
+        else:
+            cache.cache_len += n_new
+        cache.host_len += T_new
+        return logits
 
     def decode_verified(self, cache) -> bool:
         """True when every decode step taken on `cache` so far is valid.  The one-launch decode chain (one sequence; decode_chain.hip) bounds

@@ -414,6 +414,23 @@ int aki_decode_attn_group_fwd(const void* qkv, const float* cos, const float* si
                               int32_t prefix_capacity, int32_t suffix_capacity, int32_t max_prefix_keys, int32_t max_suffix_keys, float scale,
                               int32_t dtype, void* ws, size_t ws_bytes, void* stream);
 
+/* Chunk attention - T new tokens per sample appended to a KV cache and attended in one pass (the continuation of a cached sequence by
+ * more than one token; bf16, Dh = 96, MHA).  qkv [B*T, 3*H*96] un-rotated, row b*T + t = token t of sample b.  Two launches on `stream`:
+ *   1. for every t < n_new[b]: q and k rotated at position cache_len[b] + t (= the cos/sin row), q to the workspace, k / v to cache row
+ *      cache_len[b] + t of k_cache / v_cache [B, H, capacity, 96]; rows t >= n_new[b] write nothing.
+ *   2. query t attends to keys j < cache_len[b] whose bit in col_valid_bits ([B][nwords], NULL = all valid; columns past nwords*64 are
+ *      valid) is set, and to the chunk's keys cache_len[b] + u with u <= t.  o [B*T, H*96]; rows t >= n_new[b] are written as zeros.
+ * n_new: [B] real tokens per sample of a right-padded chunk, NULL = T everywhere.  max_new: HOST upper bound of n_new (0 = T); rows of o
+ * from the 32-row block past it on are NOT written.  cache_len is not advanced.  The caller guarantees cache_len[b] + n_new[b] <= capacity
+ * (rows past the capacity are neither appended nor read).  The result is a function of the inputs alone, bit for bit.
+ * Workspace: aki_chunk_attn_workspace_bytes(B, H, T, Dh) bytes (0 for unsupported sizes), no initialisation needed.
+ * NULL pointers, B / H / T / capacity < 1 -> AKI_ERR_INVALID_ARG; Dh != 96 or dtype != AKI_DT_BF16 -> AKI_ERR_UNSUPPORTED; a short
+ * workspace -> AKI_ERR_WORKSPACE.  Purely additive: AKI_ABI_VERSION was not bumped (it stays 17). */
+size_t aki_chunk_attn_workspace_bytes(int32_t B, int32_t H, int32_t T, int32_t Dh);
+int aki_chunk_attn_fwd(const void* qkv, const float* cos, const float* sin, const int32_t* cache_len, const int32_t* n_new, void* k_cache,
+                       void* v_cache, void* o, const uint64_t* col_valid_bits, int32_t nwords, int32_t B, int32_t H, int32_t Dh, int32_t T,
+                       int32_t max_new, int32_t capacity, float scale, int32_t dtype, void* ws, size_t ws_bytes, void* stream);
+
 /* aki_decode_chain_fwd - ALL decoder layers of one decode step for ONE sequence (batch 1) in one launch (bf16 weights, or
  * AKI_DT_W8A16: e4m3 weights with one f32 scale per weight row).  Same arithmetic as the per-layer calls above
  * (aki_decode_linear_fwd -> aki_decode_attn_fused_fwd -> aki_linear_fwd + residual -> aki_decode_linear_fwd SwiGLU -> aki_linear_fwd

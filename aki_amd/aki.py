@@ -82,6 +82,8 @@ class AKI(VLMWithLanguageStream):
             lang_model=lang_model, initial_tokenizer_len=initial_tokenizer_len, gradient_checkpointing=gradient_checkpointing,
             base_img_size=base_img_size, decoder_layers_attr_name=decoder_layers_attr_name, pad_token_id=pad_token_id)
 
+    last_beam_scores = None     # after a device beam search (_beam_search_device): the returned rows' scores, HF's sequences_scores
+
     def set_trainable(self):
         """Unfreeze everything except the vision_encoder (src/aki.py:52-57)."""
         self.requires_grad_(True)
@@ -202,6 +204,76 @@ class AKI(VLMWithLanguageStream):
             out[b, : len(x)] = torch.tensor(x, dtype=torch.long)
         return out.to(dev)
 
+    def _device_beam_search_ok(self, cache, logits, K: int, eos_ids) -> bool:
+        """The device path (ops.beam_step / ops.kv_beam_reorder) is opt-in (`lang_model.device_beam_search = True`) and serves bf16 / f32
+        logits on the GPU over an ungrouped cache whose K and V are contiguous tensors in the model's dtype; anything else keeps the
+        host loop."""
+        from . import ops
+        if not getattr(self.lang_model, "device_beam_search", False):
+            return False
+        if not logits.is_cuda or logits.dtype not in (torch.bfloat16, torch.float32):
+            return False
+        if K > ops.BEAM_MAX_K or len(eos_ids) > ops.BEAM_MAX_EOS or logits.shape[-1] < 2:
+            return False
+        if getattr(cache, "kv_dtype", None) != "bf16" or getattr(cache, "group", 1) != 1:
+            return False
+        return all(t_.is_cuda and t_.is_contiguous() and t_.dtype in (torch.bfloat16, torch.float32) for t_ in list(cache.k) + list(cache.v))
+
+    def _beam_search_device(self, cache, logits, K: int, max_new_tokens: int, eos_ids, pad_id: int, length_penalty: float, early_stopping,
+                            proc=None, use_graph: bool = False):
+        """_beam_search with the per-token work on the device: ops.beam_logprob (f32 log-softmax), the processors, ops.beam_step (the
+        2K candidates, ranked - exactly equal scores by the lower beam * V + token - and all of the BeamSearchScorer bookkeeping), and
+        ops.kv_beam_reorder, which moves only the cache rows written since the prefill, in place: the cache tensors keep their
+        addresses, so the decode step at B*K rows is replayed from a DecodeGraph.  The host looks at the done flags every 8th token."""
+        from . import ops
+        from .phi3 import DecodeGraph
+        dev = logits.device
+        B = logits.shape[0]
+        self.last_beam_scores = []
+        if max_new_tokens <= 0:
+            return torch.zeros((B, 0), dtype=torch.long, device=dev)
+        if cache.host_len + max_new_tokens - 1 > cache.capacity:                   # before any launch
+            raise ops.AkiError(f"KV cache is full: {cache.host_len} of {cache.capacity} rows used, beam search needs {max_new_tokens - 1} more; "
+                               "size it with lang_model(..., use_cache=True, cache_capacity=...)")
+        lm = self.lang_model
+        cache.select_rows(torch.arange(B, device=dev).repeat_interleave(K))        # the one copy of the prompt rows: B -> B*K
+        table = ops.KVBeamTable(list(cache.k) + list(cache.v))
+        start_len, host_len0 = cache.cache_len.clone(), cache.host_len
+        pos_lo = int(start_len.min())                  # once per call: a ragged batch's short prompts write below the longest prompt's end
+        st = ops.BeamState(B, K, max_new_tokens, dev, eos_ids, pad_id, length_penalty, early_stopping)
+        logp = torch.empty((B * K, logits.shape[-1]), dtype=torch.float32, device=dev)
+
+        def select(step_logits, t):
+            ops.beam_logprob(step_logits, out=logp)
+            if proc is not None:                       # HF: the processors see each beam's log-softmax scores and its own tokens
+                proc.apply(logp, out=logp, tokens=st.seqs, step=t)
+            ops.beam_step(logp, st, t, last=t + 1 == max_new_tokens)
+
+        select(logits.repeat_interleave(K, dim=0).contiguous(), 0)
+        stepper = DecodeGraph(lm, cache) if use_graph else None
+        for t in range(1, max_new_tokens):
+            if t % 8 == 0 and bool(st.done.all()):     # frozen samples make the late look harmless
+                break
+            if cache.host_len > host_len0:
+                ops.kv_beam_reorder(table, st.parent, start_len, cache.cache_len, K, pos_lo, cache.host_len)
+            if stepper is not None:
+                step_logits = stepper.step(st.next_ids)
+            else:
+                step_logits = lm.decode_step(input_ids=st.next_ids, past_key_values=cache)
+            select(step_logits, t)
+        count = st.hyp_count.tolist()
+        score, length, toks = st.hyp_score.tolist(), st.hyp_len.tolist(), st.hyp_tokens.cpu()
+        best = []                                      # last_beam_scores: HF's sequences_scores of the returned rows (f32, length-normalised)
+        for b in range(B):                             # the best hypothesis; among equal scores the lowest slot
+            i = max(range(count[b]), key=lambda j: (score[b][j], -j))
+            best.append(toks[b, i, :length[b][i]])
+            self.last_beam_scores.append(score[b][i])
+        width = max(x.numel() for x in best)
+        out = torch.full((B, width), pad_id, dtype=torch.long)
+        for b, x in enumerate(best):
+            out[b, : x.numel()] = x
+        return out.to(dev)
+
     def _continue_from_cache(self, vision_x, lang_x, attention_mask, cache, max_new_tokens):
         """The prefill of generate(past_key_values=cache) - the reference's continuation call (src/aki.py:193-200): the new ids `lang_x`
         [B, T] are appended to the cache (Phi3ForCausalLM._continue: one chunked pass with lang_model.chunked_continue, T decode steps
@@ -269,7 +341,9 @@ class AKI(VLMWithLanguageStream):
         in HF order, row b*N + j being continuation j of sample b: one prefill, token 0 of each row drawn from its sample's prefill logits, then
         the same loops at batch B*N - the device sampler's row index is b*N + j.  The prompt's K/V rows are replicated N times (select_rows)
         unless `lang_model.share_prompt_kv = True`, with which the N rows of a sample read ONE copy of them (AkiKVCache.share_prefix +
-        ops.decode_attn_group; bf16 model and cache, head_dim 96, more than one new token - anything else stays replicated); without sampling it raises ValueError, with beams NotImplementedError), beam search (`num_beams=K`, `length_penalty`, `early_stopping`; one returned sequence per sample).
+        ops.decode_attn_group; bf16 model and cache, head_dim 96, more than one new token - anything else stays replicated); without sampling it raises ValueError, with beams NotImplementedError), beam search (`num_beams=K`, `length_penalty`, `early_stopping`; one returned sequence per sample;
+        `lang_model.device_beam_search = True` runs the search on the device - ops.beam_step and ops.kv_beam_reorder, _beam_search_device -
+        where the host loop is used otherwise; off by default: its step time has not been measured yet).
         Logits processors, applied on the device in every mode and in HF's order (ops.LogitsProcessors): `repetition_penalty`,
         `no_repeat_ngram_size`, `bad_words_ids`, `min_length` / `min_new_tokens` (eos ids banned until that many tokens are
         generated), `suppress_tokens`, `begin_suppress_tokens`.  As in HF `generate` with inputs_embeds only, they see the generated
@@ -355,7 +429,11 @@ class AKI(VLMWithLanguageStream):
                                     pk["begin_suppress_tokens"], pk["bad_words_ids"])
         proc = proc if proc.active else None       # no processor: exactly the launches of a plain generate
         if num_beams > 1:
-            tokens = self._beam_search(cache, logits, num_beams, max_new_tokens, eos_ids, pad_id, length_penalty, early_stopping, proc)
+            if self._device_beam_search_ok(cache, logits, num_beams, eos_ids):
+                tokens = self._beam_search_device(cache, logits, num_beams, max_new_tokens, eos_ids, pad_id, length_penalty, early_stopping,
+                                                  proc, use_graph)
+            else:
+                tokens = self._beam_search(cache, logits, num_beams, max_new_tokens, eos_ids, pad_id, length_penalty, early_stopping, proc)
             self._post_forward_hook()
             return tokens
         if n_ret > 1:

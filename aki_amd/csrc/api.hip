@@ -74,6 +74,13 @@ int sample_pick_launch(const void* logits, int B, int V, int ld, const int64_t* 
                        int min_len, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids,
                        const int* bad_off, int n_bad, int n_bad_ids, int step, float temperature, int top_k, float top_p, uint64_t seed,
                        uint64_t offset, float* probs, int ld_probs, hipStream_t s);
+int beam_logprob_launch(const void* logits, int in_f32, int rows, int V, int ld, float* out, int ld_out, hipStream_t s);
+int beam_step_launch(const float* logp, int ld, int B, int K, int V, int t, int max_new, float* beam_scores, const int64_t* seqs_in,
+                     int64_t* seqs_out, float* hyp_score, int* hyp_len, int64_t* hyp_tokens, int* hyp_count, unsigned char* done,
+                     int64_t* next_ids, int* parent, const int64_t* eos, int n_eos, int64_t pad, float length_penalty, int early, int last,
+                     hipStream_t s);
+int kv_beam_reorder_launch(void* const* table, int n_tensors, const int* parent, const int* start_len, const int* cache_len, int B, int K,
+                           int H, int cap, int row_bytes, int pos_lo, int pos_hi, hipStream_t s);
 int sft_collate_launch(const int64_t* ids, const int64_t* labels, const int64_t* mask, const int* offsets, int B, int T_out,
                        int64_t pad_id, int64_t ignore_index, int left, int64_t* out_ids, int64_t* out_labels, int64_t* out_mask,
                        hipStream_t s);
@@ -866,6 +873,36 @@ int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const 
                             done_at, embed_weight, additional_weight, max_original_id, d, next_embeds, scores, (int)ld_scores, repetition_penalty,
                             no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets,
                             n_bad, n_bad_ids, step, temperature, top_k, top_p, seed, offset, probs_out, (int)ld_probs, (hipStream_t)stream);
+}
+
+int aki_beam_logprob(const void* logits, int32_t dtype, int32_t rows, int32_t V, int64_t ld, float* out, int64_t ld_out, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(logits && out && rows > 0 && V > 0 && ld >= V && ld < (1ll << 31) && ld_out >= V && ld_out < (1ll << 31));
+  if (dtype != AKI_DT_BF16 && dtype != AKI_DT_F32) return AKI_ERR_UNSUPPORTED;
+  return beam_logprob_launch(logits, dtype == AKI_DT_F32, rows, V, (int)ld, out, (int)ld_out, (hipStream_t)stream);
+}
+
+int aki_beam_step(const float* logp, int64_t ld, int32_t B, int32_t K, int32_t V, int32_t t, int32_t max_new, float* beam_scores,
+                  const int64_t* seqs_in, int64_t* seqs_out, float* hyp_score, int32_t* hyp_len, int64_t* hyp_tokens, int32_t* hyp_count,
+                  uint8_t* done, int64_t* next_ids, int32_t* parent, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                  float length_penalty, int32_t early_stopping, int32_t last, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(logp && beam_scores && seqs_out && hyp_score && hyp_len && hyp_tokens && hyp_count && done && next_ids && parent);
+  AKI_CHECK_ARG(B > 0 && V >= 2 && ld >= V && ld < (1ll << 31) && t >= 0 && t < max_new && (t == 0 || seqs_in) && seqs_in != seqs_out);
+  AKI_CHECK_ARG(n_eos >= 0 && (n_eos == 0 || eos_ids) && length_penalty == length_penalty);
+  if (K < 1 || K > AKI_BEAM_MAX_K || n_eos > AKI_BEAM_MAX_EOS || (int64_t)K * V >= (1ll << 31)) return AKI_ERR_UNSUPPORTED;
+  return beam_step_launch(logp, (int)ld, B, K, V, t, max_new, beam_scores, seqs_in, seqs_out, hyp_score, hyp_len, hyp_tokens, hyp_count, done,
+                          next_ids, parent, eos_ids, n_eos, pad_token_id, length_penalty, early_stopping, last ? 1 : 0, (hipStream_t)stream);
+}
+
+int aki_kv_beam_reorder(void* const* table, int32_t n_tensors, const int32_t* parent, const int32_t* start_len, const int32_t* cache_len,
+                        int32_t B, int32_t K, int32_t H, int32_t capacity, int32_t row_bytes, int32_t pos_lo, int32_t pos_hi, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(table && parent && start_len && cache_len && n_tensors > 0 && B > 0 && H > 0 && capacity > 0 && row_bytes > 0);
+  AKI_CHECK_ARG(pos_lo >= 0 && pos_lo <= pos_hi && pos_hi <= capacity);
+  if (K < 1 || K > AKI_BEAM_MAX_K || row_bytes % 4 != 0 || H > 65535 || (int64_t)n_tensors * B > 65535) return AKI_ERR_UNSUPPORTED;
+  return kv_beam_reorder_launch(table, n_tensors, parent, start_len, cache_len, B, K, H, capacity, row_bytes, pos_lo, pos_hi,
+                                (hipStream_t)stream);
 }
 
 size_t aki_mma_mask_to_table_workspace_bytes(int32_t B, int32_t L) {

@@ -943,7 +943,122 @@ def _sample_scratch(B: int, V: int, dev) -> torch.Tensor:
     return _SAMPLE_SCRATCH[key]
 
 
-SKINNY_NORM_FUSED = True          # tools (decode_bench.py --norm-launch): False = the RMSNorm of 2-8 row decode GEMMs as a launch of its own
+# ---- beam search on the device (beam.hip) ----------------------------------------------------------------------------------------
+BEAM_MAX_K, BEAM_MAX_EOS, KV_BEAM_REORDER_CHUNK = L.AKI_BEAM_MAX_K, L.AKI_BEAM_MAX_EOS, L.AKI_KV_BEAM_REORDER_CHUNK
+
+
+def beam_logprob(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """f32 log-softmax [rows, V] of bf16 / f32 logits [rows, V] (row stride >= V), one launch (aki_beam_logprob): f32 arithmetic in a
+    fixed order - the same inputs give the same bits on every run."""
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise AkiError("beam_logprob takes logits [rows, V] with unit column stride and a row stride >= V")
+    rows, V = logits.shape
+    dev = _dev(logits, out)
+    if out is None:
+        out = torch.empty((rows, V), dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or tuple(out.shape) != (rows, V) or out.stride(1) != 1 or out.stride(0) < V:
+        raise AkiError("beam_logprob: out is f32 [rows, V] with unit column stride")
+    L.check(L.load().aki_beam_logprob(_ptr(logits), _dt(logits), rows, V, logits.stride(0), _ptr(out), out.stride(0), _stream()),
+            "aki_beam_logprob")
+    return out
+
+
+class BeamState:
+    """The device state of one beam search (ops.beam_step), allocated once: running `beam_scores` f32 [B, K] (beam 0 of a sample starts at
+    0, the others at -1e9: all beams start identical), the beams' tokens `seqs` int64 [B*K, max_new] (a ping-pong pair: `seqs` is the
+    buffer the last step wrote), the hypotheses `hyp_score` f32 [B, K], `hyp_len` int32 [B, K], `hyp_tokens` int64 [B, K, max_new],
+    `hyp_count` int32 [B], the samples' `done` flags uint8 [B], and the last step's `next_ids` int64 [B*K] and `parent` int32 [B*K]
+    (global rows b*K + beam).  early_stopping: True, False, or anything else ("never"), as HF's BeamSearchScorer reads it."""
+
+    def __init__(self, B: int, K: int, max_new: int, device, eos_ids=(), pad_token_id: int = 0, length_penalty: float = 1.0,
+                 early_stopping=False):
+        B, K, max_new = int(B), int(K), int(max_new)
+        eos = sorted(set(int(e) for e in eos_ids))
+        if B < 1 or max_new < 1 or not 1 <= K <= BEAM_MAX_K or len(eos) > BEAM_MAX_EOS:
+            raise AkiError(f"BeamState: B >= 1, max_new >= 1, 1 <= K <= {BEAM_MAX_K} and at most {BEAM_MAX_EOS} eos ids are expected")
+        dev = torch.device(device)
+        self.B, self.K, self.max_new = B, K, max_new
+        self.pad_token_id, self.length_penalty = int(pad_token_id), float(length_penalty)
+        self.early = 1 if early_stopping is True else (0 if early_stopping is False else 2)
+        self.eos = torch.tensor(eos, dtype=torch.int64, device=dev) if eos else None
+        self.beam_scores = torch.zeros((B, K), dtype=torch.float32, device=dev)
+        self.beam_scores[:, 1:] = -1e9
+        self._seqs = [torch.zeros((B * K, max_new), dtype=torch.int64, device=dev) for _ in range(2)]
+        self._cur = 0
+        self.hyp_score = torch.zeros((B, K), dtype=torch.float32, device=dev)
+        self.hyp_len = torch.zeros((B, K), dtype=torch.int32, device=dev)
+        self.hyp_tokens = torch.zeros((B, K, max_new), dtype=torch.int64, device=dev)
+        self.hyp_count = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.done = torch.zeros((B,), dtype=torch.uint8, device=dev)
+        self.next_ids = torch.zeros((B * K,), dtype=torch.int64, device=dev)
+        self.parent = torch.arange(B * K, dtype=torch.int32, device=dev)
+
+    @property
+    def seqs(self) -> torch.Tensor:
+        return self._seqs[self._cur]
+
+
+def beam_step(logp: torch.Tensor, state: BeamState, t: int, last: bool = False) -> BeamState:
+    """One step of the search for every sample, one launch (aki_beam_step; the per-token body of AKI._beam_search): the 2K best of
+    logp[b*K + k, v] + beam_scores[b, k] ranked by score (exactly equal scores: the lower k*V + v first), the EOS / hypothesis / done
+    bookkeeping of HF's BeamSearchScorer, state.seqs re-ordered by parent and extended by token t.  logp: f32 [B*K, V] (row stride >= V).
+    last: the closing step.  Capturable: no host value is read."""
+    if logp.dtype != torch.float32 or logp.dim() != 2 or logp.stride(1) != 1 or logp.shape[0] != state.B * state.K \
+            or logp.stride(0) < logp.shape[1]:
+        raise AkiError("beam_step takes f32 log-probabilities [B*K, V] with unit column stride")
+    if _dev(logp) != state.beam_scores.device:
+        raise AkiError("beam_step: logp and the state are on different devices")
+    t = int(t)
+    if not 0 <= t < state.max_new:
+        raise AkiError(f"beam_step: step {t} is outside [0, {state.max_new})")
+    src, dst = state._seqs[state._cur], state._seqs[1 - state._cur]
+    L.check(L.load().aki_beam_step(_ptr(logp), logp.stride(0), state.B, state.K, logp.shape[1], t, state.max_new, _ptr(state.beam_scores),
+                                   _ptr(src), _ptr(dst), _ptr(state.hyp_score), _ptr(state.hyp_len), _ptr(state.hyp_tokens),
+                                   _ptr(state.hyp_count), _ptr(state.done), _ptr(state.next_ids), _ptr(state.parent), _ptr(state.eos),
+                                   0 if state.eos is None else state.eos.numel(), state.pad_token_id, state.length_penalty, state.early,
+                                   1 if last else 0, _stream()), "aki_beam_step")
+    state._cur = 1 - state._cur
+    return state
+
+
+class KVBeamTable:
+    """The device table of ops.kv_beam_reorder: the base addresses of the cache tensors [B*K, H, capacity, Dh] (every layer's K and V),
+    built once per search.  The tensors are held, so the addresses stay valid."""
+
+    def __init__(self, tensors):
+        self.tensors = list(tensors)
+        t0 = self.tensors[0]
+        for t_ in self.tensors:
+            if t_.dim() != 4 or t_.shape != t0.shape or t_.dtype != t0.dtype or not t_.is_contiguous() or not t_.is_cuda or t_.device != t0.device:
+                raise AkiError("kv_beam_reorder: contiguous GPU tensors [rows, H, capacity, Dh] of one shape and dtype are expected")
+        self.rows, self.H, self.capacity, Dh = t0.shape
+        self.row_bytes = Dh * t0.element_size()
+        if self.row_bytes % 4 or any(t_.data_ptr() % 16 for t_ in self.tensors):
+            raise AkiError("kv_beam_reorder: rows of a multiple of 4 bytes in 16-byte aligned tensors are expected")
+        self.table = torch.tensor([t_.data_ptr() for t_ in self.tensors], dtype=torch.int64, device=t0.device)
+
+
+def kv_beam_reorder(table: KVBeamTable, parent: torch.Tensor, start_len: torch.Tensor, cache_len: torch.Tensor, K: int, pos_lo: int,
+                    pos_hi: int) -> None:
+    """Beam search's cache re-ordering in place, one launch over all tensors of `table` (aki_kv_beam_reorder):
+    t[b*K + n, h, pos, :] = t[parent[b*K + n], h, pos, :] for start_len[row] <= pos < cache_len[row] - the rows written since the prefill; the
+    prompt rows, identical across the beams of a sample, never move.  parent / start_len / cache_len: int32 [rows] on the device;
+    [pos_lo, pos_hi): host bounds of those positions (they size the grid only).  Samples whose parents are the identity are skipped."""
+    K = int(K)
+    rows = table.rows
+    for t_ in (parent, start_len, cache_len):
+        if t_.dtype != torch.int32 or not t_.is_contiguous() or t_.device != table.table.device or t_.numel() != rows:
+            raise AkiError("kv_beam_reorder: parent, start_len and cache_len are contiguous int32 [rows] on the cache's device")
+    if not 1 <= K <= BEAM_MAX_K or rows % K:
+        raise AkiError(f"kv_beam_reorder: 1 <= K <= {BEAM_MAX_K} dividing the cache's {rows} rows is expected")
+    pos_lo, pos_hi = max(int(pos_lo), 0), min(int(pos_hi), table.capacity)
+    if pos_hi <= pos_lo:
+        return
+    L.check(L.load().aki_kv_beam_reorder(_ptr(table.table), len(table.tensors), _ptr(parent), _ptr(start_len), _ptr(cache_len), rows // K, K,
+                                         table.H, table.capacity, table.row_bytes, pos_lo, pos_hi, _stream()), "aki_kv_beam_reorder")
+
+
+SKINNY_NORM_FUSED = True        # tools (decode_bench.py --norm-launch): False = the RMSNorm of 2-8 row decode GEMMs as a launch of its own
 
 
 def decode_linear(x: torch.Tensor, w: torch.Tensor, rms_weight: torch.Tensor, eps: float, act: int = ACT_NONE,

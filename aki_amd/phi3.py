@@ -833,6 +833,12 @@ class Phi3ForCausalLM(nn.Module):
                                                     # the same run's logits check of the 32-layer model misses the tiny-model bar (0.24 - 0.34 against
                                                     # 0.10 - 0.13): off until that difference is explained
 
+    device_beam_search = False                      # True: generate(num_beams=K) selects, keeps its hypotheses and re-orders the cache rows
+                                                    # written since the prefill on the device (ops.beam_step, ops.kv_beam_reorder;
+                                                    # AKI._beam_search_device) instead of the host loop with its whole-cache index_select.
+                                                    # Off until tools/beam_bench.py has been run on an MI355X: the step times of the two
+                                                    # forms are not measured (README)
+
     def set_kv_cache_dtype(self, dtype: str = "bf16"):
         """Format of the KV caches this model allocates from now on (a use_cache=True forward, AKI.generate): "bf16" (the default) or
         "fp8_e4m3" - e4m3 K/V bytes with one f32 scale per (layer, sample, head, position), 0.52x the bytes that a batched or

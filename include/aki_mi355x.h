@@ -853,6 +853,50 @@ int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const 
                     int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
                     uint64_t offset, float* probs_out, int64_t ld_probs, void* stream);
 
+/* ---- beam search on the device (beam.hip).  HF `GenerationMixin` beam search with a `BeamSearchScorer`, the algorithm AKI._beam_search
+ * runs on the host: 2K candidates per step, hypotheses normalised by generated_length ** length_penalty, at most K per sample.
+ * Purely additive: AKI_ABI_VERSION was not bumped (it stays 17). */
+#define AKI_BEAM_MAX_K 16
+#define AKI_BEAM_MAX_EOS 8
+#define AKI_KV_BEAM_REORDER_CHUNK 16   /* cache positions one workgroup of aki_kv_beam_reorder owns */
+
+/* aki_beam_logprob - out[r, v] = x - (m + log(sum_v exp(x - m))), m = max_v x, for rows r < rows of logits [rows, ld] (AKI_DT_BF16 or
+ * AKI_DT_F32, V columns used) -> out f32 [rows, ld_out].  f32 arithmetic, one workgroup per row, a fixed reduction order (no atomics):
+ * the same inputs give the same bits on every run.  out == logits is allowed for f32. */
+int aki_beam_logprob(const void* logits, int32_t dtype, int32_t rows, int32_t V, int64_t ld, float* out, int64_t ld_out, void* stream);
+
+/* aki_beam_step - one step of the search for every sample, one launch, no host value read.  logp f32 [B*K, ld] holds the (processed)
+ * log-probabilities of the beams' next token, beam_scores f32 [B, K] the running sums (in / out), t the number of tokens generated so
+ * far (the step writes token t), 1 <= K <= AKI_BEAM_MAX_K, 2 <= V, K * V < 2^31, 0 <= t < max_new, n_eos <= AKI_BEAM_MAX_EOS.
+ *   candidates   the 2K best of logp[b*K + k, v] + beam_scores[b, k] (one f32 addition), ranked by score, descending; among exactly equal
+ *                scores the lower flat index k * V + v comes first.  The ranking does not depend on how the work is laid out.
+ *   walk         in rank order: an eos candidate of rank < K becomes a hypothesis with score sum / (t + 1) ** length_penalty (f32), one of
+ *                rank >= K is dropped; the first K others become the running beams: beam_scores[b, n], next_ids[b*K + n],
+ *                parent[b*K + n] = the GLOBAL row b*K + beam, seqs_out[b*K + n] = seqs_in[parent] + [token].  Unfilled slots: -1e9,
+ *                pad_token_id, parent b*K.
+ *   hypotheses   at most K per sample in hyp_score f32 [B, K], hyp_len int32 [B, K], hyp_tokens int64 [B, K, max_new], hyp_count int32 [B]
+ *                (all zero before step 0): a new one takes a free slot, or - when its score is strictly better than the worst held -
+ *                the worst one's slot (among equal worst scores the lowest slot).
+ *   done         when K hypotheses are held: early_stopping 1 -> done; 0 -> done when the worst held score >= the best running score /
+ *                (t + 1) ** length_penalty; any other value -> never.  A sample with done[b] != 0 at entry is frozen: nothing of its state
+ *                is touched, next_ids = pad_token_id, parent = the identity, seqs_out = seqs_in + [pad_token_id].
+ *   last != 0    the closing step: the running beams of a sample not done, with score > -1e8, become hypotheses with this step's token.
+ * seqs_in / seqs_out: int64 [B*K, max_new], two different buffers (the caller swaps them every step; seqs_in may be NULL at t == 0). */
+int aki_beam_step(const float* logp, int64_t ld, int32_t B, int32_t K, int32_t V, int32_t t, int32_t max_new, float* beam_scores,
+                  const int64_t* seqs_in, int64_t* seqs_out, float* hyp_score, int32_t* hyp_len, int64_t* hyp_tokens, int32_t* hyp_count,
+                  uint8_t* done, int64_t* next_ids, int32_t* parent, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                  float length_penalty, int32_t early_stopping, int32_t last, void* stream);
+
+/* aki_kv_beam_reorder - beam search's cache re-ordering (HF `_reorder_cache`) in place, for the rows written since the prefill only:
+ * for each of the n_tensors tensors [B*K, H, capacity, row_bytes] whose base addresses `table` holds (DEVICE memory: the K and V
+ * tensors of every layer), dst[b*K + n, h, pos, :] = src[parent[b*K + n], h, pos, :] for start_len[row] <= pos < cache_len[row] (row: both the
+ * destination's and the source's).  Rows move as bytes: 16-byte vectors when row_bytes % 16 == 0 (bases 16-byte aligned), 4-byte words when
+ * row_bytes % 4 == 0.  [pos_lo, pos_hi): host bounds of the positions any row may move (the grid's extent; the device lengths decide).
+ * A sample whose parents are the identity is skipped; a parent outside [b*K, b*K + K) is read as the identity.  Positions outside
+ * [start_len, cache_len) are neither read nor written.  One launch; n_tensors * B <= 65535, H <= 65535, K <= AKI_BEAM_MAX_K. */
+int aki_kv_beam_reorder(void* const* table, int32_t n_tensors, const int32_t* parent, const int32_t* start_len, const int32_t* cache_len,
+                        int32_t B, int32_t K, int32_t H, int32_t capacity, int32_t row_bytes, int32_t pos_lo, int32_t pos_hi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,10 +22,6 @@
 
 namespace aki {
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-
 struct GemvParams {
   const bf16_t* x; const bf16_t* w; const bf16_t* bias; const bf16_t* residual; bf16_t* y;
   const bf16_t* norm_w; float norm_eps;       // optional fused RMSNorm of the x rows (decode: the layer's pre-norm)
@@ -70,22 +66,7 @@ __device__ __forceinline__ void gemv_consume(const u32x4 (&w)[U][NR], const char
   }
 }
 
-// weight-only fp8 (e4m3 weights, bf16 activations): a 16-byte weight chunk holds 16 k-values and meets two 16-byte x chunks;
-// v_cvt_scalef32_pk_bf16_fp8 (scale 1) turns two weights into a bf16 pair in one instruction (exact: e4m3 fits bf16) for the same dot2:
-// 16 VALU operations per 16 weights (until round 5: v_cvt_pk_f32_fp8 + v_cvt_pk_bf16_f32 + dot2 = 24, and the e4m3 decode was VALU-bound).
-__device__ __forceinline__ float dot16_w8(const u32x4 w, const u32x4 x0, const u32x4 x1, float acc) {
-  const bf16x8_t xa = __builtin_bit_cast(bf16x8_t, x0), xb = __builtin_bit_cast(bf16x8_t, x1);
-#define AKI_W8_PAIR(word, hi, xv, i0)                                                                               \
-  {                                                                                                                 \
-    const bf16x2_t wb = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((unsigned)(word), 1.0f, hi);   /* two e4m3 -> a bf16 pair in ONE instruction, exact */ \
-    acc = __builtin_amdgcn_fdot2_f32_bf16(wb, __builtin_shufflevector(xv, xv, i0, i0 + 1), acc, false);             \
-  }
-  AKI_W8_PAIR(w[0], false, xa, 0) AKI_W8_PAIR(w[0], true, xa, 2) AKI_W8_PAIR(w[1], false, xa, 4) AKI_W8_PAIR(w[1], true, xa, 6)
-  AKI_W8_PAIR(w[2], false, xb, 0) AKI_W8_PAIR(w[2], true, xb, 2) AKI_W8_PAIR(w[3], false, xb, 4) AKI_W8_PAIR(w[3], true, xb, 6)
-#undef AKI_W8_PAIR
-  return acc;
-}
-
+// weight-only fp8 (e4m3 weights, bf16 activations); the dot product is dot16_w8 (weight_dot.h)
 template <int NR, int U>
 __device__ __forceinline__ void gemv_issue_w8(const uint8_t* const (&wr)[NR], int c, u32x4 (&w)[U][NR]) {
 #pragma unroll
@@ -661,8 +642,8 @@ __global__ __launch_bounds__(KS * 64) void skinny_gemm_w8_kernel(const GemvParam
 #pragma unroll
           for (int t = 0; t < NS; ++t) {
             const unsigned d0 = wa[u][t][j >> 1][(j & 1) * 2], d1 = wa[u][t][j >> 1][(j & 1) * 2 + 1];
-            const bf16x2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, true);
-            const bf16x2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, true);
+            const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, true);
+            const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, true);
             const u32x4 wq = u32x4{__builtin_bit_cast(unsigned, p0), __builtin_bit_cast(unsigned, p1), __builtin_bit_cast(unsigned, p2), __builtin_bit_cast(unsigned, p3)};
             acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wq), xb, acc[t], 0, 0, 0);
           }

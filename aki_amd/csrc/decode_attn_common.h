@@ -4,6 +4,7 @@
 // fused item.  The outputs of these kernels are compared bit for bit (aki_device.h); the order of operations they share is this text.
 #pragma once
 #include "aki_device.h"
+#include "weight_dot.h"      // dot8_bf16: the score of one key
 
 namespace aki {
 
@@ -134,17 +135,6 @@ __device__ __forceinline__ RopeRow rope_row(const float* cos, const float* sin, 
 __device__ __forceinline__ void rope_rotate_half(const RopeRow& t, float x0, float x1, __bf16& r0, __bf16& r1) {
   r0 = (__bf16)(x0 * t.c0 - x1 * t.s0);
   r1 = (__bf16)(x1 * t.c1 + x0 * t.s1);
-}
-
-// NB: indexing the u32x4 and bit-casting each dword (bit_cast<bf16x2>(a[i])) is folded by hipcc 7.2 into four uses of
-// dword 0; viewing the whole 16 bytes as bf16x8 and slicing pairs with shufflevector selects the right operands.
-__device__ __forceinline__ float dot8_bf16(const u32x4 a, const u32x4 b, float acc) {
-  const bf16x8 a8 = __builtin_bit_cast(bf16x8, a), b8 = __builtin_bit_cast(bf16x8, b);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a8, a8, 0, 1), __builtin_shufflevector(b8, b8, 0, 1), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a8, a8, 2, 3), __builtin_shufflevector(b8, b8, 2, 3), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a8, a8, 4, 5), __builtin_shufflevector(b8, b8, 4, 5), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a8, a8, 6, 7), __builtin_shufflevector(b8, b8, 6, 7), acc, false);
-  return acc;
 }
 
 // ---- the bf16 item: keys [k_begin, k_end) of one K/V slab ([cap][96] rows at kb / vb) against one query, one wave ----------------

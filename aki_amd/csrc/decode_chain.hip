@@ -10,7 +10,7 @@
 // resident workgroups hold (~60 MB chip-wide), across phase AND layer seams.  1.64 ms per greedy token (0.59 of the peak).
 //
 // How.  grid = n_layers x (qkv | attention | o_proj | gate_up | down) workgroups in DISPATCH ORDER = dependency order.  A
-// workgroup: (1) finds its (layer, phase, slice) from blockIdx, (2) requests the weights of its first CH_PF* batches (non-temporal
+// workgroup: (1) finds its (layer, phase, slice) from blockIdx, (2) requests the weights of the batches its format's plan prefetches (ChainPlan; non-temporal
 // loads into register slots), (3) one lane polls a READY flag of its producer phase (relaxed agent-scope loads + s_sleep; attention
 // items poll the flag of THEIR HEAD's 18 qkv workgroups), (4) stages its input vector from the hand-off buffer into LDS (RMSNorm
 // fused where the layer has one), (5) dot products out of registers, batch by batch, the next batch requested as a slot frees;
@@ -41,47 +41,6 @@
 
 namespace aki {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 chain_bf16x8_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 chain_bf16x2_t;
-
-__device__ __forceinline__ float cdot8(const u32x4 a, const u32x4 b, float acc) {
-  const chain_bf16x8_t a8 = __builtin_bit_cast(chain_bf16x8_t, a), b8 = __builtin_bit_cast(chain_bf16x8_t, b);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a8, a8, 0, 1), __builtin_shufflevector(b8, b8, 0, 1), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a8, a8, 2, 3), __builtin_shufflevector(b8, b8, 2, 3), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a8, a8, 4, 5), __builtin_shufflevector(b8, b8, 4, 5), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a8, a8, 6, 7), __builtin_shufflevector(b8, b8, 6, 7), acc, false);
-  return acc;
-}
-// weight-only fp8: same pairing as decode.hip's dot16_w8 (a 16-byte weight chunk = 16 k-values against two x chunks)
-__device__ __forceinline__ float cdot16_w8(const u32x4 w, const u32x4 x0, const u32x4 x1, float acc) {
-  const chain_bf16x8_t xa = __builtin_bit_cast(chain_bf16x8_t, x0), xb = __builtin_bit_cast(chain_bf16x8_t, x1);
-#define AKI_CW8_PAIR(word, hi, xv, i0)                                                                              \
-  {                                                                                                                 \
-    const chain_bf16x2_t wb = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((unsigned)(word), 1.0f, hi);   /* two e4m3 -> a bf16 pair in ONE instruction, exact */ \
-    acc = __builtin_amdgcn_fdot2_f32_bf16(wb, __builtin_shufflevector(xv, xv, i0, i0 + 1), acc, false);             \
-  }
-  AKI_CW8_PAIR(w[0], false, xa, 0) AKI_CW8_PAIR(w[0], true, xa, 2) AKI_CW8_PAIR(w[1], false, xa, 4) AKI_CW8_PAIR(w[1], true, xa, 6)
-  AKI_CW8_PAIR(w[2], false, xb, 0) AKI_CW8_PAIR(w[2], true, xb, 2) AKI_CW8_PAIR(w[3], false, xb, 4) AKI_CW8_PAIR(w[3], true, xb, 6)
-#undef AKI_CW8_PAIR
-  return acc;
-}
-// MXFP4 weights: mxfp4.hip's w4_scale and dot32_w4, instruction for instruction (a 16-byte weight chunk = one block of 32 k with ONE e8m0
-// byte, against four x chunks; dword i of w carries k 8i .. 8i+7 = x chunk i; the block scale rides in the convert's scale operand)
-__device__ __forceinline__ float cw4_scale(unsigned byte) { return __builtin_bit_cast(float, byte << 23); }
-__device__ __forceinline__ float cdot32_w4(const u32x4 w, const float scale, const u32x4 (&x)[4], float acc) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const chain_bf16x8_t xv = __builtin_bit_cast(chain_bf16x8_t, x[i]);
-#define AKI_CW4_PAIR(sel, i0)                                                                                      \
-  {                                                                                                                \
-    const chain_bf16x2_t wb = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[i], scale, sel);   /* byte sel: low nibble -> element 0, high -> 1 */ \
-    acc = __builtin_amdgcn_fdot2_f32_bf16(wb, __builtin_shufflevector(xv, xv, i0, i0 + 1), acc, false);            \
-  }
-    AKI_CW4_PAIR(0, 0) AKI_CW4_PAIR(1, 2) AKI_CW4_PAIR(2, 4) AKI_CW4_PAIR(3, 6)
-#undef AKI_CW4_PAIR
-  }
-  return acc;
-}
 // the weight format of a chain: what a 16-byte chunk of a weight row holds
 enum ChainFmt : int { CH_BF16 = 0, CH_W8 = 1, CH_W4 = 2 };      // 8 bf16 | 16 e4m3 (+ an f32 scale per row) | 32 e2m1 = one MX block (+ its e8m0 byte)
 
@@ -112,25 +71,35 @@ constexpr int CH_SHARDS = 16;
 constexpr int CH_FLAGS = 32;
 constexpr int CH_SYNC_WORDS = (CH_SHARDS + 1 + CH_FLAGS) * 32;   // 128-byte lines, in 4-byte words
 constexpr int CH_PHASES = 5;             // [0] qkv [1] attention (per-head mergers) [2] o_proj [3] gate_up [4] down
-// feature batches per workgroup (one staging of x each) of the qkv / o_proj / gate_up / down phases
-// Two each: 576 / 192 / 1024 / 384 workgroups per layer.  More batches cut the x traffic (the bare stream runs 1.41 ms per token at two,
-// 1.20 ms at {8,4,16,4}) but every batch after the first is loaded AFTER the dependency wait, on the critical path of its phase:
-// with the waits in, {1,1,1,1} 1.90, {2,2,2,2} 1.80, {4,4,4,4} 2.40, {8,4,16,4} 3.04 ms per token (tools/decode_chain_regimes.py).
-constexpr int CH_NBQ = 2, CH_NBO = 2, CH_NBG = 4, CH_NBD = 2;
-// ... of which this many are requested BEFORE the wait (register slots): with both batches of qkv / o_proj on chip when their input arrives, those phases
-// take x staging + 1.2 us instead of + 4 us (tools/decode_chain_edges.py); gate_up is bandwidth-bound whatever is prefetched; 1.78 -> 1.62 ms per token.
-constexpr int CH_PFQ = 2, CH_PFO = 2, CH_PFG = 2, CH_PFD = 2;
-// e4m3 weights (half the bytes, 24 VALU operations per 16 weights to widen them): ONE batch per workgroup, requested before the wait - that chain is
-// all dependency latency and the second batch's dot products (2 us) sat on it: {1,1,1,1} 1.37 ms per token, {2,2,2,2}/{2,2,2,2} 1.48, five launches 1.46
-// (tools/decode_chain_w8.py).
-// MXFP4 weights (a quarter of the bytes; a 16-byte chunk is one block of 32 k and its e8m0 byte): the e4m3 settings - its rows per wave, ONE batch
-// per workgroup, weights and scale bytes requested before the wait - so the same 576 / 192 / 1024 / 384 workgroups per layer at the same 127 VGPRs
-// and LDS: the residency of the e4m3 chain.  Times and the lab presets tried: tools/w4_decode_bench.py --chain, DESIGN section 4, EXPERIMENTS.md.
-constexpr int CH_TOUCH = 0;
-constexpr int CH_QKV_BY_HEAD = 1;
-constexpr int CH_XREP = 8;               // room for copies of every hand-off vector: consumer j reads copy j % xrep
-constexpr int CH_XREP_USED = 1;          // copies in use: every copy is one more write-through store per producing lane, and at the product's
-                                         // 100-600 consumers per phase one copy reads fastest (1 / 2 / 4 copies: 1.66 / 1.68 / 1.71 ms per token)
+// Block [0] of a layer is laid out and zeroed but not used: the qkv workgroups arrive at their HEAD's counter (head_sync) and the attention items
+// poll their head's flag, so nobody arrives at or waits on the qkv phase as a whole (the done_sync of a head-major phase is ignored).
+constexpr int CH_POLL_SLEEP = 8;         // s_sleep(1) between two looks at a flag (x 64 cycles); 0..32 made no difference (EXPERIMENTS.md)
+// Every hand-off vector exists ONCE: each further copy is one more write-through store per producing lane, and at 100-600 consumers per phase one
+// copy reads fastest (1 / 2 / 4 copies: 1.66 / 1.68 / 1.71 ms per token).
+//
+// The batch plan of a weight format: the ONE place that says how a layer is cut into workgroups.  The kernel instantiates its phases from it and the
+// host computes the workgroup counts from it.  A workgroup takes nb batches of 4 waves x (rows per wave) weight rows against one staging of x, and
+// requests the first pf of them BEFORE the dependency wait (register slots).
+struct ChainPlan {
+  int nrd, nrf;                 // weight rows per wave and batch on the K = d matrices (qkv, o_proj, gate_up) / the K = F matrix (down)
+  int nbq, nbo, nbg, nbd;       // batches per workgroup: qkv, o_proj, gate_up, down
+  int pfq, pfo, pfg, pfd;       // ... of which requested before the wait
+};
+// bf16: 576 / 192 / 1024 / 384 workgroups per layer.  More batches cut the x traffic (the bare stream runs 1.41 ms per token at two, 1.20 ms at
+// {8,4,16,4}) but every batch loaded AFTER the wait is on the critical path of its phase: with the waits in, {1,1,1,1} 1.90, {2,2,2,2} 1.80,
+// {4,4,4,4} 2.40, {8,4,16,4} 3.04 ms per token.  With both batches of qkv / o_proj on chip when their input arrives those phases take x staging
+// + 1.2 us instead of + 4 us (tools/decode_chain_edges.py); gate_up is bandwidth-bound whatever is prefetched; 1.78 -> 1.62 ms per token.
+// e4m3 (half the bytes, 16 VALU operations per 16 weights to widen them): twice the rows per wave, ONE batch per workgroup, requested before the wait
+// - that chain is all dependency latency and a second batch's dot products (2 us) sat on it: {1,1,1,1} 1.37 ms per token, {2,2,2,2} 1.48, five
+// launches 1.46.
+// MXFP4 (a quarter of the bytes; a 16-byte chunk is one block of 32 k and its e8m0 byte): the e4m3 plan, weights and scale bytes requested before the
+// wait - the same 576 / 192 / 1024 / 384 workgroups per layer at the same 127 VGPRs and LDS: the residency of the e4m3 chain.
+// The plans that lost (27 presets, touch-ahead loads, capped residency) and their times: EXPERIMENTS.md, DESIGN section 4.
+constexpr ChainPlan chain_plan(ChainFmt fmt) {
+  return fmt == CH_BF16 ? ChainPlan{2, 1, 2, 2, 4, 2, 2, 2, 2, 2} : ChainPlan{4, 2, 1, 1, 1, 1, 1, 1, 1, 1};
+}
+// rows of w_qkv per workgroup divide a head's 96: the qkv workgroups are laid out head-major and an attention item waits for ITS head's producers
+constexpr int chain_head_wgs(ChainPlan pl) { return 96 / (4 * pl.nrd * pl.nbq); }
 constexpr unsigned CH_SPIN_LIMIT = 200000u;
 // the batched chain's ring depths (steps of 64 k per wave held in registers; see chain_gemm): qkv, o_proj, gate_up (two streams), down (+ its x ring)
 constexpr int CH_B_RQ = 6, CH_B_RO = 6, CH_B_RG = 4, CH_B_RD = 6;         // <= 128 VGPRs: two 512-thread workgroups per CU
@@ -145,19 +114,15 @@ struct ChainParams {
   unsigned* sync;         // [n_layers][CH_PHASES][CH_SYNC_WORDS], then [n_layers][H] attention tickets: all zero when the call starts (two sets)
   unsigned* attn_cnt;     // a ticket per (layer, head): nothing is re-armed inside the launch
   unsigned* head_sync;    // [n_layers][H][2 lines]: arrivals of the 96 / rows-per-workgroup x 3 qkv workgroups that produce head h's q, k, v and
-                          // the head's READY flag (qkv_by_head): an attention item waits for ITS head's 18 producers, not for the phase's 576
-  int qkv_by_head;        // wgs per (section, head) of the qkv phase when its workgroups are laid out head-major, else 0 (one flag for the phase)
+                          // the head's READY flag: an attention item waits for ITS head's 18 producers, not for the phase's 576
   unsigned* err;          // sticky error word (outside the counter sets)
   unsigned* epoch;        // calls completed on this workspace: its parity says which of the TWO counter sets this call uses (see the kernel)
   int cnt_words;          // 4-byte words of one counter set; sync / head_sync / attn_cnt point into set 0
-  bf16_t* qkv; bf16_t* attn_o; bf16_t* h1; bf16_t* act; bf16_t* hbuf;   // hand-off vectors (copy 0); hbuf = 2 x d
-  int rep_stride;         // elements between the copies of a hand-off vector
+  bf16_t* qkv; bf16_t* attn_o; bf16_t* h1; bf16_t* act; bf16_t* hbuf;   // hand-off vectors; hbuf = 2 x d
   float* part;            // [H][S][DEC_PSTRIDE]
   int n_qkv, n_attn, n_o, n_gu, n_down, wg_layer;
-  int sleep_n, xrep, nflags, nowait;   // product: 8, CH_XREP_USED, CH_FLAGS, 0; the lab library can change them (aki_lab_set_chain)
-  int nbq, nbo, nbg, nbd;              // batches of 4 x FPW features per workgroup of the qkv / o_proj / gate_up / down phases
-  int touch;                           // 1: a waiting workgroup pulls the batches it holds no registers for towards L2 / the Infinity Cache
 #ifdef AKI_LAB_HOOKS
+  int nowait;                          // lab: no dependency waits at all (WRONG results - the time of the bare weight stream in this workgroup structure)
   unsigned long long* stamps;          // lab: [phase 0..4][workgroup < 2048][8] wall-clock stamps (100 MHz) of layer `stamp_layer`
   int stamp_layer;
   unsigned fault_code;                 // lab: the wait with this code (layer << 8 | phase) gives up at once (fault injection for the host's recovery path)
@@ -170,8 +135,10 @@ struct ChainParams {
     if ((p).stamps && (layer) == (p).stamp_layer && threadIdx.x == 0 && (wg) < 2048)                              \
       (p).stamps[((size_t)(phase) * 2048 + (wg)) * 8 + (k)] = wall_clock64();                                     \
   } while (0)
+#define AKI_CHAIN_NOWAIT(p) ((p).nowait != 0)
 #else
 #define AKI_CHAIN_STAMP(p, layer, phase, wg, k) do { } while (0)
+#define AKI_CHAIN_NOWAIT(p) false
 #endif
 
 // ---- hand-off primitives ------------------------------------------------------------------------------------------------
@@ -186,8 +153,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t chain_rsrc(const void* p, int 
 // One lane polls this workgroup's READY flag of the producer phase; bounded.  On give-up: error word, then every flag of the
 // launch is raised (so the rest drains in microseconds).
 __device__ __forceinline__ void chain_wait(const ChainParams& p, unsigned* sync, int wg, unsigned code) {
-  if (threadIdx.x == 0 && sync != nullptr && !p.nowait) {
-    unsigned* flag = sync + (CH_SHARDS + 1 + (wg % p.nflags)) * 32;
+  if (threadIdx.x == 0 && sync != nullptr && !AKI_CHAIN_NOWAIT(p)) {
+    unsigned* flag = sync + (CH_SHARDS + 1 + (wg % CH_FLAGS)) * 32;
     unsigned spins = 0;
     auto give_up = [&]() {
       AKI_ST_AGENT(p.err, code);
@@ -199,7 +166,7 @@ __device__ __forceinline__ void chain_wait(const ChainParams& p, unsigned* sync,
     else
 #endif
     while (AKI_LD_AGENT(flag) == 0u) {
-      for (int i = 0; i < p.sleep_n; ++i) __builtin_amdgcn_s_sleep(1);
+      for (int i = 0; i < CH_POLL_SLEEP; ++i) __builtin_amdgcn_s_sleep(1);
       if (++spins > CH_SPIN_LIMIT) { give_up(); break; }
     }
   }
@@ -237,18 +204,18 @@ __device__ __forceinline__ void chain_publish(unsigned* sync, int idx, int n) {
 // rows are gate rows f.. and up rows n_out + f.. (NR/2 features).  NORM: x is RMS-normalised (weight norm_w) on its way into LDS.
 // A workgroup takes `nb` batches of 4 x FPW consecutive features against ONE staging of x: every workgroup reads its whole input
 // vector through the fabric (sc1), and at one batch per workgroup those reads were 15 % of all bytes moved - the weight stream
-// ran at exactly 6.3 TB/s / 1.15 with the dependency waits switched off (tools/decode_chain_ab.py).  Batch 0 is loaded before the
+// ran at exactly 6.3 TB/s / 1.15 with the dependency waits switched off (EXPERIMENTS.md).  The plan's first PF batches are loaded before the
 // wait; batch b+1 as soon as the dot products have released the registers of batch b, under its reduction and epilogue.
 // FMT = CH_W4: a chunk is one MX block; a row is NBLK = K / 32 of them (K/2 bytes) with NBLK dense scale bytes at w_scale (read as bytes).  KC =
 // ceil(NBLK / 64): K = 3072 is 96 blocks = 1.5 per lane, and lanes 32-63 have no second chunk - the load AND the dot product of chunk c = lane + 64 kc
 // are predicated on c < NBLK (mxfp4.hip's gemv_w4_kernel runs those lanes through one sweep only; an unpredicated load would run past the last
 // row of the matrix, a zero product could flip the sign of a zero sum).  The scale bytes travel with the weights, in the same prefetch slots,
-// before the wait.  Per lane and row: chunks ascending, cdot32_w4 into one f32, the xor-shuffle reduction, nothing multiplied after it.
+// before the wait.  Per lane and row: chunks ascending, dot32_w4 into one f32, the xor-shuffle reduction, nothing multiplied after it.
 template <int NR, int KC, bool SWIGLU, bool NORM, ChainFmt FMT, int NB, int PF, int NBLK = KC * 64>
 __device__ __forceinline__ unsigned chain_gemv(const ChainParams& p, int wg, int n_wg, const void* w, const float* w_scale, int K, int n_out,
-                                           const bf16_t* x, int x_rep, const bf16_t* norm_w, const bf16_t* residual, int res_rep, bf16_t* y,
-                                           int y_reps, unsigned* wait_sync, unsigned* done_sync, unsigned code, char* sx, float* s_red,
-                                           int head_per = 0, unsigned* head_sync = nullptr) {
+                                           const bf16_t* x, const bf16_t* norm_w, const bf16_t* residual, bf16_t* y, unsigned* wait_sync,
+                                           unsigned* done_sync, unsigned code, char* sx, float* s_red, int head_per = 0,
+                                           unsigned* head_sync = nullptr) {
   constexpr int FPW = SWIGLU ? NR / 2 : NR;
   constexpr bool W8 = FMT == CH_W8, W4 = FMT == CH_W4;
   static_assert(!W4 || (NBLK <= KC * 64 && NBLK > (KC - 1) * 64), "W4: KC = ceil(blocks per row / 64)");
@@ -298,32 +265,11 @@ __device__ __forceinline__ unsigned chain_gemv(const ChainParams& p, int wg, int
   AKI_CHAIN_STAMP(p, (int)(code >> 8), (int)(code & 255) - 1, wg, 0);
   // (2) the weight loads of this wave's first PF batches, before anything that depends on another workgroup
   static_for_chain<PF>([&](auto b_c) { issue(fbase + decltype(b_c)::value * 4 * FPW, b_c); });
-  // (2b) the batches beyond the register slots: one dword per 128-byte line, default cache policy, result unused - the lines travel
-  // HBM -> Infinity Cache -> this XCD's L2 while the workgroup waits, and the real (nt) loads after the wait find them on the die
-  unsigned touched = 0;
-  if constexpr (PF < NB) {
-    if (p.touch) {
-#pragma unroll
-      for (int b = PF; b < NB; ++b)
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          const int f = min(fbase + b * 4 * FPW + (r % FPW), n_out - 1);
-          const int row = (SWIGLU && r >= FPW) ? n_out + f : f;
-          const char* wr = (const char*)w + (size_t)row * row_bytes;
-          constexpr int RB = W4 ? NBLK * 16 : KC * 1024;      // bytes of a row
-#pragma unroll
-          for (int o = 0; o < RB; o += 64 * 128)
-            if (o + lane * 128 < RB) touched |= *(volatile const __attribute__((address_space(1))) unsigned*)(wr + o + lane * 128);
-        }
-    }
-  }
   // (3) the producer phase has published
   chain_wait(p, wait_sync, wg, code);
   AKI_CHAIN_STAMP(p, (int)(code >> 8), (int)(code & 255) - 1, wg, 1);
-  // (4) x -> LDS.  Handed-off bytes: sc1 loads only, from this workgroup's copy of the vector.
+  // (4) x -> LDS.  Handed-off bytes: sc1 loads only.
   const int nchunk = K / 8;
-  x += (size_t)(x_rep ? (wg % p.xrep) * p.rep_stride : 0);
-  if (residual != nullptr && res_rep) residual += (size_t)(wg % p.xrep) * p.rep_stride;
   const __amdgpu_buffer_rsrc_t rx = chain_rsrc(x, K * 2);
   if constexpr (NORM) {
     // y = bf16(x * rsqrt(mean(x^2) + eps) * w): decode.hip's gemv_bf16_kernel staging, the row kept in registers between the passes
@@ -364,7 +310,6 @@ __device__ __forceinline__ unsigned chain_gemv(const ChainParams& p, int wg, int
     for (int c = tid; c < nchunk; c += 256) *(u32x4*)(sx + (size_t)c * 16) = ld_sc1_b128(rx, c * 16);
   }
   __syncthreads();
-  asm volatile("" :: "v"(touched));    // the touch loads are older than the x loads above: nothing waits here
   AKI_CHAIN_STAMP(p, (int)(code >> 8), (int)(code & 255) - 1, wg, 2);
   static_for_chain<NB>([&](auto b_c) {
     constexpr int b = decltype(b_c)::value;
@@ -390,16 +335,16 @@ __device__ __forceinline__ unsigned chain_gemv(const ChainParams& p, int wg, int
 #pragma unroll
           for (int i = 0; i < 4; ++i) x4[i] = *(const u32x4*)(sx + ((size_t)4 * c + i) * 16);
 #pragma unroll
-          for (int r = 0; r < NR; ++r) acc[r] = cdot32_w4(wv[SL][r][kc], cw4_scale(wsb[SL][r][kc]), x4, acc[r]);
+          for (int r = 0; r < NR; ++r) acc[r] = dot32_w4(wv[SL][r][kc], w4_scale(wsb[SL][r][kc]), x4, acc[r]);
         }
       } else if constexpr (W8) {
         const u32x4 x0 = *(const u32x4*)(sx + (size_t)(2 * c) * 16), x1 = *(const u32x4*)(sx + (size_t)(2 * c + 1) * 16);
 #pragma unroll
-        for (int r = 0; r < NR; ++r) acc[r] = cdot16_w8(wv[SL][r][kc], x0, x1, acc[r]);
+        for (int r = 0; r < NR; ++r) acc[r] = dot16_w8(wv[SL][r][kc], x0, x1, acc[r]);
       } else {
         const u32x4 xc = *(const u32x4*)(sx + (size_t)c * 16);
 #pragma unroll
-        for (int r = 0; r < NR; ++r) acc[r] = cdot8(wv[SL][r][kc], xc, acc[r]);
+        for (int r = 0; r < NR; ++r) acc[r] = dot8_bf16(wv[SL][r][kc], xc, acc[r]);
       }
     }
     // the next batch's loads, as soon as the registers are free (the barrier keeps the scheduler from renaming them upwards)
@@ -423,16 +368,13 @@ __device__ __forceinline__ unsigned chain_gemv(const ChainParams& p, int wg, int
         out[f] = v;
       }
       // n_out is a multiple of FPW on every matrix of the stack: a wave's features are all in range or none is
-      for (int rep = 0; rep < min(y_reps, p.xrep); ++rep) {
-        bf16_t* yr = y + (size_t)rep * p.rep_stride + f0;
-        if constexpr (FPW == 4) {
-          const unsigned long long o = (unsigned long long)pack_bf16x2(out[0], out[1]) | ((unsigned long long)pack_bf16x2(out[2], out[3]) << 32);
-          AKI_ST_AGENT((unsigned long long*)yr, o);
-        } else if constexpr (FPW == 2) {
-          AKI_ST_AGENT((unsigned*)yr, pack_bf16x2(out[0], out[1]));
-        } else {
-          AKI_ST_AGENT((unsigned short*)yr, (unsigned short)(pack_bf16x2(out[0], 0.f) & 0xffffu));
-        }
+      if constexpr (FPW == 4) {
+        const unsigned long long o = (unsigned long long)pack_bf16x2(out[0], out[1]) | ((unsigned long long)pack_bf16x2(out[2], out[3]) << 32);
+        AKI_ST_AGENT((unsigned long long*)(y + f0), o);
+      } else if constexpr (FPW == 2) {
+        AKI_ST_AGENT((unsigned*)(y + f0), pack_bf16x2(out[0], out[1]));
+      } else {
+        AKI_ST_AGENT((unsigned short*)(y + f0), (unsigned short)(pack_bf16x2(out[0], 0.f) & 0xffffu));
       }
     }
   });
@@ -570,10 +512,10 @@ __device__ __forceinline__ unsigned chain_gemm(const ChainParams& p, int wg, int
     }
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
-      const chain_bf16x8_t xb = __builtin_bit_cast(chain_bf16x8_t, x2[hh]);
+      const bf16x8 xb = __builtin_bit_cast(bf16x8, x2[hh]);
 #pragma unroll
       for (int t = 0; t < NS; ++t)
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(chain_bf16x8_t, wr[SL][t][hh]), xb, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wr[SL][t][hh]), xb, acc[t], 0, 0, 0);
     }
     if constexpr (i + R < KSL) {
       // the slot is free once the MFMAs above have read it; the barriers keep the scheduler from renaming the ring into KSL live steps
@@ -640,8 +582,8 @@ __device__ __forceinline__ unsigned chain_gemm(const ChainParams& p, int wg, int
 // BT (the batched chain): an item is (sequence b, head, split); the K/V caches are [B][H][cap][96], qkv / attn_o are [B][n] rows, lengths,
 // valid bits, tickets and partials are per sequence.  BT = false compiles to the one-sequence code unchanged (b = 0).
 template <bool BT = false>
-__device__ __forceinline__ void chain_attn(const ChainParams& p, const aki_decode_chain_layer& ly, int layer, int wg, unsigned* wait_sync,
-                                           unsigned* done_sync, unsigned code, char* smem) {
+__device__ __forceinline__ void chain_attn(const ChainParams& p, const aki_decode_chain_layer& ly, int layer, int wg, unsigned* done_sync,
+                                           unsigned code, char* smem) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // per-wave LDS: s_q, s_k, s_v (96 bf16 each, 16-byte aligned) and the merge scratch (DEC_MERGE_FLOATS floats)
   bf16_t* s_q = (bf16_t*)(smem + wave * 3072);
@@ -692,27 +634,23 @@ __device__ __forceinline__ void chain_attn(const ChainParams& p, const aki_decod
     if (lane * 128 < rows * 192) touch0 = *(gptr_u32)(vt + lane * 128);
     if ((lane + 64) * 128 < rows * 192) touch1 = *(gptr_u32)(vt + (lane + 64) * 128);
   }
-  if (p.qkv_by_head && !p.nowait) {
-    // per wave: the flag of THIS item's head (lane 0 polls; a wave is one item and nothing below is a workgroup barrier)
-    if (live && lane == 0) {
-      const unsigned* flag = p.head_sync + ((size_t)layer * p.H + h) * 64 + 32;
-      unsigned spins = 0;
-      while (AKI_LD_AGENT(flag) == 0u) {
-        for (int i = 0; i < p.sleep_n; ++i) __builtin_amdgcn_s_sleep(1);
-        if (++spins > CH_SPIN_LIMIT) { AKI_ST_AGENT(p.err, code); break; }
-        if ((spins & 63u) == 0u && AKI_LD_AGENT(p.err) != 0u) break;      // somebody gave up: drain
-      }
+  // per wave: the flag of THIS item's head (lane 0 polls; a wave is one item and nothing below is a workgroup barrier)
+  if (live && lane == 0 && !AKI_CHAIN_NOWAIT(p)) {
+    const unsigned* flag = p.head_sync + ((size_t)layer * p.H + h) * 64 + 32;
+    unsigned spins = 0;
+    while (AKI_LD_AGENT(flag) == 0u) {
+      for (int i = 0; i < CH_POLL_SLEEP; ++i) __builtin_amdgcn_s_sleep(1);
+      if (++spins > CH_SPIN_LIMIT) { AKI_ST_AGENT(p.err, code); break; }
+      if ((spins & 63u) == 0u && AKI_LD_AGENT(p.err) != 0u) break;      // somebody gave up: drain
     }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-  } else {
-    chain_wait(p, wait_sync, wg, code);
   }
+  __builtin_amdgcn_wave_barrier();
+  asm volatile("" ::: "memory");
   AKI_CHAIN_STAMP(p, layer, 1, wg, 1);
   if (!live) return;                                     // no workgroup barrier below this line
   if (work) {
     if (lane < 48) {
-      const bf16_t* row = BT ? p.qkv + (size_t)b * 3 * p.H * 96 + h * 96 : p.qkv + (size_t)(item % p.xrep) * p.rep_stride + h * 96;
+      const bf16_t* row = p.qkv + (size_t)b * 3 * p.H * 96 + h * 96;
       const RopeRow rr = rope_row(p.cos, p.sin, ln, lane);
       const float q0 = bf16_bits_to_f32(AKI_LD_AGENT(row + lane));
       const float q1 = bf16_bits_to_f32(AKI_LD_AGENT(row + lane + 48));
@@ -757,10 +695,10 @@ __device__ __forceinline__ void chain_attn(const ChainParams& p, const aki_decod
         for (int i = 0; i < 12; ++i) kr[i] = *(const u32x4*)(s_k + i * 8);
       }
       bool ok = j < k_end;
-      if (p.vbits && (base >> 6) < p.nwords) ok = ok && ((p.vbits[(BT ? (size_t)b * p.nwords : 0) + (base >> 6)] >> lane) & 1ull);
+      if (p.vbits && (base >> 6) < p.nwords) ok = ok && ((p.vbits[(size_t)b * p.nwords + (base >> 6)] >> lane) & 1ull);
       float s = 0.f;
 #pragma unroll
-      for (int i = 0; i < 12; ++i) s = cdot8(kr[i], *(const u32x4*)(s_q + i * 8), s);
+      for (int i = 0; i < 12; ++i) s = dot8_bf16(kr[i], *(const u32x4*)(s_q + i * 8), s);
       asm volatile("" : "+v"(s));
       __builtin_amdgcn_sched_barrier(0);
       issue_v(base);                                     // the K registers are free now; the lines were touched before the wait
@@ -832,15 +770,8 @@ __device__ __forceinline__ void chain_attn(const ChainParams& p, const aki_decod
   __builtin_amdgcn_wave_barrier();
   if (lane < 12) {
     const u32x4 ov = split_finish(s_mg, lane);
-    if constexpr (BT) {
-      const __amdgpu_buffer_rsrc_t ro = chain_rsrc(p.attn_o + (size_t)b * p.H * 96, p.H * 96 * 2);
-      __builtin_amdgcn_raw_buffer_store_b128(ov, ro, (h * 96 + lane * 8) * 2, 0, 16);     // sc1: write-through
-    } else {
-      for (int rep = 0; rep < p.xrep; ++rep) {
-        const __amdgpu_buffer_rsrc_t ro = chain_rsrc(p.attn_o + (size_t)rep * p.rep_stride, p.H * 96 * 2);
-        __builtin_amdgcn_raw_buffer_store_b128(ov, ro, (h * 96 + lane * 8) * 2, 0, 16);     // sc1: write-through
-      }
-    }
+    const __amdgpu_buffer_rsrc_t ro = chain_rsrc(p.attn_o + (size_t)b * p.H * 96, p.H * 96 * 2);
+    __builtin_amdgcn_raw_buffer_store_b128(ov, ro, (h * 96 + lane * 8) * 2, 0, 16);     // sc1: write-through
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   chain_arrive(done_sync, bh, nB * p.H, lane);           // one arrival per (sequence, head)
@@ -849,94 +780,92 @@ __device__ __forceinline__ void chain_attn(const ChainParams& p, const aki_decod
 #endif
 }
 
+// ---- the counters of a call: one of two sets, by the parity of the calls completed on this workspace ------------------------------
+// Every polled word must be zero when a call starts.  Until round 5 a small kernel in front of the chain zeroed them (4.7-5.3 us of a
+// 1637 us token, profiles/r05_decode_token_trace.txt).  Now call k uses set k & 1 and zeroes the OTHER set for call k + 1 (a store or two per
+// workgroup, any time during the call: nobody polls that set now - the previous call on this workspace has ended, it is stream-ordered).  k lives
+// in the workspace: the workgroup that completes the LAST phase writes k + 1.  Every workgroup of the launch has read k by then: the last
+// phase completes only after every phase before it has, and a workgroup arrives at its phase's counter after all it does with k.  (After a
+// give-up - sticky error word - the sets are in no defined state: the caller zero-fills the workspace before using it again.)  The word and
+// the sets are read and written at agent scope or across a kernel boundary only.
+// p arrives pointing into set 0 and leaves pointing into this call's set; returns k.
+template <int THREADS>
+__device__ __forceinline__ unsigned chain_counter_set(ChainParams& p) {
+  const unsigned ep = (unsigned)__builtin_amdgcn_readfirstlane((int)AKI_LD_AGENT(p.epoch));
+  const size_t cur = (ep & 1u) ? (size_t)p.cnt_words : 0;
+  u32x4* other = (u32x4*)(p.sync + ((size_t)p.cnt_words - cur));
+  const int bid = blockIdx.x, n16 = p.cnt_words / 4, per = (n16 + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int z_end = min(n16, (bid + 1) * per);
+  for (int i = bid * per + (int)threadIdx.x; i < z_end; i += THREADS) other[i] = u32x4{0u, 0u, 0u, 0u};
+  p.sync += cur; p.head_sync += cur; p.attn_cnt += cur;
+  return ep;
+}
+
 // KCD = d / 512, KCF = F / 512 (bf16) - the register arrays are static; W8 halves both, W4 quarters them (d: 1.5 chunks per lane -> 2, the second predicated).
-template <int KCD, int KCF, ChainFmt FMT, int NBQ, int NBO, int NBG, int NBD, int PFQ = 1, int PFO = 1, int PFG = 1, int PFDN = 1, int OCC = 1>
-__global__ __launch_bounds__(256, OCC) void decode_chain_kernel(const ChainParams p0) {
+template <int KCD, int KCF, ChainFmt FMT>
+__global__ __launch_bounds__(256) void decode_chain_kernel(const ChainParams p0) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* s_red = (float*)(smem + 16384);
   char* sx = smem;
   const int bid = blockIdx.x;
-  // ---- the counters of this call: one of two sets, by the parity of the calls completed on this workspace --------------------
-  // Every polled word must be zero when a call starts.  Until round 5 a small kernel in front of the chain zeroed them (4.7-5.3 us of a
-  // 1637 us token, profiles/r05_decode_token_trace.txt).  Now call k uses set k & 1 and zeroes the OTHER set for call k + 1 (a store or two per
-  // workgroup, any time during the call: nobody polls that set now - the previous call on this workspace has ended, it is stream-ordered).  k lives
-  // in the workspace: the workgroup that completes the LAST phase writes k + 1.  Every workgroup of the launch has read k by then: the last
-  // phase completes only after every phase before it has, and a workgroup arrives at its phase's counter after all it does with k.  (After a
-  // give-up - sticky error word - the sets are in no defined state: the caller zero-fills the workspace before using it again.)  The word and
-  // the sets are read and written at agent scope or across a kernel boundary only.
   ChainParams p = p0;
-  const unsigned ep = (unsigned)__builtin_amdgcn_readfirstlane((int)AKI_LD_AGENT(p0.epoch));
-  {
-    const size_t cur = (ep & 1u) ? (size_t)p0.cnt_words : 0;
-    p.sync = p0.sync + cur; p.head_sync = p0.head_sync + cur; p.attn_cnt = p0.attn_cnt + cur;
-    u32x4* other = (u32x4*)(p0.sync + ((size_t)p0.cnt_words - cur));
-    const int n16 = p0.cnt_words / 4, per = (n16 + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int z_end = min(n16, (bid + 1) * per);
-    for (int i = bid * per + (int)threadIdx.x; i < z_end; i += 256) other[i] = u32x4{0u, 0u, 0u, 0u};
-  }
+  const unsigned ep = chain_counter_set<256>(p);
   const int layer = bid / p.wg_layer;
   int r = bid - layer * p.wg_layer;
   const aki_decode_chain_layer& ly = p.layers[layer];
   unsigned* sy = p.sync + (size_t)layer * CH_PHASES * CH_SYNC_WORDS;
   unsigned* prev_down = layer > 0 ? sy - CH_SYNC_WORDS : nullptr;          // phase 4 of the layer before
   const bf16_t* h0 = layer == 0 ? p.h_in : p.hbuf + ((layer - 1) & 1) * p.d;
-  const int h0_rep = layer == 0 ? 0 : 1;                                   // the embedding has one copy
   const bool last = layer == p.n_layers - 1;
   bf16_t* h2 = last ? p.h_out : p.hbuf + (layer & 1) * p.d;
   const unsigned code = ((unsigned)layer << 8);
   constexpr bool W8 = FMT == CH_W8, W4 = FMT == CH_W4;
-  constexpr int NRD = (W8 || W4) ? 4 : 2;  // rows per wave on the K = d matrices (W4: W8's rows over half the bytes - decode_chain_launch)
+  constexpr ChainPlan PL = chain_plan(FMT);
+  constexpr int NRD = PL.nrd, NRF = PL.nrf;
+  static_assert(96 % (4 * PL.nrd * PL.nbq) == 0, "a head's 96 rows of q, k and v are whole qkv workgroups (head-major layout, one READY flag per head)");
   constexpr int KD = W4 ? (KCD + 3) / 4 : (W8 ? KCD / 2 : KCD);
-  constexpr int NRF = (W8 || W4) ? 2 : 1;  // rows per wave on the K = F matrix
   constexpr int KF = W4 ? (KCF + 3) / 4 : (W8 ? KCF / 2 : KCF);
   constexpr int BD = W4 ? KCD * 16 : KD * 64, BF = W4 ? KCF * 16 : KF * 64;      // W4: blocks of 32 k per row of the K = d / K = F matrices
   if (r < p.n_qkv) {
-    chain_gemv<NRD, KD, false, true, FMT, NBQ, PFQ, BD>(p, r, p.n_qkv, ly.w_qkv, ly.s_qkv, p.d, 3 * p.H * 96, h0, h0_rep, (const bf16_t*)ly.norm1, nullptr, 0, p.qkv,
-                                          CH_XREP, prev_down, sy + 0 * CH_SYNC_WORDS, code | 1u, sx, s_red, p.qkv_by_head,
-                                          p.head_sync + (size_t)layer * p.H * 64);
+    chain_gemv<NRD, KD, false, true, FMT, PL.nbq, PL.pfq, BD>(p, r, p.n_qkv, ly.w_qkv, ly.s_qkv, p.d, 3 * p.H * 96, h0, (const bf16_t*)ly.norm1, nullptr, p.qkv, prev_down,
+                                                              sy + 0 * CH_SYNC_WORDS, code | 1u, sx, s_red, chain_head_wgs(PL),
+                                                              p.head_sync + (size_t)layer * p.H * 64);
     return;
   }
   r -= p.n_qkv;
   if (r < p.n_attn) {
-    chain_attn<false>(p, ly, layer, r, sy + 0 * CH_SYNC_WORDS, sy + 1 * CH_SYNC_WORDS, code | 2u, smem);
+    chain_attn<false>(p, ly, layer, r, sy + 1 * CH_SYNC_WORDS, code | 2u, smem);
     return;
   }
   r -= p.n_attn;
   if (r < p.n_o) {
-    chain_gemv<NRD, KD, false, false, FMT, NBO, PFO, BD>(p, r, p.n_o, ly.w_o, ly.s_o, p.H * 96, p.d, p.attn_o, 1, nullptr, h0, h0_rep, p.h1, CH_XREP,
-                                           sy + 1 * CH_SYNC_WORDS, sy + 2 * CH_SYNC_WORDS, code | 3u, sx, s_red);
+    chain_gemv<NRD, KD, false, false, FMT, PL.nbo, PL.pfo, BD>(p, r, p.n_o, ly.w_o, ly.s_o, p.H * 96, p.d, p.attn_o, nullptr, h0, p.h1, sy + 1 * CH_SYNC_WORDS,
+                                                               sy + 2 * CH_SYNC_WORDS, code | 3u, sx, s_red);
     return;
   }
   r -= p.n_o;
   if (r < p.n_gu) {
-    chain_gemv<NRD, KD, true, true, FMT, NBG, PFG, BD>(p, r, p.n_gu, ly.w_gate_up, ly.s_gate_up, p.d, p.F, p.h1, 1, (const bf16_t*)ly.norm2, nullptr, 0, p.act,
-                                         CH_XREP, sy + 2 * CH_SYNC_WORDS, sy + 3 * CH_SYNC_WORDS, code | 4u, sx, s_red);
+    chain_gemv<NRD, KD, true, true, FMT, PL.nbg, PL.pfg, BD>(p, r, p.n_gu, ly.w_gate_up, ly.s_gate_up, p.d, p.F, p.h1, (const bf16_t*)ly.norm2, nullptr, p.act,
+                                                             sy + 2 * CH_SYNC_WORDS, sy + 3 * CH_SYNC_WORDS, code | 4u, sx, s_red);
     return;
   }
   r -= p.n_gu;
-  const unsigned fin = chain_gemv<NRF, KF, false, false, FMT, NBD, PFDN, BF>(p, r, p.n_down, ly.w_down, ly.s_down, p.F, p.d, p.act, 1, nullptr, p.h1, 1, h2,
-                                                                         last ? 1 : CH_XREP, sy + 3 * CH_SYNC_WORDS, sy + 4 * CH_SYNC_WORDS, code | 5u, sx, s_red);
+  const unsigned fin = chain_gemv<NRF, KF, false, false, FMT, PL.nbd, PL.pfd, BF>(p, r, p.n_down, ly.w_down, ly.s_down, p.F, p.d, p.act, nullptr, p.h1, h2,
+                                                                                  sy + 3 * CH_SYNC_WORDS, sy + 4 * CH_SYNC_WORDS, code | 5u, sx, s_red);
   if (last && fin && threadIdx.x == 0) AKI_ST_AGENT(p.epoch, ep + 1u);      // the call is complete: the next one takes the other set
 }
 
 // ---- the batched chain: 2..8 sequences per step ------------------------------------------------------------------------------
 // Same dataflow launch, same counters, same attention items (now per sequence); the four GEMV phases become 16-feature MFMA tiles
-// (chain_gemm).  Workgroups per layer: qkv 576 (head-major: 18 per head) | attention ceil(B * H * S / 4) | o_proj 192 | gate_up 512 | down 192.
+// (chain_gemm).  Workgroups per layer: qkv 576 (head-major: 18 per head) | attention ceil(B * H * S / 8) | o_proj 192 | gate_up 512 | down 192.
 // RQ / RO / RG / RD: the ring depths (steps of 64 k whose operands a wave holds; the first ring-full is requested before the wait).
+constexpr int CH_B_HEAD_WGS = 96 / 16;      // 96 rows of a head = six 16-feature tiles: 18 workgroups produce one head's q, k and v
 template <int RQ, int RO, int RG, int RD>
 __global__ __launch_bounds__(512) void decode_chain_b_kernel(const ChainParams p0) {      // 144 VGPRs = ONE workgroup per CU; held to 128 (two per CU) the bare stream is faster, the step with its waits slower: EXPERIMENTS.md
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int bid = blockIdx.x;
-  ChainParams p = p0;                                      // the counter set of this call: see decode_chain_kernel
-  const unsigned ep = (unsigned)__builtin_amdgcn_readfirstlane((int)AKI_LD_AGENT(p0.epoch));
-  {
-    const size_t cur = (ep & 1u) ? (size_t)p0.cnt_words : 0;
-    p.sync = p0.sync + cur; p.head_sync = p0.head_sync + cur; p.attn_cnt = p0.attn_cnt + cur;
-    u32x4* other = (u32x4*)(p0.sync + ((size_t)p0.cnt_words - cur));
-    const int n16 = p0.cnt_words / 4, per = (n16 + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int z_end = min(n16, (bid + 1) * per);
-    for (int i = bid * per + (int)threadIdx.x; i < z_end; i += 512) other[i] = u32x4{0u, 0u, 0u, 0u};
-  }
+  ChainParams p = p0;
+  const unsigned ep = chain_counter_set<512>(p);
   const int layer = bid / p.wg_layer;
   int r = bid - layer * p.wg_layer;
   const aki_decode_chain_layer& ly = p.layers[layer];
@@ -949,12 +878,12 @@ __global__ __launch_bounds__(512) void decode_chain_b_kernel(const ChainParams p
   const unsigned code = ((unsigned)layer << 8);
   if (r < p.n_qkv) {
     chain_gemm<6, false, 0, RQ>(p, r, p.n_qkv, ly.w_qkv, 3 * p.H * 96, h0, (const bf16_t*)ly.norm1, nullptr, p.qkv, prev_down, sy + 0 * CH_SYNC_WORDS,
-                                code | 1u, smem, p.qkv_by_head, p.head_sync + (size_t)layer * p.H * 64);
+                                code | 1u, smem, CH_B_HEAD_WGS, p.head_sync + (size_t)layer * p.H * 64);
     return;
   }
   r -= p.n_qkv;
   if (r < p.n_attn) {
-    chain_attn<true>(p, ly, layer, r, sy + 0 * CH_SYNC_WORDS, sy + 1 * CH_SYNC_WORDS, code | 2u, smem);
+    chain_attn<true>(p, ly, layer, r, sy + 1 * CH_SYNC_WORDS, code | 2u, smem);
     return;
   }
   r -= p.n_attn;
@@ -976,28 +905,54 @@ __global__ __launch_bounds__(512) void decode_chain_b_kernel(const ChainParams p
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 static inline size_t chain_cnt_bytes(int n_layers, int H, int B = 1) { return aki_align_up((size_t)n_layers * ((size_t)CH_PHASES * CH_SYNC_WORDS + (size_t)B * H + (size_t)H * 64) * 4, 256); }
-static inline size_t chain_vec_elems(int d, int H, int F) { return aki_align_up((size_t)(3 * H * 96 + H * 96 + d + F + 2 * d) * 2 + 256, 256) / 2; }   // one copy (one row)
+static inline size_t chain_vec_elems(int d, int H, int F) { return aki_align_up((size_t)(3 * H * 96 + H * 96 + d + F + 2 * d) * 2 + 256, 256) / 2; }   // the hand-off vectors of one sequence
 
-#ifdef AKI_LAB_HOOKS
-static int g_chain_sleep = 8, g_chain_xrep = CH_XREP_USED, g_chain_nflags = CH_FLAGS, g_chain_nowait = 0, g_chain_nb = 0, g_chain_lds_pad = 0, g_chain_stamp_layer = -1, g_chain_touch = -1;
-static unsigned long long* g_chain_stamps = nullptr;
-static unsigned g_chain_fault_code = 0;
-static int g_chain_fault_skip = 0;
-#endif
-
-// workspace: counter set 0 | counter set 1 | 256 bytes: the sticky error word (+0) and the count of completed calls (+64) | hand-off vectors | partials
-size_t decode_chain_err_offset(int n_layers, int H) { return 2 * chain_cnt_bytes(n_layers, H); }
-
-// the batched chain: counters (tickets per sequence and head) x 2 | error word, call count | the hand-off rows [B][n] | partials per sequence
+// workspace: counter set 0 | counter set 1 | 256 bytes: the sticky error word (+0) and the count of completed calls (+64) | the hand-off rows [B][n] |
+// partials per sequence.  The batched chain's counter sets carry a ticket per (sequence, head).
 size_t decode_chain_b_err_offset(int n_layers, int H, int B) { return 2 * chain_cnt_bytes(n_layers, H, B); }
 size_t decode_chain_b_ws_bytes(int n_layers, int d, int H, int F, int cap, int B) {
   const size_t tiles = ((size_t)cap + 63) / 64;
   return 2 * chain_cnt_bytes(n_layers, H, B) + 256 + (size_t)B * chain_vec_elems(d, H, F) * 2 + (size_t)B * H * tiles * DEC_PSTRIDE * 4;
 }
+size_t decode_chain_err_offset(int n_layers, int H) { return decode_chain_b_err_offset(n_layers, H, 1); }
+size_t decode_chain_ws_bytes(int n_layers, int d, int H, int F, int cap) { return decode_chain_b_ws_bytes(n_layers, d, H, F, cap, 1); }
 
-size_t decode_chain_ws_bytes(int n_layers, int d, int H, int F, int cap) {
-  const size_t tiles = ((size_t)cap + 63) / 64;
-  return 2 * chain_cnt_bytes(n_layers, H) + 256 /* error word, call count */ + chain_vec_elems(d, H, F) * 2 * CH_XREP + (size_t)H * tiles * DEC_PSTRIDE * 4;
+#ifdef AKI_LAB_HOOKS
+static int g_chain_nowait = 0, g_chain_stamp_layer = -1;
+static unsigned long long* g_chain_stamps = nullptr;
+static unsigned g_chain_fault_code = 0;
+static int g_chain_fault_skip = 0;
+#endif
+
+// What both launches share: the step's arguments, the cut of the cache, the workspace layout above and the lab library's instruments.
+static void chain_params(ChainParams& p, const aki_decode_chain_args* a, int B) {
+  const int d = a->d, H = a->H, F = a->F;
+  p.layers = a->layers; p.n_layers = a->n_layers; p.B = B;
+  p.h_in = (const bf16_t*)a->h_in; p.h_out = (bf16_t*)a->h_out;
+  p.cos = a->cos; p.sin = a->sin; p.cache_len = a->cache_len; p.vbits = a->col_valid_bits; p.nwords = a->nwords;
+  p.d = d; p.H = H; p.F = F; p.cap = a->capacity; p.scale = a->scale; p.eps = a->rms_eps;
+  split_plan((size_t)B * H, a->capacity, a->max_keys, p.S, p.T);
+  char* ws = (char*)a->workspace;
+  const size_t cb = chain_cnt_bytes(a->n_layers, H, B);
+  p.sync = (unsigned*)ws;
+  p.head_sync = p.sync + (size_t)a->n_layers * CH_PHASES * CH_SYNC_WORDS;          // 128-byte lines first, the tickets behind them
+  p.attn_cnt = p.head_sync + (size_t)a->n_layers * H * 64;
+  p.err = (unsigned*)(ws + 2 * cb);
+  p.epoch = p.err + 16;
+  p.cnt_words = (int)(cb / 4);
+  bf16_t* v = (bf16_t*)(ws + 2 * cb + 256);
+  p.qkv = v; v += (size_t)B * 3 * H * 96;
+  p.attn_o = v; v += (size_t)B * H * 96;
+  p.h1 = v; v += (size_t)B * d;
+  p.act = v; v += (size_t)B * F;
+  p.hbuf = v;
+  p.part = (float*)(ws + 2 * cb + 256 + (size_t)B * chain_vec_elems(d, H, F) * 2);
+#ifdef AKI_LAB_HOOKS
+  p.nowait = g_chain_nowait;
+  p.stamps = g_chain_stamps; p.stamp_layer = g_chain_stamp_layer;
+  p.fault_code = 0;
+  if (g_chain_fault_code != 0u && g_chain_fault_skip-- == 0) { p.fault_code = g_chain_fault_code; g_chain_fault_code = 0; }     // one shot
+#endif
 }
 
 // The batched chain is built, bit-identical to the five launches per layer and NOT faster (3.3-3.5 vs 3.2 ms per step at batch 8: 1664 fat
@@ -1009,72 +964,46 @@ static int decode_chain_b_launch(const aki_decode_chain_args* a, hipStream_t str
   if (a->Dh != 96 || d != 3072 || H != 32 || F != 8192 || a->dtype != AKI_DT_BF16 || B < 2 || B > 8) return AKI_ERR_UNSUPPORTED;
   if (a->workspace_bytes < decode_chain_b_ws_bytes(a->n_layers, d, H, F, a->capacity, B) || ((uintptr_t)a->workspace & 255)) return AKI_ERR_WORKSPACE;
   ChainParams p;
-  p.layers = a->layers; p.n_layers = a->n_layers; p.B = B;
-  p.h_in = (const bf16_t*)a->h_in; p.h_out = (bf16_t*)a->h_out;
-  p.cos = a->cos; p.sin = a->sin; p.cache_len = a->cache_len; p.vbits = a->col_valid_bits; p.nwords = a->nwords;
-  p.d = d; p.H = H; p.F = F; p.cap = a->capacity; p.scale = a->scale; p.eps = a->rms_eps;
-  split_plan((size_t)B * H, a->capacity, a->max_keys, p.S, p.T);
-  char* ws = (char*)a->workspace;
-  const size_t cb = chain_cnt_bytes(a->n_layers, H, B);
-  p.sync = (unsigned*)ws;
-  p.head_sync = p.sync + (size_t)a->n_layers * CH_PHASES * CH_SYNC_WORDS;
-  p.attn_cnt = p.head_sync + (size_t)a->n_layers * H * 64;
-  p.err = (unsigned*)(ws + 2 * cb);
-  p.epoch = p.err + 16;
-  p.cnt_words = (int)(cb / 4);
-  bf16_t* v = (bf16_t*)(ws + 2 * cb + 256);
-  p.rep_stride = 0;
-  p.qkv = v; v += (size_t)B * 3 * H * 96;
-  p.attn_o = v; v += (size_t)B * H * 96;
-  p.h1 = v; v += (size_t)B * d;
-  p.act = v; v += (size_t)B * F;
-  p.hbuf = v;
-  p.part = (float*)(ws + 2 * cb + 256 + (size_t)B * chain_vec_elems(d, H, F) * 2);
-  p.nbq = p.nbo = p.nbg = p.nbd = 1;
+  chain_params(p, a, B);
   p.n_qkv = 3 * H * 96 / 16;
   p.n_attn = (B * H * p.S + 7) / 8;
   p.n_o = d / 16;
   p.n_gu = F / 16;
   p.n_down = d / 16;
   p.wg_layer = p.n_qkv + p.n_attn + p.n_o + p.n_gu + p.n_down;
-  p.qkv_by_head = 6;                      // 96 rows of a head = six 16-feature tiles: 18 workgroups produce one head's q, k and v
-  p.sleep_n = 8; p.xrep = 1; p.nflags = CH_FLAGS; p.nowait = 0; p.touch = 0;
-#ifdef AKI_LAB_HOOKS
-  p.sleep_n = g_chain_sleep; p.nowait = g_chain_nowait;
-  p.stamps = g_chain_stamps; p.stamp_layer = g_chain_stamp_layer;
-  p.fault_code = 0;
-  if (g_chain_fault_code != 0u && g_chain_fault_skip-- == 0) { p.fault_code = g_chain_fault_code; g_chain_fault_code = 0; }
-#endif
   // LDS: the normalised / copied rows of a K = 3072 phase (49 KB at eight rows); the partial tiles (16 KB with SwiGLU) and the attention phase's
   // per-wave scratch (12 KB) lie over them
   int SMEM = B * (3072 * 2 + 16);
   if (SMEM < 8 * 3072) SMEM = 8 * 3072;       // eight attention items x 3 KB; the partial tiles take 16 KB
   const dim3 grid((unsigned)a->n_layers * (unsigned)p.wg_layer), block(512);
+  const auto kernel = decode_chain_b_kernel<CH_B_RQ, CH_B_RO, CH_B_RG, CH_B_RD>;
   AKI_CLEAR_ERR();
-#define AKI_CHAIN_B_LAUNCH(RQ, RO, RG, RD)                                                                                                  \
-  do {                                                                                                                                      \
-    static bool attr = false;                                                                                                               \
-    if (!attr) {                                                                                                                            \
-      if (hipFuncSetAttribute((const void*)decode_chain_b_kernel<RQ, RO, RG, RD>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * (3072 * 2 + 16)) != hipSuccess) \
-        return AKI_ERR_LAUNCH;                                                                                                              \
-      attr = true;                                                                                                                          \
-    }                                                                                                                                       \
-    hipLaunchKernelGGL((decode_chain_b_kernel<RQ, RO, RG, RD>), grid, block, SMEM, stream, p);                                               \
-  } while (0)
-#ifdef AKI_LAB_HOOKS
-  if (g_chain_nb == 1) AKI_CHAIN_B_LAUNCH(6, 6, 2, 4);
-  else if (g_chain_nb == 2) AKI_CHAIN_B_LAUNCH(6, 6, 6, 8);
-  else if (g_chain_nb == 3) AKI_CHAIN_B_LAUNCH(6, 6, 4, 8);
-  else if (g_chain_nb == 4) AKI_CHAIN_B_LAUNCH(3, 3, 2, 4);
-  else
-#endif
-  AKI_CHAIN_B_LAUNCH(CH_B_RQ, CH_B_RO, CH_B_RG, CH_B_RD);
-#undef AKI_CHAIN_B_LAUNCH
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * (3072 * 2 + 16)) != hipSuccess) return AKI_ERR_LAUNCH;
+    attr = true;
+  }
+  hipLaunchKernelGGL(kernel, grid, block, SMEM, stream, p);
   AKI_LAUNCH_CHECK();
   return AKI_OK;
 }
-
 #endif   // AKI_LAB_HOOKS: the batched chain
+
+// One sequence: the workgroup counts of the format's plan, then the launch of the kernel instantiated from the same plan.
+template <ChainFmt FMT>
+static void chain_launch(ChainParams& p, hipStream_t stream) {
+  constexpr ChainPlan PL = chain_plan(FMT);
+  auto wgs = [](int n_out, int fpw, int nb) { return (n_out + 4 * fpw * nb - 1) / (4 * fpw * nb); };
+  p.n_qkv = wgs(3 * p.H * 96, PL.nrd, PL.nbq);
+  p.n_attn = (p.H * p.S + 3) / 4;
+  p.n_o = wgs(p.d, PL.nrd, PL.nbo);
+  p.n_gu = wgs(p.F, PL.nrd / 2, PL.nbg);
+  p.n_down = wgs(p.d, PL.nrf, PL.nbd);
+  p.wg_layer = p.n_qkv + p.n_attn + p.n_o + p.n_gu + p.n_down;
+  constexpr int SMEM = 16384 + 64;       // x (<= 8192 bf16) + the norm's partial sums; the attention phase carves 4 x 3 KiB of it
+  const dim3 grid((unsigned)p.n_layers * (unsigned)p.wg_layer), block(256);
+  hipLaunchKernelGGL((decode_chain_kernel<6, 16, FMT>), grid, block, SMEM, stream, p);
+}
 
 int decode_chain_launch(const aki_decode_chain_args* a, hipStream_t stream) {
 #ifdef AKI_LAB_HOOKS
@@ -1091,141 +1020,17 @@ int decode_chain_launch(const aki_decode_chain_args* a, hipStream_t stream) {
   if (!(d == 3072 && F == 8192)) return AKI_ERR_UNSUPPORTED;     // the register arrays are sized at compile time: Phi-3.5-mini
   if (a->workspace_bytes < decode_chain_ws_bytes(a->n_layers, d, H, F, a->capacity) || ((uintptr_t)a->workspace & 255)) return AKI_ERR_WORKSPACE;
   ChainParams p;
-  p.layers = a->layers; p.n_layers = a->n_layers; p.B = 1;
-  p.h_in = (const bf16_t*)a->h_in; p.h_out = (bf16_t*)a->h_out;
-  p.cos = a->cos; p.sin = a->sin; p.cache_len = a->cache_len; p.vbits = a->col_valid_bits; p.nwords = a->nwords;
-  p.d = d; p.H = H; p.F = F; p.cap = a->capacity; p.scale = a->scale; p.eps = a->rms_eps;
-  split_plan((size_t)H, a->capacity, a->max_keys, p.S, p.T);
-  char* ws = (char*)a->workspace;
-  const size_t cb = chain_cnt_bytes(a->n_layers, H);
-  p.sync = (unsigned*)ws;
-  p.head_sync = p.sync + (size_t)a->n_layers * CH_PHASES * CH_SYNC_WORDS;          // 128-byte lines first, the tickets behind them
-  p.attn_cnt = p.head_sync + (size_t)a->n_layers * H * 64;
-  p.err = (unsigned*)(ws + 2 * cb);
-  p.epoch = p.err + 16;
-  p.cnt_words = (int)(cb / 4);
-  bf16_t* v = (bf16_t*)(ws + 2 * cb + 256);
-  p.rep_stride = (int)chain_vec_elems(d, H, F);
-  p.qkv = v; v += 3 * H * 96;
-  p.attn_o = v; v += H * 96;
-  p.h1 = v; v += d;
-  p.act = v; v += F;
-  p.hbuf = v;
-  p.part = (float*)(ws + 2 * cb + 256 + chain_vec_elems(d, H, F) * 2 * CH_XREP);
-  const int rd = (w8 || w4) ? 4 : 2, rf = (w8 || w4) ? 2 : 1;     // rows per wave and batch (see the kernel)
-  p.nbq = (w8 || w4) ? 1 : CH_NBQ; p.nbo = (w8 || w4) ? 1 : CH_NBO; p.nbg = (w8 || w4) ? 1 : CH_NBG; p.nbd = (w8 || w4) ? 1 : CH_NBD;
-#ifdef AKI_LAB_HOOKS
-  if (!w4) {
-    const int presets[][4] = {{w8 ? 1 : CH_NBQ, w8 ? 1 : CH_NBO, w8 ? 1 : CH_NBG, w8 ? 1 : CH_NBD}, {8, 8, 8, 8}, {4, 2, 8, 2}, {8, 2, 8, 4}, {4, 4, 4, 4}, {16, 4, 16, 4}, {8, 2, 16, 2}, {1, 1, 1, 1}, {8, 4, 16, 4}, {2, 1, 4, 1}, {4, 2, 4, 2}, {2, 2, 4, 2}, {2, 2, 2, 2}, {2, 2, 4, 2}, {2, 2, 4, 2}, {2, 2, 8, 2}, {2, 2, 4, 4}, {2, 2, 4, 2}, {2, 2, 8, 2}, {2, 2, 4, 2}, {2, 2, 4, 4}, {4, 2, 8, 4}, {2, 2, 4, 2}, {4, 4, 8, 4}, {2, 2, 4, 2}, {2, 2, 4, 2}, {2, 2, 4, 2}};
-    const int* ps = presets[(w8 && g_chain_nb != 9 && g_chain_nb != 20 && g_chain_nb != 21 && (g_chain_nb < 12 || g_chain_nb > 14)) ? 0 : g_chain_nb];
-    p.nbq = ps[0]; p.nbo = ps[1]; p.nbg = ps[2]; p.nbd = ps[3];
-    if (w8 && g_chain_nb == 20) { p.nbq = 1; p.nbo = 1; p.nbg = 2; p.nbd = 1; }
-    if (w8 && g_chain_nb == 21) { p.nbq = 1; p.nbo = 1; p.nbg = 1; p.nbd = 2; }
-    if (w8 && g_chain_nb == 7) { p.nbq = 2; p.nbo = 2; p.nbg = 2; p.nbd = 2; }
-  }
-  // MXFP4 variants (tools/w4_decode_bench.py --variants): 7 / 12 two batches everywhere, one / both requested before the wait (12 = W8's BYTES per
-  // workgroup); 20 / 21 two batches on gate_up / down only; 13 two on gate_up and down
-  if (w4 && (g_chain_nb == 7 || g_chain_nb == 12)) { p.nbq = 2; p.nbo = 2; p.nbg = 2; p.nbd = 2; }
-  if (w4 && g_chain_nb == 20) { p.nbg = 2; }
-  if (w4 && g_chain_nb == 21) { p.nbd = 2; }
-  if (w4 && g_chain_nb == 13) { p.nbg = 2; p.nbd = 2; }
-#endif
-  auto wgs = [&](int n_out, int fpw, int nb) { return (n_out + 4 * fpw * nb - 1) / (4 * fpw * nb); };
-  p.n_qkv = wgs(3 * H * 96, rd, p.nbq);
-  p.n_attn = (H * p.S + 3) / 4;
-  p.n_o = wgs(d, rd, p.nbo);
-  p.n_gu = wgs(F, rd / 2, p.nbg);
-  p.n_down = wgs(d, rf, p.nbd);
-  p.wg_layer = p.n_qkv + p.n_attn + p.n_o + p.n_gu + p.n_down;
-  {
-    const int rows_wg = 4 * rd * p.nbq;                 // rows of w_qkv per workgroup
-    p.qkv_by_head = (CH_QKV_BY_HEAD && 96 % rows_wg == 0) ? 96 / rows_wg : 0;
-  }
-  p.sleep_n = 8; p.xrep = CH_XREP_USED; p.nflags = CH_FLAGS; p.nowait = 0; p.touch = CH_TOUCH;
-#ifdef AKI_LAB_HOOKS
-  p.sleep_n = g_chain_sleep; p.xrep = g_chain_xrep; p.nflags = g_chain_nflags; p.nowait = g_chain_nowait;
-  if (g_chain_touch >= 0) { p.touch = g_chain_touch & 1; if (g_chain_touch & 2) p.qkv_by_head = 0; }      // lab: touch | (one flag for the whole qkv phase) << 1
-  p.stamps = g_chain_stamps; p.stamp_layer = g_chain_stamp_layer;
-  p.fault_code = 0;
-  if (g_chain_fault_code != 0u && g_chain_fault_skip-- == 0) { p.fault_code = g_chain_fault_code; g_chain_fault_code = 0; }     // one shot
-#endif
+  chain_params(p, a, 1);
   AKI_CLEAR_ERR();
   // Every polled word is zero when the kernel starts: the caller zero-fills the workspace once, and each call leaves the counter set of the NEXT
-  // call zeroed (see the top of the kernel).  History: hipMemsetAsync in front of every call was used first - eager calls were fine, but as a
+  // call zeroed (chain_counter_set).  History: hipMemsetAsync in front of every call was used first - eager calls were fine, but as a
   // captured memset node (ROCm 7.2, 1 MB) it left a constant non-zero word pattern in the block in some processes: every READY flag then read
   // "set", no workgroup ever waited, and the replayed step ran at the speed of the bare weight stream (1.28 ms) with wrong logits, while the
   // 2-layer graph test of the time happened to pass.  tests/test_decode_gpu.py compares a FULL-DEPTH graph replay with the five-launch path,
   // and every timing tool checks logits.  A zeroing kernel of this library in front of every call came next (4.7-5.3 us per token).
-  int SMEM = 16384 + 64;                 // x (<= 8192 bf16) + the norm's partial sums; the attention phase carves 4 x 3 KiB of it
-#ifdef AKI_LAB_HOOKS
-  SMEM += g_chain_lds_pad;               // lab: unused LDS that limits the workgroups resident per CU (160 KiB / SMEM)
-#endif
-  const dim3 grid((unsigned)a->n_layers * (unsigned)p.wg_layer), block(256);
-#define AKI_CHAIN_LAUNCH(W8V, A, B, C, D)                                                                                                   \
-  do {                                                                                                                                      \
-    if (SMEM > 48 * 1024) (void)hipFuncSetAttribute((const void*)decode_chain_kernel<6, 16, W8V, A, B, C, D>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM); \
-    hipLaunchKernelGGL((decode_chain_kernel<6, 16, W8V, A, B, C, D>), grid, block, SMEM, stream, p);                                         \
-  } while (0)
-#define AKI_CHAIN_LAUNCH3(W8V, A, B, C, D, PA, PB, PC, PD, OC)                                                                               \
-  do {                                                                                                                                      \
-    if (SMEM > 48 * 1024) (void)hipFuncSetAttribute((const void*)decode_chain_kernel<6, 16, W8V, A, B, C, D, PA, PB, PC, PD, OC>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM); \
-    hipLaunchKernelGGL((decode_chain_kernel<6, 16, W8V, A, B, C, D, PA, PB, PC, PD, OC>), grid, block, SMEM, stream, p);                     \
-  } while (0)
-#define AKI_CHAIN_LAUNCH2(W8V, A, B, C, D, PA, PB, PC, PD)                                                                                   \
-  do {                                                                                                                                      \
-    if (SMEM > 48 * 1024) (void)hipFuncSetAttribute((const void*)decode_chain_kernel<6, 16, W8V, A, B, C, D, PA, PB, PC, PD>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM); \
-    hipLaunchKernelGGL((decode_chain_kernel<6, 16, W8V, A, B, C, D, PA, PB, PC, PD>), grid, block, SMEM, stream, p);                         \
-  } while (0)
-#ifdef AKI_LAB_HOOKS
-  if (w8 && g_chain_nb == 12) AKI_CHAIN_LAUNCH2(CH_W8, 2, 2, 2, 2, 2, 2, 2, 2);
-  else if (w8 && g_chain_nb == 13) AKI_CHAIN_LAUNCH2(CH_W8, 2, 2, 4, 2, 2, 2, 2, 2);
-  else if (w8 && g_chain_nb == 14) AKI_CHAIN_LAUNCH2(CH_W8, 2, 2, 4, 2, 2, 2, 2, 1);
-  else if (w8 && g_chain_nb == 7) AKI_CHAIN_LAUNCH2(CH_W8, 2, 2, 2, 2, 1, 1, 1, 1);
-  else if (w8 && g_chain_nb == 9) AKI_CHAIN_LAUNCH2(CH_W8, 2, 1, 4, 1, 2, 1, 4, 1);
-  else if (w8 && g_chain_nb == 20) AKI_CHAIN_LAUNCH2(CH_W8, 1, 1, 2, 1, 1, 1, 2, 1);
-  else if (w8 && g_chain_nb == 21) AKI_CHAIN_LAUNCH2(CH_W8, 1, 1, 1, 2, 1, 1, 1, 2);
-  else
-#endif
-  if (w8) AKI_CHAIN_LAUNCH2(CH_W8, 1, 1, 1, 1, 1, 1, 1, 1);
-#ifdef AKI_LAB_HOOKS
-  else if (w4 && g_chain_nb == 7) AKI_CHAIN_LAUNCH2(CH_W4, 2, 2, 2, 2, 1, 1, 1, 1);
-  else if (w4 && g_chain_nb == 12) AKI_CHAIN_LAUNCH2(CH_W4, 2, 2, 2, 2, 2, 2, 2, 2);
-  else if (w4 && g_chain_nb == 13) AKI_CHAIN_LAUNCH2(CH_W4, 1, 1, 2, 2, 1, 1, 2, 2);
-  else if (w4 && g_chain_nb == 20) AKI_CHAIN_LAUNCH2(CH_W4, 1, 1, 2, 1, 1, 1, 2, 1);
-  else if (w4 && g_chain_nb == 21) AKI_CHAIN_LAUNCH2(CH_W4, 1, 1, 1, 2, 1, 1, 1, 2);
-#endif
-  // MXFP4: W8's rows per wave (4 on K = d, 2 on K = F), one batch per workgroup, every weight and scale byte requested before the wait
-  else if (w4) AKI_CHAIN_LAUNCH2(CH_W4, 1, 1, 1, 1, 1, 1, 1, 1);
-#ifdef AKI_LAB_HOOKS
-  else if (g_chain_nb == 1) AKI_CHAIN_LAUNCH(CH_BF16, 8, 8, 8, 8);
-  else if (g_chain_nb == 2) AKI_CHAIN_LAUNCH(CH_BF16, 4, 2, 8, 2);
-  else if (g_chain_nb == 3) AKI_CHAIN_LAUNCH(CH_BF16, 8, 2, 8, 4);
-  else if (g_chain_nb == 4) AKI_CHAIN_LAUNCH(CH_BF16, 4, 4, 4, 4);
-  else if (g_chain_nb == 5) AKI_CHAIN_LAUNCH(CH_BF16, 16, 4, 16, 4);
-  else if (g_chain_nb == 6) AKI_CHAIN_LAUNCH(CH_BF16, 8, 2, 16, 2);
-  else if (g_chain_nb == 7) AKI_CHAIN_LAUNCH(CH_BF16, 1, 1, 1, 1);
-  else if (g_chain_nb == 8) AKI_CHAIN_LAUNCH(CH_BF16, 8, 4, 16, 4);
-  else if (g_chain_nb == 9) AKI_CHAIN_LAUNCH(CH_BF16, 2, 1, 4, 1);
-  else if (g_chain_nb == 10) AKI_CHAIN_LAUNCH(CH_BF16, 4, 2, 4, 2);
-  else if (g_chain_nb == 11) AKI_CHAIN_LAUNCH(CH_BF16, 2, 2, 4, 2);
-  else if (g_chain_nb == 12) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 2, 2, 2, 2, 2, 2);      // batches requested before the wait: qkv, o, gate_up, down
-  else if (g_chain_nb == 13) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 2, 2, 2, 2, 2);
-  else if (g_chain_nb == 14) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 2, 2, 2, 2, 1);
-  else if (g_chain_nb == 15) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 8, 2, 2, 2, 2, 1);
-  else if (g_chain_nb == 16) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 4, 2, 2, 2, 1);
-  else if (g_chain_nb == 17) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 2, 2, 2, 1, 2);
-  else if (g_chain_nb == 18) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 8, 2, 2, 2, 2, 2);
-  else if (g_chain_nb == 19) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 2, 2, 2, 1, 1);
-  else if (g_chain_nb == 20) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 4, 2, 2, 1, 1);
-  else if (g_chain_nb == 21) AKI_CHAIN_LAUNCH2(CH_BF16, 4, 2, 8, 4, 2, 2, 2, 1);
-  else if (g_chain_nb == 22) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 2, 1, 1, 1, 1);
-  else if (g_chain_nb == 23) AKI_CHAIN_LAUNCH2(CH_BF16, 4, 4, 8, 4, 1, 1, 1, 1);
-  else if (g_chain_nb == 24) AKI_CHAIN_LAUNCH3(CH_BF16, 2, 2, 4, 2, 2, 2, 2, 1, 4);
-  else if (g_chain_nb == 25) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 2, 2, 2, 4, 2);   // every weight of every phase before the wait: ~250 VGPRs, 2 workgroups per CU
-  else if (g_chain_nb == 26) AKI_CHAIN_LAUNCH2(CH_BF16, 2, 2, 4, 2, 2, 2, 3, 2);   // the product's batches held to 128 VGPRs (4 workgroups per CU; spills)
-#endif
-  else AKI_CHAIN_LAUNCH2(CH_BF16, CH_NBQ, CH_NBO, CH_NBG, CH_NBD, CH_PFQ, CH_PFO, CH_PFG, CH_PFD);
-#undef AKI_CHAIN_LAUNCH
+  if (w8) chain_launch<CH_W8>(p, stream);
+  else if (w4) chain_launch<CH_W4>(p, stream);
+  else chain_launch<CH_BF16>(p, stream);
   AKI_LAUNCH_CHECK();
   return AKI_OK;
 }
@@ -1233,23 +1038,12 @@ int decode_chain_launch(const aki_decode_chain_args* a, hipStream_t stream) {
 }  // namespace aki
 
 #ifdef AKI_LAB_HOOKS
-// Lab build only: poll period (x 64 cycles), copies of the hand-off vectors (1..8), READY flags per phase (1..32), and
-// nowait = 1: no dependency waits at all (WRONG results - the time of the bare weight stream in this workgroup structure).
+// Lab build only.
 // device buffer of 5 x 2048 x 8 uint64 (or NULL) and the layer whose workgroups stamp their wall clock into it (tools/decode_chain_edges.py)
 extern "C" void aki_lab_set_chain_stamps(void* buf, int layer) { aki::g_chain_stamps = (unsigned long long*)buf; aki::g_chain_stamp_layer = layer; }
-extern "C" void aki_lab_set_chain_lds(int pad_bytes) { aki::g_chain_lds_pad = pad_bytes < 0 ? 0 : (pad_bytes > 140 * 1024 ? 140 * 1024 : pad_bytes); }
-// MXFP4 chains (product: one batch per workgroup) know 7 {2,2,2,2}, 12 {2,2,2,2} all before the wait, 13 {1,1,2,2}, 20 {1,1,2,1}, 21 {1,1,1,2}; any other preset = the product.
-// preset of batches per workgroup (qkv, o_proj, gate_up, down): 0 product {2,2,2,2}, 1 {8,8,8,8}, 2 {4,2,8,2}, 3 {8,2,8,4}, 4 {4,4,4,4}, 5 {16,4,16,4}, 6 {8,2,16,2}, 7 {1,1,1,1}, 8 {8,4,16,4}, 9 {2,1,4,1}, 10 {4,2,4,2}, 11 {2,2,4,2}
-extern "C" void aki_lab_set_chain_nb(int preset) { aki::g_chain_nb = (preset >= 0 && preset <= 26) ? preset : 0; }
-extern "C" void aki_lab_set_chain(int sleep_n, int xrep, int nflags, int nowait) {
-  aki::g_chain_sleep = sleep_n < 0 ? 0 : sleep_n;
-  aki::g_chain_xrep = xrep < 1 ? 1 : (xrep > aki::CH_XREP ? aki::CH_XREP : xrep);
-  aki::g_chain_nflags = nflags < 1 ? 1 : (nflags > aki::CH_FLAGS ? aki::CH_FLAGS : nflags);
-  aki::g_chain_nowait = nowait ? 1 : 0;
-}
+// 1: no dependency waits at all (WRONG results - the time of the bare weight stream in this workgroup structure); 0: back to the chain
+extern "C" void aki_lab_set_chain_nowait(int nowait) { aki::g_chain_nowait = nowait ? 1 : 0; }
 // Fault injection: the chain launch number `skip` from now (0 = the next one) treats the wait `code` = layer << 8 | phase (phase 1 qkv, 3 o_proj,
 // 4 gate_up, 5 down; layer >= 1 for phase 1) as given up at once - error word set, every flag raised, garbage output.  One shot; code 0 disarms.
 extern "C" void aki_lab_set_chain_fault(int code, int skip) { aki::g_chain_fault_code = (unsigned)code; aki::g_chain_fault_skip = skip < 0 ? 0 : skip; }
-// -1: the product setting; 0 / 1: touch loads of the batches beyond the register slots off / on.
-extern "C" void aki_lab_set_chain_touch(int touch) { aki::g_chain_touch = touch; }
 #endif

@@ -16,10 +16,9 @@
 #include <type_traits>
 
 #include "aki_device.h"
+#include "weight_dot.h"
 
 namespace aki {
-
-typedef __attribute__((ext_vector_type(2))) __bf16 w4_bf16x2;
 
 struct W4Params {
   const bf16_t* x; const uint8_t* w; const uint8_t* ws; const bf16_t* bias; const bf16_t* residual; bf16_t* y;
@@ -80,25 +79,6 @@ int quant_mxfp4_launch(const void* w, int N, int K, int ldw, uint8_t* wq, uint8_
   hipLaunchKernelGGL(mxfp4_quant_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)w, wq, ws, N, K, ldw);
   AKI_LAUNCH_CHECK();
   return AKI_OK;
-}
-
-// the scale operand of the convert: an f32 whose exponent field is the e8m0 byte, i.e. 2^(byte - 127)
-__device__ __forceinline__ float w4_scale(unsigned byte) { return __builtin_bit_cast(float, byte << 23); }
-
-// one block: 16 bytes of nibbles (32 k) against four 16-byte x chunks; dword i of w carries k 8i .. 8i+7 = x chunk i
-__device__ __forceinline__ float dot32_w4(const u32x4 w, const float scale, const u32x4 (&x)[4], float acc) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const bf16x8 xv = __builtin_bit_cast(bf16x8, x[i]);
-#define AKI_W4_PAIR(sel, i0)                                                                                      \
-  {                                                                                                               \
-    const w4_bf16x2 wb = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[i], scale, sel);   /* byte sel: low nibble -> element 0, high -> 1 */ \
-    acc = __builtin_amdgcn_fdot2_f32_bf16(wb, __builtin_shufflevector(xv, xv, i0, i0 + 1), acc, false);           \
-  }
-    AKI_W4_PAIR(0, 0) AKI_W4_PAIR(1, 2) AKI_W4_PAIR(2, 4) AKI_W4_PAIR(3, 6)
-#undef AKI_W4_PAIR
-  }
-  return acc;
 }
 
 // U chunks (of 32 k) per lane for NR weight rows: every weight load and scale byte is requested before the first dot product
@@ -330,8 +310,8 @@ __global__ __launch_bounds__(KS * 64) void skinny_gemm_w4_kernel(const W4Params 
           for (int t = 0; t < NS; ++t) {
             const unsigned d = wa[u][t][j];
             const float s = w4_scale(sc[u][t]);
-            const w4_bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 0), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 1);
-            const w4_bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 2), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 3);
+            const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 0), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 1);
+            const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 2), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, 3);
             const u32x4 wq = u32x4{__builtin_bit_cast(unsigned, p0), __builtin_bit_cast(unsigned, p1), __builtin_bit_cast(unsigned, p2), __builtin_bit_cast(unsigned, p3)};
             acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wq), xb, acc[t], 0, 0, 0);
           }

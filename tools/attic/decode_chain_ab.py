@@ -1,9 +1,9 @@
 """The one-launch decode step (decode_chain.hip) under the lab library's knobs, alternating settings in ONE process on one box:
 poll period, copies of the hand-off vectors, READY flags per phase, and `nowait` (no dependency waits: wrong results, the time
 of the bare weight stream in this workgroup structure).  hipGraph replay, host wall clock per token.
-    python tools/decode_chain_ab.py [--prompt 655] [--steps 48] [--fp8]"""
+    python tools/attic/decode_chain_ab.py [--prompt 655] [--steps 48] [--fp8]"""
 import argparse, json, os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 
 

@@ -1,9 +1,9 @@
 """The one-launch decode step under different launch conditions (lab library): the same kernel has been seen at 1.2 ms and at
 3.4 ms per token.  For each preset of batches per workgroup and number of vector copies: (a) the chain alone, eager, same
 position; (b) DecodeGraph replay + argmax (the greedy loop), at two cache capacities; (c) DecodeGraph replay with constant ids.
-    python tools/decode_chain_regimes.py"""
+    python tools/attic/decode_chain_regimes.py"""
 import json, os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 
 # batches per workgroup {qkv, o, gate_up, down} / batches requested before the wait

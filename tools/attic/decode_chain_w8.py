@@ -1,8 +1,8 @@
 """e4m3-weight decode, batch 1: the one-launch chain under the lab library's batch / prefetch presets against the five-launch path, ONE
 process on one box, hipGraph replay + argmax, logits of 6 greedy steps checked against the five-launch path.
-    python tools/decode_chain_w8.py"""
+    python tools/attic/decode_chain_w8.py"""
 import json, os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 
 PRESETS = {0: "{1,1,1,1}/{1,1,1,1} (product)", 7: "{2,2,2,2}/{1,1,1,1}", 12: "{2,2,2,2}/{2,2,2,2}", 20: "{1,1,2,1}/{1,1,2,1}", 21: "{1,1,1,2}/{1,1,1,2}", 9: "{2,1,4,1}/{2,1,4,1}",

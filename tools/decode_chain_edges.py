@@ -10,7 +10,6 @@ import torch
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layer", type=int, default=16)
-    ap.add_argument("--preset", type=int, default=0)
     ap.add_argument("--dump", default=None, help="save the raw stamps [phase][workgroup][slot] (.npy)")
     ap.add_argument("--batch", type=int, default=1, help="2..8: the batched chain")
     ap.add_argument("--nowait", action="store_true", help="no dependency waits (wrong results): the lifetimes of the workgroups of the bare stream")
@@ -32,12 +31,11 @@ def main():
     table = ops.MaskTable.from_host([[(4, 148, 4, 148)]] * B, torch.ones(B, L, dtype=torch.bool).numpy(), [L] * B, "cuda")
     names = ["qkv", "attention", "o_proj", "gate_up", "down"]
     with _lib.use_lab(0) as lab, torch.no_grad():
-        lab.aki_lab_set_chain_nb(a.preset)
         from aki_amd import _lib
         _lib._lib = _lib.load_lab()            # the batched chain is compiled into the lab library only (round 6)
         lm.model.use_decode_chain_batched = True
         if a.nowait:
-            lab.aki_lab_set_chain(8, 1, 32, 1)
+            lab.aki_lab_set_chain_nowait(1)
         out = lm(inputs_embeds=x, attention_mask=table, use_cache=True, cache_capacity=L + 136)
         cache = out.past_key_values
         ids = out.logits[:, -1].float().argmax(-1)
@@ -48,8 +46,7 @@ def main():
         lm.decode_step(input_ids=ids, past_key_values=cache)
         torch.cuda.synchronize()
         lab.aki_lab_set_chain_stamps(None, -1)
-        lab.aki_lab_set_chain(8, 1, 32, 0)
-        lab.aki_lab_set_chain_nb(0)
+        lab.aki_lab_set_chain_nowait(0)
     s = stamps.cpu().numpy().astype(np.float64) / 100.0          # microseconds
     if a.dump:
         np.save(a.dump, stamps.cpu().numpy())

@@ -11,9 +11,8 @@ prefills.  Every child runs under its own time limit; the first one that fails e
     python tools/w4_decode_bench.py [--steps 32] [--rounds 3] [--shapes 1x655,8x655,16x655,16x4096] [--out profiles/w4_decode_bench.json]
 --chain: the batch-1 question only -> profiles/w4_chain_bench.json.  One child alternates FOUR legs at batch 1, prompt 655: the bf16 chain, the
 e4m3 chain, MXFP4 on five launches per layer and the MXFP4 chain (Phi3Model.decode_chain_w4); the logits of the MXFP4 chain's first steps are
-checked against MXFP4 on five launches, bit for bit.  --variants 7,12,13,20,21 adds legs of the MXFP4 chain under the lab library's batch /
-prefetch presets (aki_lab_set_chain_nb, decode_chain.hip), alternating in the same process - then EVERY leg runs on the lab library.
-    python tools/w4_decode_bench.py --chain [--variants 7,12,13,20,21] [--steps 32] [--rounds 3]"""
+checked against MXFP4 on five launches, bit for bit.
+    python tools/w4_decode_bench.py --chain [--steps 32] [--rounds 3]"""
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -82,26 +81,18 @@ def child_shape(a, B, L):
     print("ROW " + json.dumps(row), flush=True)
 
 
-W4_PRESETS = {7: "{2,2,2,2} batches, one requested before the wait", 12: "{2,2,2,2} batches, all requested before the wait",
-              13: "{1,1,2,2} batches, all requested before the wait", 20: "{1,1,2,1} batches, all requested before the wait",
-              21: "{1,1,1,2} batches, all requested before the wait"}
-
-
 def child_chain(a):
-    """Batch 1, prompt 655: bf16 chain | e4m3 chain | MXFP4 on five launches | MXFP4 chain (+ lab presets of the MXFP4 chain), alternating."""
-    import contextlib
+    """Batch 1, prompt 655: bf16 chain | e4m3 chain | MXFP4 on five launches | MXFP4 chain, alternating."""
     import torch
-    from aki_amd import _lib
     from aki_amd.phi3 import DecodeGraph
     B, L = 1, a.prompt
-    variants = [int(v) for v in a.variants.split(",") if v]
     lm = build_lm(a.layers)
-    legs = [("bf16_chain", "bf16", True, False, 0), ("e4m3_chain", "e4m3", True, False, 0), ("mxfp4", "mxfp4", False, False, 0),
-            ("mxfp4_chain", "mxfp4", True, True, 0)] + [(f"mxfp4_chain_preset_{v}", "mxfp4", True, True, v) for v in variants]
+    legs = [("bf16_chain", "bf16", True, False), ("e4m3_chain", "e4m3", True, False), ("mxfp4", "mxfp4", False, False),
+            ("mxfp4_chain", "mxfp4", True, True)]
     best, first = {}, {}
-    with (_lib.use_lab(0) if variants else contextlib.nullcontext()) as lab, torch.no_grad():
+    with torch.no_grad():
         for _ in range(a.rounds):
-            for name, fmt, chain, w4c, preset in legs:
+            for name, fmt, chain, w4c in legs:
                 set_format(lm, None)
                 lm.model.use_decode_chain = True
                 lm.model.decode_chain_w4 = w4c
@@ -109,8 +100,6 @@ def child_chain(a):
                 cache = out.past_key_values
                 ids = out.logits[:, -1].float().argmax(-1)
                 set_format(lm, fmt)
-                if lab is not None:
-                    lab.aki_lab_set_chain_nb(preset)
                 st = DecodeGraph(lm, cache)
                 head = []
                 for _ in range(3):
@@ -131,18 +120,14 @@ def child_chain(a):
                 best[name] = min(best.get(name, float("inf")), ms)
                 del st, cache, out
                 torch.cuda.empty_cache()
-        if lab is not None:
-            lab.aki_lab_set_chain_nb(0)
     bad = {k: int((v != first["mxfp4"]).sum()) for k, v in first.items() if k.startswith("mxfp4_chain")}
     assert not any(bad.values()), f"MXFP4 chain logits differ from MXFP4 on five launches: {bad}"
     row = {"batch": B, "prompt": L, "ms_per_step": {k: round(v, 4) for k, v in best.items()},
-           "library": "lab (same kernels; presets switchable)" if variants else "product",
+           "library": "product",
            "mxfp4_chain_logits_differing_from_five_launches": bad,
            "mxfp4_chain_vs_mxfp4_five_launches": round(best["mxfp4"] / best["mxfp4_chain"], 3),
            "mxfp4_chain_vs_e4m3_chain": round(best["e4m3_chain"] / best["mxfp4_chain"], 3),
            "mxfp4_chain_beats_e4m3_chain": bool(best["mxfp4_chain"] < best["e4m3_chain"])}
-    if variants:
-        row["presets"] = {f"mxfp4_chain_preset_{v}": W4_PRESETS.get(v, "?") for v in variants}
     print("ROW " + json.dumps(row), flush=True)
 
 
@@ -175,7 +160,6 @@ def main():
     ap.add_argument("--limit", type=int, default=240, help="time limit of one child process, seconds")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "w4_decode_bench.json"))
     ap.add_argument("--chain", action="store_true", help="batch 1 only: bf16 chain, e4m3 chain, MXFP4 on five launches, MXFP4 chain -> profiles/w4_chain_bench.json")
-    ap.add_argument("--variants", default="", help="with --chain: lab presets of the MXFP4 chain to time as further legs, e.g. 7,12,13,20,21")
     ap.add_argument("--prompt", type=int, default=655, help="with --chain: the prompt length")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -223,7 +207,7 @@ def main():
 def main_chain(a):
     out = a.out if a.out != os.path.join(ROOT, "profiles", "w4_decode_bench.json") else os.path.join(ROOT, "profiles", "w4_chain_bench.json")
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "chain", "--steps", str(a.steps), "--rounds", str(a.rounds), "--layers", str(a.layers),
-           "--prompt", str(a.prompt), "--variants", a.variants]
+           "--prompt", str(a.prompt)]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.limit)
     except subprocess.TimeoutExpired:

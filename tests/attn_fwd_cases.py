@@ -55,13 +55,11 @@ Input families, everything rounded to bf16 first.
             the exact path).  Three keys of the first tile carry v = +-2^x, x chosen so that they hold about half of M_o on the lifted
             rows: the CPU test asserts a median share in [0.3, 0.7] and a 5th percentile >= 0.1 - the first tile's loss is 8 bars or more.
 
-Not reached by this table: a persistent workgroup that snakes over several ranks of its pair.  A rank of the 64-row core is 256 rows
+A persistent workgroup that snakes over several ranks of its pair is the subject of tests/attn_walk_cases.py (the same bar, heads that
+share data so that B * H of a few hundred stays affordable in float64), not of this table: a rank of the 64-row core is 256 rows
 (attn_core64_bf16_launch: nqt = ceil(L / 256), splits = min(ceil(CUs / (B H)), nqt)), so a workgroup walks a second rank only where
-ceil(CUs / (B H)) < ceil(L / 256): with 256 compute units B * H >= 18 at L = 4096, >= 32 at L = 2304, >= 14 at L = 5000 - everywhere
-150 million query-key pairs or more in float64 on the CPU, several times the largest case here and far from "H <= 2, small B".  The
-32-row core (ranks of 128 rows, splits >= L / 256) needs B * H >= 35 at L = 2048.  ranks_per_workgroup() states the rule; the CPU
-test asserts that no case of the table passes 1 and that the shape tests/test_attn64_gpu.py keeps under the coarse bar (1 x 32 x 4096,
-and 2 x 32 x 4096 in its determinism test) does.
+ceil(CUs / (B H)) < ceil(L / 256), and the 32-row core (ranks of 128 rows, splits >= L / 256) needs B * H >= 35 at L = 2048.
+ranks_per_workgroup() states the rule; the CPU test asserts that no case of THIS table passes 1.
 """
 import os
 import re

@@ -5,12 +5,15 @@ Reference: /root/reference/codes/open_flamingo/src/aki.py  (__init__ :10-50, set
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import List, Optional, Tuple, Union
 
 import torch
 from torch import nn
 
+from . import ops
 from .helpers import PerceiverResampler
+from .phi3 import AkiKVCache, DecodeGraph
 from .vlm import VLMWithLanguageStream
 
 
@@ -70,17 +73,86 @@ def _embedding_tables(emb: nn.Module, logits: torch.Tensor):
     return (w, extra, max_orig) if logits.shape[-1] <= rows else None
 
 
-class AKI(VLMWithLanguageStream):
-    def __init__(self, vision_encoder: nn.Module, lang_model: nn.Module, vis_feature_dim: int, initial_tokenizer_len: int,
-                 pad_token_id: int, decoder_layers_attr_name: str = None, gradient_checkpointing: bool = False,
-                 base_img_size: Optional[int] = None, num_vision_tokens: int = 144):
-        self._special_tokens = {"media_token": "<image>", "end_of_trunk_token": "<|endofchunk|>"}
-        lang_embedding_dim = lang_model.get_input_embeddings().weight.shape[1]
-        super().__init__(
-            vision_encoder=vision_encoder,
-            vision_tokenizer=PerceiverResampler(dim=vis_feature_dim, dim_inner=lang_embedding_dim, num_latents=num_vision_tokens),
-            lang_model=lang_model, initial_tokenizer_len=initial_tokenizer_len, gradient_checkpointing=gradient_checkpointing,
-            base_img_size=base_img_size, decoder_layers_attr_name=decoder_layers_attr_name, pad_token_id=pad_token_id)
+# The keyword arguments of `generate`, resolved and validated by _parse_generate_kwargs.  rng: None or a torch.Generator (sample_next) or an
+# ops.DeviceGenerator, which device_rng repeats (else None: no device sampler); n_ret: num_return_sequences; eos_ids: a set; processors:
+# the logits-processor keywords (PROCESSOR_KWARGS) with None read as the neutral value.
+GenerateOptions = namedtuple("GenerateOptions", "num_beams do_sample temperature top_k top_p rng device_rng length_penalty early_stopping "
+                                                "n_ret max_new_tokens eos_ids pad_id use_graph processors")
+
+
+def _parse_generate_kwargs(kwargs: dict, default_pad_id, default_eos_ids, from_cache: bool) -> GenerateOptions:
+    """Every keyword of `generate` popped from `kwargs`, checked and given its default, before any device work.  default_eos_ids: a callable,
+    asked only when the caller passes no `eos_token_id`; from_cache: generate(past_key_values=...).  A keyword that is left over
+    (`logits_processor`, `stopping_criteria`, `output_scores`, `generation_config`, ...) raises ValueError instead of being ignored."""
+    num_beams = int(kwargs.pop("num_beams", 1))
+    do_sample = bool(kwargs.pop("do_sample", False))
+    temperature = float(kwargs.pop("temperature", 1.0))
+    top_k = int(kwargs.pop("top_k", 0) or 0)
+    top_p = float(kwargs.pop("top_p", 1.0))
+    rng = kwargs.pop("generator", None)
+    length_penalty = float(kwargs.pop("length_penalty", 1.0))
+    early_stopping = kwargs.pop("early_stopping", False)
+    device_rng = rng if isinstance(rng, ops.DeviceGenerator) else None
+    if device_rng is not None:
+        if not do_sample or num_beams > 1:
+            raise ValueError("generator=DeviceGenerator(...) selects the device sampler: it needs do_sample=True and num_beams=1")
+        if not 0.0 < top_p <= 1.0 or top_k < 0:
+            raise ValueError("the device sampler takes 0 < top_p <= 1 and top_k >= 0")
+    n_ret = int(kwargs.pop("num_return_sequences", 1))
+    if n_ret < 1:
+        raise ValueError("num_return_sequences must be at least 1")
+    if n_ret > 1 and num_beams > 1:
+        raise NotImplementedError("num_return_sequences > 1 with beam search")
+    if num_beams < 1 or (num_beams > 1 and do_sample):
+        raise NotImplementedError("beam-sample decoding (num_beams > 1 with do_sample=True)")
+    if n_ret > 1 and not do_sample:
+        raise ValueError("num_return_sequences > 1 needs do_sample=True: greedy decoding returns one sequence per sample")
+    if do_sample and temperature <= 0:
+        raise ValueError("temperature must be positive")
+    if from_cache and (num_beams > 1 or n_ret > 1):
+        raise NotImplementedError("generate(past_key_values=...) continues one sequence per cached row: beam search and "
+                                  "num_return_sequences > 1 start from a fresh prefill")
+    max_new_tokens = int(kwargs.pop("max_new_tokens", kwargs.pop("max_length", 20)))
+    # HF `generate` stops on generation_config.eos_token_id when the caller passes none (the reference's callers pass only
+    # max_new_tokens / do_sample: local_demo.py:76-87, eval_cv_bench/eval.py:99-104); `eos_token_id=[]` switches it off.
+    eos = kwargs.pop("eos_token_id", None)
+    if eos is None:
+        eos = default_eos_ids()
+    eos_ids = set([eos] if isinstance(eos, int) else (eos or []))
+    pad_id = kwargs.pop("pad_token_id", default_pad_id)
+    use_graph = kwargs.pop("use_graph", None)
+    if use_graph is None:
+        use_graph = max_new_tokens >= 8          # capture costs about two eager steps
+    processors = _pop_processor_kwargs(kwargs)
+    _reject_unused_kwargs(kwargs)
+    return GenerateOptions(num_beams=num_beams, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, rng=rng,
+                           device_rng=device_rng, length_penalty=length_penalty, early_stopping=early_stopping, n_ret=n_ret,
+                           max_new_tokens=max_new_tokens, eos_ids=eos_ids, pad_id=pad_id, use_graph=use_graph, processors=processors)
+
+
+def _device_sampler_args(opt: GenerateOptions):
+    """ops.sample_pick's own arguments when a DeviceGenerator selected the device sampler, else None: one offset per generate call."""
+    g = opt.device_rng
+    return None if g is None else dict(temperature=opt.temperature, top_k=opt.top_k, top_p=opt.top_p, seed=g.seed, offset=g.next_offset())
+
+
+def _first_eos(tokens: torch.Tensor, eos_t: torch.Tensor):
+    """tokens [B, n], eos_t [E] -> (finished [B] bool: the row holds an EOS; index [B] int64 of its first one, 0 where it holds none)."""
+    hit = (tokens[:, :, None] == eos_t[None, None, :]).any(-1)
+    return hit.any(1), hit.to(torch.int32).argmax(1)
+
+
+def _pad_rows(rows, pad_id: int, device) -> torch.Tensor:
+    """A list of 1-D int64 token rows of any lengths -> [B, longest] on `device`, the shorter rows filled up with pad_id."""
+    out = torch.full((len(rows), max(x.numel() for x in rows)), pad_id, dtype=torch.long)
+    for b, x in enumerate(rows):
+        out[b, : x.numel()] = x
+    return out.to(device)
+
+
+class AkiMethods:
+    """Everything the train-time class below and its HF-Hub twin (modeling_aki.AKI) share: the two differ in their constructors only, so
+    each is this class in front of VLMWithLanguageStream plus an __init__."""
 
     last_beam_scores = None     # after a device beam search (_beam_search_device): the returned rows' scores, HF's sequences_scores
 
@@ -197,18 +269,12 @@ class AKI(VLMWithLanguageStream):
             cache.select_rows(gather)
             step_logits = self.lang_model.decode_step(input_ids=nxt_tok.view(-1).to(dev), past_key_values=cache)
             logp = torch.log_softmax(step_logits.float(), dim=-1)
-        best = [max(h, key=lambda x: x[0])[1] for h in hyps]
-        width = max(len(x) for x in best)
-        out = torch.full((B, width), pad_id, dtype=torch.long)
-        for b, x in enumerate(best):
-            out[b, : len(x)] = torch.tensor(x, dtype=torch.long)
-        return out.to(dev)
+        return _pad_rows([torch.tensor(max(h, key=lambda x: x[0])[1], dtype=torch.long) for h in hyps], pad_id, dev)
 
     def _device_beam_search_ok(self, cache, logits, K: int, eos_ids) -> bool:
         """The device path (ops.beam_step / ops.kv_beam_reorder) is opt-in (`lang_model.device_beam_search = True`) and serves bf16 / f32
         logits on the GPU over an ungrouped cache whose K and V are contiguous tensors in the model's dtype; anything else keeps the
         host loop."""
-        from . import ops
         if not getattr(self.lang_model, "device_beam_search", False):
             return False
         if not logits.is_cuda or logits.dtype not in (torch.bfloat16, torch.float32):
@@ -225,8 +291,6 @@ class AKI(VLMWithLanguageStream):
         2K candidates, ranked - exactly equal scores by the lower beam * V + token - and all of the BeamSearchScorer bookkeeping), and
         ops.kv_beam_reorder, which moves only the cache rows written since the prefill, in place: the cache tensors keep their
         addresses, so the decode step at B*K rows is replayed from a DecodeGraph.  The host looks at the done flags every 8th token."""
-        from . import ops
-        from .phi3 import DecodeGraph
         dev = logits.device
         B = logits.shape[0]
         self.last_beam_scores = []
@@ -268,19 +332,15 @@ class AKI(VLMWithLanguageStream):
             i = max(range(count[b]), key=lambda j: (score[b][j], -j))
             best.append(toks[b, i, :length[b][i]])
             self.last_beam_scores.append(score[b][i])
-        width = max(x.numel() for x in best)
-        out = torch.full((B, width), pad_id, dtype=torch.long)
-        for b, x in enumerate(best):
-            out[b, : x.numel()] = x
-        return out.to(dev)
+        return _pad_rows(best, pad_id, dev)
 
     def _continue_from_cache(self, vision_x, lang_x, attention_mask, cache, max_new_tokens):
         """The prefill of generate(past_key_values=cache) - the reference's continuation call (src/aki.py:193-200): the new ids `lang_x`
         [B, T] are appended to the cache (Phi3ForCausalLM._continue: one chunked pass with lang_model.chunked_continue, T decode steps
-        without) and each sample's logits row n_new[b] - 1 is returned with the cache.  attention_mask, if given, spans the cached tokens
-        and the new ids; its last T columns are ones followed by zeros per row (a right-padded chunk), which gives n_new."""
-        from . import ops
-        from .phi3 import AkiKVCache
+        without); then the same greedy / sampling loops run as behind a prefill.  Returns (cache, each sample's logits row n_new[b] - 1,
+        (cache_len clone, host_len) behind the new ids - what _trim_cache_to_returned counts from).  attention_mask, if given, spans the
+        cached tokens and the new ids (width past length + T, else ValueError); its last T columns are ones followed by zeros per row (a
+        right-padded chunk, else ValueError), which gives n_new; ragged rows need `lang_model.chunked_continue = True`."""
         if vision_x is not None:
             raise NotImplementedError("new images on top of an existing KV cache: the reference cannot do it either "
                                       "(its mask for the new chunk would not cover the cached columns); start a new prefill")
@@ -310,240 +370,150 @@ class AKI(VLMWithLanguageStream):
                                f"{max_new_tokens - 1} more; size it with lang_model(..., use_cache=True, cache_capacity=...)")
         self._prepare_inputs_for_forward(vision_tokens=None, lang_x=lang_x, attention_mask=attention_mask, past_key_values=cache)
         logits = self.lang_model._continue(lang_x, None, cache, n_new=n_new).logits           # [B, T, V']
-        if n_new is None:
-            return cache, logits[:, -1]
-        return cache, logits[torch.arange(B, device=logits.device), n_new.long() - 1]
+        last = logits[:, -1] if n_new is None else logits[torch.arange(B, device=logits.device), n_new.long() - 1]
+        return cache, last, (cache.cache_len.clone(), cache.host_len)           # the caller's cache: the state behind the new ids
 
     @staticmethod
     def _trim_cache_to_returned(cache, start_len, host_len0, out, eos_t):
         """The end of generate(past_key_values=...): every row's cache ends right before its last returned token.  start_len / host_len0:
         the cache's lengths behind the new ids; out [B, steps]: the returned tokens; a row's last token is its first EOS, or column
-        steps - 1.  The decode loops step finished rows on with pad tokens until their next look at the flags - those rows are cut off here."""
+        steps - 1.  The decode loops themselves run past that point: the graph / device loop looks at the finished flags only every 8th token,
+        and until then ops.greedy_pick / ops.sample_pick feed a finished row pad tokens and advance its cache_len like any other (the host
+        loop does the same to the finished rows of a batch), so pad-token rows land behind the EOS.  They are cut off here by rewinding
+        cache_len, at B = 1 and per row in a batch: the rows behind are dead and the next append overwrites them."""
         steps = out.shape[1]
         kept = torch.full_like(start_len, steps - 1)
         if eos_t is not None:
-            hit = (out[:, :, None] == eos_t[None, None, :]).any(-1)
-            kept = torch.where(hit.any(1), hit.to(torch.int32).argmax(1).to(kept.dtype), kept)
+            finished, first = _first_eos(out, eos_t)
+            kept = torch.where(finished, first.to(kept.dtype), kept)
         cache.cache_len.copy_(start_len + kept)
         cache.host_len = host_len0 + steps - 1
 
-    @torch.no_grad()
-    def generate(self, vision_x, lang_x, image_size=None, attention_mask=None, past_key_values=None,
-                 past_media_locations=None, past_vision_tokens=None, **kwargs):
-        """Generation (src/aki.py:136-209 + src/aki_generation.py:36-86; local_demo.py / eval.py call it with
-        do_sample=False): MMA prefill into a KV cache, then one HIP decode step per token.  Like HF `generate` called with
-        `inputs_embeds` only, the return value holds just the NEW tokens [B, <= max_new_tokens]; finished rows are padded
-        with pad_token_id.  Decoding modes, selected by the HF keyword arguments the reference forwards (`**kwargs`,
-        src/aki.py:160-207): greedy (default), sampling (`do_sample=True` with `temperature`, `top_k`, `top_p`, optional
-        `generator`; a `aki_amd.DeviceGenerator(seed)` there selects the device sampler - ops.sample_pick, one launch per token inside the
-        same three-launch / replayed-graph loop as greedy, draws that depend on (seed, call, token index, row) and not on the batch -
-        while None or a `torch.Generator` keeps the `sample_next` path; `num_return_sequences=N` with sampling returns [B*N, <= max_new_tokens]
-        in HF order, row b*N + j being continuation j of sample b: one prefill, token 0 of each row drawn from its sample's prefill logits, then
-        the same loops at batch B*N - the device sampler's row index is b*N + j.  The prompt's K/V rows are replicated N times (select_rows)
-        unless `lang_model.share_prompt_kv = True`, with which the N rows of a sample read ONE copy of them (AkiKVCache.share_prefix +
-        ops.decode_attn_group; bf16 model and cache, head_dim 96, more than one new token - anything else stays replicated); without sampling it raises ValueError, with beams NotImplementedError), beam search (`num_beams=K`, `length_penalty`, `early_stopping`; one returned sequence per sample;
-        `lang_model.device_beam_search = True` runs the search on the device - ops.beam_step and ops.kv_beam_reorder, _beam_search_device -
-        where the host loop is used otherwise; off by default: its step time has not been measured yet).
-        Logits processors, applied on the device in every mode and in HF's order (ops.LogitsProcessors): `repetition_penalty`,
-        `no_repeat_ngram_size`, `bad_words_ids`, `min_length` / `min_new_tokens` (eos ids banned until that many tokens are
-        generated), `suppress_tokens`, `begin_suppress_tokens`.  As in HF `generate` with inputs_embeds only, they see the generated
-        tokens, never the prompt; beam search applies them to each beam's log-softmax scores.  Any other keyword (`logits_processor`,
-        `stopping_criteria`, `output_scores`, `generation_config`, ...) raises ValueError instead of being ignored.
-        `past_key_values=cache` (the AkiKVCache of a use_cache=True forward or of an earlier turn; `vision_x` must be None) continues from
-        the cache instead of a prefill: `lang_x` [B, T] holds the NEW ids only and `attention_mask`, if given, spans past + new ids (width
-        past length + T, else ValueError) with a right-padded new part (ones then zeros per row, else ValueError; ragged rows need
-        `lang_model.chunked_continue = True`).  The new ids are appended to the cache, then the same greedy / sampling loops run.  The return
-        value is again the new tokens only.  The LAST returned token of a row - its EOS where it hit one, else the last column - is not in
-        the cache, so the next turn's `lang_x` must begin with it: on return cache_len[b] = its value before the call + n_new[b] + (tokens
-        returned for row b) - 1.  The loops themselves run past that point: the graph / device loop looks at the finished flags only every
-        8th token, and until then ops.greedy_pick / ops.sample_pick feed a finished row pad tokens and advance its cache_len like any
-        other (the host loop does the same to the finished rows of a batch), so pad-token rows land behind the EOS.  A call from a cache
-        therefore rewinds cache_len to the rule above before it returns (_trim_cache_to_returned; the rows behind are dead and the next
-        append overwrites them), at B = 1 and per row in a batch - there the next turn's chunk is ragged (chunked_continue).  The cache
-        must have room for T + max_new_tokens - 1 more rows (AkiError before any launch otherwise); beam search and
-        num_return_sequences > 1 from a cache raise NotImplementedError.
-        Differences from the reference, both only visible for B > 1 (where the reference is inconsistent, SURVEY 3.5): the
-        prompt batch is right-padded and every sample continues from its own length."""
-        num_beams = int(kwargs.pop("num_beams", 1))
-        do_sample = bool(kwargs.pop("do_sample", False))
-        temperature = float(kwargs.pop("temperature", 1.0))
-        top_k = int(kwargs.pop("top_k", 0) or 0)
-        top_p = float(kwargs.pop("top_p", 1.0))
-        rng = kwargs.pop("generator", None)
-        length_penalty = float(kwargs.pop("length_penalty", 1.0))
-        early_stopping = kwargs.pop("early_stopping", False)
-        from . import ops
-        device_rng = rng if isinstance(rng, ops.DeviceGenerator) else None
-        if device_rng is not None:
-            if not do_sample or num_beams > 1:
-                raise ValueError("generator=DeviceGenerator(...) selects the device sampler: it needs do_sample=True and num_beams=1")
-            if not 0.0 < top_p <= 1.0 or top_k < 0:
-                raise ValueError("the device sampler takes 0 < top_p <= 1 and top_k >= 0")
-        n_ret = int(kwargs.pop("num_return_sequences", 1))
-        if n_ret < 1:
-            raise ValueError("num_return_sequences must be at least 1")
-        if n_ret > 1 and num_beams > 1:
-            raise NotImplementedError("num_return_sequences > 1 with beam search")
-        if num_beams < 1 or (num_beams > 1 and do_sample):
-            raise NotImplementedError("beam-sample decoding (num_beams > 1 with do_sample=True)")
-        if n_ret > 1 and not do_sample:
-            raise ValueError("num_return_sequences > 1 needs do_sample=True: greedy decoding returns one sequence per sample")
-        if do_sample and temperature <= 0:
-            raise ValueError("temperature must be positive")
-        if past_key_values is not None and (num_beams > 1 or n_ret > 1):
-            raise NotImplementedError("generate(past_key_values=...) continues one sequence per cached row: beam search and "
-                                      "num_return_sequences > 1 start from a fresh prefill")
-        max_new_tokens = int(kwargs.pop("max_new_tokens", kwargs.pop("max_length", 20)))
-        # HF `generate` stops on generation_config.eos_token_id when the caller passes none (the reference's callers pass only
-        # max_new_tokens / do_sample: local_demo.py:76-87, eval_cv_bench/eval.py:99-104); `eos_token_id=[]` switches it off.
-        eos = kwargs.pop("eos_token_id", None)
-        if eos is None:
-            eos = self.default_eos_token_ids()
-        eos_ids = set([eos] if isinstance(eos, int) else (eos or []))
-        pad_id = kwargs.pop("pad_token_id", self.pad_token_id)
-        use_graph = kwargs.pop("use_graph", None)
-        if use_graph is None:
-            use_graph = max_new_tokens >= 8          # capture costs about two eager steps
-        pk = _pop_processor_kwargs(kwargs)
-        _reject_unused_kwargs(kwargs)
-        if past_key_values is not None:
-            cache, logits = self._continue_from_cache(vision_x, lang_x, attention_mask, past_key_values, max_new_tokens)
-            B = lang_x.shape[0]
-            appended = (cache.cache_len.clone(), cache.host_len)       # the caller's cache: the state behind the new ids
+    def _prefill_prompt(self, vision_x, lang_x, attention_mask, max_new_tokens):
+        """The prompt stage of a generate() without a cache: splice plan, vision side, MMA prefill into a KV cache with room for the new
+        tokens.  Returns (cache, logits [B, V'] of each sample's last real token, None) - the triple of _continue_from_cache, whose third
+        item is None because no caller's cache was appended to."""
+        plan = self._start_splice_plan(lang_x)
+        vision_tokens = self.vision_tokenizer(self._encode_vision_x(vision_x=vision_x))
+        new_inputs = self._prepare_inputs_for_forward(vision_tokens=vision_tokens, lang_x=lang_x, attention_mask=attention_mask,
+                                                      padding_side="right", splice_plan=plan)
+        L = new_inputs["inputs_embeds"].shape[1]
+        out = self.lang_model(inputs_embeds=new_inputs["inputs_embeds"], attention_mask=new_inputs["attention_mask"], use_cache=True,
+                              cache_capacity=L + max_new_tokens, last_token_logits=True)
+        return out.past_key_values, out.logits[:, 0], None
+
+    def _expand_rows(self, cache, logits, n_ret: int, max_new_tokens: int):
+        """num_return_sequences = N continuations per sample behind one prefill: row b * N + j continues sample b (HF order), so the device
+        sampler's row index is b * N + j.  Returns the logits at B * N rows: token 0 of every row is drawn from its sample's prefill logits.
+        The prompt's K/V rows are replicated N times (select_rows) unless `lang_model.share_prompt_kv = True`, with which the N rows of a
+        sample read ONE copy of them (AkiKVCache.share_prefix + ops.decode_attn_group) where a grouped cache is possible: a bf16 model and
+        cache, head_dim 96, more than one new token - anything else stays replicated."""
+        B = logits.shape[0]
+        logits = logits.repeat_interleave(n_ret, dim=0)
+        if getattr(self.lang_model, "share_prompt_kv", False) and max_new_tokens > 1 and AkiKVCache.can_share_prefix(cache):
+            cache.share_prefix(n_ret)
         else:
-            if vision_x is None:
-                raise NotImplementedError("text-only generation is outside the AKI hot path")
-            plan = self._start_splice_plan(lang_x)
-            vision_tokens = self.vision_tokenizer(self._encode_vision_x(vision_x=vision_x))
-            new_inputs = self._prepare_inputs_for_forward(vision_tokens=vision_tokens, lang_x=lang_x, attention_mask=attention_mask,
-                                                          padding_side="right", splice_plan=plan)
-            table = new_inputs["attention_mask"]
-            L = new_inputs["inputs_embeds"].shape[1]
-            out = self.lang_model(inputs_embeds=new_inputs["inputs_embeds"], attention_mask=table, use_cache=True,
-                                  cache_capacity=L + max_new_tokens, last_token_logits=True)
-            cache = out.past_key_values
-            B = lang_x.shape[0]
-            logits = out.logits[:, 0]                                                  # logits of each sample's last real token
-        proc = ops.LogitsProcessors(logits.shape[-1], logits.device, pk["repetition_penalty"], pk["no_repeat_ngram_size"],
-                                    max(int(pk["min_length"]), int(pk["min_new_tokens"])), sorted(eos_ids), pk["suppress_tokens"],
-                                    pk["begin_suppress_tokens"], pk["bad_words_ids"])
-        proc = proc if proc.active else None       # no processor: exactly the launches of a plain generate
-        if num_beams > 1:
-            if self._device_beam_search_ok(cache, logits, num_beams, eos_ids):
-                tokens = self._beam_search_device(cache, logits, num_beams, max_new_tokens, eos_ids, pad_id, length_penalty, early_stopping,
-                                                  proc, use_graph)
-            else:
-                tokens = self._beam_search(cache, logits, num_beams, max_new_tokens, eos_ids, pad_id, length_penalty, early_stopping, proc)
-            self._post_forward_hook()
-            return tokens
-        if n_ret > 1:
-            # N continuations per sample: one prefill, then row b * N + j continues sample b.  Token 0 of every row is drawn from its
-            # sample's prefill logits; with lang_model.share_prompt_kv = True the rows of a sample read ONE copy of its prompt K/V where a
-            # grouped cache is possible (a bf16 model and cache, head_dim 96), otherwise the prompt rows are replicated.
-            from .phi3 import AkiKVCache
-            logits = logits.repeat_interleave(n_ret, dim=0)
-            if getattr(self.lang_model, "share_prompt_kv", False) and max_new_tokens > 1 and AkiKVCache.can_share_prefix(cache):
-                cache.share_prefix(n_ret)
-            else:
-                cache.select_rows(torch.arange(B, device=logits.device).repeat_interleave(n_ret))
-            B = B * n_ret
-        tokens = torch.full((B, max_new_tokens), pad_id, dtype=torch.long, device=lang_x.device)
-        done = torch.zeros(B, dtype=torch.bool, device=lang_x.device)
-        eos_t = torch.tensor(sorted(eos_ids), dtype=torch.long, device=lang_x.device) if eos_ids else None
-        lm = self.lang_model
-        # The one-launch decode chain (one sequence, decode_chain.hip) bounds every dependency wait; a wait that gives up leaves garbage in that
-        # step's output and a sticky error word.  Both loops below read the word wherever they synchronise anyway (every 8th token) and once at the
-        # end; on an error the tokens after the last verified point are decoded again on the five-launch-per-layer path: nothing unverified is
-        # ever returned (lm.decode_verified switches the chain off for this cache and warns).
+            cache.select_rows(torch.arange(B, device=logits.device).repeat_interleave(n_ret))
+        return logits
+
+    # The one-launch decode chain (one sequence, decode_chain.hip) bounds every dependency wait; a wait that gives up leaves garbage in that
+    # step's output and a sticky error word.  Both decode loops below read the word wherever they synchronise anyway (every 8th token) and once
+    # at the end; on an error the tokens after the last verified point are decoded again on the five-launch-per-layer path: nothing unverified
+    # is ever returned (lm.decode_verified switches the chain off for this cache and warns).
+
+    def _decode_on_device(self, opt: GenerateOptions, cache, logits, proc, eos_t):
+        """The pick loop on the device: greedy, or sampling on the device (ops.sample_pick in the pick's place: the same loop, the same three
+        launches per token; draws that depend on (seed, call, token index, row) and not on the batch).  The pick (argmax, pad for finished
+        rows, append, eos check, cache_len advance, the next step's embedding row) is one launch behind the decode step (inside the replayed
+        graph where there is one); the host looks at the finished flags every 8th token instead of syncing per token.  Until that look
+        ops.greedy_pick / ops.sample_pick feed a finished row pad tokens and advance its cache_len like any other, so pad-token rows land
+        behind the EOS in the cache (_trim_cache_to_returned cuts them off for a caller who keeps the cache).
+        logits [B, V'] bf16 on the GPU: the prompt stage's; proc: the active ops.LogitsProcessors or None; eos_t: the eos ids as an int64
+        tensor or None.  Returns the new tokens [B, <= max_new_tokens], cut behind the last row's EOS where every row hit one."""
+        lm, dev, B, max_new_tokens, pad_id = self.lang_model, logits.device, logits.shape[0], opt.max_new_tokens, opt.pad_id
+        tokens = torch.full((B, max_new_tokens), pad_id, dtype=torch.long, device=dev)
         chained = lambda: getattr(cache, "chain", None) is not None
         stepper = None
-        on_device = logits.is_cuda and logits.dtype == torch.bfloat16
-        if device_rng is not None and not on_device:
-            raise ValueError("the device sampler needs bf16 logits on the GPU")
-        sampler = None                              # ops.sample_pick's own arguments: one offset per generate call
-        if device_rng is not None:
-            sampler = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=device_rng.seed, offset=device_rng.next_offset())
-        if use_graph and (not do_sample or sampler is not None) and on_device:
-            # Greedy, or sampling on the device (ops.sample_pick in the pick's place: the same loop, the same three launches per token).
-            # The pick (argmax, pad for finished rows, append, eos check, cache_len advance, the next step's embedding row) is one launch
-            # behind the decode step (inside the replayed graph where there is one); the host looks at the finished flags every 8th token
-            # instead of syncing per token.
-            from . import ops
-            from .phi3 import DecodeGraph
-            done8 = torch.zeros(B, dtype=torch.uint8, device=lang_x.device)
-            done_at = torch.full((B,), -1, dtype=torch.int32, device=lang_x.device)
-            start_len, host_len0 = cache.cache_len.clone(), cache.host_len
-            pick = dict(pad_token_id=pad_id, eos_ids=eos_t, done=done8, tokens=tokens, start_len=start_len, done_at=done_at)
-            pick_op = ops.greedy_pick
-            if sampler is not None:
-                pick.update(sampler)
-                pick_op = ops.sample_pick
-            if proc is not None:                    # the processors read tokens[:, :t] and t from cache_len: replays and rewinds stay right
-                pick["processors"] = proc
-            ids = torch.zeros(B, dtype=torch.long, device=lang_x.device)
-            emb_mod = lm.get_input_embeddings()
-            embed = _embedding_tables(emb_mod, logits)
-            nxt_emb = None if embed is None else torch.empty((B, emb_mod.weight.shape[1]), dtype=torch.bfloat16, device=lang_x.device)
-            pick_e = pick if embed is None else dict(pick, embed=embed, next_embeds=nxt_emb)
-            pick_op(logits.contiguous(), ids, cache_len=cache.cache_len, advance=False, **pick_e)      # token 0, from the prefill
-            t, t_ok = 1, 1                                  # tokens[:, :t_ok] are verified (token 0 comes from the prefill, not from the chain)
-            period = 8 if eos_t is not None else 32         # host synchronisations: the EOS check needs them often, the chain's verification alone does not
-            while True:
-                ok = True
-                while t < max_new_tokens:
-                    if t % period == 0 and (eos_t is not None or chained()):
-                        if chained() and not lm.decode_verified(cache):
-                            ok = False
-                            break
-                        t_ok = t
-                        if eos_t is not None and bool(done8.all()):
-                            break
-                    if stepper is not None:
-                        stepper.step_greedy()
+        done8 = torch.zeros(B, dtype=torch.uint8, device=dev)
+        done_at = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        start_len, host_len0 = cache.cache_len.clone(), cache.host_len
+        pick = dict(pad_token_id=pad_id, eos_ids=eos_t, done=done8, tokens=tokens, start_len=start_len, done_at=done_at)
+        pick_op = ops.greedy_pick
+        sampler = _device_sampler_args(opt)
+        if sampler is not None:
+            pick.update(sampler)
+            pick_op = ops.sample_pick
+        if proc is not None:                    # the processors read tokens[:, :t] and t from cache_len: replays and rewinds stay right
+            pick["processors"] = proc
+        ids = torch.zeros(B, dtype=torch.long, device=dev)
+        emb_mod = lm.get_input_embeddings()
+        embed = _embedding_tables(emb_mod, logits)
+        nxt_emb = None if embed is None else torch.empty((B, emb_mod.weight.shape[1]), dtype=torch.bfloat16, device=dev)
+        pick_e = pick if embed is None else dict(pick, embed=embed, next_embeds=nxt_emb)
+        pick_op(logits.contiguous(), ids, cache_len=cache.cache_len, advance=False, **pick_e)      # token 0, from the prefill
+        t, t_ok = 1, 1                                  # tokens[:, :t_ok] are verified (token 0 comes from the prefill, not from the chain)
+        period = 8 if eos_t is not None else 32         # host synchronisations: the EOS check needs them often, the chain's verification alone does not
+        while True:
+            ok = True
+            while t < max_new_tokens:
+                if t % period == 0 and (eos_t is not None or chained()):
+                    if chained() and not lm.decode_verified(cache):
+                        ok = False
+                        break
+                    t_ok = t
+                    if eos_t is not None and bool(done8.all()):
+                        break
+                if stepper is not None:
+                    stepper.step_greedy()
+                else:
+                    # One sequence on the one-launch decode chain is three launches per token (chain, head, pick + embedding):
+                    # the host runs far ahead of them and a hipGraph would only add its capture (about 12 ms per call, 7 tokens' worth).
+                    # Anything else - batches, the five-launch-per-layer path - is ~165 launches per token and is captured after its first
+                    # eager step.
+                    if nxt_emb is not None:
+                        lg = lm.decode_step(inputs_embeds=nxt_emb, past_key_values=cache, advance=False)
                     else:
-                        # One sequence on the one-launch decode chain is three launches per token (chain, head, pick + embedding):
-                        # the host runs far ahead of them and a hipGraph would only add its capture (about 12 ms per call, 7 tokens' worth).
-                        # Anything else - batches, the five-launch-per-layer path - is ~165 launches per token and is captured after its first
-                        # eager step.
-                        if nxt_emb is not None:
-                            lg = lm.decode_step(inputs_embeds=nxt_emb, past_key_values=cache, advance=False)
-                        else:
-                            lg = lm.decode_step(input_ids=ids, past_key_values=cache, advance=False)
-                        pick_op(lg, ids, cache_len=cache.cache_len, advance=True, **pick_e)
-                        if not chained():
-                            stepper = DecodeGraph(lm, cache, greedy=pick)
-                            stepper.ids.copy_(ids)
-                    t += 1
-                if ok and chained() and not lm.decode_verified(cache):
-                    ok = False
-                if ok:
-                    break
-                # recovery: back to the last verified token, then on without the chain.  The finished flags are rebuilt from the verified tokens
-                # (a batch can hold rows that finished before that point; one sequence would have ended the loop there)
-                t = t_ok
-                cache.cache_len.copy_(start_len + (t_ok - 1))
-                cache.host_len = host_len0 + (t_ok - 1)
-                tokens[:, t_ok:] = pad_id
-                done8.zero_()
-                done_at.fill_(-1)
-                if eos_t is not None:
-                    hit = (tokens[:, :t_ok, None] == eos_t[None, None, :]).any(-1)
-                    fin = hit.any(1)
-                    done8.copy_(fin.to(torch.uint8))
-                    done_at.copy_(torch.where(fin, hit.to(torch.int32).argmax(1).to(torch.int32), torch.full_like(done_at, -1)))
-                ids.copy_(tokens[:, t_ok - 1])
-                if nxt_emb is not None:
-                    nxt_emb.copy_(emb_mod(ids))
-            steps = t
-            if eos_t is not None and bool(done8.all()):
-                steps = int(done_at.max()) + 1
-            if past_key_values is not None:
-                self._trim_cache_to_returned(cache, *appended, tokens[:, :steps], eos_t)
-            self._post_forward_hook()
-            return tokens[:, :steps]
-        if use_graph:
-            from .phi3 import DecodeGraph
-            stepper = DecodeGraph(lm, cache)
+                        lg = lm.decode_step(input_ids=ids, past_key_values=cache, advance=False)
+                    pick_op(lg, ids, cache_len=cache.cache_len, advance=True, **pick_e)
+                    if not chained():
+                        stepper = DecodeGraph(lm, cache, greedy=pick)
+                        stepper.ids.copy_(ids)
+                t += 1
+            if ok and chained() and not lm.decode_verified(cache):
+                ok = False
+            if ok:
+                break
+            # recovery: back to the last verified token, then on without the chain.  The finished flags are rebuilt from the verified tokens
+            # (a batch can hold rows that finished before that point; one sequence would have ended the loop there)
+            t = t_ok
+            cache.cache_len.copy_(start_len + (t_ok - 1))
+            cache.host_len = host_len0 + (t_ok - 1)
+            tokens[:, t_ok:] = pad_id
+            done8.zero_()
+            done_at.fill_(-1)
+            if eos_t is not None:
+                finished, first = _first_eos(tokens[:, :t_ok], eos_t)
+                done8.copy_(finished.to(torch.uint8))
+                done_at.copy_(torch.where(finished, first.to(torch.int32), torch.full_like(done_at, -1)))
+            ids.copy_(tokens[:, t_ok - 1])
+            if nxt_emb is not None:
+                nxt_emb.copy_(emb_mod(ids))
+        if eos_t is not None and bool(done8.all()):
+            return tokens[:, :int(done_at.max()) + 1]
+        return tokens[:, :t]
+
+    def _decode_on_host(self, opt: GenerateOptions, cache, logits, proc, eos_t):
+        """The loop that picks on the host, one synchronisation per token where there is an EOS id: `sample_next` sampling (generator None or
+        a torch.Generator), the device sampler outside a graph, and greedy where the device loop does not apply (f32, use_graph=False).  The
+        decode step is replayed from a DecodeGraph with use_graph.  A finished row of a batch is stepped on with pad tokens until every row
+        has finished.  Arguments as _decode_on_device; returns the new tokens [B, <= max_new_tokens], cut where every row has finished."""
+        lm, B, max_new_tokens, pad_id = self.lang_model, logits.shape[0], opt.max_new_tokens, opt.pad_id
+        do_sample, temperature, top_k, top_p, rng = opt.do_sample, opt.temperature, opt.top_k, opt.top_p, opt.rng
+        tokens = torch.full((B, max_new_tokens), pad_id, dtype=torch.long, device=logits.device)
+        done = torch.zeros(B, dtype=torch.bool, device=logits.device)
+        chained = lambda: getattr(cache, "chain", None) is not None
+        sampler = _device_sampler_args(opt)
+        stepper = DecodeGraph(lm, cache) if opt.use_graph else None
         t, n_out = 0, max_new_tokens
         ck = None                                           # the state at the last verified point of a chained decode
         while True:
@@ -578,9 +548,87 @@ class AKI(VLMWithLanguageStream):
             cache.cache_len.copy_(cl)
             tokens[:, t:] = pad_id
             n_out, stepper = max_new_tokens, None           # a graph captured around the chain is gone with it
-            if use_graph:
+            if opt.use_graph:
                 stepper = DecodeGraph(lm, cache)
-        if past_key_values is not None:
-            self._trim_cache_to_returned(cache, *appended, tokens[:, :n_out], eos_t)
-        self._post_forward_hook()
         return tokens[:, :n_out]
+
+    @torch.no_grad()
+    def generate(self, vision_x, lang_x, image_size=None, attention_mask=None, past_key_values=None,
+                 past_media_locations=None, past_vision_tokens=None, **kwargs):
+        """Generation (src/aki.py:136-209 + src/aki_generation.py:36-86; local_demo.py / eval.py call it with do_sample=False): MMA prefill
+        into a KV cache, then one HIP decode step per token.
+
+        Arguments: `vision_x` (B, T_img, F=1, C, H, W) and `lang_x` [B, T_txt] with <image> placeholders, `attention_mask` [B, T_txt], as
+        for forward; the HF keyword arguments the reference forwards (`**kwargs`, src/aki.py:160-207): `max_new_tokens` (or `max_length`;
+        20), `eos_token_id` (default: default_eos_token_ids(); [] switches stopping off), `pad_token_id`, `use_graph` (replay the decode step
+        from a hipGraph; default: from 8 new tokens on) and the ones below.  Any other keyword raises ValueError (_parse_generate_kwargs).
+        Modes:
+          * greedy (default).
+          * sampling: `do_sample=True` with `temperature`, `top_k`, `top_p` and an optional `generator`.  An `aki_amd.DeviceGenerator(seed)`
+            there selects the device sampler (ops.sample_pick; bf16 on the GPU), None or a `torch.Generator` the `sample_next` path.
+          * `num_return_sequences=N` with sampling: N continuations per sample, [B*N, <= max_new_tokens] in HF order (row b*N + j is
+            continuation j of sample b) behind one prefill (_expand_rows).  ValueError without sampling, NotImplementedError with beams.
+          * beam search: `num_beams=K`, `length_penalty`, `early_stopping`; one returned sequence per sample.  `lang_model.device_beam_search
+            = True` runs the search on the device (_beam_search_device) where it can; the host loop (_beam_search) is used otherwise and by
+            default: the device path's step time has not been measured yet.
+          * logits processors, in every mode, on the device and in HF's order (ops.LogitsProcessors): `repetition_penalty`,
+            `no_repeat_ngram_size`, `bad_words_ids`, `min_length` / `min_new_tokens` (eos ids banned until that many tokens are generated),
+            `suppress_tokens`, `begin_suppress_tokens`.  As in HF `generate` with inputs_embeds only, they see the generated tokens, never
+            the prompt; beam search applies them to each beam's log-softmax scores.
+          * `past_key_values=cache` (the AkiKVCache of a use_cache=True forward or of an earlier turn; `vision_x` must be None) continues
+            from the cache instead of a prefill: `lang_x` [B, T] holds the NEW ids only and `attention_mask`, if given, spans past + new ids
+            (_continue_from_cache).  Greedy and sampling only: beam search and N > 1 from a cache raise NotImplementedError.
+        Returns, like HF `generate` called with `inputs_embeds` only, just the NEW tokens [B, <= max_new_tokens]; finished rows are padded
+        with pad_token_id.
+        After a call from a cache the LAST returned token of a row - its EOS where it hit one, else the last column - is not in the cache,
+        so the next turn's `lang_x` must begin with it: on return cache_len[b] = its value before the call + n_new[b] + (tokens returned
+        for row b) - 1, at B = 1 and per row in a batch - there the next turn's chunk is ragged (chunked_continue).  The cache must have
+        room for T + max_new_tokens - 1 more rows (AkiError before any launch otherwise).
+        Differences from the reference, both only visible for B > 1 (where the reference is inconsistent, SURVEY 3.5): the
+        prompt batch is right-padded and every sample continues from its own length."""
+        opt = _parse_generate_kwargs(kwargs, self.pad_token_id, self.default_eos_token_ids, past_key_values is not None)
+        if past_key_values is not None:
+            cache, logits, appended = self._continue_from_cache(vision_x, lang_x, attention_mask, past_key_values, opt.max_new_tokens)
+        elif vision_x is None:
+            raise NotImplementedError("text-only generation is outside the AKI hot path")
+        else:
+            cache, logits, appended = self._prefill_prompt(vision_x, lang_x, attention_mask, opt.max_new_tokens)
+        pk = opt.processors
+        proc = ops.LogitsProcessors(logits.shape[-1], logits.device, pk["repetition_penalty"], pk["no_repeat_ngram_size"],
+                                    max(int(pk["min_length"]), int(pk["min_new_tokens"])), sorted(opt.eos_ids), pk["suppress_tokens"],
+                                    pk["begin_suppress_tokens"], pk["bad_words_ids"])
+        proc = proc if proc.active else None       # no processor: exactly the launches of a plain generate
+        if opt.num_beams > 1:
+            beam = (opt.num_beams, opt.max_new_tokens, opt.eos_ids, opt.pad_id, opt.length_penalty, opt.early_stopping, proc)
+            if self._device_beam_search_ok(cache, logits, opt.num_beams, opt.eos_ids):
+                tokens = self._beam_search_device(cache, logits, *beam, opt.use_graph)
+            else:
+                tokens = self._beam_search(cache, logits, *beam)
+        else:
+            if opt.n_ret > 1:
+                logits = self._expand_rows(cache, logits, opt.n_ret, opt.max_new_tokens)
+            eos_t = torch.tensor(sorted(opt.eos_ids), dtype=torch.long, device=logits.device) if opt.eos_ids else None
+            on_device = logits.is_cuda and logits.dtype == torch.bfloat16
+            if opt.device_rng is not None and not on_device:
+                raise ValueError("the device sampler needs bf16 logits on the GPU")
+            if opt.use_graph and (not opt.do_sample or opt.device_rng is not None) and on_device:
+                tokens = self._decode_on_device(opt, cache, logits, proc, eos_t)
+            else:
+                tokens = self._decode_on_host(opt, cache, logits, proc, eos_t)
+            if appended is not None:               # the caller's cache: every row ends right before its last returned token
+                self._trim_cache_to_returned(cache, *appended, tokens, eos_t)
+        self._post_forward_hook()
+        return tokens
+
+
+class AKI(AkiMethods, VLMWithLanguageStream):
+    def __init__(self, vision_encoder: nn.Module, lang_model: nn.Module, vis_feature_dim: int, initial_tokenizer_len: int,
+                 pad_token_id: int, decoder_layers_attr_name: str = None, gradient_checkpointing: bool = False,
+                 base_img_size: Optional[int] = None, num_vision_tokens: int = 144):
+        self._special_tokens = {"media_token": "<image>", "end_of_trunk_token": "<|endofchunk|>"}
+        lang_embedding_dim = lang_model.get_input_embeddings().weight.shape[1]
+        super().__init__(
+            vision_encoder=vision_encoder,
+            vision_tokenizer=PerceiverResampler(dim=vis_feature_dim, dim_inner=lang_embedding_dim, num_latents=num_vision_tokens),
+            lang_model=lang_model, initial_tokenizer_len=initial_tokenizer_len, gradient_checkpointing=gradient_checkpointing,
+            base_img_size=base_img_size, decoder_layers_attr_name=decoder_layers_attr_name, pad_token_id=pad_token_id)

@@ -13,10 +13,9 @@ from __future__ import annotations
 
 from typing import Optional
 
-import torch
 from huggingface_hub import PyTorchModelHubMixin
 
-from .aki import AKI as _TrainTimeAKI
+from .aki import AkiMethods
 from .helpers import PerceiverResampler
 from .phi3 import Phi3ForCausalLM
 from .siglip import SiglipVisionTransformer
@@ -43,7 +42,10 @@ def native_language_model(lang_model_path: str, **hf_kwargs) -> Phi3ForCausalLM:
     return lm
 
 
-class AKI(VLMWithLanguageStream, PyTorchModelHubMixin):
+class AKI(AkiMethods, VLMWithLanguageStream, PyTorchModelHubMixin):
+    """forward, generate and every helper are the train-time class's (aki.AkiMethods; src/modeling_aki.py:83-226 is identical to
+    src/aki.py:65-209): only the constructor differs."""
+
     def __init__(self, vision_encoder_path: str, lang_model_path: str, pad_token_id: int, initial_tokenizer_len: Optional[int] = None,
                  tokenizer=None, decoder_layers_attr_name: str = None, gradient_checkpointing: bool = False,
                  base_img_size: Optional[int] = None, num_vision_tokens: int = 144):
@@ -62,10 +64,3 @@ class AKI(VLMWithLanguageStream, PyTorchModelHubMixin):
         if tokenizer is not None:
             self.lang_model.config.vocab_size = len(tokenizer)
             self.set_special_token_ids({v: tokenizer.convert_tokens_to_ids(v) for v in self.special_tokens.values()})
-
-    set_trainable = _TrainTimeAKI.set_trainable
-    default_eos_token_ids = _TrainTimeAKI.default_eos_token_ids
-    _should_apply_weight_decay = _TrainTimeAKI._should_apply_weight_decay
-    forward = _TrainTimeAKI.forward          # src/modeling_aki.py:83-151 is identical to src/aki.py:65-134
-    generate = _TrainTimeAKI.generate        # MMA prefill + HIP decode steps (aki_amd/aki.py)
-    _beam_search = _TrainTimeAKI._beam_search

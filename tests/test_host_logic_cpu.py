@@ -79,3 +79,13 @@ def test_activation_checkpointing_switch_recomputes_and_keeps_names():
     with torch.no_grad():                                    # inference goes straight through
         blk(x)
     assert blk.calls == 1
+
+
+def test_hub_twin_shares_every_attribute_of_the_train_time_class():
+    """The two model classes differ in their constructors only: whatever the train-time class has - methods, helpers, class-level defaults,
+    inherited or its own - the HF-Hub twin has as the identical object.  No list of names: a method added to one reaches the other."""
+    from aki_amd import aki, modeling_aki
+    names = [n for n in dir(aki.AKI) if not n.startswith("__")]
+    assert "generate" in names and "forward" in names
+    different = [n for n in names if getattr(modeling_aki.AKI, n, None) is not getattr(aki.AKI, n)]
+    assert not different, different

@@ -67,3 +67,76 @@ def test_natively_loaded_modules_match_transformers(tmp_path):
         vt = native_vision_tower(pv).to("cuda").eval()
         gotv = vt(px.cuda()).last_hidden_state.cpu()
         assert (gotv - wantv).abs().max().item() <= 1e-5 * max(1.0, wantv.abs().max().item())
+
+
+@pytest.fixture(scope="module")
+def both_classes(tmp_path_factory):
+    """(HF-Hub twin, train-time class) over the same weights: the twin from the tiny checkpoints, the train-time class from fresh native modules
+    on the same paths with the twin's state loaded.  bf16 on the GPU (the tiny head dimension, 96, is the full model's), eval()."""
+    from aki_amd import aki, modeling_aki
+    T = gen.TINY
+    _, _, pv, pl = _tiny_checkpoints(str(tmp_path_factory.mktemp("ckpt")))
+    twin = modeling_aki.AKI(pv, pl, pad_token_id=T["pad_token_id"], initial_tokenizer_len=T["vocab"], num_vision_tokens=T["num_vision_tokens"])
+    vt = modeling_aki.native_vision_tower(pv)
+    train = aki.AKI(vt, modeling_aki.native_language_model(pl), vis_feature_dim=vt.config.hidden_size, initial_tokenizer_len=T["vocab"],
+                    pad_token_id=T["pad_token_id"], decoder_layers_attr_name="model.layers", num_vision_tokens=T["num_vision_tokens"])
+    train.load_state_dict(twin.state_dict(), strict=True)
+    for m in (twin, train):
+        m.set_special_token_ids({"<image>": T["media_token_id"], "<|endofchunk|>": T["eoc_token_id"]})
+        m.to(device="cuda", dtype=torch.bfloat16).eval()
+    return twin, train
+
+
+def _two_prompts():
+    """Two samples, one image each, 12 prompt ids with one <image>; the second row is right-padded by three."""
+    T = gen.TINY
+    g = torch.Generator().manual_seed(5)
+    vx = torch.randn(2, 1, 1, 3, T["image"], T["image"], generator=g).to("cuda", torch.bfloat16)
+    lx = torch.randint(3, 31000, (2, 12), generator=g)
+    lx[:, 1] = T["media_token_id"]
+    am = torch.ones_like(lx)
+    lx[1, -3:], am[1, -3:] = T["pad_token_id"], 0
+    return vx, lx.cuda(), am.cuda()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_hub_twin_generates_the_train_time_tokens_greedy(both_classes, use_graph):
+    vx, lx, am = _two_prompts()
+    got, want = (m.generate(vx, lx, attention_mask=am, max_new_tokens=6, eos_token_id=[], use_graph=use_graph) for m in both_classes)
+    assert got.shape == (2, 6) and torch.equal(got, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("on_device", [False, True])
+def test_hub_twin_generates_the_train_time_tokens_beam_search(both_classes, on_device):
+    """num_beams=2 with the host loop and with lang_model.device_beam_search = True: the device path admits the tiny bf16 model (as
+    test_beam_gpu.py relies on), so the twin reports the scores of the rows it returns there."""
+    vx, lx, am = _two_prompts()
+    for m in both_classes:
+        m.lang_model.device_beam_search, m.last_beam_scores = on_device, None
+    try:
+        got, want = (m.generate(vx, lx, attention_mask=am, max_new_tokens=5, eos_token_id=[], num_beams=2) for m in both_classes)
+    finally:
+        for m in both_classes:
+            m.lang_model.device_beam_search = False
+    twin, train = both_classes
+    assert got.shape == (2, 5) and torch.equal(got, want)
+    assert (twin.last_beam_scores is not None) == on_device and twin.last_beam_scores == train.last_beam_scores
+
+
+@pytest.mark.gpu
+def test_hub_twin_continues_from_a_cache_like_the_train_time_class(both_classes):
+    """generate(past_key_values=cache): 3 new ids per row on top of a prefilled cache with spare capacity, then 4 greedy tokens."""
+    vx, lx, am = _two_prompts()
+    new_ids = torch.randint(3, 31000, (2, 3), generator=torch.Generator().manual_seed(6)).cuda()
+    outs, lens = [], []
+    with torch.no_grad():
+        for m in both_classes:
+            prep = m._prepare_inputs_for_forward(vision_tokens=m.vision_tokenizer(m._encode_vision_x(vx)), lang_x=lx, attention_mask=am,
+                                                 padding_side="right")
+            cache = m.lang_model(inputs_embeds=prep["inputs_embeds"], attention_mask=prep["attention_mask"], use_cache=True,
+                                 cache_capacity=prep["inputs_embeds"].shape[1] + 16, last_token_logits=True).past_key_values
+            outs.append(m.generate(None, new_ids, past_key_values=cache, max_new_tokens=4, eos_token_id=[]))
+            lens.append(cache.cache_len.clone())
+    assert outs[0].shape == (2, 4) and torch.equal(outs[0], outs[1]) and torch.equal(lens[0], lens[1])

@@ -7,7 +7,8 @@ libaki_mi355x.so (hand-written HIP); see include/aki_mi355x.h for the C ABI.
 from ._lib import AkiError  # noqa: F401
 
 _LAZY = {"AKI": ("aki", "AKI"), "create_model_and_transforms": ("factory", "create_model_and_transforms"),
-         "build_aki": ("factory", "build_aki"), "AKIPretrained": ("modeling_aki", "AKI"), "DeviceGenerator": ("ops", "DeviceGenerator")}
+         "build_aki": ("factory", "build_aki"), "AKIPretrained": ("modeling_aki", "AKI"), "DeviceGenerator": ("ops", "DeviceGenerator"),
+         "AkiGenerateOutput": ("aki", "AkiGenerateOutput"), "AkiScoreOutput": ("aki", "AkiScoreOutput")}
 
 
 def __getattr__(name):  # lazy: `import aki_amd` alone must not pull torch (tooling, build script)

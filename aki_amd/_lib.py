@@ -19,6 +19,7 @@ AKI_PLAN_STRIDE = 12
 AKI_ABI_VERSION = 17
 AKI_LOGITS_PROCESS_MAX_V = 131072
 AKI_BEAM_MAX_K, AKI_BEAM_MAX_EOS, AKI_KV_BEAM_REORDER_CHUNK = 16, 8, 16
+AKI_LOGPROB_MAX_TOP, AKI_LOGPROB_MAX_V = 8, 262144
 
 
 class AkiError(RuntimeError):
@@ -240,6 +241,9 @@ SIGNATURES = {
     "aki_beam_step": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 11 + [C.c_int32, C.c_int64, C.c_float, C.c_int32,
                                                                                                 C.c_int32, C.c_void_p]),
     "aki_kv_beam_reorder": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p]),
+    "aki_token_logprob": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_int32, C.c_void_p]),
     "aki_sft_collate_pad": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 4),
     "aki_mma_mask_to_table_workspace_bytes": (C.c_size_t, [C.c_int32] * 2),
     "aki_mma_mask_to_table": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),

@@ -6,10 +6,16 @@ Reference: /root/reference/codes/open_flamingo/src/aki.py  (__init__ :10-50, set
 from __future__ import annotations
 
 from collections import namedtuple
+from dataclasses import dataclass
 from typing import List, Optional, Tuple, Union
 
 import torch
 from torch import nn
+
+try:  # the HF container generate's structured outputs subclass
+    from transformers.utils import ModelOutput
+except Exception:  # pragma: no cover - transformers is present in this image
+    ModelOutput = object
 
 from . import ops
 from .helpers import PerceiverResampler
@@ -75,9 +81,57 @@ def _embedding_tables(emb: nn.Module, logits: torch.Tensor):
 
 # The keyword arguments of `generate`, resolved and validated by _parse_generate_kwargs.  rng: None or a torch.Generator (sample_next) or an
 # ops.DeviceGenerator, which device_rng repeats (else None: no device sampler); n_ret: num_return_sequences; eos_ids: a set; processors:
-# the logits-processor keywords (PROCESSOR_KWARGS) with None read as the neutral value.
+# the logits-processor keywords (PROCESSOR_KWARGS) with None read as the neutral value; output_logprobs / top_logprobs: the per-token
+# log-probabilities of the returned tokens and that many alternatives (ops.token_logprob).
 GenerateOptions = namedtuple("GenerateOptions", "num_beams do_sample temperature top_k top_p rng device_rng length_penalty early_stopping "
-                                                "n_ret max_new_tokens eos_ids pad_id use_graph processors")
+                                                "n_ret max_new_tokens eos_ids pad_id use_graph processors output_logprobs top_logprobs")
+
+
+@dataclass
+class AkiGenerateOutput(ModelOutput):
+    """What `generate(..., output_logprobs=True)` returns.  sequences: what generate returns without the keyword, int64 [rows, steps];
+    logprobs f32 [rows, steps]: the log-probability of every returned token under the raw model distribution of its step; top_token_ids
+    int64 [rows, steps, k] and top_logprobs f32 [rows, steps, k]: the k most likely tokens of each step and theirs (None for k = 0).
+    Positions behind a row's EOS hold 0.0, -1 and 0.0.  All on the device."""
+    sequences: Optional[torch.Tensor] = None
+    logprobs: Optional[torch.Tensor] = None
+    top_token_ids: Optional[torch.Tensor] = None
+    top_logprobs: Optional[torch.Tensor] = None
+
+
+@dataclass
+class AkiScoreOutput(ModelOutput):
+    """What `score` returns.  logprobs f32 [B, N, T]: the teacher-forced log-probability of every continuation token, zero behind each
+    length; sum_logprobs f32 [B, N]; lengths int64 [B, N]; top_token_ids int64 [B, N, T, k] and top_logprobs f32 [B, N, T, k] as in
+    AkiGenerateOutput (None for k = 0; -1 and 0.0 behind each length).  All on the device."""
+    logprobs: Optional[torch.Tensor] = None
+    sum_logprobs: Optional[torch.Tensor] = None
+    lengths: Optional[torch.Tensor] = None
+    top_token_ids: Optional[torch.Tensor] = None
+    top_logprobs: Optional[torch.Tensor] = None
+
+
+class _LogprobBuffers:
+    """The outputs of ops.token_logprob for one decode loop, pre-filled with the skipped values: lp f32 [rows, steps], and for k > 0
+    top_ids int64 [rows, steps, k] and top_lp f32 [rows, steps, k] (else None)."""
+
+    def __init__(self, rows: int, steps: int, k: int, device):
+        self.k = k
+        self.lp = torch.zeros((rows, steps), dtype=torch.float32, device=device)
+        self.top_ids = torch.full((rows, steps, k), -1, dtype=torch.int64, device=device) if k else None
+        self.top_lp = torch.zeros((rows, steps, k), dtype=torch.float32, device=device) if k else None
+
+    def args(self) -> dict:
+        return dict(top_k=self.k, out_logprob=self.lp, out_top_ids=self.top_ids, out_top_logprobs=self.top_lp)
+
+    def reset_from(self, t: int):
+        self.lp[:, t:] = 0.0
+        if self.k:
+            self.top_ids[:, t:] = -1
+            self.top_lp[:, t:] = 0.0
+
+    def cut(self, n: int):
+        return self.lp[:, :n], (self.top_ids[:, :n] if self.k else None), (self.top_lp[:, :n] if self.k else None)
 
 
 def _parse_generate_kwargs(kwargs: dict, default_pad_id, default_eos_ids, from_cache: bool) -> GenerateOptions:
@@ -124,10 +178,19 @@ def _parse_generate_kwargs(kwargs: dict, default_pad_id, default_eos_ids, from_c
     if use_graph is None:
         use_graph = max_new_tokens >= 8          # capture costs about two eager steps
     processors = _pop_processor_kwargs(kwargs)
+    output_logprobs = bool(kwargs.pop("output_logprobs", False))
+    top_logprobs = int(kwargs.pop("top_logprobs", 0) or 0)
+    if top_logprobs and not output_logprobs:
+        raise ValueError("top_logprobs needs output_logprobs=True")
+    if not 0 <= top_logprobs <= ops.LOGPROB_MAX_TOP:
+        raise ValueError(f"top_logprobs must be in 0..{ops.LOGPROB_MAX_TOP}")
+    if output_logprobs and num_beams > 1:
+        raise NotImplementedError("output_logprobs with num_beams > 1: beam search keeps last_beam_scores")
     _reject_unused_kwargs(kwargs)
     return GenerateOptions(num_beams=num_beams, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, rng=rng,
                            device_rng=device_rng, length_penalty=length_penalty, early_stopping=early_stopping, n_ret=n_ret,
-                           max_new_tokens=max_new_tokens, eos_ids=eos_ids, pad_id=pad_id, use_graph=use_graph, processors=processors)
+                           max_new_tokens=max_new_tokens, eos_ids=eos_ids, pad_id=pad_id, use_graph=use_graph, processors=processors,
+                           output_logprobs=output_logprobs, top_logprobs=top_logprobs)
 
 
 def _device_sampler_args(opt: GenerateOptions):
@@ -429,7 +492,8 @@ class AkiMethods:
         ops.greedy_pick / ops.sample_pick feed a finished row pad tokens and advance its cache_len like any other, so pad-token rows land
         behind the EOS in the cache (_trim_cache_to_returned cuts them off for a caller who keeps the cache).
         logits [B, V'] bf16 on the GPU: the prompt stage's; proc: the active ops.LogitsProcessors or None; eos_t: the eos ids as an int64
-        tensor or None.  Returns the new tokens [B, <= max_new_tokens], cut behind the last row's EOS where every row hit one."""
+        tensor or None.  Returns (the new tokens [B, <= max_new_tokens], cut behind the last row's EOS where every row hit one; the
+        _LogprobBuffers of opt.output_logprobs, uncut, else None)."""
         lm, dev, B, max_new_tokens, pad_id = self.lang_model, logits.device, logits.shape[0], opt.max_new_tokens, opt.pad_id
         tokens = torch.full((B, max_new_tokens), pad_id, dtype=torch.long, device=dev)
         chained = lambda: getattr(cache, "chain", None) is not None
@@ -450,7 +514,13 @@ class AkiMethods:
         embed = _embedding_tables(emb_mod, logits)
         nxt_emb = None if embed is None else torch.empty((B, emb_mod.weight.shape[1]), dtype=torch.bfloat16, device=dev)
         pick_e = pick if embed is None else dict(pick, embed=embed, next_embeds=nxt_emb)
-        pick_op(logits.contiguous(), ids, cache_len=cache.cache_len, advance=False, **pick_e)      # token 0, from the prefill
+        # output_logprobs: one ops.token_logprob behind each pick (in-loop form: it reads the index the pick just wrote from cache_len)
+        lpb = _LogprobBuffers(B, max_new_tokens, opt.top_logprobs, dev) if opt.output_logprobs else None
+        lp = None if lpb is None or max_new_tokens < 1 else dict(lpb.args(), tokens=tokens, cache_len=cache.cache_len, start_len=start_len, done_at=done_at)
+        logits = logits.contiguous()
+        pick_op(logits, ids, cache_len=cache.cache_len, advance=False, **pick_e)      # token 0, from the prefill
+        if lp is not None:
+            ops.token_logprob(logits, **lp)
         t, t_ok = 1, 1                                  # tokens[:, :t_ok] are verified (token 0 comes from the prefill, not from the chain)
         period = 8 if eos_t is not None else 32         # host synchronisations: the EOS check needs them often, the chain's verification alone does not
         while True:
@@ -475,8 +545,10 @@ class AkiMethods:
                     else:
                         lg = lm.decode_step(input_ids=ids, past_key_values=cache, advance=False)
                     pick_op(lg, ids, cache_len=cache.cache_len, advance=True, **pick_e)
+                    if lp is not None:
+                        ops.token_logprob(lg, **lp)
                     if not chained():
-                        stepper = DecodeGraph(lm, cache, greedy=pick)
+                        stepper = DecodeGraph(lm, cache, greedy=pick if lp is None else dict(pick, logprob=lp))
                         stepper.ids.copy_(ids)
                 t += 1
             if ok and chained() and not lm.decode_verified(cache):
@@ -489,6 +561,8 @@ class AkiMethods:
             cache.cache_len.copy_(start_len + (t_ok - 1))
             cache.host_len = host_len0 + (t_ok - 1)
             tokens[:, t_ok:] = pad_id
+            if lpb is not None:
+                lpb.reset_from(t_ok)
             done8.zero_()
             done_at.fill_(-1)
             if eos_t is not None:
@@ -499,14 +573,14 @@ class AkiMethods:
             if nxt_emb is not None:
                 nxt_emb.copy_(emb_mod(ids))
         if eos_t is not None and bool(done8.all()):
-            return tokens[:, :int(done_at.max()) + 1]
-        return tokens[:, :t]
+            return tokens[:, :int(done_at.max()) + 1], lpb
+        return tokens[:, :t], lpb
 
     def _decode_on_host(self, opt: GenerateOptions, cache, logits, proc, eos_t):
         """The loop that picks on the host, one synchronisation per token where there is an EOS id: `sample_next` sampling (generator None or
         a torch.Generator), the device sampler outside a graph, and greedy where the device loop does not apply (f32, use_graph=False).  The
         decode step is replayed from a DecodeGraph with use_graph.  A finished row of a batch is stepped on with pad tokens until every row
-        has finished.  Arguments as _decode_on_device; returns the new tokens [B, <= max_new_tokens], cut where every row has finished."""
+        has finished.  Arguments and return value as _decode_on_device; the tokens [B, <= max_new_tokens] are cut where every row has finished."""
         lm, B, max_new_tokens, pad_id = self.lang_model, logits.shape[0], opt.max_new_tokens, opt.pad_id
         do_sample, temperature, top_k, top_p, rng = opt.do_sample, opt.temperature, opt.top_k, opt.top_p, opt.rng
         tokens = torch.full((B, max_new_tokens), pad_id, dtype=torch.long, device=logits.device)
@@ -514,6 +588,7 @@ class AkiMethods:
         chained = lambda: getattr(cache, "chain", None) is not None
         sampler = _device_sampler_args(opt)
         stepper = DecodeGraph(lm, cache) if opt.use_graph else None
+        lpb = _LogprobBuffers(B, max_new_tokens, opt.top_logprobs, logits.device) if opt.output_logprobs else None
         t, n_out = 0, max_new_tokens
         ck = None                                           # the state at the last verified point of a chained decode
         while True:
@@ -532,6 +607,8 @@ class AkiMethods:
                     nxt = sample_next(x, temperature, top_k, top_p, rng) if do_sample else x.float().argmax(dim=-1)
                 nxt = torch.where(done, torch.full_like(nxt, pad_id), nxt)
                 tokens[:, t] = nxt
+                if lpb is not None:                 # the raw logits of this step, at the token returned; rows finished before it are skipped
+                    ops.token_logprob(logits, ids=nxt, skip=done.to(torch.uint8), step=t, **lpb.args())
                 t += 1
                 if eos_t is not None:
                     done = done | (nxt[:, None] == eos_t[None, :]).any(-1)
@@ -547,10 +624,77 @@ class AkiMethods:
             t, logits, done, cl, cache.host_len = ck
             cache.cache_len.copy_(cl)
             tokens[:, t:] = pad_id
+            if lpb is not None:
+                lpb.reset_from(t)
             n_out, stepper = max_new_tokens, None           # a graph captured around the chain is gone with it
             if opt.use_graph:
                 stepper = DecodeGraph(lm, cache)
-        return tokens[:, :n_out]
+        return tokens[:, :n_out], lpb
+
+    @torch.no_grad()
+    def score(self, vision_x, lang_x, continuations, attention_mask=None, continuation_lengths=None, top_logprobs: int = 0,
+              use_graph: Optional[bool] = None):
+        """The teacher-forced log-likelihood of N given continuations per prompt behind ONE prefill - the counterpart of
+        `num_return_sequences`, and what a multiple-choice eval ranks its answers by.  vision_x / lang_x / attention_mask: the prompt batch,
+        as for generate; continuations int64 [B, N, T]; continuation_lengths [B, N] with values in 1..T (default: all T);
+        top_logprobs = k <= ops.LOGPROB_MAX_TOP alternatives per position; use_graph: replay the decode steps from a hipGraph (default:
+        from T = 8 on, generate's rule).  Returns an AkiScoreOutput: logprobs [B, N, T] with logprobs[b, n, t] = log p(continuations[b, n, t]
+        | prompt b, continuations[b, n, :t]) under the raw model distribution (the f32 log-softmax of the step's logits, as
+        generate(output_logprobs=True) reports it), zero behind each length; sum_logprobs [B, N]; lengths; the top-k pair.
+        Column 0 is scored from the prefill's logits; step t = 1 .. T - 1 feeds continuations[..., t - 1] to one decode step over the
+        B * N rows (_expand_rows: replicated prompt rows, or one shared copy under lang_model.share_prompt_kv) and its logits score
+        continuations[..., t].  A row past its length is fed pad_token_id and writes zeros, the way the decode loops treat finished rows.
+        Shapes and lengths are checked before any launch."""
+        k = int(top_logprobs)
+        if not 0 <= k <= ops.LOGPROB_MAX_TOP:
+            raise ValueError(f"top_logprobs must be in 0..{ops.LOGPROB_MAX_TOP}")
+        if not torch.is_tensor(continuations) or continuations.dtype != torch.long or continuations.dim() != 3:
+            raise ValueError("score takes continuations as an int64 tensor [B, N, T]")
+        B, N, T = continuations.shape
+        if lang_x is None or lang_x.dim() != 2 or lang_x.shape[0] != B or N < 1 or T < 1:
+            raise ValueError(f"score: continuations [B, N, T] with N, T >= 1 and B = the prompt batch are expected, got {tuple(continuations.shape)} "
+                             f"for lang_x {None if lang_x is None else tuple(lang_x.shape)}")
+        if continuation_lengths is None:
+            lengths = torch.full((B, N), T, dtype=torch.long)
+        else:
+            lengths = torch.as_tensor(continuation_lengths)
+            if tuple(lengths.shape) != (B, N) or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+                raise ValueError(f"continuation_lengths is an integer tensor [B, N] = [{B}, {N}]")
+            lengths = lengths.long()
+            if int(lengths.min()) < 1 or int(lengths.max()) > T:
+                raise ValueError(f"continuation_lengths must lie in 1..T = 1..{T}")
+        if vision_x is None:
+            raise NotImplementedError("text-only generation is outside the AKI hot path")
+        cache, logits, _ = self._prefill_prompt(vision_x, lang_x, attention_mask, T)
+        if N > 1:
+            logits = self._expand_rows(cache, logits, N, T)
+        lm, dev, rows = self.lang_model, logits.device, B * N
+        lengths = lengths.to(dev)
+        live = torch.arange(T, device=dev)[:, None] < lengths.reshape(1, rows)                 # [T, rows]: step-major, a step's row is contiguous
+        ids = continuations.to(dev).reshape(rows, T).t().contiguous()
+        fed = torch.where(live, ids, torch.full_like(ids, self.pad_token_id))
+        skip = (~live).to(torch.uint8)
+        buf = _LogprobBuffers(rows, T, k, dev)
+        ops.token_logprob(logits, ids=ids[0], skip=skip[0], step=0, **buf.args())
+
+        def steps(graph: bool):
+            stepper = DecodeGraph(lm, cache) if graph else None
+            for t in range(1, T):
+                lg = stepper.step(fed[t - 1]) if stepper is not None else lm.decode_step(input_ids=fed[t - 1], past_key_values=cache)
+                ops.token_logprob(lg, ids=ids[t], skip=skip[t], step=t, **buf.args())
+
+        if T > 1:
+            len0, host_len0 = cache.cache_len.clone(), cache.host_len
+            graph = T >= 8 if use_graph is None else bool(use_graph)
+            steps(graph)
+            if not lm.decode_verified(cache):      # a chained step (one row) failed its check: the same steps again on the per-layer path
+                cache.cache_len.copy_(len0)
+                cache.host_len = host_len0
+                steps(graph)
+        self._post_forward_hook()
+        shape = lambda x: None if x is None else x.reshape(B, N, T, k)
+        return AkiScoreOutput(logprobs=buf.lp.reshape(B, N, T), sum_logprobs=buf.lp.sum(1).reshape(B, N), lengths=lengths,
+                              top_token_ids=shape(buf.top_ids), top_logprobs=shape(buf.top_lp))
 
     @torch.no_grad()
     def generate(self, vision_x, lang_x, image_size=None, attention_mask=None, past_key_values=None,
@@ -578,6 +722,15 @@ class AkiMethods:
           * `past_key_values=cache` (the AkiKVCache of a use_cache=True forward or of an earlier turn; `vision_x` must be None) continues
             from the cache instead of a prefill: `lang_x` [B, T] holds the NEW ids only and `attention_mask`, if given, spans past + new ids
             (_continue_from_cache).  Greedy and sampling only: beam search and N > 1 from a cache raise NotImplementedError.
+          * `output_logprobs=True` (with `top_logprobs=k`, k <= ops.LOGPROB_MAX_TOP = 8): the call returns an AkiGenerateOutput whose
+            `sequences` are the tokens described below, with `logprobs` f32 [rows, steps] and, for k > 0, `top_token_ids` int64 /
+            `top_logprobs` f32 [rows, steps, k], all on the device and cut with the tokens.  The log-probabilities come from the RAW model
+            distribution - the f32 log-softmax of each step's logits before logits processors, temperature, top-k or top-p - read at the
+            token that was returned: HF's compute_transition_scores(sequences, logits, normalize_logits=True).  One ops.token_logprob
+            launch behind each pick (inside the replayed graph where there is one).  Positions behind a row's EOS hold 0.0, -1 and 0.0.
+            Greedy, sampling, N continuations and from a cache; with num_beams > 1 NotImplementedError (beam search keeps
+            last_beam_scores).  `top_logprobs` without `output_logprobs`, or above the limit: ValueError.  `score` is the counterpart
+            for continuations the caller supplies.
         Returns, like HF `generate` called with `inputs_embeds` only, just the NEW tokens [B, <= max_new_tokens]; finished rows are padded
         with pad_token_id.
         After a call from a cache the LAST returned token of a row - its EOS where it hit one, else the last column - is not in the cache,
@@ -612,12 +765,15 @@ class AkiMethods:
             if opt.device_rng is not None and not on_device:
                 raise ValueError("the device sampler needs bf16 logits on the GPU")
             if opt.use_graph and (not opt.do_sample or opt.device_rng is not None) and on_device:
-                tokens = self._decode_on_device(opt, cache, logits, proc, eos_t)
+                tokens, lpb = self._decode_on_device(opt, cache, logits, proc, eos_t)
             else:
-                tokens = self._decode_on_host(opt, cache, logits, proc, eos_t)
+                tokens, lpb = self._decode_on_host(opt, cache, logits, proc, eos_t)
             if appended is not None:               # the caller's cache: every row ends right before its last returned token
                 self._trim_cache_to_returned(cache, *appended, tokens, eos_t)
         self._post_forward_hook()
+        if opt.output_logprobs:                    # never with beams (_parse_generate_kwargs)
+            lp, top_ids, top_lp = lpb.cut(tokens.shape[1])
+            return AkiGenerateOutput(sequences=tokens, logprobs=lp, top_token_ids=top_ids, top_logprobs=top_lp)
         return tokens
 
 

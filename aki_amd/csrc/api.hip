@@ -81,6 +81,9 @@ int beam_step_launch(const float* logp, int ld, int B, int K, int V, int t, int 
                      hipStream_t s);
 int kv_beam_reorder_launch(void* const* table, int n_tensors, const int* parent, const int* start_len, const int* cache_len, int B, int K,
                            int H, int cap, int row_bytes, int pos_lo, int pos_hi, hipStream_t s);
+int token_logprob_launch(const void* logits, int in_f32, int rows, int V, int ld, const int64_t* ids, const int64_t* tokens, int tokens_ld,
+                         const int* cache_len, const int* start_len, int step, const unsigned char* skip, const int* done_at, int top_k,
+                         float* out_logprob, int64_t* out_top_ids, float* out_top_logprobs, int out_ld, int out_cols, hipStream_t s);
 int sft_collate_launch(const int64_t* ids, const int64_t* labels, const int64_t* mask, const int* offsets, int B, int T_out,
                        int64_t pad_id, int64_t ignore_index, int left, int64_t* out_ids, int64_t* out_labels, int64_t* out_mask,
                        hipStream_t s);
@@ -903,6 +906,21 @@ int aki_kv_beam_reorder(void* const* table, int32_t n_tensors, const int32_t* pa
   if (K < 1 || K > AKI_BEAM_MAX_K || row_bytes % 4 != 0 || H > 65535 || (int64_t)n_tensors * B > 65535) return AKI_ERR_UNSUPPORTED;
   return kv_beam_reorder_launch(table, n_tensors, parent, start_len, cache_len, B, K, H, capacity, row_bytes, pos_lo, pos_hi,
                                 (hipStream_t)stream);
+}
+
+int aki_token_logprob(const void* logits, int32_t dtype, int32_t rows, int32_t V, int64_t ld, const int64_t* ids, const int64_t* tokens,
+                      int64_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step, const uint8_t* skip,
+                      const int32_t* done_at, int32_t top_k, float* out_logprob, int64_t* out_top_ids, float* out_top_logprobs,
+                      int64_t out_ld, int32_t out_cols, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(logits && out_logprob && (ids || tokens) && (cache_len != nullptr) == (start_len != nullptr));
+  AKI_CHECK_ARG(rows > 0 && V > 0 && ld >= V && ld < (1ll << 31) && step >= 0 && out_cols > 0 && out_ld >= out_cols && out_ld < (1ll << 31));
+  AKI_CHECK_ARG(!tokens || (tokens_ld > 0 && tokens_ld < (1ll << 31)));
+  if ((dtype != AKI_DT_BF16 && dtype != AKI_DT_F32) || top_k < 0 || top_k > AKI_LOGPROB_MAX_TOP || V > AKI_LOGPROB_MAX_V) return AKI_ERR_UNSUPPORTED;
+  AKI_CHECK_ARG(top_k == 0 || (out_top_ids && out_top_logprobs));
+  return token_logprob_launch(logits, dtype == AKI_DT_F32, rows, V, (int)ld, ids, tokens, tokens ? (int)tokens_ld : 0, cache_len, start_len,
+                              step, skip, done_at, top_k, out_logprob, out_top_ids, out_top_logprobs, (int)out_ld, out_cols,
+                              (hipStream_t)stream);
 }
 
 size_t aki_mma_mask_to_table_workspace_bytes(int32_t B, int32_t L) {

@@ -963,6 +963,69 @@ def beam_logprob(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> to
     return out
 
 
+# ---- per-token log-probabilities (logprob.hip) -----------------------------------------------------------------------------------
+LOGPROB_MAX_TOP, LOGPROB_MAX_V = L.AKI_LOGPROB_MAX_TOP, L.AKI_LOGPROB_MAX_V
+
+
+def token_logprob(logits: torch.Tensor, ids: Optional[torch.Tensor] = None, top_k: int = 0, skip: Optional[torch.Tensor] = None,
+                  step: int = 0, tokens: Optional[torch.Tensor] = None, cache_len: Optional[torch.Tensor] = None,
+                  start_len: Optional[torch.Tensor] = None, done_at: Optional[torch.Tensor] = None,
+                  out_logprob: Optional[torch.Tensor] = None, out_top_ids: Optional[torch.Tensor] = None,
+                  out_top_logprobs: Optional[torch.Tensor] = None):
+    """The log-probability of one token per row under the f32 log-softmax of bf16 / f32 logits [rows, V] (row stride >= V), with the
+    `top_k` <= LOGPROB_MAX_TOP most likely columns and theirs, one launch (aki_token_logprob; fixed reduction order: the same inputs give
+    the same bits on every run).  Returns (logprob f32 [rows, cols], top ids int64 [rows, cols, top_k] or None, top logprobs f32 [rows,
+    cols, top_k] or None): the outputs passed in, or new ones of one column (step + 1 columns when a step is given), filled with the
+    skipped values.  Row r writes column t = step + (cache_len[r] - start_len[r] when cache_len is given), nothing when t is outside the
+    outputs.
+    Plain form: `ids` int64 [rows], optional `skip` uint8 [rows] (such rows write logprob 0, ids -1, top logprobs 0) and `step`.
+    In-loop form, behind ops.greedy_pick / ops.sample_pick with the same tensors: `tokens` int64 [rows, *] (the token is tokens[r, t]),
+    `cache_len` / `start_len` int32 [rows] and `done_at` int32 [rows] (a row that finished before step t is skipped; the step that picked
+    its EOS is scored).  Capturable: no host value is read.  An id outside [0, V) gives NaN."""
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise AkiError("token_logprob takes logits [rows, V] with unit column stride and a row stride >= V")
+    rows, V = logits.shape
+    top_k, step = int(top_k), int(step)
+    if not 0 <= top_k <= LOGPROB_MAX_TOP or step < 0 or not 1 <= V <= LOGPROB_MAX_V or rows < 1:
+        raise AkiError(f"token_logprob: 0 <= top_k <= {LOGPROB_MAX_TOP}, step >= 0, rows >= 1 and 1 <= V <= {LOGPROB_MAX_V} are expected")
+    dev = _dev(logits, ids, skip, tokens, cache_len, start_len, done_at, out_logprob, out_top_ids, out_top_logprobs)
+    _dt(logits)
+    if (ids is None) == (tokens is None):
+        raise AkiError("token_logprob takes the tokens either as ids [rows] or as tokens [rows, *] (the in-loop form)")
+    if (cache_len is None) != (start_len is None):
+        raise AkiError("token_logprob: cache_len and start_len go together")
+    for t_, dt in ((ids, torch.int64), (tokens, torch.int64), (skip, torch.uint8), (cache_len, torch.int32), (start_len, torch.int32),
+                   (done_at, torch.int32)):
+        if t_ is not None and (t_.dtype != dt or not t_.is_contiguous()):
+            raise AkiError(f"token_logprob: a contiguous {dt} tensor is expected, got {t_.dtype} {tuple(t_.shape)}")
+    for t_ in (ids, skip, cache_len, start_len, done_at):
+        if t_ is not None and tuple(t_.shape) != (rows,):
+            raise AkiError(f"token_logprob: a per-row tensor [{rows}] is expected, got {tuple(t_.shape)}")
+    if tokens is not None and (tokens.dim() != 2 or tokens.shape[0] != rows or tokens.shape[1] < 1):
+        raise AkiError("token_logprob: tokens is [rows, >= 1]")
+    if out_logprob is None:
+        cols = tokens.shape[1] if tokens is not None else step + 1
+        out_logprob = torch.zeros((rows, cols), dtype=torch.float32, device=dev)
+    if out_logprob.dtype != torch.float32 or out_logprob.dim() != 2 or out_logprob.shape[0] != rows or not out_logprob.is_contiguous():
+        raise AkiError("token_logprob: out_logprob is contiguous f32 [rows, cols]")
+    cols = out_logprob.shape[1]
+    if top_k > 0:
+        if out_top_ids is None:
+            out_top_ids = torch.full((rows, cols, top_k), -1, dtype=torch.int64, device=dev)
+        if out_top_logprobs is None:
+            out_top_logprobs = torch.zeros((rows, cols, top_k), dtype=torch.float32, device=dev)
+        for t_, dt in ((out_top_ids, torch.int64), (out_top_logprobs, torch.float32)):
+            if t_.dtype != dt or tuple(t_.shape) != (rows, cols, top_k) or not t_.is_contiguous():
+                raise AkiError(f"token_logprob: the top-k outputs are contiguous [rows, cols, top_k] = [{rows}, {cols}, {top_k}], int64 ids and f32 logprobs")
+    else:
+        out_top_ids = out_top_logprobs = None
+    L.check(L.load().aki_token_logprob(_ptr(logits), _dt(logits), rows, V, logits.stride(0), _ptr(ids), _ptr(tokens),
+                                       0 if tokens is None else tokens.stride(0), _ptr(cache_len), _ptr(start_len), step, _ptr(skip),
+                                       _ptr(done_at), top_k, _ptr(out_logprob), _ptr(out_top_ids), _ptr(out_top_logprobs), cols, cols,
+                                       _stream()), "aki_token_logprob")
+    return out_logprob, out_top_ids, out_top_logprobs
+
+
 class BeamState:
     """The device state of one beam search (ops.beam_step), allocated once: running `beam_scores` f32 [B, K] (beam 0 of a sample starts at
     0, the others at -1e9: all beams start identical), the beams' tokens `seqs` int64 [B*K, max_new] (a ping-pong pair: `seqs` is the

@@ -218,7 +218,8 @@ class DecodeGraph:
         """greedy (optional): the arguments of ops.greedy_pick except logits / next_ids / cache_len / advance - the pick then sits INSIDE the
         replayed step and writes the next step's input ids itself: one replay per token (`step_greedy`), nothing else on the stream.
         With a "seed" key the dict holds ops.sample_pick's arguments instead (temperature, top_k, top_p, seed, offset): the captured pick
-        is the device sampler, whose draw depends on the device-side token index, so one capture serves every replay."""
+        is the device sampler, whose draw depends on the device-side token index, so one capture serves every replay.
+        With a "logprob" key (the in-loop arguments of ops.token_logprob) that launch is captured right behind the pick."""
         self.lm, self.cache = lm, cache
         B = cache.cache_len.shape[0]
         self.ids = torch.zeros((B,), dtype=torch.long, device=cache.cache_len.device)
@@ -244,8 +245,12 @@ class DecodeGraph:
                 self.logits = lm.decode_step(input_ids=self.ids, past_key_values=cache)
             else:                                   # the pick advances cache_len itself: one launch less per token
                 self.logits = lm.decode_step(input_ids=self.ids, past_key_values=cache, advance=False)
-                pick = ops.sample_pick if "seed" in self.greedy else ops.greedy_pick
-                pick(self.logits, self.ids, cache_len=cache.cache_len, advance=True, **self.greedy)
+                args = dict(self.greedy)
+                logprob = args.pop("logprob", None)
+                pick = ops.sample_pick if "seed" in args else ops.greedy_pick
+                pick(self.logits, self.ids, cache_len=cache.cache_len, advance=True, **args)
+                if logprob is not None:             # right behind the pick: it scores the token at the index the pick just wrote
+                    ops.token_logprob(self.logits, **logprob)
         cache.host_len = saved_host
 
     def step_greedy(self) -> torch.Tensor:

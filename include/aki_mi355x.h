@@ -897,6 +897,35 @@ int aki_beam_step(const float* logp, int64_t ld, int32_t B, int32_t K, int32_t V
 int aki_kv_beam_reorder(void* const* table, int32_t n_tensors, const int32_t* parent, const int32_t* start_len, const int32_t* cache_len,
                         int32_t B, int32_t K, int32_t H, int32_t capacity, int32_t row_bytes, int32_t pos_lo, int32_t pos_hi, void* stream);
 
+/* ---- per-token log-probabilities (logprob.hip): what `generate(output_logprobs=True)` and `score` launch behind every pick.
+ * Purely additive: AKI_ABI_VERSION was not bumped (it stays 17). */
+#define AKI_LOGPROB_MAX_TOP 8        /* alternatives per position */
+#define AKI_LOGPROB_MAX_V 262144     /* columns per row */
+
+/* aki_token_logprob - for each row r < rows of logits [rows, ld] (AKI_DT_BF16 or AKI_DT_F32, V <= AKI_LOGPROB_MAX_V columns used), one
+ * workgroup, one launch, no host value read, no workspace:
+ *   lse       m + log(sum_v exp(x_v - m)), m = max_v x_v: f32, a fixed reduction order, no float atomics - the same inputs give the same
+ *             bits on every run.  Columns may hold -inf, never a whole row; NaN inputs are unspecified (nothing is written out of bounds).
+ *             The raw model distribution: HF's compute_transition_scores(sequences, logits, normalize_logits=True).
+ *   position  t = step + (cache_len ? cache_len[r] - start_len[r] : 0) (cache_len and start_len: both or neither), evaluated on the
+ *             device: behind aki_greedy_pick / aki_sample_pick that is the index the pick just wrote, so one captured graph serves every
+ *             replay.  t outside [0, out_cols): the row writes nothing.
+ *   token     ids[r] when ids is given, else tokens[r * tokens_ld + t] (int64).  out_logprob[r * out_ld + t] = x_id - lse; an id outside
+ *             [0, V) (or t >= tokens_ld) writes NaN and reads nothing outside the row.
+ *   top_k     0 .. AKI_LOGPROB_MAX_TOP alternatives: the top_k columns with the largest input values (ranked on the inputs, which are exact;
+ *             equal values: the lower column first) go to out_top_ids[(r * out_ld + t) * top_k + j] (int64) with x - lse in
+ *             out_top_logprobs[...]; -inf columns come last with logprob -inf; a row with fewer than top_k columns ends with id -1, -inf.
+ *   skipped   a row with skip[r] != 0, or with done_at[r] >= 0 && done_at[r] < t (it finished at an earlier step and carries pad tokens;
+ *             the step that picked its EOS, done_at[r] == t, is scored): logprob 0.0, top ids -1, top logprobs 0.0.
+ * Rows are read with 16-byte vectors when logits and ld * element size are 16-byte aligned, column by column otherwise.
+ * AKI_ERR_INVALID_ARG: null logits / out_logprob, neither ids nor tokens, one of cache_len / start_len alone, top_k > 0 without both top
+ * outputs, rows / V < 1, ld < V, step < 0, out_cols < 1, out_ld < out_cols, tokens_ld < 1 with tokens.  AKI_ERR_UNSUPPORTED: dtype, top_k
+ * outside 0 .. AKI_LOGPROB_MAX_TOP, V > AKI_LOGPROB_MAX_V. */
+int aki_token_logprob(const void* logits, int32_t dtype, int32_t rows, int32_t V, int64_t ld, const int64_t* ids, const int64_t* tokens,
+                      int64_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step, const uint8_t* skip,
+                      const int32_t* done_at, int32_t top_k, float* out_logprob, int64_t* out_top_ids, float* out_top_logprobs,
+                      int64_t out_ld, int32_t out_cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

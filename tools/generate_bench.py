@@ -8,8 +8,11 @@ per-token cost they add, measured on the same box in the same process.
 --sample: every round also runs `do_sample=True` twice in the same process - with a torch.Generator (the `sample_next` loop) and with a
 DeviceGenerator (ops.sample_pick inside the greedy loop) - and reports both per-token times and the device sampler's excess over greedy.
 --batch B: B copies of the sample (the batched decode path; a hipGraph replay per token).
+--logprobs K (K >= 0; -1 = off, the default): every round also runs with output_logprobs=True, top_logprobs=K (one ops.token_logprob launch
+behind each pick), alternating with the plain leg in the same process; reports the per-token cost it adds (median and spread over the
+rounds) and merges the result into profiles/logprob_bench.json under "batch<B>_k<K>".
     python tools/generate_bench.py [--new 256] [--fp8] [--txt 64] [--repetition-penalty 1.2] [--no-repeat-ngram 3]
-                                   [--sample --temperature 0.8 --top-k 50 --top-p 0.9] [--batch 8]"""
+                                   [--sample --temperature 0.8 --top-k 50 --top-p 0.9] [--batch 8] [--logprobs 8 --rounds 4]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -33,7 +36,9 @@ def main():
     ap.add_argument("--num-return-sequences", type=int, default=1, help="N sampled continuations per prompt (device sampler): one more leg per round")
     ap.add_argument("--no-share-prompt-kv", action="store_true", help="with --num-return-sequences: replicate the prompt K/V N times (the A/B form; "
                     "without it the leg switches lang_model.share_prompt_kv on)")
+    ap.add_argument("--logprobs", type=int, default=-1, help="K >= 0: one more leg per round with output_logprobs=True, top_logprobs=K (-1: off)")
     a = ap.parse_args()
+    lp_kw = dict(output_logprobs=True, top_logprobs=a.logprobs) if a.logprobs >= 0 else None
     proc_kw = {}
     if a.repetition_penalty != 1.0:
         proc_kw["repetition_penalty"] = a.repetition_penalty
@@ -66,6 +71,8 @@ def main():
     run(16)                                   # warm-up: allocator, lazily-built folds, the graph capture path
     if proc_kw:
         run(16, **proc_kw)
+    if lp_kw:
+        run(16, **lp_kw)
     sample_kw = dict(do_sample=True, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
     if a.sample:
         import aki_amd
@@ -90,6 +97,15 @@ def main():
         res["rounds"].append({"first_token_ms": round(t1 * 1e3, 2), "first_token_host_issue_ms": round(h1 * 1e3, 2), "total_ms": round(tn * 1e3, 2),
                               "ms_per_new_token_after_the_first": round((tn - t1) * 1e3 / (a.new - 1), 4),
                               "new_tokens_per_s_end_to_end": round(a.new / tn, 1)})
+        if lp_kw:
+            t1l, _ = run(1, **lp_kw)
+            tnl, out_l = run(a.new, **lp_kw)
+            assert torch.equal(out_l.sequences, ref), "generate with logprobs returns other tokens than without"
+            assert out_l.logprobs.shape == (a.batch, a.new) and bool(torch.isfinite(out_l.logprobs).all())
+            per_l = (tnl - t1l) * 1e3 / (a.new - 1)
+            r = res["rounds"][-1]
+            r["logprobs_ms_per_new_token_after_the_first"] = round(per_l, 4)
+            r["logprobs_added_us_per_token"] = round((per_l - r["ms_per_new_token_after_the_first"]) * 1e3, 2)
         if proc_kw:
             t1p, _ = run(1, **proc_kw)
             tnp, toks_p = run(a.new, **proc_kw)
@@ -132,6 +148,18 @@ def main():
     if proc_kw:
         add = sorted(r["processors_added_us_per_token"] for r in res["rounds"])
         res["processors_added_us_per_token_median"] = add[len(add) // 2]
+    if lp_kw:
+        add = sorted(r["logprobs_added_us_per_token"] for r in res["rounds"])
+        plain = sorted(r["ms_per_new_token_after_the_first"] for r in res["rounds"])
+        res["logprobs"] = {"top_logprobs": a.logprobs, "added_us_per_token_median": add[len(add) // 2], "added_us_per_token_min": add[0],
+                           "added_us_per_token_max": add[-1], "plain_ms_per_token_median": plain[len(plain) // 2],
+                           "plain_ms_per_token_min": plain[0], "plain_ms_per_token_max": plain[-1]}
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "logprob_bench.json")
+        book = json.load(open(path)) if os.path.exists(path) else {}
+        book[f"batch{a.batch}_k{a.logprobs}"] = res
+        with open(path, "w") as f:
+            json.dump(book, f, indent=1, sort_keys=True)
+            f.write("\n")
     print(json.dumps(res))
 
 

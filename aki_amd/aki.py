@@ -83,8 +83,13 @@ def _embedding_tables(emb: nn.Module, logits: torch.Tensor):
 # ops.DeviceGenerator, which device_rng repeats (else None: no device sampler); n_ret: num_return_sequences; eos_ids: a set; processors:
 # the logits-processor keywords (PROCESSOR_KWARGS) with None read as the neutral value; output_logprobs / top_logprobs: the per-token
 # log-probabilities of the returned tokens and that many alternatives (ops.token_logprob).
+# constraint: None, a constraint.TokenConstraint or a list of one per sample (constrained decoding; bound to the device in generate).
 GenerateOptions = namedtuple("GenerateOptions", "num_beams do_sample temperature top_k top_p rng device_rng length_penalty early_stopping "
-                                                "n_ret max_new_tokens eos_ids pad_id use_graph processors output_logprobs top_logprobs")
+                                                "n_ret max_new_tokens eos_ids pad_id use_graph processors output_logprobs top_logprobs "
+                                                "constraint")
+
+# the processors that ban tokens outright: together with a constraint they could leave a row with nothing allowed
+BANNING_KWARGS = ("no_repeat_ngram_size", "bad_words_ids", "min_length", "min_new_tokens", "suppress_tokens", "begin_suppress_tokens")
 
 
 @dataclass
@@ -134,10 +139,11 @@ class _LogprobBuffers:
         return self.lp[:, :n], (self.top_ids[:, :n] if self.k else None), (self.top_lp[:, :n] if self.k else None)
 
 
-def _parse_generate_kwargs(kwargs: dict, default_pad_id, default_eos_ids, from_cache: bool) -> GenerateOptions:
+def _parse_generate_kwargs(kwargs: dict, default_pad_id, default_eos_ids, from_cache: bool, batch: Optional[int] = None) -> GenerateOptions:
     """Every keyword of `generate` popped from `kwargs`, checked and given its default, before any device work.  default_eos_ids: a callable,
-    asked only when the caller passes no `eos_token_id`; from_cache: generate(past_key_values=...).  A keyword that is left over
-    (`logits_processor`, `stopping_criteria`, `output_scores`, `generation_config`, ...) raises ValueError instead of being ignored."""
+    asked only when the caller passes no `eos_token_id`; from_cache: generate(past_key_values=...); batch: the number of samples, which a
+    list of constraints has to match.  A keyword that is left over (`logits_processor`, `stopping_criteria`, `output_scores`,
+    `generation_config`, `prefix_allowed_tokens_fn`, ...) raises ValueError instead of being ignored."""
     num_beams = int(kwargs.pop("num_beams", 1))
     do_sample = bool(kwargs.pop("do_sample", False))
     temperature = float(kwargs.pop("temperature", 1.0))
@@ -186,11 +192,26 @@ def _parse_generate_kwargs(kwargs: dict, default_pad_id, default_eos_ids, from_c
         raise ValueError(f"top_logprobs must be in 0..{ops.LOGPROB_MAX_TOP}")
     if output_logprobs and num_beams > 1:
         raise NotImplementedError("output_logprobs with num_beams > 1: beam search keeps last_beam_scores")
+    constraint = kwargs.pop("constraint", None)
+    if constraint is not None:
+        from .constraint import TokenConstraint
+        if num_beams > 1:
+            raise NotImplementedError("constraint with num_beams > 1: beam search under a token constraint")
+        banning = [k for k in BANNING_KWARGS if processors[k]]
+        if banning:
+            raise ValueError(f"constraint together with {banning}: a processor that bans tokens can leave a constrained row with nothing "
+                             "allowed; only repetition_penalty composes with a constraint")
+        if not isinstance(constraint, TokenConstraint):
+            constraint = list(constraint) if isinstance(constraint, (list, tuple)) else [constraint]
+            if not constraint or any(not isinstance(c, TokenConstraint) for c in constraint):
+                raise ValueError("constraint is an aki_amd.TokenConstraint or a list of one per sample")
+            if batch is not None and len(constraint) != batch:
+                raise ValueError(f"constraint lists {len(constraint)} constraints for a batch of {batch} samples")
     _reject_unused_kwargs(kwargs)
     return GenerateOptions(num_beams=num_beams, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, rng=rng,
                            device_rng=device_rng, length_penalty=length_penalty, early_stopping=early_stopping, n_ret=n_ret,
                            max_new_tokens=max_new_tokens, eos_ids=eos_ids, pad_id=pad_id, use_graph=use_graph, processors=processors,
-                           output_logprobs=output_logprobs, top_logprobs=top_logprobs)
+                           output_logprobs=output_logprobs, top_logprobs=top_logprobs, constraint=constraint)
 
 
 def _device_sampler_args(opt: GenerateOptions):
@@ -607,6 +628,8 @@ class AkiMethods:
                     nxt = sample_next(x, temperature, top_k, top_p, rng) if do_sample else x.float().argmax(dim=-1)
                 nxt = torch.where(done, torch.full_like(nxt, pad_id), nxt)
                 tokens[:, t] = nxt
+                if proc is not None and sampler is None:        # a constraint's next state (ops.sample_pick stores it itself)
+                    proc.advance_states(nxt, t, done)
                 if lpb is not None:                 # the raw logits of this step, at the token returned; rows finished before it are skipped
                     ops.token_logprob(logits, ids=nxt, skip=done.to(torch.uint8), step=t, **lpb.args())
                 t += 1
@@ -719,6 +742,19 @@ class AkiMethods:
             `no_repeat_ngram_size`, `bad_words_ids`, `min_length` / `min_new_tokens` (eos ids banned until that many tokens are generated),
             `suppress_tokens`, `begin_suppress_tokens`.  As in HF `generate` with inputs_embeds only, they see the generated tokens, never
             the prompt; beam search applies them to each beam's log-softmax scores.
+          * `constraint=` an `aki_amd.TokenConstraint` (aki_amd/constraint.py), or a list of one per sample: constrained decoding.  The
+            automaton's table lives on the device, the mask is the last stage of the logits processors and the pick stores each row's
+            next state, so the launches per token and the host's look every 8th token stay as they are.  Every returned row is a walk of
+            its automaton; an eos id can be emitted only in an accepting state (`TokenConstraint.from_choices(choices, V)` + `eos_token_id`
+            gives "one of the choices, then EOS").  Greedy, sampling (both samplers), `num_return_sequences` (row b*N + j starts in
+            sample b's start state), from a cache, with `output_logprobs` (still the RAW distribution) and with `repetition_penalty`.
+            Refused before any device work: `num_beams > 1` (NotImplementedError); a processor that bans tokens
+            (`no_repeat_ngram_size`, `bad_words_ids`, `min_length` / `min_new_tokens`, `suppress_tokens`, `begin_suppress_tokens`: the
+            pair could leave a row with nothing allowed), a list whose length is not B, a constraint built for another V than the
+            logits' width V', an eos id used as a transition, a reachable state that allows nothing (ValueError).  HF's
+            `prefix_allowed_tokens_fn` callback stays refused: a Python call per row per step cannot ride the device loop.
+            Greedy decoding inside a trie takes the locally best allowed token: it does NOT return the most likely choice as a whole;
+            `score` ranks a closed set of answers by likelihood.
           * `past_key_values=cache` (the AkiKVCache of a use_cache=True forward or of an earlier turn; `vision_x` must be None) continues
             from the cache instead of a prefill: `lang_x` [B, T] holds the NEW ids only and `attention_mask`, if given, spans past + new ids
             (_continue_from_cache).  Greedy and sampling only: beam search and N > 1 from a cache raise NotImplementedError.
@@ -739,7 +775,20 @@ class AkiMethods:
         room for T + max_new_tokens - 1 more rows (AkiError before any launch otherwise).
         Differences from the reference, both only visible for B > 1 (where the reference is inconsistent): the
         prompt batch is right-padded and every sample continues from its own length."""
-        opt = _parse_generate_kwargs(kwargs, self.pad_token_id, self.default_eos_token_ids, past_key_values is not None)
+        opt = _parse_generate_kwargs(kwargs, self.pad_token_id, self.default_eos_token_ids, past_key_values is not None,
+                                     batch=None if lang_x is None else lang_x.shape[0])
+        con = None
+        if opt.constraint is not None:             # the host half of binding: the table with its eos columns, checked before any launch
+            from .constraint import constraint_for_rows
+            if lang_x is None:
+                raise ValueError("generate(constraint=...) needs lang_x")
+            con, rows_start = constraint_for_rows(opt.constraint, lang_x.shape[0], opt.n_ret)
+            head = self.lang_model.get_output_embeddings()
+            # V': DecoupledLinear's output is the original ids followed by the added ones (helpers.py), a plain head's its rows
+            width = int(head.max_original_id) + 1 + int(head.additional_out_features) if hasattr(head, "max_original_id") else int(head.out_features)
+            if con.V != width:
+                raise ValueError(f"the constraint was built for V = {con.V}, the logits have {width} columns")
+            con.with_eos(sorted(opt.eos_ids))
         if past_key_values is not None:
             cache, logits, appended = self._continue_from_cache(vision_x, lang_x, attention_mask, past_key_values, opt.max_new_tokens)
         elif vision_x is None:
@@ -747,9 +796,10 @@ class AkiMethods:
         else:
             cache, logits, appended = self._prefill_prompt(vision_x, lang_x, attention_mask, opt.max_new_tokens)
         pk = opt.processors
+        bound = None if con is None else con.bind(sorted(opt.eos_ids), logits.device, rows_start)
         proc = ops.LogitsProcessors(logits.shape[-1], logits.device, pk["repetition_penalty"], pk["no_repeat_ngram_size"],
                                     max(int(pk["min_length"]), int(pk["min_new_tokens"])), sorted(opt.eos_ids), pk["suppress_tokens"],
-                                    pk["begin_suppress_tokens"], pk["bad_words_ids"])
+                                    pk["begin_suppress_tokens"], pk["bad_words_ids"], constraint=bound)
         proc = proc if proc.active else None       # no processor: exactly the launches of a plain generate
         if opt.num_beams > 1:
             beam = (opt.num_beams, opt.max_new_tokens, opt.eos_ids, opt.pad_id, opt.length_penalty, opt.early_stopping, proc)

@@ -61,19 +61,22 @@ int greedy_pick_launch(const void* logits, int B, int V, int ld, const int64_t* 
 int logits_process_launch(const void* logits, int in_f32, int B, int V, int ld, float* out, int ld_out, const int64_t* tokens, int tokens_ld,
                           const int* cache_len, const int* start_len, int step, const unsigned char* done, float penalty, int ngram,
                           int min_len, const int64_t* eos, int n_eos, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress,
-                          int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad, int n_bad_ids, hipStream_t s);
+                          int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad, int n_bad_ids,
+                          const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s);
 int greedy_pick_processed_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done,
                                  int64_t* ids, int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at,
                                  const void* emb_main, const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores,
                                  int ld_scores, float penalty, int ngram, int min_len, const int64_t* suppress, int n_suppress,
                                  const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad,
-                                 int n_bad_ids, hipStream_t s);
+                                 int n_bad_ids,
+                                 const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s);
 int sample_pick_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done, int64_t* ids,
                        int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at, const void* emb_main,
                        const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores, int ld_scores, float penalty, int ngram,
                        int min_len, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids,
                        const int* bad_off, int n_bad, int n_bad_ids, int step, float temperature, int top_k, float top_p, uint64_t seed,
-                       uint64_t offset, float* probs, int ld_probs, hipStream_t s);
+                       uint64_t offset, float* probs, int ld_probs,
+                       const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s);
 int beam_logprob_launch(const void* logits, int in_f32, int rows, int V, int ld, float* out, int ld_out, hipStream_t s);
 int beam_step_launch(const float* logp, int ld, int B, int K, int V, int t, int max_new, float* beam_scores, const int64_t* seqs_in,
                      int64_t* seqs_out, float* hyp_score, int* hyp_len, int64_t* hyp_tokens, int* hyp_count, unsigned char* done,
@@ -803,11 +806,18 @@ static bool processors_ok(int32_t V, float penalty, int32_t ngram, int32_t min_l
          n_bad_ids >= n_bad && (n_bad == 0 || (bad_ids && bad_offsets));
 }
 
-int aki_logits_process(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out, const int64_t* tokens,
-                       int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step, const uint8_t* done,
-                       float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* eos_ids, int32_t n_eos,
-                       const int64_t* suppress_ids, int32_t n_suppress, const int64_t* begin_suppress_ids, int32_t n_begin_suppress,
-                       const int64_t* bad_ids, const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, void* stream) {
+// The constrained forms (include/aki_mi355x.h): a device table with a row for every state and a state history with at least its start column.
+static bool constraint_ok(int32_t V, const int16_t* table, int64_t table_ld, int32_t n_states, const int32_t* states, int32_t states_ld) {
+  return table && states && n_states > 0 && n_states <= 32767 && table_ld >= V && table_ld < (1ll << 31) && states_ld >= 1;
+}
+
+// the shared bodies: the plain entry points hand over a null constraint and launch exactly what they launched before
+static int logits_process_checked(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
+                                  const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step,
+                                  const uint8_t* done, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length,
+                                  const int64_t* eos_ids, int32_t n_eos, const int64_t* suppress_ids, int32_t n_suppress,
+                                  const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids,
+                                  const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
   AKI_CLEAR_ERR();
   AKI_CHECK_ARG(logits && out && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && ld_out >= V && ld_out < (1ll << 31) && step >= 0);
   AKI_CHECK_ARG((!tokens || tokens_ld > 0) && n_eos >= 0 && (n_eos == 0 || eos_ids));
@@ -816,16 +826,40 @@ int aki_logits_process(const void* logits, int32_t dtype, int32_t B, int32_t V, 
   if (dtype != AKI_DT_BF16 && dtype != AKI_DT_F32) return AKI_ERR_UNSUPPORTED;
   return logits_process_launch(logits, dtype == AKI_DT_F32, B, V, (int)ld, out, (int)ld_out, tokens, tokens_ld, cache_len, start_len, step, done,
                                repetition_penalty, no_repeat_ngram_size, min_length, eos_ids, n_eos, suppress_ids, n_suppress,
-                               begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids, (hipStream_t)stream);
+                               begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids, table, (int)table_ld, n_states, states, states_ld, (hipStream_t)stream);
 }
 
-int aki_greedy_pick_processed(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
-                              uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
-                              int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
-                              int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
-                              int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
-                              const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
-                              int32_t n_bad, int32_t n_bad_ids, void* stream) {
+int aki_logits_process(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out, const int64_t* tokens,
+                       int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step, const uint8_t* done,
+                       float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* eos_ids, int32_t n_eos,
+                       const int64_t* suppress_ids, int32_t n_suppress, const int64_t* begin_suppress_ids, int32_t n_begin_suppress,
+                       const int64_t* bad_ids, const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, void* stream) {
+  return logits_process_checked(logits, dtype, B, V, ld, out, ld_out, tokens, tokens_ld, cache_len, start_len, step, done, repetition_penalty,
+                                no_repeat_ngram_size, min_length, eos_ids, n_eos, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress,
+                                bad_ids, bad_offsets, n_bad, n_bad_ids, nullptr, 0, 0, nullptr, 0, stream);
+}
+
+int aki_logits_process_constrained(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
+                                   const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step,
+                                   const uint8_t* done, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length,
+                                   const int64_t* eos_ids, int32_t n_eos, const int64_t* suppress_ids, int32_t n_suppress,
+                                   const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids,
+                                   const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld,
+                                   int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(V > 0 && constraint_ok(V, table, table_ld, n_states, states, states_ld));
+  return logits_process_checked(logits, dtype, B, V, ld, out, ld_out, tokens, tokens_ld, cache_len, start_len, step, done, repetition_penalty,
+                                no_repeat_ngram_size, min_length, eos_ids, n_eos, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress,
+                                bad_ids, bad_offsets, n_bad, n_bad_ids, table, table_ld, n_states, states, states_ld, stream);
+}
+
+static int greedy_pick_processed_checked(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                                         uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                                         int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                                         int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                                         int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                                         const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                                         int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
   AKI_CLEAR_ERR();
   AKI_CHECK_ARG(logits && next_ids && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && n_eos >= 0 && (n_eos == 0 || eos_ids));
   AKI_CHECK_ARG((!tokens || tokens_ld > 0) && (!advance || cache_len) && (advance == 0 || advance == 1));
@@ -844,17 +878,45 @@ int aki_greedy_pick_processed(const void* logits, int32_t B, int32_t V, int64_t 
   return greedy_pick_processed_launch(logits, B, V, (int)ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len,
                                       advance, done_at, embed_weight, additional_weight, max_original_id, d, next_embeds, scores, (int)ld_scores,
                                       repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
-                                      n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids, (hipStream_t)stream);
+                                      n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids, table, (int)table_ld, n_states, states, states_ld, (hipStream_t)stream);
 }
 
-int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
-                    uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
-                    int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
-                    int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
-                    int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
-                    const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
-                    int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
-                    uint64_t offset, float* probs_out, int64_t ld_probs, void* stream) {
+int aki_greedy_pick_processed(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                              uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                              int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                              int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                              int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                              const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                              int32_t n_bad, int32_t n_bad_ids, void* stream) {
+  return greedy_pick_processed_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
+                                       embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
+                                       no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
+                                       n_bad_ids, nullptr, 0, 0, nullptr, 0, stream);
+}
+
+int aki_greedy_pick_constrained(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                                uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                                int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                                int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                                int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                                const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                                int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(V > 0 && constraint_ok(V, table, table_ld, n_states, states, states_ld));
+  return greedy_pick_processed_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
+                                       embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
+                                       no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
+                                       n_bad_ids, table, table_ld, n_states, states, states_ld, stream);
+}
+
+static int sample_pick_checked(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                               uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                               int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                               int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                               int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                               const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                               int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                               uint64_t offset, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
   AKI_CLEAR_ERR();
   AKI_CHECK_ARG(logits && next_ids && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && n_eos >= 0 && (n_eos == 0 || eos_ids));
   AKI_CHECK_ARG((!tokens || tokens_ld > 0) && (!advance || cache_len) && (advance == 0 || advance == 1) && step >= 0);
@@ -875,7 +937,37 @@ int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const 
   return sample_pick_launch(logits, B, V, (int)ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
                             done_at, embed_weight, additional_weight, max_original_id, d, next_embeds, scores, (int)ld_scores, repetition_penalty,
                             no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets,
-                            n_bad, n_bad_ids, step, temperature, top_k, top_p, seed, offset, probs_out, (int)ld_probs, (hipStream_t)stream);
+                            n_bad, n_bad_ids, step, temperature, top_k, top_p, seed, offset, probs_out, (int)ld_probs, table, (int)table_ld, n_states, states, states_ld, (hipStream_t)stream);
+}
+
+int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                    uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                    int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                    int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                    int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                    const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                    int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                    uint64_t offset, float* probs_out, int64_t ld_probs, void* stream) {
+  return sample_pick_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
+                             embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
+                             no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
+                             n_bad_ids, step, temperature, top_k, top_p, seed, offset, probs_out, ld_probs, nullptr, 0, 0, nullptr, 0, stream);
+}
+
+int aki_sample_pick_constrained(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                                uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                                int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                                int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                                int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                                const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                                int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                                uint64_t offset, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(V > 0 && constraint_ok(V, table, table_ld, n_states, states, states_ld));
+  return sample_pick_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
+                             embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
+                             no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
+                             n_bad_ids, step, temperature, top_k, top_p, seed, offset, probs_out, ld_probs, table, table_ld, n_states, states, states_ld, stream);
 }
 
 int aki_beam_logprob(const void* logits, int32_t dtype, int32_t rows, int32_t V, int64_t ld, float* out, int64_t ld_out, void* stream) {

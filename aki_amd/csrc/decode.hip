@@ -1500,11 +1500,27 @@ __device__ __forceinline__ bool pick_better(float a, int ia, float b, int ib) {
   return a > b || (a == b && ia < ib);
 }
 
+// Constrained decoding (aki_amd/constraint.py): a deterministic automaton over token ids.  table[s, v] is the state behind token v in state
+// s, negative = v is not allowed in s; states[b, n] is the state in which row b picks its generated token n (column 0: the start state).
+// The state is addressed by the token index, like the processors' history, never carried in a counter: a replayed graph, a rewind of
+// cache_len after a chain give-up and a repeated step then read and write the right column with nothing to reset.
+struct ConstraintParams {
+  const int16_t* table; int table_ld, n_states;
+  int* states; int states_ld;
+};
+
+// states[b, n], or -1 where there is nothing to read (no constraint, n outside the history)
+__device__ __forceinline__ int constraint_state(const ConstraintParams* c, int b, int n) {
+  if (c == nullptr || c->table == nullptr || n < 0 || n >= c->states_ld) return -1;
+  return c->states[(size_t)b * c->states_ld + n];
+}
+
 constexpr int PICK_THREADS = 1024;
 // The pick's bookkeeping tail, shared by the greedy and the sampling kernels: thread 0 holds the picked id `bi` and what it requested before
-// the scan (was_done, len0, start0, eos4); pad for finished rows, append, eos check, cache_len advance, then every thread gathers the
-// next step's embedding row.
-__device__ __forceinline__ void pick_finish(const PickParams& p, int b, bool was_done, int len0, int start0, const int64_t (&eos4)[4], int bi) {
+// the scan (was_done, len0, start0, eos4; cs: the row's state under a constraint `c`); pad for finished rows, append, the next state, eos
+// check, cache_len advance, then every thread gathers the next step's embedding row.
+__device__ __forceinline__ void pick_finish(const PickParams& p, int b, bool was_done, int len0, int start0, const int64_t (&eos4)[4], int bi,
+                                            const ConstraintParams* c = nullptr, int cs = -1) {
   __shared__ int64_t s_next;
   const int tid = threadIdx.x;
   if (tid == 0) {
@@ -1515,6 +1531,12 @@ __device__ __forceinline__ void pick_finish(const PickParams& p, int b, bool was
       if (p.advance) p.cache_len[b] = len0 + 1;
     }
     if (p.tokens != nullptr && t >= 0 && t < p.tokens_ld) p.tokens[(size_t)b * p.tokens_ld + t] = nxt;
+    if (c != nullptr && c->table != nullptr && t >= 0 && t + 1 < c->states_ld) {
+      // a finished row keeps its state; a state or a token outside the table gives -1, which the mask reads as "row untouched"
+      int ns = cs;
+      if (!was_done) ns = (cs >= 0 && cs < c->n_states && bi >= 0 && bi < p.V) ? (int)c->table[(size_t)cs * c->table_ld + bi] : -1;
+      c->states[(size_t)b * c->states_ld + t + 1] = ns;
+    }
     p.ids[b] = nxt;
     s_next = nxt;
     if (p.done != nullptr && !was_done) {
@@ -1540,7 +1562,7 @@ __device__ __forceinline__ void pick_finish(const PickParams& p, int b, bool was
 // loads each instead of 16 trips of one (19.4 -> measured in profiles/r05_decode_token_trace.txt).
 // F32: the row to scan is `rowf` (an f32 row of processed scores, see logits processors below), not p.logits
 template <bool F32>
-__device__ __forceinline__ void greedy_pick_row(const PickParams& p, const float* rowf) {
+__device__ __forceinline__ void greedy_pick_row(const PickParams& p, const float* rowf, const ConstraintParams* c = nullptr) {
   __shared__ float s_v[PICK_THREADS / 64];
   __shared__ int s_i[PICK_THREADS / 64];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1549,6 +1571,7 @@ __device__ __forceinline__ void greedy_pick_row(const PickParams& p, const float
   bool was_done = false;
   int len0 = 0, start0 = 0;
   int64_t eos4[4] = {-1, -1, -1, -1};                        // token ids are >= 0: -1 matches nothing
+  int cs = -1;
   if (tid == 0) {
     was_done = p.done != nullptr && p.done[b] != 0;
     if (p.cache_len != nullptr) {
@@ -1558,6 +1581,7 @@ __device__ __forceinline__ void greedy_pick_row(const PickParams& p, const float
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       if (i < p.n_eos) eos4[i] = p.eos[i];
+    if (c != nullptr) cs = constraint_state(c, b, p.step + (p.cache_len != nullptr ? len0 + p.advance - start0 : 0));
   }
   float best = -INFINITY;
   int bi = 0x7fffffff;
@@ -1620,7 +1644,7 @@ __device__ __forceinline__ void greedy_pick_row(const PickParams& p, const float
     for (int w = 1; w < PICK_THREADS / 64; ++w)
       if (pick_better(s_v[w], s_i[w], best, bi)) { best = s_v[w]; bi = s_i[w]; }
   }
-  pick_finish(p, b, was_done, len0, start0, eos4, bi);
+  pick_finish(p, b, was_done, len0, start0, eos4, bi, c, cs);
 }
 
 __global__ __launch_bounds__(PICK_THREADS) void greedy_pick_kernel(const PickParams p) { greedy_pick_row<false>(p, nullptr); }
@@ -1646,6 +1670,7 @@ int greedy_pick_launch(const void* logits, int B, int V, int ld, const int64_t* 
 //                         at least the whole word's length (SequenceBiasLogitsProcessor's rule)
 //   4 minimum length      -inf for every eos id while n < min_length (MinLength / MinNewTokensLength: the prompt length is 0 here)
 //   5 suppress tokens     -inf always; begin-suppress tokens -inf at n == 0
+//   6 token constraint    (not HF's: ConstraintParams above) -inf for every token the row's state states[b, n] does not allow, n unclamped
 // n = step + (cache_len ? cache_len[b] - start_len[b] : 0), so that one captured graph serves every replay.  Rows with done[b] set get the
 // plain f32 copy.  One workgroup per row, O(V + n * ngram + bad-word ids); ids outside [0, V) are skipped.
 struct ProcParams {
@@ -1660,6 +1685,7 @@ struct ProcParams {
   const int64_t* suppress; int n_suppress;
   const int64_t* begin_suppress; int n_begin;
   const int64_t* bad_ids; const int* bad_off; int n_bad, n_bad_ids;
+  ConstraintParams c;                 // c.table == nullptr: no constraint
 };
 
 constexpr int PROC_MAX_V = 131072;   // the repetition penalty's LDS bitmap: 16 KB
@@ -1672,6 +1698,7 @@ __device__ void process_row(const ProcParams& q, int b, float* out, unsigned* s_
   const int tid = threadIdx.x, nt = blockDim.x, V = q.V;
   int n = q.step;
   if (q.cache_len != nullptr) n += q.cache_len[b] - (q.start_len != nullptr ? q.start_len[b] : 0);
+  const int n_state = n;                                     // the state history has its own width: indexed before the clamp
   n = q.tokens == nullptr ? 0 : min(max(n, 0), q.tokens_ld);
   const bool skip = q.done != nullptr && q.done[b] != 0;
   // 0: the row in f32
@@ -1730,6 +1757,34 @@ __device__ void process_row(const ProcParams& q, int b, float* out, unsigned* s_
   for (int i = tid; i < q.n_suppress; i += nt) ban(out, V, q.suppress[i]);
   if (n == 0)
     for (int i = tid; i < q.n_begin; i += nt) ban(out, V, q.begin_suppress[i]);
+  // 6: the constraint.  Like the bans it only ever writes -inf, so it shares their side of the barrier behind the penalties.  Eight int16
+  // entries per 16-byte load (a negative entry = its sign bit); a state outside the table leaves the row as it is.
+  if (q.c.table != nullptr) {
+    const int s = constraint_state(&q.c, b, n_state);
+    if (s >= 0 && s < q.c.n_states) {
+      const int16_t* row = q.c.table + (size_t)s * q.c.table_ld;
+      const bool vec = ((q.c.table_ld & 7) == 0) && ((((uintptr_t)q.c.table) & 15) == 0);
+      const bool vec_out = (((uintptr_t)out) & 15) == 0;
+      const int nvec = vec ? V / 8 : 0;
+      for (int c = tid; c < nvec; c += nt) {
+        const u32x4 w = *(const u32x4*)(row + (size_t)c * 8);
+        if (((w[0] | w[1] | w[2] | w[3]) & 0x80008000u) == 0u) continue;            // all eight allowed
+        float* o = out + (size_t)c * 8;
+        if (vec_out && ((w[0] & w[1] & w[2] & w[3]) & 0x80008000u) == 0x80008000u) {  // none allowed: the common chunk of a sparse state
+          *(float4*)o = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+          *(float4*)(o + 4) = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if (w[e] & 0x8000u) o[2 * e] = -INFINITY;
+            if (w[e] & 0x80000000u) o[2 * e + 1] = -INFINITY;
+          }
+        }
+      }
+      for (int i = nvec * 8 + tid; i < V; i += nt)
+        if (row[i] < 0) out[i] = -INFINITY;
+    }
+  }
   __syncthreads();
 }
 
@@ -1744,7 +1799,7 @@ __global__ __launch_bounds__(PICK_THREADS) void greedy_pick_processed_kernel(con
   __shared__ unsigned s_bits[PROC_MAX_V / 32];
   float* rowf = q.out + (size_t)blockIdx.x * q.ld_out;
   process_row(q, blockIdx.x, rowf, s_bits);
-  greedy_pick_row<true>(p, rowf);
+  greedy_pick_row<true>(p, rowf, &q.c);
 }
 
 // ---- sampling pick: HF's `do_sample` step (processors -> temperature -> top-k -> top-p -> softmax -> multinomial) with the greedy pick's
@@ -1870,6 +1925,7 @@ __global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickPar
   bool was_done = false;
   int len0 = 0, start0 = 0;
   int64_t eos4[4] = {-1, -1, -1, -1};
+  int cs = -1;
   if (tid == 0) {
     was_done = p.done != nullptr && p.done[b] != 0;
     if (p.cache_len != nullptr) {
@@ -1879,6 +1935,7 @@ __global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickPar
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       if (i < p.n_eos) eos4[i] = p.eos[i];
+    cs = constraint_state(&q.c, b, p.step + (p.cache_len != nullptr ? len0 + p.advance - start0 : 0));
     s_owner = 0x7fffffff; s_last = -1; s_tok = -1;
   }
   const bool row_done = p.done != nullptr && p.done[b] != 0;   // uniform: every thread reads the same byte, before thread 0 can set it
@@ -2007,7 +2064,7 @@ __global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickPar
       }
     }
   }
-  pick_finish(p, b, was_done, len0, start0, eos4, tok);
+  pick_finish(p, b, was_done, len0, start0, eos4, tok, &q.c, cs);
 }
 
 
@@ -2016,15 +2073,17 @@ static ProcParams proc_params(const void* in, int in_f32, int ld_in, float* out,
                               int min_len, const int64_t* eos, int n_eos, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress,
                               int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad, int n_bad_ids) {
   return ProcParams{in, in_f32, ld_in, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, penalty, ngram, min_len,
-                    eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off, n_bad, n_bad_ids};
+                    eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off, n_bad, n_bad_ids, ConstraintParams{}};
 }
 
 int logits_process_launch(const void* logits, int in_f32, int B, int V, int ld, float* out, int ld_out, const int64_t* tokens, int tokens_ld,
                           const int* cache_len, const int* start_len, int step, const unsigned char* done, float penalty, int ngram,
                           int min_len, const int64_t* eos, int n_eos, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress,
-                          int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad, int n_bad_ids, hipStream_t s) {
-  const ProcParams q = proc_params(logits, in_f32, ld, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, penalty, ngram,
-                                   min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off, n_bad, n_bad_ids);
+                          int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad, int n_bad_ids,
+                          const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s) {
+  ProcParams q = proc_params(logits, in_f32, ld, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, penalty, ngram,
+                             min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off, n_bad, n_bad_ids);
+  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld};
   AKI_CLEAR_ERR();
   hipLaunchKernelGGL(logits_process_kernel, dim3(B), dim3(PROC_THREADS), 0, s, q);
   AKI_LAUNCH_CHECK();
@@ -2036,13 +2095,15 @@ int greedy_pick_processed_launch(const void* logits, int B, int V, int ld, const
                                  const void* emb_main, const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores,
                                  int ld_scores, float penalty, int ngram, int min_len, const int64_t* suppress, int n_suppress,
                                  const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad,
-                                 int n_bad_ids, hipStream_t s) {
+                                 int n_bad_ids,
+                                 const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s) {
   PickParams p = {(const bf16_t*)logits, B, V, ld, eos, n_eos, pad, done, ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
                   (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out};
   // the processors see the tokens generated BEFORE this pick: n = cache_len + advance - start_len, the index the pick writes
-  const ProcParams q = proc_params(logits, 0, ld, scores, ld_scores, V, tokens, tokens_ld, cache_len, start_len, cache_len ? advance : 0, done,
-                                   penalty, ngram, min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off, n_bad,
-                                   n_bad_ids);
+  ProcParams q = proc_params(logits, 0, ld, scores, ld_scores, V, tokens, tokens_ld, cache_len, start_len, cache_len ? advance : 0, done,
+                             penalty, ngram, min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off, n_bad,
+                             n_bad_ids);
+  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld};
   AKI_CLEAR_ERR();
   hipLaunchKernelGGL(greedy_pick_processed_kernel, dim3(B), dim3(PICK_THREADS), 0, s, p, q);
   AKI_LAUNCH_CHECK();
@@ -2054,13 +2115,15 @@ int sample_pick_launch(const void* logits, int B, int V, int ld, const int64_t* 
                        const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores, int ld_scores, float penalty, int ngram,
                        int min_len, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids,
                        const int* bad_off, int n_bad, int n_bad_ids, int step, float temperature, int top_k, float top_p, uint64_t seed,
-                       uint64_t offset, float* probs, int ld_probs, hipStream_t s) {
+                       uint64_t offset, float* probs, int ld_probs,
+                       const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s) {
   PickParams p = {(const bf16_t*)logits, B, V, ld, eos, n_eos, pad, done, ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
                   (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out, step};
-  const ProcParams q = proc_params(logits, 0, ld, scores, ld_scores, V, tokens, tokens_ld, cache_len, start_len, step + (cache_len ? advance : 0),
-                                   done, penalty, ngram, min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off,
-                                   n_bad, n_bad_ids);
-  const bool processed = penalty != 1.f || ngram > 0 || n_bad > 0 || (min_len > 0 && n_eos > 0) || n_suppress > 0 || n_begin > 0;
+  ProcParams q = proc_params(logits, 0, ld, scores, ld_scores, V, tokens, tokens_ld, cache_len, start_len, step + (cache_len ? advance : 0),
+                             done, penalty, ngram, min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off,
+                             n_bad, n_bad_ids);
+  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld};
+  const bool processed = penalty != 1.f || ngram > 0 || n_bad > 0 || (min_len > 0 && n_eos > 0) || n_suppress > 0 || n_begin > 0 || c_table != nullptr;
   const SampleParams sp = {temperature, top_k, top_p, (unsigned)seed, (unsigned)(seed >> 32), (unsigned)offset, (unsigned)(offset >> 32),
                            probs, ld_probs, processed ? 1 : 0};
   AKI_CLEAR_ERR();

@@ -724,10 +724,14 @@ class LogitsProcessors:
     never the prompt.  In HF's order: repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length (eos ids banned while fewer
     tokens have been generated; min_new_tokens is the same number here), suppress_tokens, begin_suppress_tokens.  The arguments are
     checked here, on the host, and held as device tensors, so one object serves a whole generation (and a captured graph).
-    eos_ids: the ids min_length bans; a one-token bad word equal to one of them is dropped, as HF's NoBadWordsLogitsProcessor does."""
+    eos_ids: the ids min_length bans; a one-token bad word equal to one of them is dropped, as HF's NoBadWordsLogitsProcessor does.
+    constraint (a constraint.BoundConstraint, TokenConstraint.bind's result): a token automaton as the last stage - every token the row's
+    state does not allow becomes -inf (the constrained C entry points).  The state history `states()` int32 [rows, steps + 1] belongs to
+    this object, one per generation: column 0 holds each row's start state, the picks store the state behind every token they pick, and
+    all of them address it by the generated-token index, as they do the token history."""
 
     def __init__(self, V: int, device, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_length: int = 0, eos_ids=(),
-                 suppress_tokens=None, begin_suppress_tokens=None, bad_words_ids=None):
+                 suppress_tokens=None, begin_suppress_tokens=None, bad_words_ids=None, constraint=None):
         V = int(V)
         if V <= 0:
             raise ValueError(f"logits processors: a vocabulary of {V} columns")
@@ -754,10 +758,19 @@ class LogitsProcessors:
         self.V, self.penalty, self.ngram, self.min_length = V, pen, int(no_repeat_ngram_size), int(min_length)
         self.suppress, self.begin_suppress = ids("suppress_tokens", suppress_tokens), ids("begin_suppress_tokens", begin_suppress_tokens)
         self.words = words
-        self.active = bool(pen != 1.0 or self.ngram > 0 or words or (self.min_length > 0 and eos) or self.suppress or self.begin_suppress)
+        self.active = bool(pen != 1.0 or self.ngram > 0 or words or (self.min_length > 0 and eos) or self.suppress or self.begin_suppress
+                           or constraint is not None)
         if self.active and V > L.AKI_LOGITS_PROCESS_MAX_V:
             raise ValueError(f"logits processors: a vocabulary of {V} is above {L.AKI_LOGITS_PROCESS_MAX_V}")
         dev = torch.device(device)
+        if constraint is not None:
+            if constraint.V != V:
+                raise ValueError(f"the constraint was built for V = {constraint.V}, the logits have {V} columns")
+            t_ = constraint.table
+            if t_.dtype != torch.int16 or t_.dim() != 2 or t_.shape[0] != constraint.n_states or t_.shape[1] < V or not t_.is_contiguous() \
+                    or constraint.row_start.dtype != torch.int32 or t_.device.type != dev.type or constraint.row_start.device != t_.device:
+                raise AkiError("logits processors: the constraint's table is contiguous int16 [n_states, >= V] and row_start int32, on the device")
+        self.constraint, self._states = constraint, None
         i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev) if v else None
         self._eos, self._sup, self._bsup = i64(eos), i64(self.suppress), i64(self.begin_suppress)
         self._bad = i64([t for w in words for t in w])
@@ -777,6 +790,44 @@ class LogitsProcessors:
         if self._scores is None or self._scores.shape[0] != B or self._scores.device != torch.device(device):
             self._scores = torch.empty((B, (self.V + 3) // 4 * 4), dtype=torch.float32, device=device)
         return self._scores
+
+    def states(self, rows: int, steps: Optional[int] = None) -> torch.Tensor:
+        """The constraint's state history, int32 [rows, steps + 1]: allocated by the first call (which has to name `steps`, the number of
+        tokens the generation can pick), column 0 filled with the rows' start states and the rest with -1 (no state: a row is left
+        unmasked), then kept for the life of this object - a captured graph holds its address."""
+        c = self.constraint
+        if c is None:
+            raise AkiError("logits processors: states() needs a constraint")
+        if self._states is None:
+            if steps is None or int(steps) < 0:
+                raise AkiError("logits processors: the first states() call names the number of steps")
+            if c.rows != int(rows):
+                raise ValueError(f"the constraint was bound for {c.rows} rows, the call has {rows}")
+            self._states = torch.full((int(rows), int(steps) + 1), -1, dtype=torch.int32, device=c.table.device)
+            self._states[:, 0] = c.row_start
+        elif self._states.shape[0] != int(rows) or (steps is not None and int(steps) + 1 > self._states.shape[1]):
+            raise AkiError(f"logits processors: the state history is {tuple(self._states.shape)}, the call wants {rows} rows and {steps} steps; "
+                           "one LogitsProcessors serves one generation")
+        return self._states
+
+    def _constraint_args(self, rows: int, steps: Optional[int]):
+        """(table, table_ld, n_states, states, states_ld) of the constrained C entry points, or None without a constraint."""
+        if self.constraint is None:
+            return None
+        st, t_ = self.states(rows, steps), self.constraint.table
+        return (_ptr(t_), t_.stride(0), self.constraint.n_states, _ptr(st), st.shape[1])
+
+    def advance_states(self, next_ids: torch.Tensor, step: int, done: Optional[torch.Tensor] = None) -> None:
+        """For a loop that picks on the host (argmax or sample_next over apply()'s scores; the pick kernels store the state themselves):
+        states[:, step + 1] = the state behind next_ids in states[:, step], rows with done[b] keep theirs.  No-op without a constraint."""
+        if self.constraint is None or self._states is None or int(step) + 1 >= self._states.shape[1]:
+            return
+        st, tbl = self._states, self.constraint.table
+        cur = st[:, int(step)]
+        ok = (cur >= 0) & (next_ids >= 0) & (next_ids < self.V)
+        nxt = tbl[cur.clamp(min=0).long(), next_ids.clamp(0, self.V - 1)].to(torch.int32)
+        nxt = torch.where(ok, nxt, torch.full_like(nxt, -1))
+        st[:, int(step) + 1] = nxt if done is None else torch.where(done.bool(), cur, nxt)
 
     def apply(self, logits: torch.Tensor, out: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, step: int = 0,
               cache_len: Optional[torch.Tensor] = None, start_len: Optional[torch.Tensor] = None,
@@ -800,10 +851,14 @@ class LogitsProcessors:
         if tokens is not None and tokens.shape[1] == 0:
             tokens = None
         head, tail = self._tail()
-        L.check(L.load().aki_logits_process(_ptr(logits), _dt(logits), B, self.V, logits.stride(0), _ptr(out), out.stride(0), _ptr(tokens),
-                                            0 if tokens is None else tokens.shape[1], _ptr(cache_len), _ptr(start_len), int(step), _ptr(done),
-                                            *head, _ptr(self._eos), 0 if self._eos is None else self._eos.numel(), *tail, _stream()),
-                "aki_logits_process")
+        args = (_ptr(logits), _dt(logits), B, self.V, logits.stride(0), _ptr(out), out.stride(0), _ptr(tokens),
+                0 if tokens is None else tokens.shape[1], _ptr(cache_len), _ptr(start_len), int(step), _ptr(done),
+                *head, _ptr(self._eos), 0 if self._eos is None else self._eos.numel(), *tail)
+        con = self._constraint_args(B, tokens.shape[1] if tokens is not None else (int(step) + 1 if cache_len is None else None))
+        if con is not None:
+            L.check(L.load().aki_logits_process_constrained(*args, *con, _stream()), "aki_logits_process_constrained")
+            return out
+        L.check(L.load().aki_logits_process(*args, _stream()), "aki_logits_process")
         return out
 
 
@@ -849,6 +904,11 @@ def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
         head, tail = processors._tail()
         emb = (None, None, 0, 0, 0, None) if embed is None else \
             (_ptr(w), _ptr(extra), int(max_orig), 0 if extra is None else extra.shape[0], d, _ptr(next_embeds))
+        con = processors._constraint_args(B, tokens.shape[1] if tokens is not None else (1 if cache_len is None else None))
+        if con is not None:
+            L.check(L.load().aki_greedy_pick_constrained(*common, *emb, _ptr(sc), sc.stride(0), *head, *tail, *con, _stream()),
+                    "aki_greedy_pick_constrained")
+            return next_ids
         L.check(L.load().aki_greedy_pick_processed(*common, *emb, _ptr(sc), sc.stride(0), *head, *tail, _stream()), "aki_greedy_pick_processed")
         return next_ids
     if embed is None:
@@ -926,9 +986,13 @@ def sample_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
     if scores.dim() != 2 or scores.shape[0] != B or scores.shape[1] < V:
         raise AkiError("sample_pick: scores is f32 [B, >= V]")
     head, tail = processors._tail() if active else ((1.0, 0, 0), (None, 0, None, 0, None, None, 0, 0))
-    L.check(L.load().aki_sample_pick(*common, *emb, _ptr(scores), scores.stride(0), *head, *tail, int(step), float(temperature), int(top_k),
-                                     float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _ptr(probs_out),
-                                     0 if probs_out is None else probs_out.stride(0), _stream()), "aki_sample_pick")
+    args = (*common, *emb, _ptr(scores), scores.stride(0), *head, *tail, int(step), float(temperature), int(top_k), float(top_p),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _ptr(probs_out), 0 if probs_out is None else probs_out.stride(0))
+    con = processors._constraint_args(B, tokens.shape[1] if tokens is not None else (int(step) + 1 if cache_len is None else None)) if active else None
+    if con is not None:
+        L.check(L.load().aki_sample_pick_constrained(*args, *con, _stream()), "aki_sample_pick_constrained")
+        return next_ids
+    L.check(L.load().aki_sample_pick(*args, _stream()), "aki_sample_pick")
     return next_ids
 
 

@@ -853,6 +853,47 @@ int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const 
                     int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
                     uint64_t offset, float* probs_out, int64_t ld_probs, void* stream);
 
+/* ---- constrained decoding: a deterministic automaton over token ids, applied on the pick path.  Purely additive: AKI_ABI_VERSION was
+ * not bumped (it stays 17).  The three entry points below are aki_logits_process, aki_greedy_pick_processed and aki_sample_pick with
+ * five more arguments in front of `stream`; everything else is as documented there.
+ *   table      int16 [n_states, table_ld] on the device, table_ld >= V: table[s, v] = the state behind token v in state s, negative = v is
+ *              not allowed in s.  Rows are scanned with 16-byte loads when table is 16-byte aligned and table_ld % 8 == 0, else one
+ *              entry at a time.  0 < n_states <= 32767.
+ *   states     int32 [B, states_ld] on the device, states_ld >= 1: the state HISTORY of every row - states[b, n] is the state in which
+ *              generated token n is picked; column 0 holds the row's start state (the caller fills it).
+ * The mask is the last processor stage: with n the generated-token index of the entry point (before it is clamped to tokens_ld) and
+ * s = states[b, n], every column v < V with table[s, v] < 0 becomes -inf; the other columns are left as the earlier stages made them.
+ * Rows with done[b] != 0 are copied unprocessed; n outside [0, states_ld) or s outside [0, n_states) leaves the row unmasked.
+ * The two picks also store states[b, n + 1] = done[b] ? s : table[s, next] (where n + 1 < states_ld), next to tokens[b, n]: the state is
+ * addressed by the token index like the history, never carried in a counter, so a replayed graph, a rewind of cache_len and a repeated
+ * step read and write the right column.  The caller makes sure that every state a row can reach allows at least one token. */
+int aki_logits_process_constrained(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
+                                   const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step,
+                                   const uint8_t* done, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length,
+                                   const int64_t* eos_ids, int32_t n_eos, const int64_t* suppress_ids, int32_t n_suppress,
+                                   const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids,
+                                   const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld,
+                                   int32_t n_states, int32_t* states, int32_t states_ld, void* stream);
+
+int aki_greedy_pick_constrained(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                                uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                                int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                                int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                                int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                                const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                                int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states,
+                                int32_t states_ld, void* stream);
+
+int aki_sample_pick_constrained(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                                uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                                int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                                int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                                int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                                const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                                int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                                uint64_t offset, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld, int32_t n_states,
+                                int32_t* states, int32_t states_ld, void* stream);
+
 /* ---- beam search on the device (beam.hip).  HF `GenerationMixin` beam search with a `BeamSearchScorer`, the algorithm AKI._beam_search
  * runs on the host: 2K candidates per step, hypotheses normalised by generated_length ** length_penalty, at most K per sample.
  * Purely additive: AKI_ABI_VERSION was not bumped (it stays 17). */

@@ -11,8 +11,13 @@ DeviceGenerator (ops.sample_pick inside the greedy loop) - and reports both per-
 --logprobs K (K >= 0; -1 = off, the default): every round also runs with output_logprobs=True, top_logprobs=K (one ops.token_logprob launch
 behind each pick), alternating with the plain leg in the same process; reports the per-token cost it adds (median and spread over the
 rounds) and merges the result into profiles/logprob_bench.json under "batch<B>_k<K>".
+--constraint: every round also runs greedy under a token constraint (on top of --repetition-penalty where given: a penalty composes with a
+constraint, a banning processor does not), alternating with the other legs in the same process: a 16-state cycle in which state s allows the
+ids v with v % 16 == s (one automaton per sample at --batch B, joined into one table), so every token reads one table row per sequence.
+Reports the per-token cost over the processors leg (over the plain leg without one) and merges the result into
+profiles/constraint_bench.json under "batch<B>".
     python tools/generate_bench.py [--new 256] [--fp8] [--txt 64] [--repetition-penalty 1.2] [--no-repeat-ngram 3]
-                                   [--sample --temperature 0.8 --top-k 50 --top-p 0.9] [--batch 8] [--logprobs 8 --rounds 4]"""
+                                   [--sample --temperature 0.8 --top-k 50 --top-p 0.9] [--batch 8] [--logprobs 8 --rounds 4] [--constraint]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -37,6 +42,7 @@ def main():
     ap.add_argument("--no-share-prompt-kv", action="store_true", help="with --num-return-sequences: replicate the prompt K/V N times (the A/B form; "
                     "without it the leg switches lang_model.share_prompt_kv on)")
     ap.add_argument("--logprobs", type=int, default=-1, help="K >= 0: one more leg per round with output_logprobs=True, top_logprobs=K (-1: off)")
+    ap.add_argument("--constraint", action="store_true", help="one more leg per round: greedy under a 16-state token constraint")
     a = ap.parse_args()
     lp_kw = dict(output_logprobs=True, top_logprobs=a.logprobs) if a.logprobs >= 0 else None
     proc_kw = {}
@@ -78,6 +84,18 @@ def main():
         import aki_amd
         run(16, generator=torch.Generator(device=dev).manual_seed(0), **sample_kw)
         run(16, generator=aki_amd.DeviceGenerator(0), **sample_kw)
+    con_kw = None
+    if a.constraint:
+        import numpy as np
+        from aki_amd.constraint import TokenConstraint
+        head = model.lang_model.get_output_embeddings()          # V': the logits' width
+        V = int(head.max_original_id) + 1 + int(head.additional_out_features) if hasattr(head, "max_original_id") else int(head.out_features)
+        nxt = np.full((16, V), -1, dtype=np.int32)
+        for s_ in range(16):
+            nxt[s_, s_::16] = (s_ + 1) % 16
+        cyc = TokenConstraint.from_table(nxt, np.ones(16, dtype=bool))
+        con_kw = dict(proc_kw, constraint=cyc if a.batch == 1 else [cyc] * a.batch)
+        run(16, **con_kw)
     res = {"prompt_tokens_lm_stream": bench.N_TXT - 1 + bench.NV, "new_tokens": a.new, "fp8": bool(a.fp8), "mxfp4": bool(a.mxfp4), "w4_chain": bool(a.w4_chain), "rounds": []}
     if proc_kw:
         res["processors"] = proc_kw
@@ -109,7 +127,7 @@ def main():
         if proc_kw:
             t1p, _ = run(1, **proc_kw)
             tnp, toks_p = run(a.new, **proc_kw)
-            assert toks_p.shape == (1, a.new)
+            assert toks_p.shape == (a.batch, a.new)
             if ref_p is None:
                 ref_p = toks_p.clone()
             assert torch.equal(ref_p, toks_p), "generate with processors is not reproducible from call to call"
@@ -117,6 +135,15 @@ def main():
             r = res["rounds"][-1]
             r["processed_ms_per_new_token_after_the_first"] = round(per_p, 4)
             r["processors_added_us_per_token"] = round((per_p - r["ms_per_new_token_after_the_first"]) * 1e3, 2)
+        if con_kw:
+            t1c, _ = run(1, **con_kw)
+            tnc, toks_c = run(a.new, **con_kw)
+            assert toks_c.shape == (a.batch, a.new) and bool((toks_c % 16 == torch.arange(a.new, device=dev)[None, :] % 16).all()), "not a walk of the cycle"
+            per_c = (tnc - t1c) * 1e3 / (a.new - 1)
+            r = res["rounds"][-1]
+            r["constrained_ms_per_new_token_after_the_first"] = round(per_c, 4)
+            base = r.get("processed_ms_per_new_token_after_the_first", r["ms_per_new_token_after_the_first"])
+            r["constraint_added_us_per_token"] = round((per_c - base) * 1e3, 2)
         if a.sample:
             r = res["rounds"][-1]
             for leg, gen in (("torch_generator", lambda: torch.Generator(device=dev).manual_seed(0)), ("device_generator", lambda: aki_amd.DeviceGenerator(0))):
@@ -157,6 +184,23 @@ def main():
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "logprob_bench.json")
         book = json.load(open(path)) if os.path.exists(path) else {}
         book[f"batch{a.batch}_k{a.logprobs}"] = res
+        with open(path, "w") as f:
+            json.dump(book, f, indent=1, sort_keys=True)
+            f.write("\n")
+    if con_kw:
+        med = lambda k: sorted(r[k] for r in res["rounds"])[len(res["rounds"]) // 2]
+        spread = lambda k: [min(r[k] for r in res["rounds"]), max(r[k] for r in res["rounds"])]
+        res["constraint"] = {"states": 16 * a.batch, "over": "processors" if proc_kw else "plain",
+                             "added_us_per_token_median": med("constraint_added_us_per_token"),
+                             "added_us_per_token_min_max": spread("constraint_added_us_per_token"),
+                             "plain_ms_per_token_median": med("ms_per_new_token_after_the_first"),
+                             "plain_ms_per_token_min_max": spread("ms_per_new_token_after_the_first")}
+        if proc_kw:
+            res["constraint"]["processed_ms_per_token_median"] = med("processed_ms_per_new_token_after_the_first")
+            res["constraint"]["processed_ms_per_token_min_max"] = spread("processed_ms_per_new_token_after_the_first")
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "constraint_bench.json")
+        book = json.load(open(path)) if os.path.exists(path) else {}
+        book[f"batch{a.batch}"] = res
         with open(path, "w") as f:
             json.dump(book, f, indent=1, sort_keys=True)
             f.write("\n")

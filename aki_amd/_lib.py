@@ -20,6 +20,7 @@ AKI_ABI_VERSION = 17
 AKI_LOGITS_PROCESS_MAX_V = 131072
 AKI_BEAM_MAX_K, AKI_BEAM_MAX_EOS, AKI_KV_BEAM_REORDER_CHUNK = 16, 8, 16
 AKI_LOGPROB_MAX_TOP, AKI_LOGPROB_MAX_V = 8, 262144
+AKI_SLOT_MAX_ROWS = 16
 
 
 class AkiError(RuntimeError):
@@ -260,6 +261,8 @@ SIGNATURES = {
     "aki_token_logprob": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                     C.c_int32, C.c_void_p]),
+    "aki_kv_slot_admit": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p]),
+    "aki_slot_tick": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p]),
     "aki_sft_collate_pad": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 4),
     "aki_mma_mask_to_table_workspace_bytes": (C.c_size_t, [C.c_int32] * 2),
     "aki_mma_mask_to_table": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),

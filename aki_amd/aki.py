@@ -5,6 +5,7 @@ Reference: /root/reference/codes/open_flamingo/src/aki.py  (__init__ :10-50, set
 """
 from __future__ import annotations
 
+import itertools
 from collections import namedtuple
 from dataclasses import dataclass
 from typing import List, Optional, Tuple, Union
@@ -20,6 +21,7 @@ except Exception:  # pragma: no cover - transformers is present in this image
 from . import ops
 from .helpers import PerceiverResampler
 from .phi3 import AkiKVCache, DecodeGraph
+from .slots import SlotScheduler, slot_capacity
 from .vlm import VLMWithLanguageStream
 
 
@@ -212,6 +214,78 @@ def _parse_generate_kwargs(kwargs: dict, default_pad_id, default_eos_ids, from_c
                            device_rng=device_rng, length_penalty=length_penalty, early_stopping=early_stopping, n_ret=n_ret,
                            max_new_tokens=max_new_tokens, eos_ids=eos_ids, pad_id=pad_id, use_graph=use_graph, processors=processors,
                            output_logprobs=output_logprobs, top_logprobs=top_logprobs, constraint=constraint)
+
+
+# The keyword arguments of `generate_many`, resolved by _parse_many_kwargs: max_new_tokens is the default budget of a request.
+ManyOptions = namedtuple("ManyOptions", "max_new_tokens eos_ids pad_id use_graph processors")
+
+# what generate_many refuses, with the reason: (keyword, the test that it is in force, why)
+MANY_REFUSED = (
+    ("do_sample", lambda v: bool(v), "the device sampler keys a draw by the row index, so a draw would depend on the schedule"),
+    ("constraint", lambda v: v is not None, "the constraint's state history is bound to the rows of one generation, not to a slot that changes hands"),
+    ("num_beams", lambda v: v is not None and int(v) > 1, "beam search re-orders the rows of its cache; a slot is one row"),
+    ("num_return_sequences", lambda v: v is not None and int(v) > 1, "it needs sampling; pass the prompt as several requests instead"),
+    ("output_logprobs", lambda v: bool(v), "the log-probability buffers are laid out per generation, not per slot"),
+    ("past_key_values", lambda v: v is not None, "every request is prefilled into its slot; continue a cache with generate()"),
+)
+
+
+def _parse_many_kwargs(kwargs: dict, default_pad_id, default_eos_ids) -> ManyOptions:
+    """Every keyword of `generate_many` popped from `kwargs` and checked, before any device work.  The keywords of MANY_REFUSED raise
+    NotImplementedError naming the keyword and the reason; whatever is left over raises ValueError (_reject_unused_kwargs)."""
+    for name, in_force, why in MANY_REFUSED:
+        if name in kwargs and in_force(kwargs[name]):
+            raise NotImplementedError(f"generate_many does not take {name}: {why}")
+        kwargs.pop(name, None)
+    max_new_tokens = int(kwargs.pop("max_new_tokens", kwargs.pop("max_length", 20)))
+    if max_new_tokens < 1:
+        raise ValueError("generate_many: max_new_tokens must be at least 1")
+    eos = kwargs.pop("eos_token_id", None)
+    if eos is None:
+        eos = default_eos_ids()
+    eos_ids = set([eos] if isinstance(eos, int) else (eos or []))
+    pad_id = kwargs.pop("pad_token_id", default_pad_id)
+    use_graph = kwargs.pop("use_graph", None)
+    processors = _pop_processor_kwargs(kwargs)
+    _reject_unused_kwargs(kwargs)
+    return ManyOptions(max_new_tokens=max_new_tokens, eos_ids=eos_ids, pad_id=pad_id, use_graph=True if use_graph is None else bool(use_graph),
+                       processors=processors)
+
+
+def _many_requests(requests, default_budget: int):
+    """`generate_many`'s requests -> a list of (vision_x or None, lang_x [1, T], budget), shapes and budgets checked on the host."""
+    out = []
+    for i, r in enumerate(requests):
+        if not isinstance(r, (tuple, list)) or len(r) not in (2, 3):
+            raise ValueError(f"request {i}: (vision_x, lang_x) or (vision_x, lang_x, max_new_tokens) is expected")
+        vx, lx = r[0], r[1]
+        budget = int(default_budget if len(r) == 2 or r[2] is None else r[2])
+        if not torch.is_tensor(lx) or lx.dim() != 2 or lx.shape[0] != 1 or lx.shape[1] < 1 or lx.dtype != torch.long:
+            raise ValueError(f"request {i}: lang_x is an int64 tensor [1, T] without padding, T >= 1")
+        if vx is not None and (not torch.is_tensor(vx) or vx.dim() != 6 or vx.shape[0] != 1):
+            raise ValueError(f"request {i}: vision_x is [1, T_img, 1, C, H, W] or None")
+        if budget < 1:
+            raise ValueError(f"request {i}: a budget of {budget} tokens; at least 1 is expected")
+        out.append((vx, lx, budget))
+    return out
+
+
+def _pick_rows_torch(logits, ids, pad_token_id: int, eos_ids, done, tokens, cache_len, start_len, done_at, proc=None):
+    """What ops.greedy_pick does with advance = 0, in torch, for logits that are not bf16 (an f32 model: generate() picks those on the host
+    loop too): next = pad for done rows, else the argmax of the (processed) row; tokens[b, cache_len[b] - start_len[b]] = next; a row whose
+    next is an eos id becomes done at that index.  In place, on the device, no synchronisation."""
+    x = logits if proc is None else proc.apply(logits, tokens=tokens, cache_len=cache_len, start_len=start_len, done=done)
+    was_done = done.bool()
+    nxt = torch.where(was_done, torch.full_like(ids, pad_token_id), x.float().argmax(dim=-1))
+    t = (cache_len - start_len).long()
+    ok = (t >= 0) & (t < tokens.shape[1])
+    col = t.clamp(0, tokens.shape[1] - 1)[:, None]
+    tokens.scatter_(1, col, torch.where(ok, nxt, tokens.gather(1, col)[:, 0])[:, None])
+    ids.copy_(nxt)
+    if eos_ids is not None:
+        hit = (nxt[:, None] == eos_ids[None, :]).any(-1) & ~was_done
+        done_at.copy_(torch.where(hit, t.to(torch.int32), done_at))
+        done.copy_(torch.where(hit, torch.ones_like(done), done))
 
 
 def _device_sampler_args(opt: GenerateOptions):
@@ -718,6 +792,186 @@ class AkiMethods:
         shape = lambda x: None if x is None else x.reshape(B, N, T, k)
         return AkiScoreOutput(logprobs=buf.lp.reshape(B, N, T), sum_logprobs=buf.lp.sum(1).reshape(B, N), lengths=lengths,
                               top_token_ids=shape(buf.top_ids), top_logprobs=shape(buf.top_lp))
+
+    last_many_stats = None      # after generate_many: the SlotScheduler's counters (slots.SlotScheduler.stats) as a dict
+
+    def _prefill_request(self, vision_x, lang_x):
+        """One request of generate_many, prefilled at batch 1 into a cache of exactly its length: (cache, logits [1, V']).  Without an image
+        the ids go to the language model as they are (what forward does with vision_x=None)."""
+        if vision_x is not None:
+            cache, logits, _ = self._prefill_prompt(vision_x, lang_x, None, 0)
+            return cache, logits
+        out = self.lang_model(input_ids=lang_x, use_cache=True, cache_capacity=lang_x.shape[1], last_token_logits=True)
+        return out.past_key_values, out.logits[:, 0]
+
+    def _generate_one(self, vision_x, lang_x, **kwargs):
+        """generate() for one request of generate_many, as a 1-D tensor.  A request without an image is continued from a cache of its first
+        T - 1 ids (generate itself prefills image prompts only)."""
+        if vision_x is not None:
+            return self.generate(vision_x, lang_x, **kwargs)[0]
+        if lang_x.shape[1] < 2:
+            raise ValueError("a request without an image needs at least 2 prompt ids")
+        budget = int(kwargs.get("max_new_tokens", 20))
+        cache = self.lang_model(input_ids=lang_x[:, :-1], use_cache=True, cache_capacity=lang_x.shape[1] + budget,
+                                last_token_logits=True).past_key_values
+        return self.generate(None, lang_x[:, -1:], past_key_values=cache, **kwargs)[0]
+
+    @staticmethod
+    def _cut_behind_eos(row: torch.Tensor, eos_t):
+        """A 1-D token row cut behind its first EOS (EOS included)."""
+        if eos_t is None or row.numel() == 0:
+            return row
+        finished, first = _first_eos(row[None], eos_t)
+        return row[: int(first[0]) + 1] if bool(finished[0]) else row
+
+    @torch.no_grad()
+    def generate_many(self, requests, slots: int = 8, **kwargs):
+        """In-flight batching: a queue of requests served over a fixed number of decode rows ("slots").  A static batch steps a finished row
+        on with pad tokens until its longest row has finished; here a finished row is retired and refilled from the queue while the others
+        stay mid-sequence, so answers of very different lengths keep the batch occupied.
+
+        requests: a sequence of (vision_x, lang_x) or (vision_x, lang_x, max_new_tokens); vision_x [1, T_img, 1, C, H, W] or None, lang_x
+        int64 [1, T] without padding.  Returns a list of 1-D int64 device tensors in request order, each cut behind its first EOS (EOS
+        included) or at its budget.  `last_many_stats` holds the scheduler's counters afterwards.
+        Keywords: max_new_tokens (the default budget), eos_token_id, pad_token_id, use_graph and the logits processors of PROCESSOR_KWARGS
+        (one ops.LogitsProcessors for all rows: it reads each row's own history and index, and a refilled row starts with an empty one).
+        Refused with NotImplementedError (MANY_REFUSED): do_sample, constraint, num_beams > 1, num_return_sequences > 1, output_logprobs,
+        past_key_values; a LongRoPE model whose slot capacity exceeds original_max_position_embeddings (HF picks the factor set per batch,
+        not per row).  Any other keyword: ValueError.  slots above ops.SLOT_MAX_ROWS: ValueError.
+        The loop (aki_amd/slots.py holds its bookkeeping):
+          * one AkiKVCache of `slots` rows and capacity max(expanded prompt length + budget), computed from the ids on the host; the per-row
+            tokens / done / done_at / start_len / limit / ids buffers are allocated once - the captured step holds their addresses;
+          * admit: a batch-1 prefill, ops.kv_slot_admit into the slot's rows, the slot's state reset in place, token 0 picked from the
+            prefill's logits on row views (advance=False), one ops.slot_tick - a budget of 1 or an EOS as token 0 retires the row at once;
+          * decode: ONE DecodeGraph over the slot cache with the pick and ops.slot_tick inside, captured once per call; the host looks
+            every 8th replay (its only synchronisation), retires finished slots and admits pending requests into them.  A slot with
+            nothing pending stays done and parked (slot_tick keeps it on one dead cache row).
+        f32 models (logits the pick kernel does not take) replay the plain step and pick with torch operations on the device, still without
+        a synchronisation per token.  slots == 1 or a single request: generate() per request (the one-launch chain is the batch-1 path)."""
+        opt = _parse_many_kwargs(kwargs, self.pad_token_id, self.default_eos_token_ids)
+        slots = int(slots)
+        if slots < 1 or slots > ops.SLOT_MAX_ROWS:
+            raise ValueError(f"generate_many: 1 <= slots <= {ops.SLOT_MAX_ROWS} (the rows the skinny decode GEMMs take) is expected, got {slots}")
+        reqs = _many_requests(requests, opt.max_new_tokens)
+        self.last_many_stats = None
+        if not reqs:
+            self.last_many_stats = SlotScheduler(0, slots).stats()
+            return []
+        eos_list = sorted(opt.eos_ids)
+        pk = opt.processors
+        if slots == 1 or len(reqs) == 1:
+            kw = dict({k: v for k, v in pk.items()}, eos_token_id=eos_list, pad_token_id=opt.pad_id)
+            outs, sched = [], SlotScheduler(len(reqs), 1)
+            for vx, lx, budget in reqs:
+                row = self._generate_one(vx, lx, max_new_tokens=budget, **kw)
+                eos_t = torch.tensor(eos_list, dtype=torch.long, device=row.device) if eos_list else None
+                outs.append(self._cut_behind_eos(row, eos_t).clone())
+            self.last_many_stats = dict(sched.stats(), per_request_generate=True)
+            return outs
+        slots = min(slots, len(reqs))
+        lm = self.lang_model
+        flat = torch.cat([lx[0] for _, lx, _ in reqs]).tolist()       # one copy for all prompts, ahead of any launch
+        ends = list(itertools.accumulate(lx.shape[1] for _, lx, _ in reqs))
+        ids_host = [flat[e - lx.shape[1]:e] for e, (_, lx, _) in zip(ends, reqs)]
+        capacity = slot_capacity(ids_host, [b for _, _, b in reqs], self.media_token_id, self.num_tokens_per_vis)
+        rot = lm.model.rotary_emb
+        if rot.short is not None and capacity > rot.orig_max:
+            raise NotImplementedError(f"generate_many on a LongRoPE model with a slot capacity of {capacity} rows above "
+                                      f"original_max_position_embeddings = {rot.orig_max}: HF picks the factor set per batch, not per row")
+        dev = reqs[0][1].device
+        cfg = lm.config
+        H = cfg.num_attention_heads
+        Dh = getattr(cfg, "head_dim", None) or cfg.hidden_size // H
+        dtype = lm.get_input_embeddings().weight.dtype
+        cache = AkiKVCache(len(lm.model.layers), slots, H, Dh, capacity, dtype, dev, lm.kv_cache_dtype)    # valid_bits None: a lone prompt has no padding
+        max_budget = max(b for _, _, b in reqs)
+        tokens = torch.full((slots, max_budget), opt.pad_id, dtype=torch.long, device=dev)
+        done = torch.ones(slots, dtype=torch.uint8, device=dev)
+        done_at = torch.zeros(slots, dtype=torch.int32, device=dev)
+        start_len = torch.zeros(slots, dtype=torch.int32, device=dev)
+        limit = torch.ones(slots, dtype=torch.int32, device=dev)
+        eos_t = torch.tensor(eos_list, dtype=torch.long, device=dev) if eos_list else None
+        head = lm.get_output_embeddings()
+        width = int(head.max_original_id) + 1 + int(head.additional_out_features) if hasattr(head, "max_original_id") else int(head.out_features)
+
+        def processors():
+            p = ops.LogitsProcessors(width, dev, pk["repetition_penalty"], pk["no_repeat_ngram_size"],
+                                     max(int(pk["min_length"]), int(pk["min_new_tokens"])), eos_list, pk["suppress_tokens"],
+                                     pk["begin_suppress_tokens"], pk["bad_words_ids"])
+            return p if p.active else None
+
+        # the processed pick keeps a score scratch per batch size, whose address the captured step holds: the admit's one-row pick gets its own
+        proc, proc1 = processors(), processors()
+        on_device = dev.type == "cuda" and dtype == torch.bfloat16
+        tick = dict(done=done, done_at=done_at, start_len=start_len, limit=limit)
+        pick = dict(pad_token_id=opt.pad_id, eos_ids=eos_t, done=done, tokens=tokens, start_len=start_len, done_at=done_at)
+        if proc is not None:
+            pick["processors"] = proc
+            if on_device:
+                proc.scores(slots, dev)                 # allocated ahead of the capture
+        if opt.use_graph:
+            stepper = DecodeGraph(lm, cache, greedy=dict(pick, tick=tick)) if on_device else DecodeGraph(lm, cache)
+            ids = stepper.ids
+        else:
+            stepper, ids = None, torch.zeros(slots, dtype=torch.long, device=dev)
+        sched = SlotScheduler(len(reqs), slots, period=8)
+        results = {}
+        row = lambda x, s: x[s:s + 1]
+
+        def admit(req, slot):
+            vx, lx, budget = reqs[req]
+            src, logits = self._prefill_request(vx, lx)
+            ops.kv_slot_admit(src, cache, slot)
+            cache.host_len = max(cache.host_len, src.host_len)
+            cache.cache_len[slot:slot + 1].copy_(src.cache_len)
+            start_len[slot:slot + 1].copy_(src.cache_len)
+            done[slot] = 0
+            done_at[slot] = -1
+            limit[slot] = budget
+            tokens[slot] = opt.pad_id
+            args = dict(pad_token_id=opt.pad_id, eos_ids=eos_t, done=row(done, slot), tokens=row(tokens, slot), start_len=row(start_len, slot),
+                        done_at=row(done_at, slot))
+            if on_device:                               # token 0, from the prefill: the existing pick at B = 1 on row views
+                ops.greedy_pick(logits.contiguous(), row(ids, slot), cache_len=row(cache.cache_len, slot), advance=False,
+                                **(args if proc1 is None else dict(args, processors=proc1)))
+            else:
+                _pick_rows_torch(logits, row(ids, slot), cache_len=row(cache.cache_len, slot), proc=proc1, **args)
+            ops.slot_tick(row(done, slot), row(done_at, slot), row(cache.cache_len, slot), row(start_len, slot), row(limit, slot))
+            return budget == 1
+
+        def step(n):
+            for _ in range(n):
+                if stepper is not None and on_device:
+                    stepper.step_greedy()
+                    continue
+                if stepper is not None:
+                    lg = stepper.step(ids)
+                elif on_device:
+                    lg = lm.decode_step(input_ids=ids, past_key_values=cache, advance=False)
+                    ops.greedy_pick(lg, ids, cache_len=cache.cache_len, advance=True, **pick)
+                else:
+                    lg = lm.decode_step(input_ids=ids, past_key_values=cache)
+                if not on_device:
+                    _pick_rows_torch(lg, ids, opt.pad_id, eos_t, done, tokens, cache.cache_len, start_len, done_at, proc)
+                ops.slot_tick(cache_len=cache.cache_len, **tick)
+
+        def look():
+            state = torch.stack([done.to(torch.int32), done_at, cache.cache_len]).tolist()       # the one synchronisation
+            d, at, ln = state
+            # host_len bounds the row the next step appends at.  A parked row stays on its one dead cache row (ops.slot_tick), so under the
+            # captured step, whose grid is sized by the capacity, only the live rows count; eager steps size their grid by host_len and
+            # need every row's keys inside it.
+            live = [n for n, dd in zip(ln, d) if not dd]
+            cache.host_len = max(live, default=0) if stepper is not None else max(ln)
+            return d, at
+
+        def retire(req, slot, n):
+            results[req] = tokens[slot, :n].clone()
+
+        sched.run(admit, step, look, retire, room=lambda: capacity - cache.host_len)
+        self.last_many_stats = sched.stats()
+        self._post_forward_hook()
+        return sched.in_request_order(results)
 
     @torch.no_grad()
     def generate(self, vision_x, lang_x, image_size=None, attention_mask=None, past_key_values=None,

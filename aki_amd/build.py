@@ -24,7 +24,7 @@ LIB = os.path.join(LIBDIR, "libaki_mi355x.so")
 LAB_LIB = os.path.join(LIBDIR, "libaki_mi355x_lab.so")
 LAB_SOURCES = ["api.hip", "gemm_bf16.hip", "gemm_tn_bf16.hip", "mma_attn_bf16.hip", "mma_attn64_bf16.hip", "decode.hip", "decode_chain.hip"]
 LAB_ONLY_SOURCES = []     # experiments that exist in the lab library only (none at present)
-SOURCES = ["api.hip", "gemm_bf16.hip", "gemm_tn_bf16.hip", "mma_attn_bf16.hip", "mma_attn64_bf16.hip", "attn_nc_bf16.hip", "decode.hip", "decode_chain.hip", "beam.hip", "logprob.hip", "chunk_attn.hip", "train_kernels.hip", "attn_bwd_bf16.hip", "fp8_quant.hip", "mxfp4.hip", "simple_f32.hip", "aux_kernels.hip", "stack.hip"]
+SOURCES = ["api.hip", "gemm_bf16.hip", "gemm_tn_bf16.hip", "mma_attn_bf16.hip", "mma_attn64_bf16.hip", "attn_nc_bf16.hip", "decode.hip", "decode_chain.hip", "beam.hip", "logprob.hip", "slots.hip", "chunk_attn.hip", "train_kernels.hip", "attn_bwd_bf16.hip", "fp8_quant.hip", "mxfp4.hip", "simple_f32.hip", "aux_kernels.hip", "stack.hip"]
 ARCH = "gfx950"
 # per-file flags: the 64-row attention core places single VALU instructions in MFMA gaps by hand - SLP vectorisation turns its
 # f32 adds into v_pk_add_f32 plus moves (MI355X guide: packed f32 VALU beside MFMAs is an anti-lever)

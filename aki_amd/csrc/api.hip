@@ -87,6 +87,9 @@ int kv_beam_reorder_launch(void* const* table, int n_tensors, const int* parent,
 int token_logprob_launch(const void* logits, int in_f32, int rows, int V, int ld, const int64_t* ids, const int64_t* tokens, int tokens_ld,
                          const int* cache_len, const int* start_len, int step, const unsigned char* skip, const int* done_at, int top_k,
                          float* out_logprob, int64_t* out_top_ids, float* out_top_logprobs, int out_ld, int out_cols, hipStream_t s);
+int kv_slot_admit_launch(void* const* table, int n_tensors, const int* src_len, int H, int cap_src, int cap_dst, int slot, int row_bytes,
+                         int vec_bytes, int host_len, hipStream_t s);
+int slot_tick_launch(unsigned char* done, int* done_at, int* cache_len, const int* start_len, const int* limit, int B, hipStream_t s);
 int sft_collate_launch(const int64_t* ids, const int64_t* labels, const int64_t* mask, const int* offsets, int B, int T_out,
                        int64_t pad_id, int64_t ignore_index, int left, int64_t* out_ids, int64_t* out_labels, int64_t* out_mask,
                        hipStream_t s);
@@ -1013,6 +1016,24 @@ int aki_token_logprob(const void* logits, int32_t dtype, int32_t rows, int32_t V
   return token_logprob_launch(logits, dtype == AKI_DT_F32, rows, V, (int)ld, ids, tokens, tokens ? (int)tokens_ld : 0, cache_len, start_len,
                               step, skip, done_at, top_k, out_logprob, out_top_ids, out_top_logprobs, (int)out_ld, out_cols,
                               (hipStream_t)stream);
+}
+
+int aki_kv_slot_admit(void* const* table, int32_t n_tensors, const int32_t* src_len, int32_t H, int32_t cap_src, int32_t cap_dst, int32_t B,
+                      int32_t slot, int32_t row_bytes, int32_t vec_bytes, int32_t host_len, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(table && src_len && n_tensors > 0 && H > 0 && cap_src > 0 && cap_dst > 0 && B > 0 && row_bytes > 0);
+  AKI_CHECK_ARG(slot >= 0 && slot < B && host_len >= 0 && host_len <= cap_src && host_len <= cap_dst);
+  if ((vec_bytes != 4 && vec_bytes != 16) || row_bytes % vec_bytes != 0 || H > 65535 || n_tensors > 65535) return AKI_ERR_UNSUPPORTED;
+  if ((int64_t)host_len * (row_bytes / vec_bytes) >= (1ll << 40)) return AKI_ERR_UNSUPPORTED;      // the grid's x extent stays below 2^30
+  if (host_len == 0) return AKI_OK;
+  return kv_slot_admit_launch(table, n_tensors, src_len, H, cap_src, cap_dst, slot, row_bytes, vec_bytes, host_len, (hipStream_t)stream);
+}
+
+int aki_slot_tick(uint8_t* done, int32_t* done_at, int32_t* cache_len, const int32_t* start_len, const int32_t* limit, int32_t B, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(done && done_at && cache_len && start_len && limit && B > 0);
+  if (B > AKI_SLOT_MAX_ROWS) return AKI_ERR_UNSUPPORTED;
+  return slot_tick_launch(done, done_at, cache_len, start_len, limit, B, (hipStream_t)stream);
 }
 
 size_t aki_mma_mask_to_table_workspace_bytes(int32_t B, int32_t L) {

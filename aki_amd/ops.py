@@ -1185,7 +1185,77 @@ def kv_beam_reorder(table: KVBeamTable, parent: torch.Tensor, start_len: torch.T
                                          table.H, table.capacity, table.row_bytes, pos_lo, pos_hi, _stream()), "aki_kv_beam_reorder")
 
 
-SKINNY_NORM_FUSED = True        # tools (decode_bench.py --norm-launch): False = the RMSNorm of 2-8 row decode GEMMs as a launch of its own
+# ---- in-flight batching (slots.hip) -----------------------------------------------------------------------------------------------
+SLOT_MAX_ROWS = L.AKI_SLOT_MAX_ROWS
+
+
+def kv_slot_admit(src_cache, dst_cache, slot: int) -> None:
+    """One prefilled sequence into row `slot` of a larger cache (aki_kv_slot_admit): dst.k[i][slot, :, :len] = src.k[i][0, :, :len], the same
+    for v, all layers in one launch, len = src.cache_len[0] read on the device; every other byte of dst stays as it was.  src_cache: an
+    AkiKVCache of one sequence [1, H, cap_src, Dh]; dst_cache: one of B rows [B, H, cap_dst, Dh] in the same format (an fp8_e4m3 pair moves
+    its f32 scales in a second launch).  Bytes only: nothing is converted.  Rows move as 16-byte vectors when the row bytes and every tensor
+    address allow, as 4-byte words otherwise.  dst.cache_len is not touched: the row's state belongs to the caller."""
+    slot = int(slot)
+    sk, dk = list(src_cache.k) + list(src_cache.v), list(dst_cache.k) + list(dst_cache.v)
+    if getattr(src_cache, "group", 1) != 1 or getattr(dst_cache, "group", 1) != 1:
+        raise AkiError("kv_slot_admit: neither cache may be grouped (share_prefix)")
+    if src_cache.kv_dtype != dst_cache.kv_dtype or len(sk) != len(dk) or not sk:
+        raise AkiError("kv_slot_admit: both caches hold the same layers in the same kv_dtype (nothing is converted)")
+    s0, d0 = sk[0], dk[0]
+    if s0.dim() != 4 or d0.dim() != 4 or s0.shape[0] != 1 or s0.shape[1] != d0.shape[1] or s0.shape[3] != d0.shape[3] or s0.dtype != d0.dtype:
+        raise AkiError(f"kv_slot_admit: a source [1, H, cap, Dh] and a destination [B, H, cap, Dh] of one H, Dh and element type are expected, "
+                       f"got {tuple(s0.shape)} {s0.dtype} and {tuple(d0.shape)} {d0.dtype}")
+    B, H, cap_dst, Dh = d0.shape
+    cap_src = s0.shape[2]
+    if not 0 <= slot < B:
+        raise AkiError(f"kv_slot_admit: slot {slot} is outside the destination's {B} rows")
+    host_len = int(src_cache.host_len)
+    if not 0 <= host_len <= cap_src or host_len > cap_dst:
+        raise AkiError(f"kv_slot_admit: the source holds {host_len} of {cap_src} rows, the destination has room for {cap_dst}")
+    ln = src_cache.cache_len
+    if ln.dtype != torch.int32 or ln.numel() != 1 or not ln.is_cuda or ln.device != d0.device:
+        raise AkiError("kv_slot_admit: the source's cache_len is int32 [1] on the destination's device")
+
+    def launch(src, dst):
+        a, b = src[0], dst[0]
+        for t_ in src:
+            if t_.shape != a.shape or t_.dtype != a.dtype or not t_.is_contiguous() or not t_.is_cuda or t_.device != d0.device:
+                raise AkiError("kv_slot_admit: contiguous source tensors of one shape and dtype on the destination's device are expected")
+        for t_ in dst:
+            if t_.shape != b.shape or t_.dtype != b.dtype or not t_.is_contiguous() or t_.device != d0.device:
+                raise AkiError("kv_slot_admit: contiguous destination tensors of one shape and dtype on one device are expected")
+        row_bytes = (a.shape[3] if a.dim() == 4 else 1) * a.element_size()
+        if row_bytes % 4 or any(t_.data_ptr() % 4 for t_ in src + dst):
+            raise AkiError(f"kv_slot_admit: rows of {row_bytes} bytes - a multiple of 4 bytes in 4-byte aligned tensors is expected")
+        vec = 16 if row_bytes % 16 == 0 and all(t_.data_ptr() % 16 == 0 for t_ in src + dst) else 4
+        table = torch.tensor([t_.data_ptr() for t_ in src + dst], dtype=torch.int64, device=d0.device)
+        L.check(L.load().aki_kv_slot_admit(_ptr(table), len(src), _ptr(ln), H, cap_src, cap_dst, B, slot, row_bytes, vec, host_len, _stream()),
+                "aki_kv_slot_admit")
+
+    launch(sk, dk)
+    if src_cache.k_scale is not None:                 # fp8_e4m3: one f32 scale per (head, position) - [*, H, cap] read as rows of 4 bytes
+        ss, ds = list(src_cache.k_scale) + list(src_cache.v_scale), list(dst_cache.k_scale) + list(dst_cache.v_scale)
+        if len(ss) != len(sk) or len(ds) != len(dk) or any(t_.shape != s0.shape[:3] for t_ in ss) or any(t_.shape != d0.shape[:3] for t_ in ds):
+            raise AkiError("kv_slot_admit: the scales of an fp8_e4m3 cache are [rows, H, capacity] per layer")
+        launch(ss, ds)
+
+
+def slot_tick(done: torch.Tensor, done_at: torch.Tensor, cache_len: torch.Tensor, start_len: torch.Tensor, limit: torch.Tensor) -> None:
+    """The per-row token budget, one launch right behind the pick (aki_slot_tick; capturable: no host value is read).  With generated =
+    cache_len[b] - start_len[b] + 1 tokens picked by row b: a live row with generated >= limit[b] gets done[b] = 1 and done_at[b] =
+    generated - 1; a done row (done_at >= 0) is parked at cache_len[b] = start_len[b] + done_at[b], so the pad-token steps it is still fed
+    overwrite one dead cache row; a live row under its budget is not touched.  done uint8 [B], the others int32 [B], B <= SLOT_MAX_ROWS."""
+    B = done.numel()
+    for t_, dt in ((done, torch.uint8), (done_at, torch.int32), (cache_len, torch.int32), (start_len, torch.int32), (limit, torch.int32)):
+        if t_.dtype != dt or t_.dim() != 1 or t_.numel() != B or not t_.is_contiguous() or not t_.is_cuda or t_.device != done.device:
+            raise AkiError(f"slot_tick: contiguous GPU tensors [B] are expected - done uint8, done_at / cache_len / start_len / limit int32; "
+                           f"got {t_.dtype} {tuple(t_.shape)}")
+    if not 1 <= B <= SLOT_MAX_ROWS:
+        raise AkiError(f"slot_tick: 1 <= B <= {SLOT_MAX_ROWS} rows are expected, got {B}")
+    L.check(L.load().aki_slot_tick(_ptr(done), _ptr(done_at), _ptr(cache_len), _ptr(start_len), _ptr(limit), B, _stream()), "aki_slot_tick")
+
+
+SKINNY_NORM_FUSED = True       # tools (decode_bench.py --norm-launch): False = the RMSNorm of 2-8 row decode GEMMs as a launch of its own
 
 
 def decode_linear(x: torch.Tensor, w: torch.Tensor, rms_weight: torch.Tensor, eps: float, act: int = ACT_NONE,

@@ -219,7 +219,8 @@ class DecodeGraph:
         replayed step and writes the next step's input ids itself: one replay per token (`step_greedy`), nothing else on the stream.
         With a "seed" key the dict holds ops.sample_pick's arguments instead (temperature, top_k, top_p, seed, offset): the captured pick
         is the device sampler, whose draw depends on the device-side token index, so one capture serves every replay.
-        With a "logprob" key (the in-loop arguments of ops.token_logprob) that launch is captured right behind the pick."""
+        With a "logprob" key (the in-loop arguments of ops.token_logprob) that launch is captured right behind the pick.
+        With a "tick" key (ops.slot_tick's done / done_at / start_len / limit) the rows' token budgets are ticked behind the pick too."""
         self.lm, self.cache = lm, cache
         B = cache.cache_len.shape[0]
         self.ids = torch.zeros((B,), dtype=torch.long, device=cache.cache_len.device)
@@ -246,11 +247,13 @@ class DecodeGraph:
             else:                                   # the pick advances cache_len itself: one launch less per token
                 self.logits = lm.decode_step(input_ids=self.ids, past_key_values=cache, advance=False)
                 args = dict(self.greedy)
-                logprob = args.pop("logprob", None)
+                logprob, tick = args.pop("logprob", None), args.pop("tick", None)
                 pick = ops.sample_pick if "seed" in args else ops.greedy_pick
                 pick(self.logits, self.ids, cache_len=cache.cache_len, advance=True, **args)
                 if logprob is not None:             # right behind the pick: it scores the token at the index the pick just wrote
                     ops.token_logprob(self.logits, **logprob)
+                if tick is not None:                # the rows' token budgets: retires and parks rows on the device (generate_many)
+                    ops.slot_tick(cache_len=cache.cache_len, **tick)
         cache.host_len = saved_host
 
     def step_greedy(self) -> torch.Tensor:

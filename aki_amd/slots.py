@@ -1,0 +1,115 @@
+"""In-flight batching for generate: the host-side bookkeeping of `AkiMethods.generate_many` (aki_amd/aki.py).
+
+A decode batch is a fixed number of rows ("slots") over one KV cache and one captured step.  A row that has finished - its EOS, or its
+token budget (ops.slot_tick) - is parked on the device; at the host's next look it is retired and the next pending request is admitted
+into it (a batch-1 prefill + ops.kv_slot_admit) while the other rows stay mid-sequence.  Nothing in this module touches a device: the
+scheduler is driven through three callbacks, so a fake token source exercises the very loop generate_many runs."""
+from __future__ import annotations
+
+from collections import deque
+from typing import Callable, List, Optional, Sequence, Tuple
+
+
+def expanded_length(ids: Sequence[int], media_token_id: int, n_vis_tokens: int) -> int:
+    """The length of a prompt in the language stream: every `<image>` placeholder among `ids` is replaced by the n_vis_tokens vision tokens of
+    its image (the splice of VLMWithLanguageStream._prepare_inputs_for_forward), so T ids become T + (n_vis_tokens - 1) * n_images rows."""
+    ids = list(ids)
+    return len(ids) + (int(n_vis_tokens) - 1) * sum(1 for i in ids if int(i) == int(media_token_id))
+
+
+def slot_capacity(prompts: Sequence[Sequence[int]], budgets: Sequence[int], media_token_id: int, n_vis_tokens: int) -> int:
+    """Rows of the slot cache: the largest (expanded prompt length + token budget) over the requests - computed from the ids on the host."""
+    if len(prompts) != len(budgets):
+        raise ValueError("slot_capacity: one budget per prompt")
+    return max((expanded_length(p, media_token_id, n_vis_tokens) + int(b) for p, b in zip(prompts, budgets)), default=0)
+
+
+class SlotScheduler:
+    """Which request sits in which slot, which pending request goes where, and the counters of a run.  Pure bookkeeping.
+
+    `run(admit, step, look, retire)` is the whole loop:
+      admit(request, slot) -> bool   put the request into the slot (its token 0 included); True when it may have finished at once
+                                     (a budget of one token), which makes the scheduler look before it steps
+      step(n)                        n decode steps of all slots, no synchronisation
+      look() -> (done, done_at)      the only synchronisation: per slot, whether its row has finished and the index of its last token
+      retire(request, slot, n)       the row's first n = done_at + 1 tokens are the request's result: copy them out now
+      room() -> int (optional)       decode steps that still fit before the next look must happen (the cache's capacity)
+    The host looks every `period` steps.  A finished slot is retired at the first look after it finished and refilled then, lowest free
+    slot first, requests in their order; with nothing pending it stays done and parked.  The run ends at the first look after the last
+    row finished.  Counters: steps (decode steps replayed), total_row_steps = slots * steps, live_row_steps (steps that produced a returned
+    token: a request of n tokens costs n - 1, token 0 comes from its prefill), admits, looks."""
+
+    def __init__(self, n_requests: int, slots: int, period: int = 8):
+        n_requests, slots, period = int(n_requests), int(slots), int(period)
+        if n_requests < 0 or slots < 1 or period < 1:
+            raise ValueError("SlotScheduler: n_requests >= 0, slots >= 1 and period >= 1 are expected")
+        self.n_requests, self.slots, self.period = n_requests, slots, period
+        self.slot_request: List[Optional[int]] = [None] * slots
+        self.pending = deque(range(n_requests))
+        self.lengths: List[Optional[int]] = [None] * n_requests      # tokens returned per request, once retired
+        self.served_in: List[Optional[int]] = [None] * n_requests    # the slot that served it
+        self.steps = self.live_row_steps = self.total_row_steps = self.admits = self.looks = 0
+
+    def busy(self) -> bool:
+        return any(r is not None for r in self.slot_request)
+
+    def admissions(self) -> List[Tuple[int, int]]:
+        """(slot, request) for every free slot that gets a pending request now; the slots are marked taken."""
+        out = []
+        for slot in range(self.slots):
+            if not self.pending:
+                break
+            if self.slot_request[slot] is None:
+                req = self.pending.popleft()
+                self.slot_request[slot] = req
+                out.append((slot, req))
+        self.admits += len(out)
+        return out
+
+    def stepped(self, n: int) -> None:
+        self.steps += n
+        self.total_row_steps += self.slots * n
+
+    def retirements(self, done, done_at) -> List[Tuple[int, int, int]]:
+        """One look's result -> (slot, request, tokens) of every occupied slot whose row has finished; the slots are freed."""
+        self.looks += 1
+        out = []
+        for slot, req in enumerate(self.slot_request):
+            if req is not None and done[slot]:
+                n = int(done_at[slot]) + 1
+                if n < 1:
+                    raise RuntimeError(f"slot {slot} is done without a last-token index")
+                self.slot_request[slot] = None
+                self.lengths[req], self.served_in[req] = n, slot
+                self.live_row_steps += n - 1
+                out.append((slot, req, n))
+        return out
+
+    def run(self, admit: Callable[[int, int], bool], step: Callable[[int], None], look: Callable[[], tuple],
+            retire: Callable[[int, int, int], None], room: Optional[Callable[[], int]] = None) -> None:
+        while True:
+            quick = False
+            for slot, req in self.admissions():
+                quick = bool(admit(req, slot)) or quick
+            if not self.busy():
+                return
+            if not quick:
+                n = self.period if room is None else min(self.period, int(room()))
+                if n < 1:
+                    raise RuntimeError("SlotScheduler: no room for a decode step although a slot is live")
+                step(n)
+                self.stepped(n)
+            done, done_at = look()
+            for slot, req, n in self.retirements(done, done_at):
+                retire(req, slot, n)
+
+    def in_request_order(self, results: dict) -> list:
+        """{request: result} -> the results as a list in request order (every request must have been served)."""
+        missing = [r for r in range(self.n_requests) if r not in results]
+        if missing:
+            raise RuntimeError(f"requests {missing} were never served")
+        return [results[r] for r in range(self.n_requests)]
+
+    def stats(self) -> dict:
+        return {"slots": self.slots, "period": self.period, "requests": self.n_requests, "steps": self.steps,
+                "live_row_steps": self.live_row_steps, "total_row_steps": self.total_row_steps, "admits": self.admits, "looks": self.looks}

@@ -967,6 +967,30 @@ int aki_token_logprob(const void* logits, int32_t dtype, int32_t rows, int32_t V
                       const int32_t* done_at, int32_t top_k, float* out_logprob, int64_t* out_top_ids, float* out_top_logprobs,
                       int64_t out_ld, int32_t out_cols, void* stream);
 
+/* ---- in-flight batching (slots.hip): what `generate_many` launches to refill a finished row of a batch from a queue of requests.
+ * Purely additive: AKI_ABI_VERSION was not bumped (it stays 17). */
+#define AKI_SLOT_MAX_ROWS 16         /* rows of one aki_slot_tick: the decode batch the skinny decode GEMMs take */
+
+/* aki_kv_slot_admit - one prefilled sequence copied into row `slot` of a larger cache, every tensor in one launch.  `table` (DEVICE memory)
+ * holds 2 * n_tensors base addresses: first the sources [1, H, cap_src, row_bytes], then the destinations [B, H, cap_dst, row_bytes], pairwise
+ * (the K and V tensors of every layer; for an fp8_e4m3 cache the f32 scales are tensors with row_bytes 4, a launch of their own).
+ *   dst[slot, h, pos, :] = src[0, h, pos, :] for 0 <= pos < len, len = min(src_len[0], cap_src, cap_dst) read on the device (the source's
+ * cache_len); every other byte of a destination stays as it was.  Bytes only, nothing is converted.  vec_bytes is the unit the rows move in:
+ * 16 (row_bytes % 16 == 0 and every address in the table 16-byte aligned) or 4 (row_bytes % 4 == 0, addresses 4-byte aligned) - the caller,
+ * who wrote the table, states which.  host_len: a host bound of len (it sizes the grid only), 0 <= host_len <= min(cap_src, cap_dst); 0
+ * launches nothing.  AKI_ERR_INVALID_ARG: a null pointer, a count below 1, slot outside [0, B), host_len out of range.
+ * AKI_ERR_UNSUPPORTED: vec_bytes other than 4 / 16, row_bytes no multiple of it, H or n_tensors above 65535. */
+int aki_kv_slot_admit(void* const* table, int32_t n_tensors, const int32_t* src_len, int32_t H, int32_t cap_src, int32_t cap_dst, int32_t B,
+                      int32_t slot, int32_t row_bytes, int32_t vec_bytes, int32_t host_len, void* stream);
+
+/* aki_slot_tick - the per-row token budget of B <= AKI_SLOT_MAX_ROWS rows, one thread per row, launched right behind aki_greedy_pick (inside
+ * the captured step).  generated = cache_len[b] - start_len[b] + 1 is the number of tokens row b has picked (token 0 is picked from the
+ * prefill's logits with advance = 0).  A live row (done[b] == 0) with generated >= limit[b] gets done[b] = 1, done_at[b] = generated - 1.
+ * A done row with done_at[b] >= 0 - marked here or by the pick's eos check - is parked: cache_len[b] = start_len[b] + done_at[b], the cache
+ * row of the token it never feeds, so the pad-token steps a loop still gives it overwrite one dead row and never walk past its slab.  A live
+ * row under its budget is not touched.  done uint8, the others int32, all [B]. */
+int aki_slot_tick(uint8_t* done, int32_t* done_at, int32_t* cache_len, const int32_t* start_len, const int32_t* limit, int32_t B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

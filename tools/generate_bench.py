@@ -16,11 +16,103 @@ constraint, a banning processor does not), alternating with the other legs in th
 ids v with v % 16 == s (one automaton per sample at --batch B, joined into one table), so every token reads one table row per sequence.
 Reports the per-token cost over the processors leg (over the plain leg without one) and merges the result into
 profiles/constraint_bench.json under "batch<B>".
+--many: in-flight batching (many_bench below): 64 requests at this prompt with budgets 16..256 from a fixed seed, EOS off, at 8 and 16 slots;
+generate() over consecutive groups of `slots` requests (max_new_tokens = the group's largest budget) against generate_many, alternating in one
+process for at least 3 rounds.  Writes profiles/many_bench.json: returned tokens/s of both legs, the scheduler's counters, the occupancy
+the lengths alone predict for the static groups against the scheduler's live / total row-steps, and the share of wall time inside admits.
+    python tools/generate_bench.py [--many]
     python tools/generate_bench.py [--new 256] [--fp8] [--txt 64] [--repetition-penalty 1.2] [--no-repeat-ngram 3]
                                    [--sample --temperature 0.8 --top-k 50 --top-p 0.9] [--batch 8] [--logprobs 8 --rounds 4] [--constraint]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+
+
+def many_bench(a, model, dev):
+    """--many: 64 requests at the headline prompt, budgets from a fixed seed in 16..256, EOS off (random weights have no EOS behaviour, so the
+    budget IS the length distribution), at 8 and 16 slots.  Two legs alternate in one process: today's way - generate() over consecutive
+    groups of `slots` requests with max_new_tokens = the group's largest budget - and generate_many.  Writes profiles/many_bench.json."""
+    import bench
+    from aki_amd import ops
+    n_req = a.many_requests
+    g = torch.Generator(device="cpu").manual_seed(4242)
+    budgets = torch.randint(16, 257, (n_req,), generator=g).tolist()
+    reqs = []
+    for i in range(n_req):
+        vx, ids, _ = bench.synth_batch(1, dev, torch.bfloat16, model.media_token_id, seed=1000 + i)
+        reqs.append((vx, ids, budgets[i]))
+    # GPU time inside admits: an event in front of each batch-1 prefill and one behind the copy into the slot (the pick and the tick
+    # behind it are two short launches)
+    spans = []
+    real_prefill, real_admit = model._prefill_request, ops.kv_slot_admit
+
+    def prefill(vx, lx):
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        spans.append([ev, None])
+        return real_prefill(vx, lx)
+
+    def admit(src, dst, slot):
+        real_admit(src, dst, slot)
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        spans[-1][1] = ev
+
+    def static_leg(slots):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n = 0
+        for lo in range(0, n_req, slots):
+            grp = reqs[lo:lo + slots]
+            vx, ids = torch.cat([r[0] for r in grp]), torch.cat([r[1] for r in grp])
+            toks = model.generate(vx, ids, attention_mask=torch.ones_like(ids), max_new_tokens=max(r[2] for r in grp), eos_token_id=[])
+            n += sum(min(r[2], toks.shape[1]) for r in grp)       # returned tokens: each row up to its own budget
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, n
+
+    def many_leg(slots):
+        del spans[:]
+        model._prefill_request, ops.kv_slot_admit = prefill, admit
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            outs = model.generate_many(reqs, slots=slots, eos_token_id=[])
+            torch.cuda.synchronize()
+            wall = time.perf_counter() - t0
+        finally:
+            model._prefill_request, ops.kv_slot_admit = real_prefill, real_admit
+        assert [o.numel() for o in outs] == budgets
+        admit_ms = sum(s.elapsed_time(e) for s, e in spans)
+        return wall, sum(budgets), dict(model.last_many_stats), admit_ms
+
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    res = {"requests": n_req, "prompt_tokens_lm_stream": bench.N_TXT - 1 + bench.NV, "budgets": budgets, "budget_seed": 4242,
+           "method": "two legs alternating in one process, wall clock around each leg with a device synchronisation on both sides; "
+                     "tokens/s = returned tokens / wall time, prefills included", "slots": {}}
+    for slots in (8, 16):
+        groups = [budgets[lo:lo + slots] for lo in range(0, n_req, slots)]
+        predicted = sum(budgets) / sum(slots * max(grp) for grp in groups)
+        static_leg(slots), many_leg(slots)                        # warm-up: allocator, folds, capture path
+        rounds = []
+        for _ in range(max(3, a.rounds)):
+            ts, ns = static_leg(slots)
+            tm, nm, stats, admit_ms = many_leg(slots)
+            rounds.append({"static_tokens_per_s": round(ns / ts, 1), "many_tokens_per_s": round(nm / tm, 1), "static_s": round(ts, 3),
+                           "many_s": round(tm, 3), "admit_ms": round(admit_ms, 1), "admit_share_of_wall": round(admit_ms / (tm * 1e3), 4)})
+        res["slots"][str(slots)] = {
+            "rounds": rounds, "stats": stats,
+            "static_tokens_per_s_median": med([r["static_tokens_per_s"] for r in rounds]),
+            "many_tokens_per_s_median": med([r["many_tokens_per_s"] for r in rounds]),
+            "speedup_median": round(med([r["many_tokens_per_s"] / r["static_tokens_per_s"] for r in rounds]), 3),
+            "admit_share_of_wall_median": med([r["admit_share_of_wall"] for r in rounds]),
+            "static_occupancy_from_lengths": round(predicted, 4),          # sum of budgets / sum over groups of slots x group maximum
+            "many_occupancy_live_over_total": round(stats["live_row_steps"] / stats["total_row_steps"], 4),
+            "occupancy_bound_on_speedup": round(stats["live_row_steps"] / stats["total_row_steps"] / predicted, 3)}
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "many_bench.json")
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps({k: v for k, v in res.items() if k != "budgets"}))
 
 
 def main():
@@ -43,8 +135,11 @@ def main():
                     "without it the leg switches lang_model.share_prompt_kv on)")
     ap.add_argument("--logprobs", type=int, default=-1, help="K >= 0: one more leg per round with output_logprobs=True, top_logprobs=K (-1: off)")
     ap.add_argument("--constraint", action="store_true", help="one more leg per round: greedy under a 16-state token constraint")
+    ap.add_argument("--many", action="store_true", help="in-flight batching: generate() over static groups against generate_many, 64 requests with "
+                    "budgets 16..256 at 8 and 16 slots -> profiles/many_bench.json (the other legs are skipped)")
+    ap.add_argument("--many-requests", type=int, default=64)
     a = ap.parse_args()
-    lp_kw = dict(output_logprobs=True, top_logprobs=a.logprobs) if a.logprobs >= 0 else None
+    lp_kw =dict(output_logprobs=True, top_logprobs=a.logprobs) if a.logprobs >= 0 else None
     proc_kw = {}
     if a.repetition_penalty != 1.0:
         proc_kw["repetition_penalty"] = a.repetition_penalty
@@ -60,7 +155,9 @@ def main():
     if a.mxfp4:
         model.lang_model.enable_mxfp4()
     model.lang_model.model.decode_chain_w4 = bool(a.w4_chain)
-    vx, ids, am = bench.synth_batch(1, dev, torch.bfloat16, model.media_token_id, seed=1000)
+    if a.many:
+        return many_bench(a, model, dev)
+    vx, ids, am =bench.synth_batch(1, dev, torch.bfloat16, model.media_token_id, seed=1000)
     if a.batch > 1:
         vx, ids, am = vx.repeat(a.batch, 1, 1, 1, 1, 1), ids.repeat(a.batch, 1), am.repeat(a.batch, 1)
 

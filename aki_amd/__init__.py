@@ -9,7 +9,8 @@ from ._lib import AkiError  # noqa: F401
 _LAZY = {"AKI": ("aki", "AKI"), "create_model_and_transforms": ("factory", "create_model_and_transforms"),
          "build_aki": ("factory", "build_aki"), "AKIPretrained": ("modeling_aki", "AKI"), "DeviceGenerator": ("ops", "DeviceGenerator"),
          "AkiGenerateOutput": ("aki", "AkiGenerateOutput"), "AkiScoreOutput": ("aki", "AkiScoreOutput"),
-         "TokenConstraint": ("constraint", "TokenConstraint")}
+         "TokenConstraint": ("constraint", "TokenConstraint"), "RequestParams": ("slots", "RequestParams"),
+         "AkiRequestOutput": ("aki", "AkiRequestOutput")}
 
 
 def __getattr__(name):  # lazy: `import aki_amd` alone must not pull torch (tooling, build script)

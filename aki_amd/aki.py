@@ -21,7 +21,7 @@ except Exception:  # pragma: no cover - transformers is present in this image
 from . import ops
 from .helpers import PerceiverResampler
 from .phi3 import AkiKVCache, DecodeGraph
-from .slots import SlotScheduler, slot_capacity
+from .slots import RequestParams, SlotScheduler, request_seed, slot_capacity
 from .vlm import VLMWithLanguageStream
 
 
@@ -114,6 +114,17 @@ class AkiScoreOutput(ModelOutput):
     logprobs: Optional[torch.Tensor] = None
     sum_logprobs: Optional[torch.Tensor] = None
     lengths: Optional[torch.Tensor] = None
+    top_token_ids: Optional[torch.Tensor] = None
+    top_logprobs: Optional[torch.Tensor] = None
+
+
+@dataclass
+class AkiRequestOutput(ModelOutput):
+    """One request's result from `generate_many` when any request asked for log-probabilities.  tokens: what generate_many returns
+    without them, 1-D int64; logprobs f32 [n], top_token_ids int64 [n, k] and top_logprobs f32 [n, k] for the request's own
+    k = top_logprobs (None for k = 0), as in AkiGenerateOutput; all three None for a request that did not ask.  All on the device."""
+    tokens: Optional[torch.Tensor] = None
+    logprobs: Optional[torch.Tensor] = None
     top_token_ids: Optional[torch.Tensor] = None
     top_logprobs: Optional[torch.Tensor] = None
 
@@ -216,16 +227,19 @@ def _parse_generate_kwargs(kwargs: dict, default_pad_id, default_eos_ids, from_c
                            output_logprobs=output_logprobs, top_logprobs=top_logprobs, constraint=constraint)
 
 
-# The keyword arguments of `generate_many`, resolved by _parse_many_kwargs: max_new_tokens is the default budget of a request.
-ManyOptions = namedtuple("ManyOptions", "max_new_tokens eos_ids pad_id use_graph processors")
+# The keyword arguments of `generate_many`, resolved by _parse_many_kwargs: max_new_tokens is the default budget of a request, params the
+# RequestParams of a request that brings none, generator None or the ops.DeviceGenerator the sampled requests' seeds are derived from.
+ManyOptions = namedtuple("ManyOptions", "max_new_tokens eos_ids pad_id use_graph processors params generator")
 
 # what generate_many refuses, with the reason: (keyword, the test that it is in force, why)
 MANY_REFUSED = (
-    ("do_sample", lambda v: bool(v), "the device sampler keys a draw by the row index, so a draw would depend on the schedule"),
+    ("do_sample", lambda v: bool(v), "sampling belongs to a request, not to the call: pass RequestParams(do_sample=True, ...) in the request "
+                                     "tuple or as params="),
     ("constraint", lambda v: v is not None, "the constraint's state history is bound to the rows of one generation, not to a slot that changes hands"),
     ("num_beams", lambda v: v is not None and int(v) > 1, "beam search re-orders the rows of its cache; a slot is one row"),
     ("num_return_sequences", lambda v: v is not None and int(v) > 1, "it needs sampling; pass the prompt as several requests instead"),
-    ("output_logprobs", lambda v: bool(v), "the log-probability buffers are laid out per generation, not per slot"),
+    ("output_logprobs", lambda v: bool(v), "log-probabilities belong to a request, not to the call: pass RequestParams(logprobs=True, ...) in "
+                                           "the request tuple or as params="),
     ("past_key_values", lambda v: v is not None, "every request is prefilled into its slot; continue a cache with generate()"),
 )
 
@@ -247,18 +261,35 @@ def _parse_many_kwargs(kwargs: dict, default_pad_id, default_eos_ids) -> ManyOpt
     pad_id = kwargs.pop("pad_token_id", default_pad_id)
     use_graph = kwargs.pop("use_graph", None)
     processors = _pop_processor_kwargs(kwargs)
+    params = kwargs.pop("params", None)
+    if params is None:
+        params = RequestParams()
+    if not isinstance(params, RequestParams):
+        raise ValueError("generate_many: params is an aki_amd.RequestParams, the default of the requests that bring none")
+    params.check("default (params=)", ops.LOGPROB_MAX_TOP)
+    generator = kwargs.pop("generator", None)
+    if generator is not None and not isinstance(generator, ops.DeviceGenerator):
+        raise ValueError("generate_many: generator is an aki_amd.DeviceGenerator (the sampled requests' seeds are derived from it on the "
+                         "host) or None; a torch.Generator cannot seed the device sampler")
     _reject_unused_kwargs(kwargs)
     return ManyOptions(max_new_tokens=max_new_tokens, eos_ids=eos_ids, pad_id=pad_id, use_graph=True if use_graph is None else bool(use_graph),
-                       processors=processors)
+                       processors=processors, params=params, generator=generator)
 
 
-def _many_requests(requests, default_budget: int):
-    """`generate_many`'s requests -> a list of (vision_x or None, lang_x [1, T], budget), shapes and budgets checked on the host."""
+def _many_requests(requests, default_budget: int, default_params: Optional[RequestParams] = None):
+    """`generate_many`'s requests -> a list of (vision_x or None, lang_x [1, T], budget, RequestParams), shapes, budgets and parameters
+    checked on the host."""
     out = []
+    default_params = RequestParams() if default_params is None else default_params
     for i, r in enumerate(requests):
-        if not isinstance(r, (tuple, list)) or len(r) not in (2, 3):
-            raise ValueError(f"request {i}: (vision_x, lang_x) or (vision_x, lang_x, max_new_tokens) is expected")
+        if not isinstance(r, (tuple, list)) or len(r) not in (2, 3, 4):
+            raise ValueError(f"request {i}: (vision_x, lang_x), (vision_x, lang_x, max_new_tokens) or (vision_x, lang_x, max_new_tokens or "
+                             "None, RequestParams) is expected")
         vx, lx = r[0], r[1]
+        rp = default_params if len(r) < 4 or r[3] is None else r[3]
+        if not isinstance(rp, RequestParams):
+            raise ValueError(f"request {i}: its fourth entry is an aki_amd.RequestParams")
+        rp.check(i, ops.LOGPROB_MAX_TOP)
         budget = int(default_budget if len(r) == 2 or r[2] is None else r[2])
         if not torch.is_tensor(lx) or lx.dim() != 2 or lx.shape[0] != 1 or lx.shape[1] < 1 or lx.dtype != torch.long:
             raise ValueError(f"request {i}: lang_x is an int64 tensor [1, T] without padding, T >= 1")
@@ -266,8 +297,30 @@ def _many_requests(requests, default_budget: int):
             raise ValueError(f"request {i}: vision_x is [1, T_img, 1, C, H, W] or None")
         if budget < 1:
             raise ValueError(f"request {i}: a budget of {budget} tokens; at least 1 is expected")
-        out.append((vx, lx, budget))
+        out.append((vx, lx, budget, rp))
     return out
+
+
+def _many_seeds(reqs, generator) -> List[Optional[int]]:
+    """The 64-bit Philox key of every sampled request (None for the others), on the host.  A request's own `seed` is used as it is; the
+    others get slots.request_seed(S, offset, r) with r the request's position: (S, offset) = (generator.seed, generator.next_offset()) -
+    the offset is taken ONCE per generate_many call, whether or not anything samples - or, without a generator, S = 64 bits from torch's
+    CPU default generator (so torch.manual_seed reproduces a call and successive calls differ; drawn only when a request needs it) and
+    offset 0.  No device work."""
+    offset = generator.next_offset() if generator is not None else 0
+    base = generator.seed if generator is not None else None
+    seeds = []
+    for r, (_, _, _, rp) in enumerate(reqs):
+        if not rp.do_sample:
+            seeds.append(None)
+        elif rp.seed is not None:
+            seeds.append(int(rp.seed))
+        else:
+            if base is None:
+                hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
+                base = (hi << 32) | lo
+            seeds.append(request_seed(base, offset, r))
+    return seeds
 
 
 def _pick_rows_torch(logits, ids, pad_token_id: int, eos_ids, done, tokens, cache_len, start_len, done_at, proc=None):
@@ -805,16 +858,23 @@ class AkiMethods:
         return out.past_key_values, out.logits[:, 0]
 
     def _generate_one(self, vision_x, lang_x, **kwargs):
-        """generate() for one request of generate_many, as a 1-D tensor.  A request without an image is continued from a cache of its first
-        T - 1 ids (generate itself prefills image prompts only)."""
+        """generate() for one request of generate_many, as a 1-D tensor - with output_logprobs an AkiGenerateOutput of the one row's fields.
+        A request without an image is continued from a cache of its first T - 1 ids (generate itself prefills image prompts only)."""
+        def row0(out):
+            if not isinstance(out, AkiGenerateOutput):
+                return out[0]
+            first = lambda x: None if x is None else x[0]
+            return AkiGenerateOutput(sequences=out.sequences[0], logprobs=first(out.logprobs), top_token_ids=first(out.top_token_ids),
+                                     top_logprobs=first(out.top_logprobs))
+
         if vision_x is not None:
-            return self.generate(vision_x, lang_x, **kwargs)[0]
+            return row0(self.generate(vision_x, lang_x, **kwargs))
         if lang_x.shape[1] < 2:
             raise ValueError("a request without an image needs at least 2 prompt ids")
         budget = int(kwargs.get("max_new_tokens", 20))
         cache = self.lang_model(input_ids=lang_x[:, :-1], use_cache=True, cache_capacity=lang_x.shape[1] + budget,
                                 last_token_logits=True).past_key_values
-        return self.generate(None, lang_x[:, -1:], past_key_values=cache, **kwargs)[0]
+        return row0(self.generate(None, lang_x[:, -1:], past_key_values=cache, **kwargs))
 
     @staticmethod
     def _cut_behind_eos(row: torch.Tensor, eos_t):
@@ -830,19 +890,41 @@ class AkiMethods:
         on with pad tokens until its longest row has finished; here a finished row is retired and refilled from the queue while the others
         stay mid-sequence, so answers of very different lengths keep the batch occupied.
 
-        requests: a sequence of (vision_x, lang_x) or (vision_x, lang_x, max_new_tokens); vision_x [1, T_img, 1, C, H, W] or None, lang_x
-        int64 [1, T] without padding.  Returns a list of 1-D int64 device tensors in request order, each cut behind its first EOS (EOS
-        included) or at its budget.  `last_many_stats` holds the scheduler's counters afterwards.
-        Keywords: max_new_tokens (the default budget), eos_token_id, pad_token_id, use_graph and the logits processors of PROCESSOR_KWARGS
-        (one ops.LogitsProcessors for all rows: it reads each row's own history and index, and a refilled row starts with an empty one).
-        Refused with NotImplementedError (MANY_REFUSED): do_sample, constraint, num_beams > 1, num_return_sequences > 1, output_logprobs,
-        past_key_values; a LongRoPE model whose slot capacity exceeds original_max_position_embeddings (HF picks the factor set per batch,
-        not per row).  Any other keyword: ValueError.  slots above ops.SLOT_MAX_ROWS: ValueError.
+        requests: a sequence of (vision_x, lang_x), (vision_x, lang_x, max_new_tokens) or (vision_x, lang_x, max_new_tokens or None,
+        RequestParams); vision_x [1, T_img, 1, C, H, W] or None, lang_x int64 [1, T] without padding.  Returns a list of 1-D int64 device
+        tensors in request order, each cut behind its first EOS (EOS included) or at its budget.  `last_many_stats` holds the scheduler's
+        counters afterwards.
+        Keywords: max_new_tokens (the default budget), eos_token_id, pad_token_id, use_graph, the logits processors of PROCESSOR_KWARGS
+        (one ops.LogitsProcessors for all rows: it reads each row's own history and index, and a refilled row starts with an empty one),
+        params (the RequestParams of the requests that bring none) and generator (an aki_amd.DeviceGenerator or None).
+        Sampling and log-probabilities belong to the REQUEST (aki_amd.RequestParams), never to the call:
+          * do_sample=True with temperature, top_k, top_p: the device sampler with that row's own values (ops.sample_pick_rows: the four
+            per-slot arrays are written in place at admit and read by the captured step).  bf16 on the GPU only; on an f32 model a sampled
+            request is a ValueError before any device work.  A greedy request in such a call is a top_k = 1 row: the greedy pick's token.
+            A call in which nothing samples runs exactly the greedy launches.
+          * the seed rule: a request's draws are Philox4x32-10(key = its seed, counter = (generated-token index, 0, 0, 0)) - they depend
+            on the request's seed and nothing else, not on its slot, the schedule or its neighbours, and they are the draws of
+            generate(..., do_sample=True, generator=DeviceGenerator(seed)) for that request alone (which is what slots == 1 runs).
+            seed=None: slots.request_seed(S, offset, r), r the request's position in `requests`, with (S, offset) taken from
+            `generator` - its offset is bumped ONCE per generate_many call, whether or not anything samples - or, with generator=None,
+            S = 64 bits drawn on the host from torch's CPU default generator (torch.manual_seed reproduces a call; successive calls
+            differ) and offset 0.  A torch.Generator as generator: ValueError.
+          * logprobs=True with top_logprobs=k <= ops.LOGPROB_MAX_TOP: the raw-distribution values generate(output_logprobs=True) reports
+            (before processors, temperature and filters), one ops.token_logprob behind each pick, launched only when a request asks.
+            The call then returns a list of AkiRequestOutput(tokens, logprobs [n], top_token_ids [n, k], top_logprobs [n, k]), the
+            three extra fields None for the requests that did not ask (and the top fields for k = 0).
+          Bad values (temperature <= 0, top_p outside (0, 1], top_k < 0, top_logprobs outside the limit or without logprobs, a seed outside
+          [0, 2^64)): ValueError naming the request, before any device work.
+        Refused with NotImplementedError (MANY_REFUSED): constraint, num_beams > 1, num_return_sequences > 1, past_key_values, and the
+        CALL-WIDE do_sample / output_logprobs keywords (use RequestParams); a LongRoPE model whose slot capacity exceeds
+        original_max_position_embeddings (HF picks the factor set per batch, not per row).  Any other keyword (temperature, top_k, top_p,
+        top_logprobs among them): ValueError.  slots above ops.SLOT_MAX_ROWS: ValueError.  Per-request logits processors are not offered.
         The loop (aki_amd/slots.py holds its bookkeeping):
           * one AkiKVCache of `slots` rows and capacity max(expanded prompt length + budget), computed from the ids on the host; the per-row
             tokens / done / done_at / start_len / limit / ids buffers are allocated once - the captured step holds their addresses;
-          * admit: a batch-1 prefill, ops.kv_slot_admit into the slot's rows, the slot's state reset in place, token 0 picked from the
-            prefill's logits on row views (advance=False), one ops.slot_tick - a budget of 1 or an EOS as token 0 retires the row at once;
+          * admit: a batch-1 prefill, ops.kv_slot_admit into the slot's rows, the slot's state (and sampler parameters) reset in place,
+            token 0 picked from the prefill's logits on row views (advance=False; scored there too when log-probabilities are on), one
+            ops.slot_tick - a budget of 1 or an EOS as token 0 retires the row at once;
           * decode: ONE DecodeGraph over the slot cache with the pick and ops.slot_tick inside, captured once per call; the host looks
             every 8th replay (its only synchronisation), retires finished slots and admits pending requests into them.  A slot with
             nothing pending stays done and parked (slot_tick keeps it on one dead cache row).
@@ -852,39 +934,71 @@ class AkiMethods:
         slots = int(slots)
         if slots < 1 or slots > ops.SLOT_MAX_ROWS:
             raise ValueError(f"generate_many: 1 <= slots <= {ops.SLOT_MAX_ROWS} (the rows the skinny decode GEMMs take) is expected, got {slots}")
-        reqs = _many_requests(requests, opt.max_new_tokens)
+        reqs = _many_requests(requests, opt.max_new_tokens, opt.params)
+        seeds = _many_seeds(reqs, opt.generator)
         self.last_many_stats = None
         if not reqs:
             self.last_many_stats = SlotScheduler(0, slots).stats()
             return []
         eos_list = sorted(opt.eos_ids)
         pk = opt.processors
+        sampled = any(rp.do_sample for *_, rp in reqs)
+        want_lp = any(rp.logprobs for *_, rp in reqs)
+        top = max(int(rp.top_logprobs) for *_, rp in reqs)
+        lm = self.lang_model
+        dev = reqs[0][1].device
+        dtype = lm.get_input_embeddings().weight.dtype
+        on_device = dev.type == "cuda" and dtype == torch.bfloat16
+        if sampled and not on_device:
+            raise ValueError("generate_many: a sampled request needs the device sampler, which needs bf16 logits on the GPU")
+
+        def result(tok, rp, lp=None, top_ids=None, top_lp=None):
+            """One request's return value: the tokens, or an AkiRequestOutput when any request of the call asked for log-probabilities."""
+            if not want_lp:
+                return tok
+            if not rp.logprobs:
+                return AkiRequestOutput(tokens=tok)
+            k = int(rp.top_logprobs)
+            return AkiRequestOutput(tokens=tok, logprobs=lp, top_token_ids=top_ids[:, :k].clone() if k else None,
+                                    top_logprobs=top_lp[:, :k].clone() if k else None)
+
         if slots == 1 or len(reqs) == 1:
             kw = dict({k: v for k, v in pk.items()}, eos_token_id=eos_list, pad_token_id=opt.pad_id)
             outs, sched = [], SlotScheduler(len(reqs), 1)
-            for vx, lx, budget in reqs:
-                row = self._generate_one(vx, lx, max_new_tokens=budget, **kw)
+            for (vx, lx, budget, rp), seed in zip(reqs, seeds):
+                kw_r = dict(kw, max_new_tokens=budget)
+                if rp.do_sample:                        # the same stream: key seed, counter (token index, row 0, offset 0)
+                    kw_r.update(do_sample=True, temperature=float(rp.temperature), top_k=int(rp.top_k), top_p=float(rp.top_p),
+                                generator=ops.DeviceGenerator(seed))
+                if rp.logprobs:
+                    kw_r.update(output_logprobs=True, top_logprobs=int(rp.top_logprobs))
+                out = self._generate_one(vx, lx, **kw_r)
+                row = out.sequences if rp.logprobs else out
                 eos_t = torch.tensor(eos_list, dtype=torch.long, device=row.device) if eos_list else None
-                outs.append(self._cut_behind_eos(row, eos_t).clone())
+                tok = self._cut_behind_eos(row, eos_t).clone()
+                n = tok.numel()
+                if rp.logprobs:
+                    cut = lambda x: None if x is None else x[:n].clone()
+                    outs.append(AkiRequestOutput(tokens=tok, logprobs=cut(out.logprobs), top_token_ids=cut(out.top_token_ids),
+                                                 top_logprobs=cut(out.top_logprobs)))
+                else:
+                    outs.append(result(tok, rp))
             self.last_many_stats = dict(sched.stats(), per_request_generate=True)
             return outs
         slots = min(slots, len(reqs))
-        lm = self.lang_model
-        flat = torch.cat([lx[0] for _, lx, _ in reqs]).tolist()       # one copy for all prompts, ahead of any launch
-        ends = list(itertools.accumulate(lx.shape[1] for _, lx, _ in reqs))
-        ids_host = [flat[e - lx.shape[1]:e] for e, (_, lx, _) in zip(ends, reqs)]
-        capacity = slot_capacity(ids_host, [b for _, _, b in reqs], self.media_token_id, self.num_tokens_per_vis)
+        flat = torch.cat([r[1][0] for r in reqs]).tolist()       # one copy for all prompts, ahead of any launch
+        ends = list(itertools.accumulate(r[1].shape[1] for r in reqs))
+        ids_host = [flat[e - r[1].shape[1]:e] for e, r in zip(ends, reqs)]
+        capacity = slot_capacity(ids_host, [r[2] for r in reqs], self.media_token_id, self.num_tokens_per_vis)
         rot = lm.model.rotary_emb
         if rot.short is not None and capacity > rot.orig_max:
             raise NotImplementedError(f"generate_many on a LongRoPE model with a slot capacity of {capacity} rows above "
                                       f"original_max_position_embeddings = {rot.orig_max}: HF picks the factor set per batch, not per row")
-        dev = reqs[0][1].device
         cfg = lm.config
         H = cfg.num_attention_heads
         Dh = getattr(cfg, "head_dim", None) or cfg.hidden_size // H
-        dtype = lm.get_input_embeddings().weight.dtype
         cache = AkiKVCache(len(lm.model.layers), slots, H, Dh, capacity, dtype, dev, lm.kv_cache_dtype)    # valid_bits None: a lone prompt has no padding
-        max_budget = max(b for _, _, b in reqs)
+        max_budget = max(r[2] for r in reqs)
         tokens = torch.full((slots, max_budget), opt.pad_id, dtype=torch.long, device=dev)
         done = torch.ones(slots, dtype=torch.uint8, device=dev)
         done_at = torch.zeros(slots, dtype=torch.int32, device=dev)
@@ -902,15 +1016,31 @@ class AkiMethods:
 
         # the processed pick keeps a score scratch per batch size, whose address the captured step holds: the admit's one-row pick gets its own
         proc, proc1 = processors(), processors()
-        on_device = dev.type == "cuda" and dtype == torch.bfloat16
         tick = dict(done=done, done_at=done_at, start_len=start_len, limit=limit)
         pick = dict(pad_token_id=opt.pad_id, eos_ids=eos_t, done=done, tokens=tokens, start_len=start_len, done_at=done_at)
         if proc is not None:
             pick["processors"] = proc
             if on_device:
                 proc.scores(slots, dev)                 # allocated ahead of the capture
+        # a call with a sampled request: every row's sampler parameters and Philox key live in device arrays the captured pick reads
+        # (ops.sample_pick_rows).  A parked row and a greedy request are top_k = 1 rows, the greedy pick's token.
+        rows = None
+        if sampled:
+            rows = dict(temperature=torch.ones(slots, dtype=torch.float32, device=dev), top_k=torch.ones(slots, dtype=torch.int32, device=dev),
+                        top_p=torch.ones(slots, dtype=torch.float32, device=dev), seed=torch.zeros(slots, dtype=torch.int64, device=dev))
+        # log-probabilities: one ops.token_logprob behind each pick, per slot; a request's columns are [0, its tokens)
+        lpb = _LogprobBuffers(slots, max_budget, top, dev) if want_lp else None
+        lp = None if lpb is None else dict(lpb.args(), tokens=tokens, cache_len=cache.cache_len, start_len=start_len, done_at=done_at)
         if opt.use_graph:
-            stepper = DecodeGraph(lm, cache, greedy=dict(pick, tick=tick)) if on_device else DecodeGraph(lm, cache)
+            if on_device:
+                captured = dict(pick, tick=tick)
+                if rows is not None:
+                    captured.update(temperature=rows["temperature"], top_k=rows["top_k"], top_p=rows["top_p"], row_seed=rows["seed"])
+                if lp is not None:
+                    captured["logprob"] = lp
+                stepper = DecodeGraph(lm, cache, greedy=captured)
+            else:
+                stepper = DecodeGraph(lm, cache)
             ids = stepper.ids
         else:
             stepper, ids = None, torch.zeros(slots, dtype=torch.long, device=dev)
@@ -919,7 +1049,7 @@ class AkiMethods:
         row = lambda x, s: x[s:s + 1]
 
         def admit(req, slot):
-            vx, lx, budget = reqs[req]
+            vx, lx, budget, rp = reqs[req]
             src, logits = self._prefill_request(vx, lx)
             ops.kv_slot_admit(src, cache, slot)
             cache.host_len = max(cache.host_len, src.host_len)
@@ -929,13 +1059,26 @@ class AkiMethods:
             done_at[slot] = -1
             limit[slot] = budget
             tokens[slot] = opt.pad_id
+            if rows is not None:                        # the slot's sampler parameters, in place: tensor fills, nothing copied from the host
+                seed = seeds[req]
+                rows["temperature"][slot] = float(rp.temperature) if rp.do_sample else 1.0
+                rows["top_k"][slot] = int(rp.top_k) if rp.do_sample else 1
+                rows["top_p"][slot] = float(rp.top_p) if rp.do_sample else 1.0
+                rows["seed"][slot] = 0 if seed is None else (seed - (1 << 64) if seed >= 1 << 63 else seed)     # the key's bits as int64
             args = dict(pad_token_id=opt.pad_id, eos_ids=eos_t, done=row(done, slot), tokens=row(tokens, slot), start_len=row(start_len, slot),
                         done_at=row(done_at, slot))
             if on_device:                               # token 0, from the prefill: the existing pick at B = 1 on row views
-                ops.greedy_pick(logits.contiguous(), row(ids, slot), cache_len=row(cache.cache_len, slot), advance=False,
-                                **(args if proc1 is None else dict(args, processors=proc1)))
+                logits = logits.contiguous()
+                args = args if proc1 is None else dict(args, processors=proc1)
+                if rows is not None:
+                    ops.sample_pick_rows(logits, row(ids, slot), cache_len=row(cache.cache_len, slot), advance=False,
+                                         **{k: row(v, slot) for k, v in rows.items()}, **args)
+                else:
+                    ops.greedy_pick(logits, row(ids, slot), cache_len=row(cache.cache_len, slot), advance=False, **args)
             else:
                 _pick_rows_torch(logits, row(ids, slot), cache_len=row(cache.cache_len, slot), proc=proc1, **args)
+            if lp is not None:
+                ops.token_logprob(logits.contiguous(), **{k: (row(v, slot) if torch.is_tensor(v) else v) for k, v in lp.items()})
             ops.slot_tick(row(done, slot), row(done_at, slot), row(cache.cache_len, slot), row(start_len, slot), row(limit, slot))
             return budget == 1
 
@@ -948,11 +1091,16 @@ class AkiMethods:
                     lg = stepper.step(ids)
                 elif on_device:
                     lg = lm.decode_step(input_ids=ids, past_key_values=cache, advance=False)
-                    ops.greedy_pick(lg, ids, cache_len=cache.cache_len, advance=True, **pick)
+                    if rows is not None:
+                        ops.sample_pick_rows(lg, ids, cache_len=cache.cache_len, advance=True, **rows, **pick)
+                    else:
+                        ops.greedy_pick(lg, ids, cache_len=cache.cache_len, advance=True, **pick)
                 else:
                     lg = lm.decode_step(input_ids=ids, past_key_values=cache)
                 if not on_device:
                     _pick_rows_torch(lg, ids, opt.pad_id, eos_t, done, tokens, cache.cache_len, start_len, done_at, proc)
+                if lp is not None:
+                    ops.token_logprob(lg, **lp)
                 ops.slot_tick(cache_len=cache.cache_len, **tick)
 
         def look():
@@ -966,7 +1114,13 @@ class AkiMethods:
             return d, at
 
         def retire(req, slot, n):
-            results[req] = tokens[slot, :n].clone()
+            rp = reqs[req][3]
+            tok = tokens[slot, :n].clone()
+            if rp.logprobs:                             # the columns behind n may hold what the slot's previous request left: never returned
+                results[req] = result(tok, rp, lpb.lp[slot, :n].clone(), None if lpb.top_ids is None else lpb.top_ids[slot, :n],
+                                      None if lpb.top_lp is None else lpb.top_lp[slot, :n])
+            else:
+                results[req] = result(tok, rp)
 
         sched.run(admit, step, look, retire, room=lambda: capacity - cache.host_len)
         self.last_many_stats = sched.stats()

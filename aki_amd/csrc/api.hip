@@ -75,7 +75,8 @@ int sample_pick_launch(const void* logits, int B, int V, int ld, const int64_t* 
                        const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores, int ld_scores, float penalty, int ngram,
                        int min_len, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids,
                        const int* bad_off, int n_bad, int n_bad_ids, int step, float temperature, int top_k, float top_p, uint64_t seed,
-                       uint64_t offset, float* probs, int ld_probs,
+                       uint64_t offset, const float* row_temperature, const int* row_top_k, const float* row_top_p, const uint64_t* row_seed,
+                       float* probs, int ld_probs,
                        const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s);
 int beam_logprob_launch(const void* logits, int in_f32, int rows, int V, int ld, float* out, int ld_out, hipStream_t s);
 int beam_step_launch(const float* logp, int ld, int B, int K, int V, int t, int max_new, float* beam_scores, const int64_t* seqs_in,
@@ -912,6 +913,9 @@ int aki_greedy_pick_constrained(const void* logits, int32_t B, int32_t V, int64_
                                        n_bad_ids, table, table_ld, n_states, states, states_ld, stream);
 }
 
+// aki_sample_pick_rows' four device arrays of B entries, in the scalars' place (nullptr: the scalar form)
+struct SampleRowArrays { const float* temperature; const int32_t* top_k; const float* top_p; const uint64_t* seed; };
+
 static int sample_pick_checked(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
                                uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
                                int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
@@ -919,14 +923,15 @@ static int sample_pick_checked(const void* logits, int32_t B, int32_t V, int64_t
                                int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
                                const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
                                int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
-                               uint64_t offset, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
+                               uint64_t offset, const SampleRowArrays* rows, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
   AKI_CLEAR_ERR();
   AKI_CHECK_ARG(logits && next_ids && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && n_eos >= 0 && (n_eos == 0 || eos_ids));
   AKI_CHECK_ARG((!tokens || tokens_ld > 0) && (!advance || cache_len) && (advance == 0 || advance == 1) && step >= 0);
   AKI_CHECK_ARG(scores && ld_scores >= V && ld_scores < (1ll << 31));
   AKI_CHECK_ARG(processors_ok(V, repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
                               n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids));
-  AKI_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f && top_p > 0.f && top_p <= 1.f && top_k >= 0);
+  if (rows) AKI_CHECK_ARG(rows->temperature && rows->top_k && rows->top_p && rows->seed);     // device arrays: their values are the caller's to check
+  else AKI_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f && top_p > 0.f && top_p <= 1.f && top_k >= 0);
   AKI_CHECK_ARG(!probs_out || (ld_probs >= V && ld_probs < (1ll << 31)));
   if ((((uintptr_t)scores) & 15) != 0 || (ld_scores & 3) != 0) return AKI_ERR_ALIGNMENT;
   if (embed_weight) {
@@ -940,7 +945,9 @@ static int sample_pick_checked(const void* logits, int32_t B, int32_t V, int64_t
   return sample_pick_launch(logits, B, V, (int)ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
                             done_at, embed_weight, additional_weight, max_original_id, d, next_embeds, scores, (int)ld_scores, repetition_penalty,
                             no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets,
-                            n_bad, n_bad_ids, step, temperature, top_k, top_p, seed, offset, probs_out, (int)ld_probs, table, (int)table_ld, n_states, states, states_ld, (hipStream_t)stream);
+                            n_bad, n_bad_ids, step, temperature, top_k, top_p, seed, offset, rows ? rows->temperature : nullptr, rows ? rows->top_k : nullptr,
+                            rows ? rows->top_p : nullptr, rows ? rows->seed : nullptr, probs_out, (int)ld_probs, table, (int)table_ld, n_states, states, states_ld,
+                            (hipStream_t)stream);
 }
 
 int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -954,7 +961,22 @@ int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const 
   return sample_pick_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
                              embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
                              no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
-                             n_bad_ids, step, temperature, top_k, top_p, seed, offset, probs_out, ld_probs, nullptr, 0, 0, nullptr, 0, stream);
+                             n_bad_ids, step, temperature, top_k, top_p, seed, offset, nullptr, probs_out, ld_probs, nullptr, 0, 0, nullptr, 0, stream);
+}
+
+int aki_sample_pick_rows(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                         uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                         int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                         int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                         int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                         const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                         int32_t n_bad, int32_t n_bad_ids, int32_t step, const float* temperature, const int32_t* top_k, const float* top_p,
+                         const uint64_t* seed, float* probs_out, int64_t ld_probs, void* stream) {
+  const SampleRowArrays rows = {temperature, top_k, top_p, seed};
+  return sample_pick_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
+                             embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
+                             no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
+                             n_bad_ids, step, 1.f, 0, 1.f, 0ull, 0ull, &rows, probs_out, ld_probs, nullptr, 0, 0, nullptr, 0, stream);
 }
 
 int aki_sample_pick_constrained(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -970,7 +992,7 @@ int aki_sample_pick_constrained(const void* logits, int32_t B, int32_t V, int64_
   return sample_pick_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
                              embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
                              no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
-                             n_bad_ids, step, temperature, top_k, top_p, seed, offset, probs_out, ld_probs, table, table_ld, n_states, states, states_ld, stream);
+                             n_bad_ids, step, temperature, top_k, top_p, seed, offset, nullptr, probs_out, ld_probs, table, table_ld, n_states, states, states_ld, stream);
 }
 
 int aki_beam_logprob(const void* logits, int32_t dtype, int32_t rows, int32_t V, int64_t ld, float* out, int64_t ld_out, void* stream) {

@@ -1816,6 +1816,20 @@ struct SampleParams {
   int processed;                                            // the processors ran: x is the f32 scratch row, not the bf16 logits
 };
 
+// The per-row form (aki_sample_pick_rows): row b reads its own temperature[b], top_k[b], top_p[b] and Philox key seed[b] from device
+// arrays of B entries, and draws with the counter (n, 0, 0, 0) - the stream belongs to the row's seed, not to the row index, so it is the
+// draw row 0 of a batch-1 scalar call with that seed and offset 0 makes.  One workgroup per row: the values are workgroup-uniform.
+// Nothing validates the arrays on the device; bad bits stay inside the row: a temperature that is not > 0 (zero, negative, NaN) takes
+// the greedy pick, top_k[b] <= 0 or >= V is no top-k filter, top_p[b] >= 1 is no top-p filter (and a top_p that is not > 0 keeps the
+// maximum only).  top_k[b] == 1 is the greedy branch, as in the scalar form.
+struct SampleRowParams {
+  const float* temperature; const int* top_k; const float* top_p; const unsigned long long* seed;
+  float* probs; int ld_probs;
+  int processed;
+};
+template <bool ROWS> struct SampleArgs { using type = SampleParams; };
+template <> struct SampleArgs<true> { using type = SampleRowParams; };
+
 __device__ __forceinline__ unsigned sample_key(float y) {   // larger y <=> larger key; -0 and +0 share one
   unsigned u = __float_as_uint(y);
   if (u == 0x80000000u) u = 0u;
@@ -1911,7 +1925,8 @@ __device__ unsigned select_threshold(const float* rowf, int V, unsigned lo_key, 
   return pre;
 }
 
-__global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickParams p, const ProcParams q, const SampleParams sp) {
+template <bool ROWS>
+__global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickParams p, const ProcParams q, const typename SampleArgs<ROWS>::type sp) {
   __shared__ unsigned long long s_hist[SEL_BINS];           // first the processors' bitmap (PROC_MAX_V / 32 words), then the select's bins
   __shared__ unsigned long long s_w64[PICK_THREADS / 64], s_pick[2];
   __shared__ float s_wf[PICK_THREADS / 64];
@@ -1940,7 +1955,19 @@ __global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickPar
   }
   const bool row_done = p.done != nullptr && p.done[b] != 0;   // uniform: every thread reads the same byte, before thread 0 can set it
   float* probs = sp.probs ? sp.probs + (size_t)b * sp.ld_probs : nullptr;
-  const float T = sp.temperature;
+  float T, top_p;
+  int top_k;
+  unsigned seed_lo, seed_hi, ctr1, off_lo, off_hi;
+  if constexpr (ROWS) {
+    T = sp.temperature[b]; top_k = sp.top_k[b]; top_p = sp.top_p[b];
+    const unsigned long long key = sp.seed[b];
+    seed_lo = (unsigned)key; seed_hi = (unsigned)(key >> 32);
+    ctr1 = 0u; off_lo = 0u; off_hi = 0u;
+  } else {
+    T = sp.temperature; top_k = sp.top_k; top_p = sp.top_p;
+    seed_lo = sp.seed_lo; seed_hi = sp.seed_hi;
+    ctr1 = (unsigned)b; off_lo = sp.off_lo; off_hi = sp.off_hi;
+  }
   // pass 0: argmax of x in the greedy pick's ordering, y = x / T (correctly rounded) into the scratch row
   float best = -INFINITY;
   int bi = 0x7fffffff;
@@ -1997,17 +2024,18 @@ __global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickPar
     if (pick_better(s_v[w], s_i[w], best, bi)) { best = s_v[w]; bi = s_i[w]; }
   const float ymax = __fdiv_rn(best, T);
   // rows the draw has nothing to say about take the greedy pick: finished (pad), a NaN / +inf / -inf maximum, top_k == 1
-  const bool greedy = row_done || !(ymax == ymax) || ymax == INFINITY || ymax == -INFINITY || sp.top_k == 1;
+  // (the per-row form also for a temperature that is not > 0: the host validates what it writes, the kernel keeps bad bits in the row)
+  const bool greedy = row_done || !(ymax == ymax) || ymax == INFINITY || ymax == -INFINITY || top_k == 1 || (ROWS && !(T > 0.f));
   int tok = bi;
   if (greedy) {
     if (probs)
       for (int i = tid; i < V; i += PICK_THREADS) probs[i] = (!row_done && i == bi) ? 1.f : 0.f;
   } else {
     unsigned tau = 0u;
-    if (sp.top_k > 0 && sp.top_k < V)
-      tau = select_threshold<false>(rowf, V, 0u, ymax, (unsigned long long)sp.top_k, 1.f, s_hist, s_w64, s_pick);
-    if (sp.top_p < 1.f) {
-      const unsigned tp = select_threshold<true>(rowf, V, tau, ymax, 0ull, sp.top_p, s_hist, s_w64, s_pick);
+    if (top_k > 0 && top_k < V)
+      tau = select_threshold<false>(rowf, V, 0u, ymax, (unsigned long long)top_k, 1.f, s_hist, s_w64, s_pick);
+    if (top_p < 1.f) {
+      const unsigned tp = select_threshold<true>(rowf, V, tau, ymax, 0ull, top_p, s_hist, s_w64, s_pick);
       tau = tp > tau ? tp : tau;
     }
     // the draw: thread t owns the groups of four [t * gpt, (t + 1) * gpt); group sums pairwise, chunk sums in order, then the block scan
@@ -2030,7 +2058,7 @@ __global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickPar
     float incl, total;
     const float excl = block_excl_scan<float>(csum, s_wf, &incl, &total);
     const int n = p.step + (p.cache_len != nullptr ? p.cache_len[b] + p.advance - (p.start_len ? p.start_len[b] : 0) : 0);
-    const unsigned x0 = philox4x32_10_word0((unsigned)n, (unsigned)b, sp.off_lo, sp.off_hi, sp.seed_lo, sp.seed_hi);
+    const unsigned x0 = philox4x32_10_word0((unsigned)n, ctr1, off_lo, off_hi, seed_lo, seed_hi);
     const float target = (float)((((double)(x0 >> 8)) + 0.5) * (1.0 / 16777216.0) * (double)total);
     if (csum > 0.f && incl > target) atomicMin(&s_owner, tid);
     if (last >= 0) atomicMax(&s_last, last);
@@ -2115,7 +2143,8 @@ int sample_pick_launch(const void* logits, int B, int V, int ld, const int64_t* 
                        const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores, int ld_scores, float penalty, int ngram,
                        int min_len, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids,
                        const int* bad_off, int n_bad, int n_bad_ids, int step, float temperature, int top_k, float top_p, uint64_t seed,
-                       uint64_t offset, float* probs, int ld_probs,
+                       uint64_t offset, const float* row_temperature, const int* row_top_k, const float* row_top_p, const uint64_t* row_seed,
+                       float* probs, int ld_probs,
                        const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s) {
   PickParams p = {(const bf16_t*)logits, B, V, ld, eos, n_eos, pad, done, ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
                   (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out, step};
@@ -2127,7 +2156,12 @@ int sample_pick_launch(const void* logits, int B, int V, int ld, const int64_t* 
   const SampleParams sp = {temperature, top_k, top_p, (unsigned)seed, (unsigned)(seed >> 32), (unsigned)offset, (unsigned)(offset >> 32),
                            probs, ld_probs, processed ? 1 : 0};
   AKI_CLEAR_ERR();
-  hipLaunchKernelGGL(sample_pick_kernel, dim3(B), dim3(PICK_THREADS), 0, s, p, q, sp);
+  if (row_seed != nullptr) {                                // the per-row form: the four arrays stand in for the scalars
+    const SampleRowParams sr = {row_temperature, row_top_k, row_top_p, (const unsigned long long*)row_seed, probs, ld_probs, processed ? 1 : 0};
+    hipLaunchKernelGGL(sample_pick_kernel<true>, dim3(B), dim3(PICK_THREADS), 0, s, p, q, sr);
+  } else {
+    hipLaunchKernelGGL(sample_pick_kernel<false>, dim3(B), dim3(PICK_THREADS), 0, s, p, q, sp);
+  }
   AKI_LAUNCH_CHECK();
   return AKI_OK;
 }

@@ -937,6 +937,51 @@ class DeviceGenerator:
         return o
 
 
+def _sample_pick_front(name: str, logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len, advance, done_at, embed,
+                       next_embeds, processors, step, probs_out, scores, extra=()):
+    """What ops.sample_pick and ops.sample_pick_rows share: the checks of the pick's tensors, the scratch rule and the C arguments up to
+    `step` -> (those arguments, the probs_out pair, the constraint's five or None).  extra: further (tensor, dtype) pairs to check."""
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise AkiError(f"{name} takes bf16 logits [B, V] with unit column stride")
+    B, V = logits.shape
+    for t_, dt in ((next_ids, torch.int64), (tokens, torch.int64), (eos_ids, torch.int64), (done, torch.uint8), (cache_len, torch.int32),
+                   (start_len, torch.int32), (done_at, torch.int32), (probs_out, torch.float32), (scores, torch.float32), *extra):
+        if t_ is not None and (t_.dtype != dt or not t_.is_contiguous() or t_.device != logits.device):
+            raise AkiError(f"{name}: a {dt} contiguous tensor on {logits.device} is expected, got {t_.dtype} {tuple(t_.shape)}")
+    if tokens is not None and (tokens.dim() != 2 or tokens.shape[0] != B):
+        raise AkiError(f"{name}: tokens is [B, max_new_tokens]")
+    if probs_out is not None and tuple(probs_out.shape) != (B, V):
+        raise AkiError(f"{name}: probs_out is f32 [B, V]")
+    common = (_ptr(logits), B, V, logits.stride(0), _ptr(eos_ids), 0 if eos_ids is None else eos_ids.numel(), int(pad_token_id), _ptr(done),
+              _ptr(next_ids), _ptr(tokens), 0 if tokens is None else tokens.shape[1], _ptr(cache_len), _ptr(start_len), 1 if advance else 0,
+              _ptr(done_at))
+    emb = (None, None, 0, 0, 0, None)
+    if embed is not None:
+        w, extra_w, max_orig = embed
+        d = w.shape[1]
+        for t_ in (w, extra_w, next_embeds):
+            if t_ is not None and (t_.dtype != torch.bfloat16 or not t_.is_contiguous() or t_.device != logits.device or t_.shape[-1] != d):
+                raise AkiError(f"{name}: embedding tables and next_embeds are contiguous bf16 [*, d] on the logits' device")
+        if next_embeds is None or next_embeds.numel() != B * d:
+            raise AkiError(f"{name}: next_embeds is [B, d]")
+        if w.shape[0] <= max_orig:
+            raise AkiError(f"{name}: the embedding table has fewer than max_original_id + 1 rows")
+        emb = (_ptr(w), _ptr(extra_w), int(max_orig), 0 if extra_w is None else extra_w.shape[0], d, _ptr(next_embeds))
+    active = processors is not None and processors.active
+    if active and processors.V != V:
+        raise AkiError(f"{name}: the processors were built for V = {processors.V}, the logits have {V} columns")
+    if V > L.AKI_LOGITS_PROCESS_MAX_V:
+        raise AkiError(f"{name}: a vocabulary of {V} is above {L.AKI_LOGITS_PROCESS_MAX_V}")
+    if scores is None:
+        scores = processors.scores(B, logits.device) if active else _sample_scratch(B, V, logits.device)
+    if scores.dim() != 2 or scores.shape[0] != B or scores.shape[1] < V:
+        raise AkiError(f"{name}: scores is f32 [B, >= V]")
+    head, tail = processors._tail() if active else ((1.0, 0, 0), (None, 0, None, 0, None, None, 0, 0))
+    con = processors._constraint_args(B, tokens.shape[1] if tokens is not None else (int(step) + 1 if cache_len is None else None)) if active else None
+    return ((*common, *emb, _ptr(scores), scores.stride(0), *head, *tail, int(step)),
+            (_ptr(probs_out), 0 if probs_out is None else probs_out.stride(0)), con)
+
+
 def sample_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int = 0, eos_ids: Optional[torch.Tensor] = None,
                 done: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, cache_len: Optional[torch.Tensor] = None,
                 start_len: Optional[torch.Tensor] = None, advance: bool = False, done_at: Optional[torch.Tensor] = None,
@@ -948,51 +993,44 @@ def sample_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
     counter = (n, b, offset))[0], n = step + (cache_len[b] + advance - start_len[b] when cache_len is given) - the index tokens[b, n] is
     written at.  probs_out: optional f32 [B, V], the filtered distribution the draw was made from.  scores: the f32 [B, >= V] scratch
     (default: the processors' own, or one kept per shape).  Capturable: no host value is read."""
-    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
-        raise AkiError("sample_pick takes bf16 logits [B, V] with unit column stride")
-    B, V = logits.shape
-    for t_, dt in ((next_ids, torch.int64), (tokens, torch.int64), (eos_ids, torch.int64), (done, torch.uint8), (cache_len, torch.int32),
-                   (start_len, torch.int32), (done_at, torch.int32), (probs_out, torch.float32), (scores, torch.float32)):
-        if t_ is not None and (t_.dtype != dt or not t_.is_contiguous() or t_.device != logits.device):
-            raise AkiError(f"sample_pick: a {dt} contiguous tensor on {logits.device} is expected, got {t_.dtype} {tuple(t_.shape)}")
-    if tokens is not None and (tokens.dim() != 2 or tokens.shape[0] != B):
-        raise AkiError("sample_pick: tokens is [B, max_new_tokens]")
-    if probs_out is not None and tuple(probs_out.shape) != (B, V):
-        raise AkiError("sample_pick: probs_out is f32 [B, V]")
     if not (float(temperature) > 0.0) or not (0.0 < float(top_p) <= 1.0) or int(top_k) < 0 or int(step) < 0:
         raise ValueError(f"sample_pick: temperature > 0, 0 < top_p <= 1, top_k >= 0 and step >= 0 are expected, got {temperature}, {top_p}, {top_k}, {step}")
-    common = (_ptr(logits), B, V, logits.stride(0), _ptr(eos_ids), 0 if eos_ids is None else eos_ids.numel(), int(pad_token_id), _ptr(done),
-              _ptr(next_ids), _ptr(tokens), 0 if tokens is None else tokens.shape[1], _ptr(cache_len), _ptr(start_len), 1 if advance else 0,
-              _ptr(done_at))
-    emb = (None, None, 0, 0, 0, None)
-    if embed is not None:
-        w, extra, max_orig = embed
-        d = w.shape[1]
-        for t_ in (w, extra, next_embeds):
-            if t_ is not None and (t_.dtype != torch.bfloat16 or not t_.is_contiguous() or t_.device != logits.device or t_.shape[-1] != d):
-                raise AkiError("sample_pick: embedding tables and next_embeds are contiguous bf16 [*, d] on the logits' device")
-        if next_embeds is None or next_embeds.numel() != B * d:
-            raise AkiError("sample_pick: next_embeds is [B, d]")
-        if w.shape[0] <= max_orig:
-            raise AkiError("sample_pick: the embedding table has fewer than max_original_id + 1 rows")
-        emb = (_ptr(w), _ptr(extra), int(max_orig), 0 if extra is None else extra.shape[0], d, _ptr(next_embeds))
-    active = processors is not None and processors.active
-    if active and processors.V != V:
-        raise AkiError(f"sample_pick: the processors were built for V = {processors.V}, the logits have {V} columns")
-    if V > L.AKI_LOGITS_PROCESS_MAX_V:
-        raise AkiError(f"sample_pick: a vocabulary of {V} is above {L.AKI_LOGITS_PROCESS_MAX_V}")
-    if scores is None:
-        scores = processors.scores(B, logits.device) if active else _sample_scratch(B, V, logits.device)
-    if scores.dim() != 2 or scores.shape[0] != B or scores.shape[1] < V:
-        raise AkiError("sample_pick: scores is f32 [B, >= V]")
-    head, tail = processors._tail() if active else ((1.0, 0, 0), (None, 0, None, 0, None, None, 0, 0))
-    args = (*common, *emb, _ptr(scores), scores.stride(0), *head, *tail, int(step), float(temperature), int(top_k), float(top_p),
-            int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _ptr(probs_out), 0 if probs_out is None else probs_out.stride(0))
-    con = processors._constraint_args(B, tokens.shape[1] if tokens is not None else (int(step) + 1 if cache_len is None else None)) if active else None
+    front, probs, con = _sample_pick_front("sample_pick", logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len, advance,
+                                           done_at, embed, next_embeds, processors, step, probs_out, scores)
+    args = (*front, float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, *probs)
     if con is not None:
         L.check(L.load().aki_sample_pick_constrained(*args, *con, _stream()), "aki_sample_pick_constrained")
         return next_ids
     L.check(L.load().aki_sample_pick(*args, _stream()), "aki_sample_pick")
+    return next_ids
+
+
+def sample_pick_rows(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int = 0, eos_ids: Optional[torch.Tensor] = None,
+                     done: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, cache_len: Optional[torch.Tensor] = None,
+                     start_len: Optional[torch.Tensor] = None, advance: bool = False, done_at: Optional[torch.Tensor] = None,
+                     embed=None, next_embeds: Optional[torch.Tensor] = None, processors: Optional[LogitsProcessors] = None, step: int = 0,
+                     temperature: Optional[torch.Tensor] = None, top_k: Optional[torch.Tensor] = None, top_p: Optional[torch.Tensor] = None,
+                     seed: Optional[torch.Tensor] = None, probs_out: Optional[torch.Tensor] = None,
+                     scores: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ops.sample_pick with the sampling parameters per row, one launch (aki_sample_pick_rows): `temperature` f32, `top_k` int32, `top_p`
+    f32 and `seed` int64 (its bits are the 64-bit Philox key) are contiguous device tensors [B], read by the launch - a captured step
+    serves rows whose parameters are rewritten in place.  Row b draws u = Philox4x32-10(key = seed[b], counter = (n, 0, 0, 0))[0], n as
+    in ops.sample_pick: the draw of row 0 of a B = 1 ops.sample_pick call with that seed and offset 0, so the stream belongs to the seed and
+    not to the row.  A row with top_k[b] == 1 takes ops.greedy_pick's token.  No constraint: one LogitsProcessors without one serves all
+    rows.  The VALUES in the four arrays are not checked here (no host value is read: capturable); whoever writes them validates them
+    (temperature > 0, top_k >= 0, 0 < top_p <= 1) - in the kernel a temperature that is not > 0 falls to the greedy token, top_k <= 0 or
+    >= V and top_p >= 1 switch their filter off."""
+    if int(step) < 0:
+        raise ValueError(f"sample_pick_rows: step >= 0 is expected, got {step}")
+    rows = ((temperature, torch.float32), (top_k, torch.int32), (top_p, torch.float32), (seed, torch.int64))
+    if logits.dim() == 2 and any(t_ is None or tuple(t_.shape) != (logits.shape[0],) for t_, _ in rows):
+        raise AkiError(f"sample_pick_rows: temperature (f32), top_k (int32), top_p (f32) and seed (int64) are tensors [{logits.shape[0]}]")
+    if processors is not None and processors.active and processors.constraint is not None:
+        raise AkiError("sample_pick_rows: no constrained form; ops.sample_pick takes a constraint")
+    front, probs, _ = _sample_pick_front("sample_pick_rows", logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len,
+                                         advance, done_at, embed, next_embeds, processors, step, probs_out, scores, extra=rows)
+    L.check(L.load().aki_sample_pick_rows(*front, _ptr(temperature), _ptr(top_k), _ptr(top_p), _ptr(seed), *probs, _stream()),
+            "aki_sample_pick_rows")
     return next_ids
 
 

@@ -219,6 +219,9 @@ class DecodeGraph:
         replayed step and writes the next step's input ids itself: one replay per token (`step_greedy`), nothing else on the stream.
         With a "seed" key the dict holds ops.sample_pick's arguments instead (temperature, top_k, top_p, seed, offset): the captured pick
         is the device sampler, whose draw depends on the device-side token index, so one capture serves every replay.
+        With a "row_seed" key it holds ops.sample_pick_rows' arguments (temperature, top_k, top_p and row_seed: device arrays of one entry per
+        row, the last one passed on as `seed`): the captured pick reads every row's parameters and key from those arrays at each replay, so
+        they may be rewritten in place between replays (generate_many's admit).
         With a "logprob" key (the in-loop arguments of ops.token_logprob) that launch is captured right behind the pick.
         With a "tick" key (ops.slot_tick's done / done_at / start_len / limit) the rows' token budgets are ticked behind the pick too."""
         self.lm, self.cache = lm, cache
@@ -248,7 +251,11 @@ class DecodeGraph:
                 self.logits = lm.decode_step(input_ids=self.ids, past_key_values=cache, advance=False)
                 args = dict(self.greedy)
                 logprob, tick = args.pop("logprob", None), args.pop("tick", None)
-                pick = ops.sample_pick if "seed" in args else ops.greedy_pick
+                if "row_seed" in args:
+                    args["seed"] = args.pop("row_seed")
+                    pick = ops.sample_pick_rows
+                else:
+                    pick = ops.sample_pick if "seed" in args else ops.greedy_pick
                 pick(self.logits, self.ids, cache_len=cache.cache_len, advance=True, **args)
                 if logprob is not None:             # right behind the pick: it scores the token at the index the pick just wrote
                     ops.token_logprob(self.logits, **logprob)

@@ -7,7 +7,62 @@ scheduler is driven through three callbacks, so a fake token source exercises th
 from __future__ import annotations
 
 from collections import deque
+from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple
+
+
+@dataclass(frozen=True)
+class RequestParams:
+    """What one request of generate_many asks for beyond its budget.  do_sample with temperature / top_k / top_p: the device sampler
+    (ops.sample_pick_rows) with these values in the request's row; seed: the request's own 64-bit Philox key (None: derived, see
+    request_seed) - its draws depend on (seed, generated-token index) only, never on the slot or the neighbours.  logprobs: return the
+    log-probability of every returned token under the raw model distribution, with the top_logprobs most likely alternatives."""
+    do_sample: bool = False
+    temperature: float = 1.0
+    top_k: int = 0
+    top_p: float = 1.0
+    seed: Optional[int] = None
+    logprobs: bool = False
+    top_logprobs: int = 0
+
+    def check(self, index, max_top: int) -> "RequestParams":
+        """ValueError naming request `index` (a number, or a word such as "default") for a value the device sampler or ops.token_logprob
+        does not take; max_top: ops.LOGPROB_MAX_TOP."""
+        who = f"request {index}"
+        if not float(self.temperature) > 0.0:
+            raise ValueError(f"{who}: temperature must be positive, got {self.temperature}")
+        if not 0.0 < float(self.top_p) <= 1.0:
+            raise ValueError(f"{who}: 0 < top_p <= 1 is expected, got {self.top_p}")
+        if int(self.top_k) != self.top_k or int(self.top_k) < 0:
+            raise ValueError(f"{who}: top_k is an integer >= 0, got {self.top_k}")
+        if int(self.top_logprobs) != self.top_logprobs or not 0 <= int(self.top_logprobs) <= int(max_top):
+            raise ValueError(f"{who}: top_logprobs must be in 0..{max_top}, got {self.top_logprobs}")
+        if self.top_logprobs and not self.logprobs:
+            raise ValueError(f"{who}: top_logprobs needs logprobs=True")
+        if self.seed is not None and (int(self.seed) != self.seed or not 0 <= int(self.seed) < 1 << 64):
+            raise ValueError(f"{who}: seed is an integer in [0, 2^64), got {self.seed}")
+        return self
+
+
+def philox4x32_10(counter: Sequence[int], key: Sequence[int]) -> Tuple[int, int, int, int]:
+    """Philox4x32-10 on Python integers: counter (c0, c1, c2, c3) and key (k0, k1) as 32-bit words -> the four output words."""
+    m = 0xFFFFFFFF
+    c0, c1, c2, c3 = (int(c) & m for c in counter)
+    k0, k1 = (int(k) & m for k in key)
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & m, (p0 >> 32) ^ c3 ^ k1, p0 & m
+        k0, k1 = (k0 + 0x9E3779B9) & m, (k1 + 0xBB67AE85) & m
+    return c0, c1, c2, c3
+
+
+def request_seed(seed: int, offset: int, r: int) -> int:
+    """The 64-bit Philox key of request r (its position in `requests`) of the generate_many call that took `offset` from a
+    DeviceGenerator(seed): words 0 and 1 of Philox4x32-10(key = seed, counter = (r, 0, offset lo, offset hi)) as word0 | word1 << 32.
+    Host only, Python integers.  A request's draws then use this key with the counter (generated-token index, 0, 0, 0)."""
+    seed, offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF
+    w = philox4x32_10((int(r), 0, offset & 0xFFFFFFFF, offset >> 32), (seed & 0xFFFFFFFF, seed >> 32))
+    return w[0] | (w[1] << 32)
 
 
 def expanded_length(ids: Sequence[int], media_token_id: int, n_vis_tokens: int) -> int:

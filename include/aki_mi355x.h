@@ -853,6 +853,26 @@ int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const 
                     int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
                     uint64_t offset, float* probs_out, int64_t ld_probs, void* stream);
 
+/* aki_sample_pick_rows - aki_sample_pick with the sampling parameters per ROW: the scalars temperature, top_k, top_p, seed and offset are
+ * replaced by four device arrays of B entries (float, int32, float, uint64), read by the launch itself, so a captured graph serves rows
+ * whose parameters are rewritten in place between replays.  Purely additive: AKI_ABI_VERSION was not bumped (it stays 17).
+ * Row b runs exactly aki_sample_pick's step with temperature[b], top_k[b] and top_p[b], and draws with
+ *   x0 = the first word of Philox4x32-10 with key seed[b] and counter (n, 0, 0, 0),
+ * n as above: the draw row 0 of a B = 1 aki_sample_pick call with seed = seed[b] and offset = 0 makes.  The random stream belongs to the
+ * row's seed, never to the row index, so a request keeps its stream whichever row serves it.  A row with top_k[b] == 1 takes
+ * aki_greedy_pick's id (lowest index among equal maxima): a greedy row inside a sampled batch.
+ * The entry point cannot read the arrays; the caller validates what it writes there.  Bad bits stay inside their row: a temperature that
+ * is not > 0 (0, negative, NaN) takes the greedy id, top_k[b] <= 0 or >= V is no top-k filter, top_p[b] >= 1 no top-p filter.
+ * Host checks as for aki_sample_pick (non-null pointers, B >= 1, V <= AKI_LOGITS_PROCESS_MAX_V, the scratch's alignment). */
+int aki_sample_pick_rows(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                         uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                         int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                         int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                         int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                         const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                         int32_t n_bad, int32_t n_bad_ids, int32_t step, const float* temperature, const int32_t* top_k, const float* top_p,
+                         const uint64_t* seed, float* probs_out, int64_t ld_probs, void* stream);
+
 /* ---- constrained decoding: a deterministic automaton over token ids, applied on the pick path.  Purely additive: AKI_ABI_VERSION was
  * not bumped (it stays 17).  The three entry points below are aki_logits_process, aki_greedy_pick_processed and aki_sample_pick with
  * five more arguments in front of `stream`; everything else is as documented there.

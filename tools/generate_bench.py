@@ -20,7 +20,12 @@ profiles/constraint_bench.json under "batch<B>".
 generate() over consecutive groups of `slots` requests (max_new_tokens = the group's largest budget) against generate_many, alternating in one
 process for at least 3 rounds.  Writes profiles/many_bench.json: returned tokens/s of both legs, the scheduler's counters, the occupancy
 the lengths alone predict for the static groups against the scheduler's live / total row-steps, and the share of wall time inside admits.
-    python tools/generate_bench.py [--many]
+--many --sample [--temperature T --top-k K --top-p P] [--logprobs K]: the queue with per-request sampling (many_sample_bench below): the same 64
+requests, budgets, EOS off and slot counts; the greedy queue leg and the sampled queue leg (every request RequestParams(do_sample=True,
+...) with its own seed) alternate in one process, with --logprobs K two more legs (greedy requests with logprobs=True at top_logprobs 0
+and K).  Writes profiles/many_sample_bench.json: returned tokens/s and wall ms per decode step of every leg, and each leg's excess per step
+over the greedy leg of the same round (the admits are the same work in every leg).
+    python tools/generate_bench.py [--many] [--many --sample --temperature 0.8 --top-k 50 --top-p 0.9 --logprobs 8]
     python tools/generate_bench.py [--new 256] [--fp8] [--txt 64] [--repetition-penalty 1.2] [--no-repeat-ngram 3]
                                    [--sample --temperature 0.8 --top-k 50 --top-p 0.9] [--batch 8] [--logprobs 8 --rounds 4] [--constraint]"""
 import argparse, json, os, sys, time
@@ -115,6 +120,71 @@ def many_bench(a, model, dev):
     print(json.dumps({k: v for k, v in res.items() if k != "budgets"}))
 
 
+def many_sample_bench(a, model, dev):
+    """--many --sample: generate_many with per-request sampling against the greedy queue, many_bench's requests.  Writes
+    profiles/many_sample_bench.json."""
+    import aki_amd
+    import bench
+    n_req = a.many_requests
+    g = torch.Generator(device="cpu").manual_seed(4242)
+    budgets = torch.randint(16, 257, (n_req,), generator=g).tolist()
+    reqs = []
+    for i in range(n_req):
+        vx, ids, _ = bench.synth_batch(1, dev, torch.bfloat16, model.media_token_id, seed=1000 + i)
+        reqs.append((vx, ids, budgets[i]))
+    sampler = dict(do_sample=True, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
+    legs = {"greedy": [aki_amd.RequestParams()] * n_req,
+            "sampled": [aki_amd.RequestParams(seed=0x5EED0000 + i, **sampler) for i in range(n_req)]}
+    if a.logprobs >= 0:
+        for k in sorted({0, a.logprobs}):
+            legs[f"greedy_logprobs_k{k}"] = [aki_amd.RequestParams(logprobs=True, top_logprobs=k)] * n_req
+
+    def leg(name, slots):
+        batch = [(vx, ids, b, rp) for (vx, ids, b), rp in zip(reqs, legs[name])]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        outs = model.generate_many(batch, slots=slots, eos_token_id=[])
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        toks = [o.tokens if isinstance(o, aki_amd.AkiRequestOutput) else o for o in outs]
+        assert [t.numel() for t in toks] == budgets
+        return wall, dict(model.last_many_stats)
+
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    res = {"requests": n_req, "prompt_tokens_lm_stream": bench.N_TXT - 1 + bench.NV, "budgets": budgets, "budget_seed": 4242,
+           "sampler": dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p), "top_logprobs": a.logprobs,
+           "method": "the legs alternate in one process, wall clock around each generate_many call with a device synchronisation on both "
+                     "sides; tokens/s = returned tokens / wall time, prefills included; ms_per_step = wall time / decode steps replayed, "
+                     "admits included - every leg admits the same 64 prompts, so the excess over the greedy leg of the same round is the "
+                     "pick's (and the log-probability launch's) cost per step", "slots": {}}
+    for slots in (8, 16):
+        for name in legs:
+            leg(name, slots)                                          # warm-up: allocator, folds, capture path
+        rounds = []
+        for _ in range(max(3, a.rounds)):
+            r = {}
+            for name in legs:
+                wall, stats = leg(name, slots)
+                r[name] = {"tokens_per_s": round(sum(budgets) / wall, 1), "wall_s": round(wall, 3), "steps": stats["steps"],
+                           "ms_per_step": round(wall * 1e3 / stats["steps"], 4)}
+            rounds.append(r)
+        summary = {}
+        for name in legs:
+            summary[name] = {"tokens_per_s_median": med([r[name]["tokens_per_s"] for r in rounds]),
+                             "tokens_per_s_min_max": [min(r[name]["tokens_per_s"] for r in rounds), max(r[name]["tokens_per_s"] for r in rounds)],
+                             "ms_per_step_median": med([r[name]["ms_per_step"] for r in rounds])}
+            if name != "greedy":
+                ex = [(r[name]["ms_per_step"] - r["greedy"]["ms_per_step"]) * 1e3 for r in rounds]
+                summary[name]["excess_us_per_step_over_greedy_median"] = round(med(ex), 1)
+                summary[name]["excess_us_per_step_over_greedy_min_max"] = [round(min(ex), 1), round(max(ex), 1)]
+        res["slots"][str(slots)] = {"rounds": rounds, "summary": summary}
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "many_sample_bench.json")
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps({k: v for k, v in res.items() if k != "budgets"}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--new", type=int, default=256)
@@ -136,7 +206,8 @@ def main():
     ap.add_argument("--logprobs", type=int, default=-1, help="K >= 0: one more leg per round with output_logprobs=True, top_logprobs=K (-1: off)")
     ap.add_argument("--constraint", action="store_true", help="one more leg per round: greedy under a 16-state token constraint")
     ap.add_argument("--many", action="store_true", help="in-flight batching: generate() over static groups against generate_many, 64 requests with "
-                    "budgets 16..256 at 8 and 16 slots -> profiles/many_bench.json (the other legs are skipped)")
+                    "budgets 16..256 at 8 and 16 slots -> profiles/many_bench.json (the other legs are skipped); with --sample: the greedy "
+                    "queue against the queue with per-request sampling (and --logprobs K) -> profiles/many_sample_bench.json")
     ap.add_argument("--many-requests", type=int, default=64)
     a = ap.parse_args()
     lp_kw =dict(output_logprobs=True, top_logprobs=a.logprobs) if a.logprobs >= 0 else None
@@ -156,7 +227,7 @@ def main():
         model.lang_model.enable_mxfp4()
     model.lang_model.model.decode_chain_w4 = bool(a.w4_chain)
     if a.many:
-        return many_bench(a, model, dev)
+        return many_sample_bench(a, model, dev) if a.sample else many_bench(a, model, dev)
     vx, ids, am =bench.synth_batch(1, dev, torch.bfloat16, model.media_token_id, seed=1000)
     if a.batch > 1:
         vx, ids, am = vx.repeat(a.batch, 1, 1, 1, 1, 1), ids.repeat(a.batch, 1), am.repeat(a.batch, 1)

@@ -235,11 +235,12 @@ ManyOptions = namedtuple("ManyOptions", "max_new_tokens eos_ids pad_id use_graph
 MANY_REFUSED = (
     ("do_sample", lambda v: bool(v), "sampling belongs to a request, not to the call: pass RequestParams(do_sample=True, ...) in the request "
                                      "tuple or as params="),
-    ("constraint", lambda v: v is not None, "the constraint's state history is bound to the rows of one generation, not to a slot that changes hands"),
     ("num_beams", lambda v: v is not None and int(v) > 1, "beam search re-orders the rows of its cache; a slot is one row"),
     ("num_return_sequences", lambda v: v is not None and int(v) > 1, "it needs sampling; pass the prompt as several requests instead"),
     ("output_logprobs", lambda v: bool(v), "log-probabilities belong to a request, not to the call: pass RequestParams(logprobs=True, ...) in "
                                            "the request tuple or as params="),
+    ("constraint", lambda v: v is not None, "a token constraint belongs to a request, not to the call: pass RequestParams(constraint=...) in the "
+                                            "request tuple or as params="),
     ("past_key_values", lambda v: v is not None, "every request is prefilled into its slot; continue a cache with generate()"),
 )
 
@@ -897,7 +898,7 @@ class AkiMethods:
         Keywords: max_new_tokens (the default budget), eos_token_id, pad_token_id, use_graph, the logits processors of PROCESSOR_KWARGS
         (one ops.LogitsProcessors for all rows: it reads each row's own history and index, and a refilled row starts with an empty one),
         params (the RequestParams of the requests that bring none) and generator (an aki_amd.DeviceGenerator or None).
-        Sampling and log-probabilities belong to the REQUEST (aki_amd.RequestParams), never to the call:
+        Sampling, log-probabilities and token constraints belong to the REQUEST (aki_amd.RequestParams), never to the call:
           * do_sample=True with temperature, top_k, top_p: the device sampler with that row's own values (ops.sample_pick_rows: the four
             per-slot arrays are written in place at admit and read by the captured step).  bf16 on the GPU only; on an f32 model a sampled
             request is a ValueError before any device work.  A greedy request in such a call is a top_k = 1 row: the greedy pick's token.
@@ -913,10 +914,20 @@ class AkiMethods:
             (before processors, temperature and filters), one ops.token_logprob behind each pick, launched only when a request asks.
             The call then returns a list of AkiRequestOutput(tokens, logprobs [n], top_token_ids [n, k], top_logprobs [n, k]), the
             three extra fields None for the requests that did not ask (and the top fields for k = 0).
+          * constraint=an aki_amd.TokenConstraint with one start state: the request's tokens walk that automaton (an eos id only behind an
+            accepting state).  The distinct constraints of a call (by identity) are checked against the call's eos ids and the logits'
+            width and uploaded once as one pool of tables, states not renumbered (constraint.ConstraintPool: 32767 states per
+            constraint, DEFAULT_MAX_TABLE_BYTES for the pool); each slot holds its request's place in the pool and its own state
+            history (ops.SlotConstraints), rewritten in place at admit and read by the captured pick, which masks inside the launch.
+            An unconstrained request in such a call is a row without a state: the plain token.  A call in which no request is
+            constrained launches exactly what it launched before.  Composes with do_sample (the draw is made inside the allowed set)
+            and logprobs (the raw distribution).  bf16 on the GPU only; with a banning processor (BANNING_KWARGS: the processors are
+            call-wide), another V, an eos id used as a transition or a reachable state that allows nothing: ValueError naming the
+            request, before any device work.
           Bad values (temperature <= 0, top_p outside (0, 1], top_k < 0, top_logprobs outside the limit or without logprobs, a seed outside
           [0, 2^64)): ValueError naming the request, before any device work.
-        Refused with NotImplementedError (MANY_REFUSED): constraint, num_beams > 1, num_return_sequences > 1, past_key_values, and the
-        CALL-WIDE do_sample / output_logprobs keywords (use RequestParams); a LongRoPE model whose slot capacity exceeds
+        Refused with NotImplementedError (MANY_REFUSED): num_beams > 1, num_return_sequences > 1, past_key_values, and the
+        CALL-WIDE do_sample / output_logprobs / constraint keywords (use RequestParams); a LongRoPE model whose slot capacity exceeds
         original_max_position_embeddings (HF picks the factor set per batch, not per row).  Any other keyword (temperature, top_k, top_p,
         top_logprobs among them): ValueError.  slots above ops.SLOT_MAX_ROWS: ValueError.  Per-request logits processors are not offered.
         The loop (aki_amd/slots.py holds its bookkeeping):
@@ -943,6 +954,7 @@ class AkiMethods:
         eos_list = sorted(opt.eos_ids)
         pk = opt.processors
         sampled = any(rp.do_sample for *_, rp in reqs)
+        constrained = any(rp.constraint is not None for *_, rp in reqs)
         want_lp = any(rp.logprobs for *_, rp in reqs)
         top = max(int(rp.top_logprobs) for *_, rp in reqs)
         lm = self.lang_model
@@ -951,6 +963,20 @@ class AkiMethods:
         on_device = dev.type == "cuda" and dtype == torch.bfloat16
         if sampled and not on_device:
             raise ValueError("generate_many: a sampled request needs the device sampler, which needs bf16 logits on the GPU")
+        head = lm.get_output_embeddings()
+        width = int(head.max_original_id) + 1 + int(head.additional_out_features) if hasattr(head, "max_original_id") else int(head.out_features)
+        pool = None
+        if constrained:                                 # the host half: every table with its eos columns, checked before any device work
+            from .constraint import ConstraintPool
+            pool = ConstraintPool(eos_list, [rp.constraint for *_, rp in reqs], width)
+            banning = [k for k in BANNING_KWARGS if pk[k]]
+            if banning:
+                first = next(i for i, (*_, rp) in enumerate(reqs) if rp.constraint is not None)
+                raise ValueError(f"request {first}: a constraint together with {banning}: a processor that bans tokens can leave a constrained row "
+                                 "with nothing allowed (the processors are call-wide here); only repetition_penalty composes with a constraint")
+            if not on_device:
+                first = next(i for i, (*_, rp) in enumerate(reqs) if rp.constraint is not None)
+                raise ValueError(f"request {first}: a constrained request needs the device pick, which needs bf16 logits on the GPU")
 
         def result(tok, rp, lp=None, top_ids=None, top_lp=None):
             """One request's return value: the tokens, or an AkiRequestOutput when any request of the call asked for log-probabilities."""
@@ -972,6 +998,8 @@ class AkiMethods:
                                 generator=ops.DeviceGenerator(seed))
                 if rp.logprobs:
                     kw_r.update(output_logprobs=True, top_logprobs=int(rp.top_logprobs))
+                if rp.constraint is not None:
+                    kw_r.update(constraint=rp.constraint)
                 out = self._generate_one(vx, lx, **kw_r)
                 row = out.sequences if rp.logprobs else out
                 eos_t = torch.tensor(eos_list, dtype=torch.long, device=row.device) if eos_list else None
@@ -1005,13 +1033,11 @@ class AkiMethods:
         start_len = torch.zeros(slots, dtype=torch.int32, device=dev)
         limit = torch.ones(slots, dtype=torch.int32, device=dev)
         eos_t = torch.tensor(eos_list, dtype=torch.long, device=dev) if eos_list else None
-        head = lm.get_output_embeddings()
-        width = int(head.max_original_id) + 1 + int(head.additional_out_features) if hasattr(head, "max_original_id") else int(head.out_features)
 
         def processors():
             p = ops.LogitsProcessors(width, dev, pk["repetition_penalty"], pk["no_repeat_ngram_size"],
                                      max(int(pk["min_length"]), int(pk["min_new_tokens"])), eos_list, pk["suppress_tokens"],
-                                     pk["begin_suppress_tokens"], pk["bad_words_ids"])
+                                     pk["begin_suppress_tokens"], pk["bad_words_ids"], slot_constraints=constrained)
             return p if p.active else None
 
         # the processed pick keeps a score scratch per batch size, whose address the captured step holds: the admit's one-row pick gets its own
@@ -1022,6 +1048,12 @@ class AkiMethods:
             pick["processors"] = proc
             if on_device:
                 proc.scores(slots, dev)                 # allocated ahead of the capture
+        # a call with a constrained request: the pool of tables (uploaded once), and per slot the place of its request's table and its state
+        # history, allocated ahead of the capture and rewritten in place at admit.  An unconstrained request is a state -1 row.
+        slot_con = None
+        if constrained:
+            slot_con = ops.SlotConstraints(pool.bind(dev), slots, max_budget)
+            pick["slot_constraints"] = slot_con
         # a call with a sampled request: every row's sampler parameters and Philox key live in device arrays the captured pick reads
         # (ops.sample_pick_rows).  A parked row and a greedy request are top_k = 1 rows, the greedy pick's token.
         rows = None
@@ -1065,11 +1097,15 @@ class AkiMethods:
                 rows["top_k"][slot] = int(rp.top_k) if rp.do_sample else 1
                 rows["top_p"][slot] = float(rp.top_p) if rp.do_sample else 1.0
                 rows["seed"][slot] = 0 if seed is None else (seed - (1 << 64) if seed >= 1 << 63 else seed)     # the key's bits as int64
+            if slot_con is not None:                    # the slot's automaton: where its table begins, its start state in column 0
+                slot_con.admit(slot, pool.base[req], pool.n_states[req], pool.start[req])
             args = dict(pad_token_id=opt.pad_id, eos_ids=eos_t, done=row(done, slot), tokens=row(tokens, slot), start_len=row(start_len, slot),
                         done_at=row(done_at, slot))
             if on_device:                               # token 0, from the prefill: the existing pick at B = 1 on row views
                 logits = logits.contiguous()
                 args = args if proc1 is None else dict(args, processors=proc1)
+                if slot_con is not None:
+                    args = dict(args, slot_constraints=slot_con.row(slot))
                 if rows is not None:
                     ops.sample_pick_rows(logits, row(ids, slot), cache_len=row(cache.cache_len, slot), advance=False,
                                          **{k: row(v, slot) for k, v in rows.items()}, **args)

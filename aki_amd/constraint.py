@@ -9,6 +9,9 @@ An automaton is
 `TokenConstraint.from_choices` builds the trie of a closed answer set; `from_table` is the seam for anything compiled elsewhere (a regular
 expression, a JSON schema: such compilers are not part of this package).
 
+`ConstraintPool` is the form `generate_many` takes: the constraints of a queue's requests as one device table, each keeping its own state
+numbers, so the state limit holds per constraint and not per call.
+
 Greedy decoding inside a trie follows the locally best allowed token: it does NOT return the most likely choice as a whole (a choice whose
 first token is unlikely but whose rest is certain loses to one with a likely first token).  To rank a closed set of answers by their
 likelihood use `AKI.score`, which scores every answer teacher-forced behind one prefill.
@@ -166,6 +169,77 @@ class BoundConstraint:
     @property
     def rows(self) -> int:
         return int(self.row_start.numel())
+
+
+class ConstraintPool:
+    """The constraints of one `generate_many` call as ONE device table: the `with_eos(eos_ids)` tables of the distinct constraints (distinct
+    by identity: the same object is stored once) one behind the other, NOT renumbered - a state keeps the number it has in its own
+    constraint, and a row is told where its table begins (`base`) and how many states it has (ops.SlotConstraints, the per-row pick).
+    MAX_STATES therefore bounds each constraint, not the pool.  Pure host code apart from `bind`'s one upload.
+
+    constraints: one entry per request, a TokenConstraint or None (an unconstrained request).  For request i:
+      base[i], n_states[i], start[i]   the pool row of its state 0, its number of states, its start state; (0, 0, -1) without a constraint
+    total_states: the pool's rows; nbytes: what `bind` uploads, total_states * ld * 2 with ld = V rounded up to a multiple of 8.
+    V: the logits' width, which every constraint has to be built for.  Every failed check is a ValueError that names the first request
+    using the constraint; so is nbytes > max_table_bytes, with the byte count."""
+
+    def __init__(self, eos_ids, constraints: Sequence[Optional[TokenConstraint]], V: int, max_table_bytes: int = DEFAULT_MAX_TABLE_BYTES):
+        self.V, self.ld = int(V), (int(V) + 7) // 8 * 8
+        self.eos = sorted({int(e) for e in (eos_ids or [])})
+        self.members: List[TokenConstraint] = []
+        self._tables: List[np.ndarray] = []
+        self.base, self.n_states, self.start = [], [], []
+        at, off = {}, 0                 # id(constraint) -> (base, n_states, start)
+        for i, c in enumerate(constraints):
+            if c is None:
+                self.base.append(0), self.n_states.append(0), self.start.append(-1)
+                continue
+            if id(c) not in at:
+                who = f"request {i}"
+                if not isinstance(c, TokenConstraint):
+                    raise ValueError(f"{who}: constraint is an aki_amd.TokenConstraint, got {type(c).__name__}")
+                if len(c.starts) != 1:
+                    raise ValueError(f"{who}: a constraint with {len(c.starts)} start states; a request has one row, so exactly one is expected")
+                if c.V != self.V:
+                    raise ValueError(f"{who}: the constraint was built for V = {c.V}, the logits have {self.V} columns")
+                if c.n_states > MAX_STATES:
+                    raise ValueError(f"{who}: a token constraint holds at most {MAX_STATES} states, got {c.n_states}")
+                try:
+                    table = c.with_eos(self.eos)
+                except ValueError as e:
+                    raise ValueError(f"{who}: {e}") from None
+                at[id(c)] = (off, c.n_states, c.starts[0])
+                self.members.append(c)
+                self._tables.append(table)
+                off += c.n_states
+            b, n, s = at[id(c)]
+            self.base.append(b), self.n_states.append(n), self.start.append(s)
+        self.total_states = off
+        self.nbytes = self.total_states * self.ld * 2
+        if self.nbytes > int(max_table_bytes):
+            raise ValueError(f"the constraints' device table needs {self.total_states} * {self.ld} * 2 = {self.nbytes} bytes, above "
+                             f"max_table_bytes = {int(max_table_bytes)}")
+
+    @property
+    def constrained(self) -> bool:
+        return self.total_states > 0
+
+    def table(self) -> np.ndarray:
+        """The pool on the host, int32 [total_states, V]: the members' with_eos tables concatenated as they are."""
+        return np.concatenate(self._tables, axis=0) if self._tables else np.zeros((0, self.V), dtype=np.int32)
+
+    def bind(self, device):
+        """The pool on `device`, uploaded once: int16 [total_states, ld], the columns behind V filled with -1."""
+        if not self.constrained:
+            raise ValueError("ConstraintPool.bind: no request of the call is constrained")
+        import torch
+        host = np.empty((self.total_states, self.ld), dtype=np.int16)
+        host[:, self.V:] = -1
+        off = 0
+        for t in self._tables:                      # straight into the int16 rows: no int32 copy of the whole pool on the way
+            host[off:off + t.shape[0], :self.V] = t
+            off += t.shape[0]
+        return torch.from_numpy(host).to(device)
 
 
 def constraint_for_rows(constraint, B: int, n_ret: int = 1):

@@ -68,16 +68,16 @@ int greedy_pick_processed_launch(const void* logits, int B, int V, int ld, const
                                  const void* emb_main, const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores,
                                  int ld_scores, float penalty, int ngram, int min_len, const int64_t* suppress, int n_suppress,
                                  const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad,
-                                 int n_bad_ids,
-                                 const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s);
+                                 int n_bad_ids, const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
+                                 const int* c_row_base, const int* c_row_states, hipStream_t s);
 int sample_pick_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done, int64_t* ids,
                        int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at, const void* emb_main,
                        const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores, int ld_scores, float penalty, int ngram,
                        int min_len, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids,
                        const int* bad_off, int n_bad, int n_bad_ids, int step, float temperature, int top_k, float top_p, uint64_t seed,
                        uint64_t offset, const float* row_temperature, const int* row_top_k, const float* row_top_p, const uint64_t* row_seed,
-                       float* probs, int ld_probs,
-                       const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s);
+                       float* probs, int ld_probs, const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
+                       const int* c_row_base, const int* c_row_states, hipStream_t s);
 int beam_logprob_launch(const void* logits, int in_f32, int rows, int V, int ld, float* out, int ld_out, hipStream_t s);
 int beam_step_launch(const float* logp, int ld, int B, int K, int V, int t, int max_new, float* beam_scores, const int64_t* seqs_in,
                      int64_t* seqs_out, float* hyp_score, int* hyp_len, int64_t* hyp_tokens, int* hyp_count, unsigned char* done,
@@ -815,6 +815,13 @@ static bool constraint_ok(int32_t V, const int16_t* table, int64_t table_ld, int
   return table && states && n_states > 0 && n_states <= 32767 && table_ld >= V && table_ld < (1ll << 31) && states_ld >= 1;
 }
 
+// The per-row forms: the table is a pool of n_states rows (any positive count: a row's own automaton stays below 32768 states, the pool
+// need not), and every row names its slice.  The arrays' values are the caller's: the kernel cuts a slice at the pool's end.
+static bool constraint_rows_ok(int32_t V, const int16_t* table, int64_t table_ld, int32_t n_states, const int32_t* states, int32_t states_ld,
+                               const int32_t* row_base, const int32_t* row_states) {
+  return table && states && row_base && row_states && n_states > 0 && table_ld >= V && table_ld < (1ll << 31) && states_ld >= 1;
+}
+
 // the shared bodies: the plain entry points hand over a null constraint and launch exactly what they launched before
 static int logits_process_checked(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
                                   const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step,
@@ -863,7 +870,8 @@ static int greedy_pick_processed_checked(const void* logits, int32_t B, int32_t 
                                          int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
                                          int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
                                          const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
-                                         int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
+                                         int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld,
+                                         const int32_t* row_base, const int32_t* row_states, void* stream) {
   AKI_CLEAR_ERR();
   AKI_CHECK_ARG(logits && next_ids && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && n_eos >= 0 && (n_eos == 0 || eos_ids));
   AKI_CHECK_ARG((!tokens || tokens_ld > 0) && (!advance || cache_len) && (advance == 0 || advance == 1));
@@ -882,7 +890,8 @@ static int greedy_pick_processed_checked(const void* logits, int32_t B, int32_t 
   return greedy_pick_processed_launch(logits, B, V, (int)ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len,
                                       advance, done_at, embed_weight, additional_weight, max_original_id, d, next_embeds, scores, (int)ld_scores,
                                       repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
-                                      n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids, table, (int)table_ld, n_states, states, states_ld, (hipStream_t)stream);
+                                      n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids, table, (int)table_ld, n_states, states, states_ld, row_base,
+                                      row_states, (hipStream_t)stream);
 }
 
 int aki_greedy_pick_processed(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -895,7 +904,7 @@ int aki_greedy_pick_processed(const void* logits, int32_t B, int32_t V, int64_t 
   return greedy_pick_processed_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
                                        embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
                                        no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
-                                       n_bad_ids, nullptr, 0, 0, nullptr, 0, stream);
+                                       n_bad_ids, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, stream);
 }
 
 int aki_greedy_pick_constrained(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -910,7 +919,23 @@ int aki_greedy_pick_constrained(const void* logits, int32_t B, int32_t V, int64_
   return greedy_pick_processed_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
                                        embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
                                        no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
-                                       n_bad_ids, table, table_ld, n_states, states, states_ld, stream);
+                                       n_bad_ids, table, table_ld, n_states, states, states_ld, nullptr, nullptr, stream);
+}
+
+int aki_greedy_pick_constrained_rows(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                                     uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                                     int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                                     int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                                     int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                                     const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                                     int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states,
+                                     int32_t states_ld, const int32_t* row_base, const int32_t* row_states, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(V > 0 && constraint_rows_ok(V, table, table_ld, n_states, states, states_ld, row_base, row_states));
+  return greedy_pick_processed_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
+                                       embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
+                                       no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
+                                       n_bad_ids, table, table_ld, n_states, states, states_ld, row_base, row_states, stream);
 }
 
 // aki_sample_pick_rows' four device arrays of B entries, in the scalars' place (nullptr: the scalar form)
@@ -923,7 +948,8 @@ static int sample_pick_checked(const void* logits, int32_t B, int32_t V, int64_t
                                int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
                                const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
                                int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
-                               uint64_t offset, const SampleRowArrays* rows, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
+                               uint64_t offset, const SampleRowArrays* rows, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld,
+                               const int32_t* row_base, const int32_t* row_states, void* stream) {
   AKI_CLEAR_ERR();
   AKI_CHECK_ARG(logits && next_ids && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && n_eos >= 0 && (n_eos == 0 || eos_ids));
   AKI_CHECK_ARG((!tokens || tokens_ld > 0) && (!advance || cache_len) && (advance == 0 || advance == 1) && step >= 0);
@@ -947,7 +973,7 @@ static int sample_pick_checked(const void* logits, int32_t B, int32_t V, int64_t
                             no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets,
                             n_bad, n_bad_ids, step, temperature, top_k, top_p, seed, offset, rows ? rows->temperature : nullptr, rows ? rows->top_k : nullptr,
                             rows ? rows->top_p : nullptr, rows ? rows->seed : nullptr, probs_out, (int)ld_probs, table, (int)table_ld, n_states, states, states_ld,
-                            (hipStream_t)stream);
+                            row_base, row_states, (hipStream_t)stream);
 }
 
 int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -961,7 +987,7 @@ int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const 
   return sample_pick_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
                              embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
                              no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
-                             n_bad_ids, step, temperature, top_k, top_p, seed, offset, nullptr, probs_out, ld_probs, nullptr, 0, 0, nullptr, 0, stream);
+                             n_bad_ids, step, temperature, top_k, top_p, seed, offset, nullptr, probs_out, ld_probs, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, stream);
 }
 
 int aki_sample_pick_rows(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -976,7 +1002,27 @@ int aki_sample_pick_rows(const void* logits, int32_t B, int32_t V, int64_t ld, c
   return sample_pick_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
                              embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
                              no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
-                             n_bad_ids, step, 1.f, 0, 1.f, 0ull, 0ull, &rows, probs_out, ld_probs, nullptr, 0, 0, nullptr, 0, stream);
+                             n_bad_ids, step, 1.f, 0, 1.f, 0ull, 0ull, &rows, probs_out, ld_probs, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, stream);
+}
+
+int aki_sample_pick_rows_constrained(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                                     uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                                     int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                                     int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                                     int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                                     const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                                     int32_t n_bad, int32_t n_bad_ids, int32_t step, const float* temperature, const int32_t* top_k,
+                                     const float* top_p, const uint64_t* seed, float* probs_out, int64_t ld_probs, const int16_t* table,
+                                     int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld, const int32_t* row_base,
+                                     const int32_t* row_states, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(V > 0 && constraint_rows_ok(V, table, table_ld, n_states, states, states_ld, row_base, row_states));
+  const SampleRowArrays rows = {temperature, top_k, top_p, seed};
+  return sample_pick_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
+                             embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
+                             no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
+                             n_bad_ids, step, 1.f, 0, 1.f, 0ull, 0ull, &rows, probs_out, ld_probs, table, table_ld, n_states, states, states_ld,
+                             row_base, row_states, stream);
 }
 
 int aki_sample_pick_constrained(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -992,7 +1038,7 @@ int aki_sample_pick_constrained(const void* logits, int32_t B, int32_t V, int64_
   return sample_pick_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
                              embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
                              no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
-                             n_bad_ids, step, temperature, top_k, top_p, seed, offset, nullptr, probs_out, ld_probs, table, table_ld, n_states, states, states_ld, stream);
+                             n_bad_ids, step, temperature, top_k, top_p, seed, offset, nullptr, probs_out, ld_probs, table, table_ld, n_states, states, states_ld, nullptr, nullptr, stream);
 }
 
 int aki_beam_logprob(const void* logits, int32_t dtype, int32_t rows, int32_t V, int64_t ld, float* out, int64_t ld_out, void* stream) {

@@ -1504,10 +1504,25 @@ __device__ __forceinline__ bool pick_better(float a, int ia, float b, int ib) {
 // s, negative = v is not allowed in s; states[b, n] is the state in which row b picks its generated token n (column 0: the start state).
 // The state is addressed by the token index, like the processors' history, never carried in a counter: a replayed graph, a rewind of
 // cache_len after a chain give-up and a repeated step then read and write the right column with nothing to reset.
+// The per-row form (row_base and row_states set, both or neither): `table` is a POOL of n_states rows holding several automata one behind
+// the other, each with its own state numbers from 0; row b's automaton is the row_states[b] pool rows from row_base[b] on.  Both arrays
+// are read by the launch, so a captured step serves a row whose automaton is replaced in place between replays (generate_many's admit).
 struct ConstraintParams {
   const int16_t* table; int table_ld, n_states;
   int* states; int states_ld;
+  const int* row_base; const int* row_states;
 };
+
+// The table rows row b's states index: [base, base + count).  Without the per-row arrays that is the whole table; with them the row's own
+// slice, cut at the pool's end (a negative base: no rows at all, the row is left untouched).
+struct ConstraintRow { int base, count; };
+__device__ __forceinline__ ConstraintRow constraint_row(const ConstraintParams* c, int b) {
+  if (c == nullptr || c->table == nullptr) return ConstraintRow{0, 0};
+  if (c->row_base == nullptr || c->row_states == nullptr) return ConstraintRow{0, c->n_states};
+  const int base = c->row_base[b], count = c->row_states[b];
+  if (base < 0 || base >= c->n_states) return ConstraintRow{0, 0};
+  return ConstraintRow{base, min(count, c->n_states - base)};
+}
 
 // states[b, n], or -1 where there is nothing to read (no constraint, n outside the history)
 __device__ __forceinline__ int constraint_state(const ConstraintParams* c, int b, int n) {
@@ -1517,10 +1532,10 @@ __device__ __forceinline__ int constraint_state(const ConstraintParams* c, int b
 
 constexpr int PICK_THREADS = 1024;
 // The pick's bookkeeping tail, shared by the greedy and the sampling kernels: thread 0 holds the picked id `bi` and what it requested before
-// the scan (was_done, len0, start0, eos4; cs: the row's state under a constraint `c`); pad for finished rows, append, the next state, eos
-// check, cache_len advance, then every thread gathers the next step's embedding row.
+// the scan (was_done, len0, start0, eos4; cs: the row's state under a constraint `c`, cr: its table rows); pad for finished rows, append,
+// the next state, eos check, cache_len advance, then every thread gathers the next step's embedding row.
 __device__ __forceinline__ void pick_finish(const PickParams& p, int b, bool was_done, int len0, int start0, const int64_t (&eos4)[4], int bi,
-                                            const ConstraintParams* c = nullptr, int cs = -1) {
+                                            const ConstraintParams* c = nullptr, int cs = -1, ConstraintRow cr = ConstraintRow{0, 0}) {
   __shared__ int64_t s_next;
   const int tid = threadIdx.x;
   if (tid == 0) {
@@ -1532,9 +1547,10 @@ __device__ __forceinline__ void pick_finish(const PickParams& p, int b, bool was
     }
     if (p.tokens != nullptr && t >= 0 && t < p.tokens_ld) p.tokens[(size_t)b * p.tokens_ld + t] = nxt;
     if (c != nullptr && c->table != nullptr && t >= 0 && t + 1 < c->states_ld) {
-      // a finished row keeps its state; a state or a token outside the table gives -1, which the mask reads as "row untouched"
+      // a finished row keeps its state; a state or a token outside the table gives -1, which the mask reads as "row untouched".  The entry
+      // is stored as it stands: under the per-row form a number local to the row's automaton
       int ns = cs;
-      if (!was_done) ns = (cs >= 0 && cs < c->n_states && bi >= 0 && bi < p.V) ? (int)c->table[(size_t)cs * c->table_ld + bi] : -1;
+      if (!was_done) ns = (cs >= 0 && cs < cr.count && bi >= 0 && bi < p.V) ? (int)c->table[(size_t)(cr.base + cs) * c->table_ld + bi] : -1;
       c->states[(size_t)b * c->states_ld + t + 1] = ns;
     }
     p.ids[b] = nxt;
@@ -1572,6 +1588,7 @@ __device__ __forceinline__ void greedy_pick_row(const PickParams& p, const float
   int len0 = 0, start0 = 0;
   int64_t eos4[4] = {-1, -1, -1, -1};                        // token ids are >= 0: -1 matches nothing
   int cs = -1;
+  ConstraintRow cr = {0, 0};
   if (tid == 0) {
     was_done = p.done != nullptr && p.done[b] != 0;
     if (p.cache_len != nullptr) {
@@ -1581,7 +1598,10 @@ __device__ __forceinline__ void greedy_pick_row(const PickParams& p, const float
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       if (i < p.n_eos) eos4[i] = p.eos[i];
-    if (c != nullptr) cs = constraint_state(c, b, p.step + (p.cache_len != nullptr ? len0 + p.advance - start0 : 0));
+    if (c != nullptr) {
+      cr = constraint_row(c, b);                             // two loads that depend on nothing: out with the others, ahead of the scan
+      cs = constraint_state(c, b, p.step + (p.cache_len != nullptr ? len0 + p.advance - start0 : 0));
+    }
   }
   float best = -INFINITY;
   int bi = 0x7fffffff;
@@ -1644,7 +1664,7 @@ __device__ __forceinline__ void greedy_pick_row(const PickParams& p, const float
     for (int w = 1; w < PICK_THREADS / 64; ++w)
       if (pick_better(s_v[w], s_i[w], best, bi)) { best = s_v[w]; bi = s_i[w]; }
   }
-  pick_finish(p, b, was_done, len0, start0, eos4, bi, c, cs);
+  pick_finish(p, b, was_done, len0, start0, eos4, bi, c, cs, cr);
 }
 
 __global__ __launch_bounds__(PICK_THREADS) void greedy_pick_kernel(const PickParams p) { greedy_pick_row<false>(p, nullptr); }
@@ -1760,9 +1780,10 @@ __device__ void process_row(const ProcParams& q, int b, float* out, unsigned* s_
   // 6: the constraint.  Like the bans it only ever writes -inf, so it shares their side of the barrier behind the penalties.  Eight int16
   // entries per 16-byte load (a negative entry = its sign bit); a state outside the table leaves the row as it is.
   if (q.c.table != nullptr) {
+    const ConstraintRow cr = constraint_row(&q.c, b);
     const int s = constraint_state(&q.c, b, n_state);
-    if (s >= 0 && s < q.c.n_states) {
-      const int16_t* row = q.c.table + (size_t)s * q.c.table_ld;
+    if (s >= 0 && s < cr.count) {
+      const int16_t* row = q.c.table + (size_t)(cr.base + s) * q.c.table_ld;
       const bool vec = ((q.c.table_ld & 7) == 0) && ((((uintptr_t)q.c.table) & 15) == 0);
       const bool vec_out = (((uintptr_t)out) & 15) == 0;
       const int nvec = vec ? V / 8 : 0;
@@ -1941,6 +1962,7 @@ __global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickPar
   int len0 = 0, start0 = 0;
   int64_t eos4[4] = {-1, -1, -1, -1};
   int cs = -1;
+  ConstraintRow cr = {0, 0};
   if (tid == 0) {
     was_done = p.done != nullptr && p.done[b] != 0;
     if (p.cache_len != nullptr) {
@@ -1950,6 +1972,7 @@ __global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickPar
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       if (i < p.n_eos) eos4[i] = p.eos[i];
+    cr = constraint_row(&q.c, b);
     cs = constraint_state(&q.c, b, p.step + (p.cache_len != nullptr ? len0 + p.advance - start0 : 0));
     s_owner = 0x7fffffff; s_last = -1; s_tok = -1;
   }
@@ -2092,7 +2115,7 @@ __global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickPar
       }
     }
   }
-  pick_finish(p, b, was_done, len0, start0, eos4, tok, &q.c, cs);
+  pick_finish(p, b, was_done, len0, start0, eos4, tok, &q.c, cs, cr);
 }
 
 
@@ -2111,7 +2134,7 @@ int logits_process_launch(const void* logits, int in_f32, int B, int V, int ld, 
                           const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s) {
   ProcParams q = proc_params(logits, in_f32, ld, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, penalty, ngram,
                              min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off, n_bad, n_bad_ids);
-  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld};
+  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld, nullptr, nullptr};
   AKI_CLEAR_ERR();
   hipLaunchKernelGGL(logits_process_kernel, dim3(B), dim3(PROC_THREADS), 0, s, q);
   AKI_LAUNCH_CHECK();
@@ -2123,15 +2146,15 @@ int greedy_pick_processed_launch(const void* logits, int B, int V, int ld, const
                                  const void* emb_main, const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores,
                                  int ld_scores, float penalty, int ngram, int min_len, const int64_t* suppress, int n_suppress,
                                  const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad,
-                                 int n_bad_ids,
-                                 const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s) {
+                                 int n_bad_ids, const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
+                                 const int* c_row_base, const int* c_row_states, hipStream_t s) {
   PickParams p = {(const bf16_t*)logits, B, V, ld, eos, n_eos, pad, done, ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
                   (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out};
   // the processors see the tokens generated BEFORE this pick: n = cache_len + advance - start_len, the index the pick writes
   ProcParams q = proc_params(logits, 0, ld, scores, ld_scores, V, tokens, tokens_ld, cache_len, start_len, cache_len ? advance : 0, done,
                              penalty, ngram, min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off, n_bad,
                              n_bad_ids);
-  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld};
+  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld, c_row_base, c_row_states};
   AKI_CLEAR_ERR();
   hipLaunchKernelGGL(greedy_pick_processed_kernel, dim3(B), dim3(PICK_THREADS), 0, s, p, q);
   AKI_LAUNCH_CHECK();
@@ -2144,14 +2167,14 @@ int sample_pick_launch(const void* logits, int B, int V, int ld, const int64_t* 
                        int min_len, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids,
                        const int* bad_off, int n_bad, int n_bad_ids, int step, float temperature, int top_k, float top_p, uint64_t seed,
                        uint64_t offset, const float* row_temperature, const int* row_top_k, const float* row_top_p, const uint64_t* row_seed,
-                       float* probs, int ld_probs,
-                       const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s) {
+                       float* probs, int ld_probs, const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
+                       const int* c_row_base, const int* c_row_states, hipStream_t s) {
   PickParams p = {(const bf16_t*)logits, B, V, ld, eos, n_eos, pad, done, ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
                   (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out, step};
   ProcParams q = proc_params(logits, 0, ld, scores, ld_scores, V, tokens, tokens_ld, cache_len, start_len, step + (cache_len ? advance : 0),
                              done, penalty, ngram, min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off,
                              n_bad, n_bad_ids);
-  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld};
+  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld, c_row_base, c_row_states};
   const bool processed = penalty != 1.f || ngram > 0 || n_bad > 0 || (min_len > 0 && n_eos > 0) || n_suppress > 0 || n_begin > 0 || c_table != nullptr;
   const SampleParams sp = {temperature, top_k, top_p, (unsigned)seed, (unsigned)(seed >> 32), (unsigned)offset, (unsigned)(offset >> 32),
                            probs, ld_probs, processed ? 1 : 0};

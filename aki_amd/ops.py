@@ -728,10 +728,12 @@ class LogitsProcessors:
     constraint (a constraint.BoundConstraint, TokenConstraint.bind's result): a token automaton as the last stage - every token the row's
     state does not allow becomes -inf (the constrained C entry points).  The state history `states()` int32 [rows, steps + 1] belongs to
     this object, one per generation: column 0 holds each row's start state, the picks store the state behind every token they pick, and
-    all of them address it by the generated-token index, as they do the token history."""
+    all of them address it by the generated-token index, as they do the token history.
+    slot_constraints=True: the picks will be handed a SlotConstraints (one automaton per row, generate_many) - the object is then active
+    even with every processor neutral, because the constrained pick scans the f32 scores scratch this object owns."""
 
     def __init__(self, V: int, device, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_length: int = 0, eos_ids=(),
-                 suppress_tokens=None, begin_suppress_tokens=None, bad_words_ids=None, constraint=None):
+                 suppress_tokens=None, begin_suppress_tokens=None, bad_words_ids=None, constraint=None, slot_constraints: bool = False):
         V = int(V)
         if V <= 0:
             raise ValueError(f"logits processors: a vocabulary of {V} columns")
@@ -759,7 +761,7 @@ class LogitsProcessors:
         self.suppress, self.begin_suppress = ids("suppress_tokens", suppress_tokens), ids("begin_suppress_tokens", begin_suppress_tokens)
         self.words = words
         self.active = bool(pen != 1.0 or self.ngram > 0 or words or (self.min_length > 0 and eos) or self.suppress or self.begin_suppress
-                           or constraint is not None)
+                           or constraint is not None or slot_constraints)
         if self.active and V > L.AKI_LOGITS_PROCESS_MAX_V:
             raise ValueError(f"logits processors: a vocabulary of {V} is above {L.AKI_LOGITS_PROCESS_MAX_V}")
         dev = torch.device(device)
@@ -862,10 +864,75 @@ class LogitsProcessors:
         return out
 
 
+class SlotConstraints:
+    """One token automaton per ROW, for rows that change hands (generate_many's slots): what the per-row constrained picks take as
+    `slot_constraints` (aki_greedy_pick_constrained_rows / aki_sample_pick_rows_constrained).
+      pool        int16 [pool rows, ld >= V]: constraint.ConstraintPool.bind's table - the automata one behind the other, states local
+      row_base    int32 [slots]: the pool row at which the slot's automaton begins
+      row_states  int32 [slots]: its number of states (0: none)
+      states      int32 [slots, max_budget + 1]: the slot's state history, addressed by the generated-token index; -1 = no state, the row
+                  is left unmasked (an unconstrained request)
+    All four are allocated once - a captured step holds their addresses - and `admit` rewrites a slot's entries in place."""
+
+    def __init__(self, pool: torch.Tensor, slots: int, max_budget: int, _parts=None):
+        self.pool = pool
+        if _parts is not None:
+            self.row_base, self.row_states, self.states = _parts
+            return
+        dev = pool.device
+        self.row_base = torch.zeros(int(slots), dtype=torch.int32, device=dev)
+        self.row_states = torch.zeros(int(slots), dtype=torch.int32, device=dev)
+        self.states = torch.full((int(slots), int(max_budget) + 1), -1, dtype=torch.int32, device=dev)
+
+    def row(self, slot: int) -> "SlotConstraints":
+        """One-row views of everything: what a B = 1 pick on the slot's row views takes."""
+        s = int(slot)
+        return SlotConstraints(self.pool, 1, 0, _parts=(self.row_base[s:s + 1], self.row_states[s:s + 1], self.states[s:s + 1]))
+
+    def admit(self, slot: int, base: int, n: int, start: int) -> None:
+        """A new request in `slot`: its history emptied, column 0 = its start state (-1 for an unconstrained request), its table's place.
+        Tensor fills only - nothing is copied from the host or reallocated."""
+        s = int(slot)
+        self.states[s].fill_(-1)
+        self.states[s, 0] = int(start)
+        self.row_base[s] = int(base)
+        self.row_states[s] = int(n)
+
+    def _args(self, name: str, B: int, V: int, device):
+        """(table, table_ld, n_states, states, states_ld, row_base, row_states) of the per-row C entry points, checked."""
+        t_ = self.pool
+        if not torch.is_tensor(t_) or t_.dtype != torch.int16 or t_.dim() != 2 or t_.shape[0] < 1 or t_.shape[1] < V or not t_.is_contiguous() \
+                or t_.device != device:
+            raise AkiError(f"{name}: slot_constraints.pool is a contiguous int16 tensor [pool rows >= 1, >= {V}] on {device}")
+        for nm, x in (("row_base", self.row_base), ("row_states", self.row_states)):
+            if not torch.is_tensor(x) or x.dtype != torch.int32 or tuple(x.shape) != (B,) or not x.is_contiguous() or x.device != device:
+                raise AkiError(f"{name}: slot_constraints.{nm} is a contiguous int32 tensor [{B}] on {device}")
+        st = self.states
+        if not torch.is_tensor(st) or st.dtype != torch.int32 or st.dim() != 2 or st.shape[0] != B or st.shape[1] < 1 or not st.is_contiguous() \
+                or st.device != device:
+            raise AkiError(f"{name}: slot_constraints.states is a contiguous int32 tensor [{B}, >= 1] on {device}")
+        return (_ptr(t_), t_.stride(0), t_.shape[0], _ptr(st), st.shape[1], _ptr(self.row_base), _ptr(self.row_states))
+
+
+def _slot_constraint_args(name: str, slot_constraints, processors, B: int, V: int, device):
+    """The per-row constraint's seven C arguments, or None without one.  The pick scans the processors' f32 scratch, so an active
+    LogitsProcessors is needed (LogitsProcessors(..., slot_constraints=True) is one); it cannot carry a BoundConstraint of its own."""
+    if slot_constraints is None:
+        return None
+    if not isinstance(slot_constraints, SlotConstraints):
+        raise AkiError(f"{name}: slot_constraints is an ops.SlotConstraints")
+    if processors is None or not processors.active:
+        raise AkiError(f"{name}: slot_constraints needs an active LogitsProcessors (LogitsProcessors(..., slot_constraints=True)) for the scores scratch")
+    if processors.constraint is not None:
+        raise AkiError(f"{name}: slot_constraints together with a LogitsProcessors that carries a constraint of its own")
+    return slot_constraints._args(name, B, V, device)
+
+
 def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int = 0, eos_ids: Optional[torch.Tensor] = None,
                 done: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, cache_len: Optional[torch.Tensor] = None,
                 start_len: Optional[torch.Tensor] = None, advance: bool = False, done_at: Optional[torch.Tensor] = None,
-                embed=None, next_embeds: Optional[torch.Tensor] = None, processors: Optional[LogitsProcessors] = None) -> torch.Tensor:
+                embed=None, next_embeds: Optional[torch.Tensor] = None, processors: Optional[LogitsProcessors] = None,
+                slot_constraints: Optional[SlotConstraints] = None) -> torch.Tensor:
     """The step between two decode steps of a greedy `generate` as one launch (aki_greedy_pick; HF GenerationMixin's greedy branch):
     next_ids[b] = pad if done[b] else argmax(logits[b]); tokens[b, t] = next with t = cache_len[b] + advance - start_len[b]; rows whose
     next is an eos id become done (done_at[b] = t); advance: cache_len += 1.  logits: bf16 [B, V] (row stride >= V); next_ids / tokens /
@@ -874,7 +941,10 @@ def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
     embedding row (DecoupledEmbedding's two tables, src/helpers.py:440-492) is written to next_embeds in the same launch - the input of the next
     decode step.
     processors (an active LogitsProcessors): the pick scans the processed scores of the row instead, in the same launch
-    (aki_greedy_pick_processed); the history is tokens[b, :t] and the minimum length bans eos_ids."""
+    (aki_greedy_pick_processed); the history is tokens[b, :t] and the minimum length bans eos_ids.
+    slot_constraints (an ops.SlotConstraints, with an active `processors` that carries no constraint of its own): one automaton per row as
+    the last processor stage (aki_greedy_pick_constrained_rows) - row b in state s = states[b, t] is masked by pool row row_base[b] + s
+    and states[b, t + 1] receives the table entry, a state local to the row's automaton; a row in state -1 is picked unmasked."""
     if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
         raise AkiError("greedy_pick takes bf16 logits [B, V] with unit column stride")
     B, V = logits.shape
@@ -897,6 +967,7 @@ def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
             raise AkiError("greedy_pick: next_embeds is [B, d]")
         if w.shape[0] <= max_orig:
             raise AkiError("greedy_pick: the embedding table has fewer than max_original_id + 1 rows")
+    rows_con = _slot_constraint_args("greedy_pick", slot_constraints, processors, B, V, logits.device)
     if processors is not None and processors.active:
         if processors.V != V:
             raise AkiError(f"greedy_pick: the processors were built for V = {processors.V}, the logits have {V} columns")
@@ -904,6 +975,10 @@ def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
         head, tail = processors._tail()
         emb = (None, None, 0, 0, 0, None) if embed is None else \
             (_ptr(w), _ptr(extra), int(max_orig), 0 if extra is None else extra.shape[0], d, _ptr(next_embeds))
+        if rows_con is not None:
+            L.check(L.load().aki_greedy_pick_constrained_rows(*common, *emb, _ptr(sc), sc.stride(0), *head, *tail, *rows_con, _stream()),
+                    "aki_greedy_pick_constrained_rows")
+            return next_ids
         con = processors._constraint_args(B, tokens.shape[1] if tokens is not None else (1 if cache_len is None else None))
         if con is not None:
             L.check(L.load().aki_greedy_pick_constrained(*common, *emb, _ptr(sc), sc.stride(0), *head, *tail, *con, _stream()),
@@ -1011,13 +1086,14 @@ def sample_pick_rows(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id:
                      embed=None, next_embeds: Optional[torch.Tensor] = None, processors: Optional[LogitsProcessors] = None, step: int = 0,
                      temperature: Optional[torch.Tensor] = None, top_k: Optional[torch.Tensor] = None, top_p: Optional[torch.Tensor] = None,
                      seed: Optional[torch.Tensor] = None, probs_out: Optional[torch.Tensor] = None,
-                     scores: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     scores: Optional[torch.Tensor] = None, slot_constraints: Optional[SlotConstraints] = None) -> torch.Tensor:
     """ops.sample_pick with the sampling parameters per row, one launch (aki_sample_pick_rows): `temperature` f32, `top_k` int32, `top_p`
     f32 and `seed` int64 (its bits are the 64-bit Philox key) are contiguous device tensors [B], read by the launch - a captured step
     serves rows whose parameters are rewritten in place.  Row b draws u = Philox4x32-10(key = seed[b], counter = (n, 0, 0, 0))[0], n as
     in ops.sample_pick: the draw of row 0 of a B = 1 ops.sample_pick call with that seed and offset 0, so the stream belongs to the seed and
-    not to the row.  A row with top_k[b] == 1 takes ops.greedy_pick's token.  No constraint: one LogitsProcessors without one serves all
-    rows.  The VALUES in the four arrays are not checked here (no host value is read: capturable); whoever writes them validates them
+    not to the row.  A row with top_k[b] == 1 takes ops.greedy_pick's token.  A LogitsProcessors that carries a constraint is refused
+    (its row_start is fixed for its life); slot_constraints (an ops.SlotConstraints, as in ops.greedy_pick) gives every row its own
+    automaton instead (aki_sample_pick_rows_constrained): the draw is made among the tokens the row's state allows.  The VALUES in the four arrays are not checked here (no host value is read: capturable); whoever writes them validates them
     (temperature > 0, top_k >= 0, 0 < top_p <= 1) - in the kernel a temperature that is not > 0 falls to the greedy token, top_k <= 0 or
     >= V and top_p >= 1 switch their filter off."""
     if int(step) < 0:
@@ -1026,9 +1102,18 @@ def sample_pick_rows(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id:
     if logits.dim() == 2 and any(t_ is None or tuple(t_.shape) != (logits.shape[0],) for t_, _ in rows):
         raise AkiError(f"sample_pick_rows: temperature (f32), top_k (int32), top_p (f32) and seed (int64) are tensors [{logits.shape[0]}]")
     if processors is not None and processors.active and processors.constraint is not None:
-        raise AkiError("sample_pick_rows: no constrained form; ops.sample_pick takes a constraint")
+        raise AkiError("sample_pick_rows: a LogitsProcessors with a constraint of its own is not taken (no constrained form of that kind); "
+                       "pass slot_constraints, or use ops.sample_pick")
+    if logits.dim() == 2:
+        rows_con = _slot_constraint_args("sample_pick_rows", slot_constraints, processors, logits.shape[0], logits.shape[1], logits.device)
+    else:
+        rows_con = None
     front, probs, _ = _sample_pick_front("sample_pick_rows", logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len,
                                          advance, done_at, embed, next_embeds, processors, step, probs_out, scores, extra=rows)
+    if rows_con is not None:
+        L.check(L.load().aki_sample_pick_rows_constrained(*front, _ptr(temperature), _ptr(top_k), _ptr(top_p), _ptr(seed), *probs, *rows_con,
+                                                          _stream()), "aki_sample_pick_rows_constrained")
+        return next_ids
     L.check(L.load().aki_sample_pick_rows(*front, _ptr(temperature), _ptr(top_k), _ptr(top_p), _ptr(seed), *probs, _stream()),
             "aki_sample_pick_rows")
     return next_ids

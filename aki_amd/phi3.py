@@ -222,6 +222,8 @@ class DecodeGraph:
         With a "row_seed" key it holds ops.sample_pick_rows' arguments (temperature, top_k, top_p and row_seed: device arrays of one entry per
         row, the last one passed on as `seed`): the captured pick reads every row's parameters and key from those arrays at each replay, so
         they may be rewritten in place between replays (generate_many's admit).
+        A "slot_constraints" key (an ops.SlotConstraints, with "processors") is handed to either pick unchanged: one token automaton per row,
+        whose place in the pool and state history are device tensors rewritten in place at admit as well.
         With a "logprob" key (the in-loop arguments of ops.token_logprob) that launch is captured right behind the pick.
         With a "tick" key (ops.slot_tick's done / done_at / start_len / limit) the rows' token budgets are ticked behind the pick too."""
         self.lm, self.cache = lm, cache

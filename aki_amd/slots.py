@@ -8,7 +8,10 @@ from __future__ import annotations
 
 from collections import deque
 from dataclasses import dataclass
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import TYPE_CHECKING, Callable, List, Optional, Sequence, Tuple
+
+if TYPE_CHECKING:
+    from .constraint import TokenConstraint
 
 
 @dataclass(frozen=True)
@@ -16,7 +19,9 @@ class RequestParams:
     """What one request of generate_many asks for beyond its budget.  do_sample with temperature / top_k / top_p: the device sampler
     (ops.sample_pick_rows) with these values in the request's row; seed: the request's own 64-bit Philox key (None: derived, see
     request_seed) - its draws depend on (seed, generated-token index) only, never on the slot or the neighbours.  logprobs: return the
-    log-probability of every returned token under the raw model distribution, with the top_logprobs most likely alternatives."""
+    log-probability of every returned token under the raw model distribution, with the top_logprobs most likely alternatives.
+    constraint: an aki_amd.TokenConstraint with one start state, or None - the request's tokens walk that automaton (the same object may
+    serve several requests: its table is stored once); it composes with sampling and log-probabilities."""
     do_sample: bool = False
     temperature: float = 1.0
     top_k: int = 0
@@ -24,6 +29,7 @@ class RequestParams:
     seed: Optional[int] = None
     logprobs: bool = False
     top_logprobs: int = 0
+    constraint: Optional["TokenConstraint"] = None
 
     def check(self, index, max_top: int) -> "RequestParams":
         """ValueError naming request `index` (a number, or a word such as "default") for a value the device sampler or ops.token_logprob
@@ -41,6 +47,13 @@ class RequestParams:
             raise ValueError(f"{who}: top_logprobs needs logprobs=True")
         if self.seed is not None and (int(self.seed) != self.seed or not 0 <= int(self.seed) < 1 << 64):
             raise ValueError(f"{who}: seed is an integer in [0, 2^64), got {self.seed}")
+        if self.constraint is not None:
+            from .constraint import TokenConstraint
+            if not isinstance(self.constraint, TokenConstraint):
+                raise ValueError(f"{who}: constraint is an aki_amd.TokenConstraint or None, got {type(self.constraint).__name__}")
+            if len(self.constraint.starts) != 1:
+                raise ValueError(f"{who}: a constraint with {len(self.constraint.starts)} start states; a request is one row, so exactly one "
+                                 "start state is expected")
         return self
 
 

@@ -914,6 +914,42 @@ int aki_sample_pick_constrained(const void* logits, int32_t B, int32_t V, int64_
                                 uint64_t offset, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld, int32_t n_states,
                                 int32_t* states, int32_t states_ld, void* stream);
 
+/* ---- constrained decoding, one automaton per ROW (generate_many: a slot's request, and so its automaton, changes at admit under a
+ * captured step).  Purely additive: AKI_ABI_VERSION was not bumped (it stays 17).  aki_greedy_pick_constrained_rows is
+ * aki_greedy_pick_constrained, and aki_sample_pick_rows_constrained is aki_sample_pick_rows with the constraint's five arguments, each
+ * with two more device arrays of B entries in front of `stream`, read by the launch itself (no host value is read: capturable):
+ *   table      int16 [n_states, table_ld]: a POOL - several automata one behind the other, each with its own state numbers from 0
+ *              (nothing is renumbered).  n_states is the pool's row count, any positive number: the 32767 limit holds per automaton.
+ *   row_base   int32 [B]: the pool row at which row b's automaton begins.
+ *   row_states int32 [B]: the number of states of row b's automaton.
+ * With s = states[b, n], row b is masked by pool row row_base[b] + s when 0 <= s < row_states[b] and row_base[b] + s < n_states;
+ * otherwise (s = -1: an unconstrained row; row_states[b] = 0; a slice that leaves the pool; a negative base) the row is left untouched
+ * and its next state is -1.  The state the picks store in states[b, n + 1] is the table entry as it stands, a number LOCAL to the row's
+ * automaton; a row with done[b] != 0 keeps its state.  The caller rewrites row_base[b], row_states[b] and states[b, :] in place when
+ * the row changes hands; everything else is as documented for the entry points these extend. */
+int aki_greedy_pick_constrained_rows(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos,
+                                     int64_t pad_token_id, uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld,
+                                     int32_t* cache_len, const int32_t* start_len, int32_t advance, int32_t* done_at, const void* embed_weight,
+                                     const void* additional_weight, int64_t max_original_id, int64_t num_additional, int32_t d,
+                                     void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                                     int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                                     const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids,
+                                     const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld,
+                                     int32_t n_states, int32_t* states, int32_t states_ld, const int32_t* row_base,
+                                     const int32_t* row_states, void* stream);
+
+int aki_sample_pick_rows_constrained(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos,
+                                     int64_t pad_token_id, uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld,
+                                     int32_t* cache_len, const int32_t* start_len, int32_t advance, int32_t* done_at, const void* embed_weight,
+                                     const void* additional_weight, int64_t max_original_id, int64_t num_additional, int32_t d,
+                                     void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                                     int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                                     const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids,
+                                     const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, int32_t step, const float* temperature,
+                                     const int32_t* top_k, const float* top_p, const uint64_t* seed, float* probs_out, int64_t ld_probs,
+                                     const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld,
+                                     const int32_t* row_base, const int32_t* row_states, void* stream);
+
 /* ---- beam search on the device (beam.hip).  HF `GenerationMixin` beam search with a `BeamSearchScorer`, the algorithm AKI._beam_search
  * runs on the host: 2K candidates per step, hypotheses normalised by generated_length ** length_penalty, at most K per sample.
  * Purely additive: AKI_ABI_VERSION was not bumped (it stays 17). */

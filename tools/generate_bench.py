@@ -25,7 +25,11 @@ requests, budgets, EOS off and slot counts; the greedy queue leg and the sampled
 ...) with its own seed) alternate in one process, with --logprobs K two more legs (greedy requests with logprobs=True at top_logprobs 0
 and K).  Writes profiles/many_sample_bench.json: returned tokens/s and wall ms per decode step of every leg, and each leg's excess per step
 over the greedy leg of the same round (the admits are the same work in every leg).
-    python tools/generate_bench.py [--many] [--many --sample --temperature 0.8 --top-k 50 --top-p 0.9 --logprobs 8]
+--many --constraint: the queue with per-request token constraints (many_constraint_bench below): the same 64 requests, each with its OWN
+16-state cycle object (state s allows the ids v with v % 16 == s: a pool of 64 x 16 states, one table row read per row and step), against
+the greedy queue, alternating in one process at 8 and 16 slots.  Writes profiles/many_constraint_bench.json: tokens/s and ms per decode
+step of both legs, the microseconds per step the constrained leg adds (median and spread over the rounds).
+    python tools/generate_bench.py [--many] [--many --sample --temperature 0.8 --top-k 50 --top-p 0.9 --logprobs 8] [--many --constraint]
     python tools/generate_bench.py [--new 256] [--fp8] [--txt 64] [--repetition-penalty 1.2] [--no-repeat-ngram 3]
                                    [--sample --temperature 0.8 --top-k 50 --top-p 0.9] [--batch 8] [--logprobs 8 --rounds 4] [--constraint]"""
 import argparse, json, os, sys, time
@@ -185,6 +189,93 @@ def many_sample_bench(a, model, dev):
     print(json.dumps({k: v for k, v in res.items() if k != "budgets"}))
 
 
+def many_constraint_bench(a, model, dev):
+    """--many --constraint: generate_many with a token constraint per request against the greedy queue, many_bench's requests.  Writes
+    profiles/many_constraint_bench.json."""
+    import numpy as np
+    import aki_amd
+    import bench
+    from aki_amd.constraint import TokenConstraint
+    n_req = a.many_requests
+    g = torch.Generator(device="cpu").manual_seed(4242)
+    budgets = torch.randint(16, 257, (n_req,), generator=g).tolist()
+    reqs = []
+    for i in range(n_req):
+        vx, ids, _ = bench.synth_batch(1, dev, torch.bfloat16, model.media_token_id, seed=1000 + i)
+        reqs.append((vx, ids, budgets[i]))
+    head = model.lang_model.get_output_embeddings()              # V': the logits' width
+    V = int(head.max_original_id) + 1 + int(head.additional_out_features) if hasattr(head, "max_original_id") else int(head.out_features)
+    nxt = np.full((16, V), -1, dtype=np.int32)
+    for s_ in range(16):
+        nxt[s_, s_::16] = (s_ + 1) % 16
+    # one OBJECT per request: the pool stores 64 tables of 16 states (equal objects would be stored once)
+    legs = {"greedy": [aki_amd.RequestParams()] * n_req,
+            "constrained": [aki_amd.RequestParams(constraint=TokenConstraint.from_table(nxt, np.ones(16, dtype=bool))) for _ in range(n_req)]}
+
+    def leg(name, slots):
+        batch = [(vx, ids, b, rp) for (vx, ids, b), rp in zip(reqs, legs[name])]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        outs = model.generate_many(batch, slots=slots, eos_token_id=[])
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        assert [o.numel() for o in outs] == budgets
+        if name == "constrained":
+            for o in outs:
+                assert bool((o % 16 == torch.arange(o.numel(), device=dev) % 16).all()), "not a walk of the cycle"
+        return wall, dict(model.last_many_stats)
+
+    def pool_ms():
+        """What a constrained call pays once, whatever its length: the pool built on the host and uploaded (the tables' checks are cached
+        in the constraint objects after the warm-up)."""
+        from aki_amd.constraint import ConstraintPool
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ConstraintPool([], [rp.constraint for rp in legs["constrained"]], V).bind(dev)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    res = {"requests": n_req, "prompt_tokens_lm_stream": bench.N_TXT - 1 + bench.NV, "budgets": budgets, "budget_seed": 4242,
+           "constraint": "one 16-state cycle object per request (state s allows v with v % 16 == s): a pool of 64 x 16 states",
+           "pool_states": 16 * n_req, "pool_bytes": 16 * n_req * ((V + 7) // 8 * 8) * 2,
+           "method": "the two legs alternate in one process, wall clock around each generate_many call with a device synchronisation on "
+                     "both sides; tokens/s = returned tokens / wall time, prefills and the pool's one upload included; ms_per_step = wall "
+                     "time / decode steps replayed - both legs admit the same 64 prompts, so the excess over the greedy leg of the same "
+                     "round is the constrained call's cost per step: the pick's, plus the pool's build and upload (once per call, timed "
+                     "on its own as pool_ms) spread over the steps; added_us_per_step_without_the_pool takes that share out", "slots": {}}
+    for slots in (8, 16):
+        for name in legs:
+            leg(name, slots)                                          # warm-up: allocator, folds, capture path
+        rounds = []
+        for _ in range(max(3, a.rounds)):
+            r = {}
+            for name in legs:
+                wall, stats = leg(name, slots)
+                r[name] = {"tokens_per_s": round(sum(budgets) / wall, 1), "wall_s": round(wall, 3), "steps": stats["steps"],
+                           "ms_per_step": round(wall * 1e3 / stats["steps"], 4)}
+            r["pool_ms"] = round(pool_ms(), 2)
+            rounds.append(r)
+        summary = {}
+        for name in legs:
+            summary[name] = {"tokens_per_s_median": med([r[name]["tokens_per_s"] for r in rounds]),
+                             "tokens_per_s_min_max": [min(r[name]["tokens_per_s"] for r in rounds), max(r[name]["tokens_per_s"] for r in rounds)],
+                             "ms_per_step_median": med([r[name]["ms_per_step"] for r in rounds])}
+        ex = [(r["constrained"]["ms_per_step"] - r["greedy"]["ms_per_step"]) * 1e3 for r in rounds]
+        net = [e - r["pool_ms"] * 1e3 / r["constrained"]["steps"] for e, r in zip(ex, rounds)]
+        summary["constrained"]["added_us_per_step_median"] = round(med(ex), 1)
+        summary["constrained"]["added_us_per_step_min_max"] = [round(min(ex), 1), round(max(ex), 1)]
+        summary["constrained"]["pool_ms_median"] = med([r["pool_ms"] for r in rounds])
+        summary["constrained"]["added_us_per_step_without_the_pool_median"] = round(med(net), 1)
+        summary["constrained"]["added_us_per_step_without_the_pool_min_max"] = [round(min(net), 1), round(max(net), 1)]
+        res["slots"][str(slots)] = {"rounds": rounds, "summary": summary}
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "many_constraint_bench.json")
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps({k: v for k, v in res.items() if k != "budgets"}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--new", type=int, default=256)
@@ -207,7 +298,8 @@ def main():
     ap.add_argument("--constraint", action="store_true", help="one more leg per round: greedy under a 16-state token constraint")
     ap.add_argument("--many", action="store_true", help="in-flight batching: generate() over static groups against generate_many, 64 requests with "
                     "budgets 16..256 at 8 and 16 slots -> profiles/many_bench.json (the other legs are skipped); with --sample: the greedy "
-                    "queue against the queue with per-request sampling (and --logprobs K) -> profiles/many_sample_bench.json")
+                    "queue against the queue with per-request sampling (and --logprobs K) -> profiles/many_sample_bench.json; with "
+                    "--constraint: against the queue with one 16-state constraint per request -> profiles/many_constraint_bench.json")
     ap.add_argument("--many-requests", type=int, default=64)
     a = ap.parse_args()
     lp_kw =dict(output_logprobs=True, top_logprobs=a.logprobs) if a.logprobs >= 0 else None
@@ -227,6 +319,8 @@ def main():
         model.lang_model.enable_mxfp4()
     model.lang_model.model.decode_chain_w4 = bool(a.w4_chain)
     if a.many:
+        if a.constraint:
+            return many_constraint_bench(a, model, dev)
         return many_sample_bench(a, model, dev) if a.sample else many_bench(a, model, dev)
     vx, ids, am =bench.synth_batch(1, dev, torch.bfloat16, model.media_token_id, seed=1000)
     if a.batch > 1:

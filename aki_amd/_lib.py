@@ -18,6 +18,7 @@ AKI_MAX_RECTS = 8
 AKI_PLAN_STRIDE = 12
 AKI_ABI_VERSION = 17
 AKI_LOGITS_PROCESS_MAX_V = 131072
+AKI_PROCESSOR_SET_WORDS = 9
 AKI_BEAM_MAX_K, AKI_BEAM_MAX_EOS, AKI_KV_BEAM_REORDER_CHUNK = 16, 8, 16
 AKI_LOGPROB_MAX_TOP, AKI_LOGPROB_MAX_V = 8, 262144
 AKI_SLOT_MAX_ROWS = 16
@@ -272,6 +273,23 @@ SIGNATURES = {
                                                    C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                                    C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # one set of processor settings per row: (sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words) in the place of the eleven
+    # scalar processor arguments, and the per-row constraint's seven in front of the stream (a null table: no constraint)
+    "aki_logits_process_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aki_greedy_pick_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                       C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aki_sample_pick_rows_processed": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                 C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aki_beam_logprob": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "aki_beam_step": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 11 + [C.c_int32, C.c_int64, C.c_float, C.c_int32,
                                                                                                 C.c_int32, C.c_void_p]),

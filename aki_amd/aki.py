@@ -21,7 +21,7 @@ except Exception:  # pragma: no cover - transformers is present in this image
 from . import ops
 from .helpers import PerceiverResampler
 from .phi3 import AkiKVCache, DecodeGraph
-from .slots import RequestParams, SlotScheduler, request_seed, slot_capacity
+from .slots import RequestParams, SlotScheduler, banning_keywords, processor_set_key, request_seed, resolve_processors, slot_capacity
 from .vlm import VLMWithLanguageStream
 
 
@@ -896,7 +896,8 @@ class AkiMethods:
         tensors in request order, each cut behind its first EOS (EOS included) or at its budget.  `last_many_stats` holds the scheduler's
         counters afterwards.
         Keywords: max_new_tokens (the default budget), eos_token_id, pad_token_id, use_graph, the logits processors of PROCESSOR_KWARGS
-        (one ops.LogitsProcessors for all rows: it reads each row's own history and index, and a refilled row starts with an empty one),
+        (the default of every request: one ops.LogitsProcessors for all rows when no request overrides them - it reads each row's own history
+        and index, and a refilled row starts with an empty one),
         params (the RequestParams of the requests that bring none) and generator (an aki_amd.DeviceGenerator or None).
         Sampling, log-probabilities and token constraints belong to the REQUEST (aki_amd.RequestParams), never to the call:
           * do_sample=True with temperature, top_k, top_p: the device sampler with that row's own values (ops.sample_pick_rows: the four
@@ -921,15 +922,23 @@ class AkiMethods:
             history (ops.SlotConstraints), rewritten in place at admit and read by the captured pick, which masks inside the launch.
             An unconstrained request in such a call is a row without a state: the plain token.  A call in which no request is
             constrained launches exactly what it launched before.  Composes with do_sample (the draw is made inside the allowed set)
-            and logprobs (the raw distribution).  bf16 on the GPU only; with a banning processor (BANNING_KWARGS: the processors are
-            call-wide), another V, an eos id used as a transition or a reachable state that allows nothing: ValueError naming the
-            request, before any device work.
+            and logprobs (the raw distribution).  bf16 on the GPU only; another V, an eos id used as a transition or a reachable state
+            that allows nothing: ValueError naming the request, before any device work.  The banning rule is per request: a request that,
+            after resolution, carries a constraint AND a banning processor (BANNING_KWARGS) is a ValueError naming it and the keyword; a
+            constrained request next to an unconstrained one with bans is legal, and a constrained request may override a call-wide
+            banning keyword with the neutral value.  Only repetition_penalty composes with a constraint.
+          * the logits processors of PROCESSOR_KWARGS as RequestParams fields, None by default: None takes the call's value (params=, else
+            the call-wide keyword); any other value, the neutral 1.0 / 0 / () included, is the request's alone.  The distinct resolved
+            settings of a call form a pool deduplicated by value and uploaded once (ops.ProcessorSets); each slot holds one int32 set
+            index, filled at admit ahead of the pick of token 0 and read by the captured pick (aki_greedy_pick_rows /
+            aki_sample_pick_rows_processed; an f32 model's torch pick takes aki_logits_process_rows' scores).  A call whose requests all
+            resolve to ONE set launches exactly what it launched before.  Log-probabilities stay the raw distribution's.
           Bad values (temperature <= 0, top_p outside (0, 1], top_k < 0, top_logprobs outside the limit or without logprobs, a seed outside
           [0, 2^64)): ValueError naming the request, before any device work.
         Refused with NotImplementedError (MANY_REFUSED): num_beams > 1, num_return_sequences > 1, past_key_values, and the
         CALL-WIDE do_sample / output_logprobs / constraint keywords (use RequestParams); a LongRoPE model whose slot capacity exceeds
         original_max_position_embeddings (HF picks the factor set per batch, not per row).  Any other keyword (temperature, top_k, top_p,
-        top_logprobs among them): ValueError.  slots above ops.SLOT_MAX_ROWS: ValueError.  Per-request logits processors are not offered.
+        top_logprobs among them): ValueError.  slots above ops.SLOT_MAX_ROWS: ValueError.
         The loop (aki_amd/slots.py holds its bookkeeping):
           * one AkiKVCache of `slots` rows and capacity max(expanded prompt length + budget), computed from the ids on the host; the per-row
             tokens / done / done_at / start_len / limit / ids buffers are allocated once - the captured step holds their addresses;
@@ -965,15 +974,26 @@ class AkiMethods:
             raise ValueError("generate_many: a sampled request needs the device sampler, which needs bf16 logits on the GPU")
         head = lm.get_output_embeddings()
         width = int(head.max_original_id) + 1 + int(head.additional_out_features) if hasattr(head, "max_original_id") else int(head.out_features)
+        # every request's processor settings: its own, else params=, else the call-wide keyword - checked on the host against the logits'
+        # width and reduced to one value per distinct behaviour.  A call whose requests all resolve to one set runs the call-wide path.
+        resolved = [resolve_processors(rp, opt.params, pk) for *_, rp in reqs]
+        set_keys = [processor_set_key(f"request {i}", r, eos_list, width) for i, r in enumerate(resolved)]
+        mixed = len(set(set_keys)) > 1
+        if not mixed:
+            pk = resolved[0]
         pool = None
         if constrained:                                 # the host half: every table with its eos columns, checked before any device work
             from .constraint import ConstraintPool
             pool = ConstraintPool(eos_list, [rp.constraint for *_, rp in reqs], width)
-            banning = [k for k in BANNING_KWARGS if pk[k]]
-            if banning:
-                first = next(i for i, (*_, rp) in enumerate(reqs) if rp.constraint is not None)
-                raise ValueError(f"request {first}: a constraint together with {banning}: a processor that bans tokens can leave a constrained row "
-                                 "with nothing allowed (the processors are call-wide here); only repetition_penalty composes with a constraint")
+            for i, ((*_, rp), r) in enumerate(zip(reqs, resolved)):
+                banning = banning_keywords(f"request {i}", r, eos_list, width) if rp.constraint is not None else []
+                for k in PROCESSOR_KWARGS:              # what bans nothing after normalisation goes to generate() as the neutral value
+                    if rp.constraint is not None and k in BANNING_KWARGS and k not in banning:
+                        r[k] = PROCESSOR_KWARGS[k]
+                if banning:
+                    raise ValueError(f"request {i}: a constraint together with {banning}: a processor that bans tokens can leave a constrained "
+                                     "row with nothing allowed; only repetition_penalty composes with a constraint (a request overrides a "
+                                     "call-wide keyword with the neutral value in its RequestParams)")
             if not on_device:
                 first = next(i for i, (*_, rp) in enumerate(reqs) if rp.constraint is not None)
                 raise ValueError(f"request {first}: a constrained request needs the device pick, which needs bf16 logits on the GPU")
@@ -989,10 +1009,9 @@ class AkiMethods:
                                     top_logprobs=top_lp[:, :k].clone() if k else None)
 
         if slots == 1 or len(reqs) == 1:
-            kw = dict({k: v for k, v in pk.items()}, eos_token_id=eos_list, pad_token_id=opt.pad_id)
             outs, sched = [], SlotScheduler(len(reqs), 1)
-            for (vx, lx, budget, rp), seed in zip(reqs, seeds):
-                kw_r = dict(kw, max_new_tokens=budget)
+            for (vx, lx, budget, rp), seed, own in zip(reqs, seeds, resolved):
+                kw_r = dict(own, eos_token_id=eos_list, pad_token_id=opt.pad_id, max_new_tokens=budget)
                 if rp.do_sample:                        # the same stream: key seed, counter (token index, row 0, offset 0)
                     kw_r.update(do_sample=True, temperature=float(rp.temperature), top_k=int(rp.top_k), top_p=float(rp.top_p),
                                 generator=ops.DeviceGenerator(seed))
@@ -1040,14 +1059,20 @@ class AkiMethods:
                                      pk["begin_suppress_tokens"], pk["bad_words_ids"], slot_constraints=constrained)
             return p if p.active else None
 
-        # the processed pick keeps a score scratch per batch size, whose address the captured step holds: the admit's one-row pick gets its own
-        proc, proc1 = processors(), processors()
+        # the processed pick keeps a score scratch per batch size, whose address the captured step holds: the admit's one-row pick gets its own.
+        # Requests with different settings: the pool of distinct sets (uploaded once) and one set index per slot, allocated ahead of the
+        # capture and rewritten in place at admit (ops.ProcessorSets) - it stands in the place of the one LogitsProcessors.
+        psets = ops.ProcessorSets(width, dev, eos_list, set_keys, slots) if mixed else None
+        proc, proc1 = (None, None) if mixed else (processors(), processors())
         tick = dict(done=done, done_at=done_at, start_len=start_len, limit=limit)
         pick = dict(pad_token_id=opt.pad_id, eos_ids=eos_t, done=done, tokens=tokens, start_len=start_len, done_at=done_at)
         if proc is not None:
             pick["processors"] = proc
             if on_device:
                 proc.scores(slots, dev)                 # allocated ahead of the capture
+        if psets is not None and on_device:
+            pick["processor_sets"] = psets
+            psets.scores(slots, dev)
         # a call with a constrained request: the pool of tables (uploaded once), and per slot the place of its request's table and its state
         # history, allocated ahead of the capture and rewritten in place at admit.  An unconstrained request is a state -1 row.
         slot_con = None
@@ -1099,11 +1124,15 @@ class AkiMethods:
                 rows["seed"][slot] = 0 if seed is None else (seed - (1 << 64) if seed >= 1 << 63 else seed)     # the key's bits as int64
             if slot_con is not None:                    # the slot's automaton: where its table begins, its start state in column 0
                 slot_con.admit(slot, pool.base[req], pool.n_states[req], pool.start[req])
+            if psets is not None:                       # the slot's processor set, ahead of the pick of token 0
+                psets.admit(slot, set_keys[req])
             args = dict(pad_token_id=opt.pad_id, eos_ids=eos_t, done=row(done, slot), tokens=row(tokens, slot), start_len=row(start_len, slot),
                         done_at=row(done_at, slot))
             if on_device:                               # token 0, from the prefill: the existing pick at B = 1 on row views
                 logits = logits.contiguous()
                 args = args if proc1 is None else dict(args, processors=proc1)
+                if psets is not None:
+                    args = dict(args, processor_sets=psets.row(slot))
                 if slot_con is not None:
                     args = dict(args, slot_constraints=slot_con.row(slot))
                 if rows is not None:
@@ -1112,7 +1141,8 @@ class AkiMethods:
                 else:
                     ops.greedy_pick(logits, row(ids, slot), cache_len=row(cache.cache_len, slot), advance=False, **args)
             else:
-                _pick_rows_torch(logits, row(ids, slot), cache_len=row(cache.cache_len, slot), proc=proc1, **args)
+                _pick_rows_torch(logits, row(ids, slot), cache_len=row(cache.cache_len, slot),
+                                 proc=proc1 if psets is None else psets.row(slot), **args)
             if lp is not None:
                 ops.token_logprob(logits.contiguous(), **{k: (row(v, slot) if torch.is_tensor(v) else v) for k, v in lp.items()})
             ops.slot_tick(row(done, slot), row(done_at, slot), row(cache.cache_len, slot), row(start_len, slot), row(limit, slot))
@@ -1134,7 +1164,8 @@ class AkiMethods:
                 else:
                     lg = lm.decode_step(input_ids=ids, past_key_values=cache)
                 if not on_device:
-                    _pick_rows_torch(lg, ids, opt.pad_id, eos_t, done, tokens, cache.cache_len, start_len, done_at, proc)
+                    _pick_rows_torch(lg, ids, opt.pad_id, eos_t, done, tokens, cache.cache_len, start_len, done_at,
+                                     proc if psets is None else psets)
                 if lp is not None:
                     ops.token_logprob(lg, **lp)
                 ops.slot_tick(cache_len=cache.cache_len, **tick)

@@ -78,6 +78,25 @@ int sample_pick_launch(const void* logits, int B, int V, int ld, const int64_t* 
                        uint64_t offset, const float* row_temperature, const int* row_top_k, const float* row_top_p, const uint64_t* row_seed,
                        float* probs, int ld_probs, const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
                        const int* c_row_base, const int* c_row_states, hipStream_t s);
+int logits_process_rows_launch(const void* logits, int in_f32, int B, int V, int ld, float* out, int ld_out, const int64_t* tokens, int tokens_ld,
+                               const int* cache_len, const int* start_len, int step, const unsigned char* done, const int64_t* eos, int n_eos,
+                               const int* sets, int n_sets, const int* row_set, const int64_t* set_ids, int n_set_ids, const int* bad_off,
+                               int n_words, const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
+                               const int* c_row_base, const int* c_row_states, hipStream_t s);
+int greedy_pick_rows_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done, int64_t* ids,
+                            int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at, const void* emb_main,
+                            const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores, int ld_scores, const int* sets,
+                            int n_sets, const int* row_set, const int64_t* set_ids, int n_set_ids, const int* bad_off, int n_words,
+                            const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, const int* c_row_base,
+                            const int* c_row_states, hipStream_t s);
+int sample_pick_rows_processed_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done,
+                                      int64_t* ids, int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance,
+                                      int* done_at, const void* emb_main, const void* emb_extra, int64_t max_original_id, int d, void* emb_out,
+                                      float* scores, int ld_scores, const int* sets, int n_sets, const int* row_set, const int64_t* set_ids,
+                                      int n_set_ids, const int* bad_off, int n_words, int step, const float* row_temperature,
+                                      const int* row_top_k, const float* row_top_p, const uint64_t* row_seed, float* probs, int ld_probs,
+                                      const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
+                                      const int* c_row_base, const int* c_row_states, hipStream_t s);
 int beam_logprob_launch(const void* logits, int in_f32, int rows, int V, int ld, float* out, int ld_out, hipStream_t s);
 int beam_step_launch(const float* logp, int ld, int B, int K, int V, int t, int max_new, float* beam_scores, const int64_t* seqs_in,
                      int64_t* seqs_out, float* hyp_score, int* hyp_len, int64_t* hyp_tokens, int* hyp_count, unsigned char* done,
@@ -1039,6 +1058,110 @@ int aki_sample_pick_constrained(const void* logits, int32_t B, int32_t V, int64_
                              embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
                              no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
                              n_bad_ids, step, temperature, top_k, top_p, seed, offset, nullptr, probs_out, ld_probs, table, table_ld, n_states, states, states_ld, nullptr, nullptr, stream);
+}
+
+// The per-row processor forms (include/aki_mi355x.h): the pool's arrays and the rows' set indices.  Their VALUES are the caller's: the
+// kernel reads a set index outside the pool as the neutral set and cuts every range at the pools' ends.
+static bool processor_sets_ok(int32_t V, const int32_t* sets, int32_t n_sets, const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids,
+                              const int32_t* bad_offsets, int32_t n_words) {
+  return V <= AKI_LOGITS_PROCESS_MAX_V && sets && n_sets > 0 && row_set && n_set_ids >= 0 && (n_set_ids == 0 || set_ids) && n_words >= 0 &&
+         (n_words == 0 || (bad_offsets && set_ids));
+}
+
+// a NULL table: no constraint, the other six are not looked at
+static bool constraint_rows_or_none_ok(int32_t V, const int16_t* table, int64_t table_ld, int32_t n_states, const int32_t* states,
+                                       int32_t states_ld, const int32_t* row_base, const int32_t* row_states) {
+  return !table || constraint_rows_ok(V, table, table_ld, n_states, states, states_ld, row_base, row_states);
+}
+
+int aki_logits_process_rows(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
+                            const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step,
+                            const uint8_t* done, const int64_t* eos_ids, int32_t n_eos, const int32_t* sets, int32_t n_sets,
+                            const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets, int32_t n_words,
+                            const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld,
+                            const int32_t* row_base, const int32_t* row_states, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(logits && out && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && ld_out >= V && ld_out < (1ll << 31) && step >= 0);
+  AKI_CHECK_ARG((!tokens || tokens_ld > 0) && n_eos >= 0 && (n_eos == 0 || eos_ids));
+  AKI_CHECK_ARG(processor_sets_ok(V, sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words));
+  AKI_CHECK_ARG(constraint_rows_or_none_ok(V, table, table_ld, n_states, states, states_ld, row_base, row_states));
+  if (dtype != AKI_DT_BF16 && dtype != AKI_DT_F32) return AKI_ERR_UNSUPPORTED;
+  const bool con = table != nullptr;
+  return logits_process_rows_launch(logits, dtype == AKI_DT_F32, B, V, (int)ld, out, (int)ld_out, tokens, tokens_ld, cache_len, start_len, step,
+                                    done, eos_ids, n_eos, sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words, table,
+                                    con ? (int)table_ld : 0, con ? n_states : 0, con ? states : nullptr, con ? states_ld : 0,
+                                    con ? row_base : nullptr, con ? row_states : nullptr, (hipStream_t)stream);
+}
+
+// what aki_greedy_pick_rows and aki_sample_pick_rows_processed check alike
+static int pick_rows_checked(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                             const int64_t* next_ids, const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, int32_t advance,
+                             const void* embed_weight, const void* additional_weight, int64_t max_original_id, int64_t num_additional, int32_t d,
+                             const void* next_embeds, const float* scores, int64_t ld_scores, const int32_t* sets, int32_t n_sets,
+                             const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets, int32_t n_words,
+                             const int16_t* table, int64_t table_ld, int32_t n_states, const int32_t* states, int32_t states_ld,
+                             const int32_t* row_base, const int32_t* row_states) {
+  AKI_CHECK_ARG(logits && next_ids && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && n_eos >= 0 && (n_eos == 0 || eos_ids));
+  AKI_CHECK_ARG((!tokens || tokens_ld > 0) && (!advance || cache_len) && (advance == 0 || advance == 1));
+  AKI_CHECK_ARG(scores && ld_scores >= V && ld_scores < (1ll << 31));
+  AKI_CHECK_ARG(processor_sets_ok(V, sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words));
+  AKI_CHECK_ARG(constraint_rows_or_none_ok(V, table, table_ld, n_states, states, states_ld, row_base, row_states));
+  if ((((uintptr_t)scores) & 15) != 0 || (ld_scores & 3) != 0) return AKI_ERR_ALIGNMENT;
+  if (embed_weight) {
+    AKI_CHECK_ARG(next_embeds && d > 0 && d % 8 == 0 && max_original_id >= 0 && num_additional >= 0);
+    AKI_CHECK_ARG((((uintptr_t)embed_weight | (uintptr_t)additional_weight | (uintptr_t)next_embeds) & 15) == 0);
+    AKI_CHECK_ARG((int64_t)V <= max_original_id + 1 + (additional_weight ? num_additional : 0) && pad_token_id >= 0 &&
+                  pad_token_id <= max_original_id + (additional_weight ? num_additional : 0));
+  } else {
+    AKI_CHECK_ARG(!additional_weight && !next_embeds);
+  }
+  return AKI_OK;
+}
+
+int aki_greedy_pick_rows(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                         uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                         int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                         int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, const int32_t* sets,
+                         int32_t n_sets, const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets,
+                         int32_t n_words, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld,
+                         const int32_t* row_base, const int32_t* row_states, void* stream) {
+  AKI_CLEAR_ERR();
+  const int rc = pick_rows_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, next_ids, tokens, tokens_ld, cache_len, advance, embed_weight,
+                                   additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, sets, n_sets, row_set,
+                                   set_ids, n_set_ids, bad_offsets, n_words, table, table_ld, n_states, states, states_ld, row_base, row_states);
+  if (rc != AKI_OK) return rc;
+  const bool con = table != nullptr;
+  return greedy_pick_rows_launch(logits, B, V, (int)ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len,
+                                 advance, done_at, embed_weight, additional_weight, max_original_id, d, next_embeds, scores, (int)ld_scores, sets,
+                                 n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words, table, con ? (int)table_ld : 0, con ? n_states : 0,
+                                 con ? states : nullptr, con ? states_ld : 0, con ? row_base : nullptr, con ? row_states : nullptr,
+                                 (hipStream_t)stream);
+}
+
+int aki_sample_pick_rows_processed(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos,
+                                   int64_t pad_token_id, uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld,
+                                   int32_t* cache_len, const int32_t* start_len, int32_t advance, int32_t* done_at, const void* embed_weight,
+                                   const void* additional_weight, int64_t max_original_id, int64_t num_additional, int32_t d,
+                                   void* next_embeds, float* scores, int64_t ld_scores, const int32_t* sets, int32_t n_sets,
+                                   const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets,
+                                   int32_t n_words, int32_t step, const float* temperature, const int32_t* top_k, const float* top_p,
+                                   const uint64_t* seed, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld,
+                                   int32_t n_states, int32_t* states, int32_t states_ld, const int32_t* row_base, const int32_t* row_states,
+                                   void* stream) {
+  AKI_CLEAR_ERR();
+  const int rc = pick_rows_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, next_ids, tokens, tokens_ld, cache_len, advance, embed_weight,
+                                   additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, sets, n_sets, row_set,
+                                   set_ids, n_set_ids, bad_offsets, n_words, table, table_ld, n_states, states, states_ld, row_base, row_states);
+  if (rc != AKI_OK) return rc;
+  AKI_CHECK_ARG(step >= 0 && temperature && top_k && top_p && seed);
+  AKI_CHECK_ARG(!probs_out || (ld_probs >= V && ld_probs < (1ll << 31)));
+  const bool con = table != nullptr;
+  return sample_pick_rows_processed_launch(logits, B, V, (int)ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len,
+                                           start_len, advance, done_at, embed_weight, additional_weight, max_original_id, d, next_embeds, scores,
+                                           (int)ld_scores, sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words, step, temperature,
+                                           top_k, top_p, seed, probs_out, (int)ld_probs, table, con ? (int)table_ld : 0, con ? n_states : 0,
+                                           con ? states : nullptr, con ? states_ld : 0, con ? row_base : nullptr, con ? row_states : nullptr,
+                                           (hipStream_t)stream);
 }
 
 int aki_beam_logprob(const void* logits, int32_t dtype, int32_t rows, int32_t V, int64_t ld, float* out, int64_t ld_out, void* stream) {

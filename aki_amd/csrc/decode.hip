@@ -1947,7 +1947,7 @@ __device__ unsigned select_threshold(const float* rowf, int V, unsigned lo_key, 
 }
 
 template <bool ROWS>
-__global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickParams p, const ProcParams q, const typename SampleArgs<ROWS>::type sp) {
+__device__ __forceinline__ void sample_pick_body(const PickParams& p, const ProcParams& q, const typename SampleArgs<ROWS>::type& sp) {
   __shared__ unsigned long long s_hist[SEL_BINS];           // first the processors' bitmap (PROC_MAX_V / 32 words), then the select's bins
   __shared__ unsigned long long s_w64[PICK_THREADS / 64], s_pick[2];
   __shared__ float s_wf[PICK_THREADS / 64];
@@ -2118,6 +2118,72 @@ __global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickPar
   pick_finish(p, b, was_done, len0, start0, eos4, tok, &q.c, cs, cr);
 }
 
+template <bool ROWS>
+__global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickParams p, const ProcParams q, const typename SampleArgs<ROWS>::type sp) {
+  sample_pick_body<ROWS>(p, q, sp);
+}
+
+// ---- per-row logits processors (generate_many: every slot serves a request with settings of its own).  The distinct settings of a call
+// are a small pool of fixed-size records; row b names its record in row_set[b], a device int the launch reads, so a captured step serves
+// a row whose settings are replaced in place between replays.  A record is PROC_SET_WORDS 32-bit words:
+//   0 penalty (the float's bits)  1 ngram  2 min_len  3..4 suppress ids [sup0, sup1)  5..6 begin-suppress ids [bsup0, bsup1)
+//   7..8 bad words [word0, word1)
+// The id ranges index `ids` (n_ids entries: every set's lists one behind the other); a word w is ids[bad_off[w], bad_off[w + 1]), bad_off
+// holding n_words + 1 ascending offsets.  Nothing validates the arrays on the device, so bad bits stay inside their row: a set index
+// outside [0, n_sets) is the neutral set, ranges are cut at the pools' ends, a penalty that is not finite and positive is 1, and
+// process_row skips ids outside [0, V) and cuts bad_off itself.  One workgroup serves one row and every thread reads the same words, so
+// what process_row branches on around its barriers stays workgroup-uniform; the words are moved to scalar registers to say so.
+constexpr int PROC_SET_WORDS = 9;
+struct ProcSetParams {
+  const int* sets; int n_sets; const int* row_set;
+  const int64_t* ids; int n_ids; const int* bad_off; int n_words;
+};
+
+// q with row b's record in the place of the call-wide processor values (q's own are ignored)
+__device__ __forceinline__ ProcParams proc_row_params(const ProcParams& q, const ProcSetParams& ps, int b) {
+  ProcParams r = q;
+  r.penalty = 1.f; r.ngram = 0; r.min_len = 0;
+  r.suppress = nullptr; r.n_suppress = 0; r.begin_suppress = nullptr; r.n_begin = 0;
+  r.bad_ids = ps.ids; r.bad_off = ps.bad_off; r.n_bad = 0; r.n_bad_ids = ps.n_ids;
+  const int si = __builtin_amdgcn_readfirstlane(ps.row_set[b]);
+  if (si < 0 || si >= ps.n_sets) return r;
+  const int* rec = ps.sets + (size_t)si * PROC_SET_WORDS;
+  int w[PROC_SET_WORDS];
+#pragma unroll
+  for (int i = 0; i < PROC_SET_WORDS; ++i) w[i] = __builtin_amdgcn_readfirstlane(rec[i]);
+  const float pen = __int_as_float(w[0]);
+  r.penalty = (pen > 0.f && pen <= 3.0e38f) ? pen : 1.f;   // what the scalar entry points accept; NaN fails both
+  r.ngram = max(w[1], 0);
+  r.min_len = w[2];
+  const int s0 = min(max(w[3], 0), ps.n_ids), s1 = min(max(w[4], s0), ps.n_ids);
+  const int b0 = min(max(w[5], 0), ps.n_ids), b1 = min(max(w[6], b0), ps.n_ids);
+  const int w0 = min(max(w[7], 0), ps.n_words), w1 = min(max(w[8], w0), ps.n_words);
+  r.suppress = ps.ids + s0; r.n_suppress = s1 - s0;
+  r.begin_suppress = ps.ids + b0; r.n_begin = b1 - b0;
+  r.bad_off = ps.bad_off + w0; r.n_bad = w1 - w0;          // bad_off[w1] exists: n_words + 1 offsets
+  return r;
+}
+
+__global__ __launch_bounds__(PROC_THREADS) void logits_process_rows_kernel(const ProcParams q, const ProcSetParams ps) {
+  __shared__ unsigned s_bits[PROC_MAX_V / 32];
+  const ProcParams r = proc_row_params(q, ps, blockIdx.x);
+  process_row(r, blockIdx.x, r.out + (size_t)blockIdx.x * r.ld_out, s_bits);
+}
+
+__global__ __launch_bounds__(PICK_THREADS) void greedy_pick_rows_kernel(const PickParams p, const ProcParams q, const ProcSetParams ps) {
+  __shared__ unsigned s_bits[PROC_MAX_V / 32];
+  const ProcParams r = proc_row_params(q, ps, blockIdx.x);
+  float* rowf = r.out + (size_t)blockIdx.x * r.ld_out;
+  process_row(r, blockIdx.x, rowf, s_bits);
+  greedy_pick_row<true>(p, rowf, &r.c);
+}
+
+__global__ __launch_bounds__(PICK_THREADS) void sample_pick_rows_processed_kernel(const PickParams p, const ProcParams q, const ProcSetParams ps,
+                                                                                  const SampleRowParams sp) {
+  const ProcParams r = proc_row_params(q, ps, blockIdx.x);
+  sample_pick_body<true>(p, r, sp);
+}
+
 
 static ProcParams proc_params(const void* in, int in_f32, int ld_in, float* out, int ld_out, int V, const int64_t* tokens, int tokens_ld,
                               const int* cache_len, const int* start_len, int step, const unsigned char* done, float penalty, int ngram,
@@ -2185,6 +2251,62 @@ int sample_pick_launch(const void* logits, int B, int V, int ld, const int64_t* 
   } else {
     hipLaunchKernelGGL(sample_pick_kernel<false>, dim3(B), dim3(PICK_THREADS), 0, s, p, q, sp);
   }
+  AKI_LAUNCH_CHECK();
+  return AKI_OK;
+}
+
+// the per-row forms: the processor values of proc_params are placeholders, proc_row_params fills them per row
+int logits_process_rows_launch(const void* logits, int in_f32, int B, int V, int ld, float* out, int ld_out, const int64_t* tokens, int tokens_ld,
+                               const int* cache_len, const int* start_len, int step, const unsigned char* done, const int64_t* eos, int n_eos,
+                               const int* sets, int n_sets, const int* row_set, const int64_t* set_ids, int n_set_ids, const int* bad_off,
+                               int n_words, const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
+                               const int* c_row_base, const int* c_row_states, hipStream_t s) {
+  ProcParams q = proc_params(logits, in_f32, ld, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, 1.f, 0, 0, eos, n_eos,
+                             nullptr, 0, nullptr, 0, nullptr, nullptr, 0, 0);
+  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld, c_row_base, c_row_states};
+  const ProcSetParams ps = {sets, n_sets, row_set, set_ids, n_set_ids, bad_off, n_words};
+  AKI_CLEAR_ERR();
+  hipLaunchKernelGGL(logits_process_rows_kernel, dim3(B), dim3(PROC_THREADS), 0, s, q, ps);
+  AKI_LAUNCH_CHECK();
+  return AKI_OK;
+}
+
+int greedy_pick_rows_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done, int64_t* ids,
+                            int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at, const void* emb_main,
+                            const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores, int ld_scores, const int* sets,
+                            int n_sets, const int* row_set, const int64_t* set_ids, int n_set_ids, const int* bad_off, int n_words,
+                            const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, const int* c_row_base,
+                            const int* c_row_states, hipStream_t s) {
+  PickParams p = {(const bf16_t*)logits, B, V, ld, eos, n_eos, pad, done, ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
+                  (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out};
+  ProcParams q = proc_params(logits, 0, ld, scores, ld_scores, V, tokens, tokens_ld, cache_len, start_len, cache_len ? advance : 0, done,
+                             1.f, 0, 0, eos, n_eos, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, 0);
+  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld, c_row_base, c_row_states};
+  const ProcSetParams ps = {sets, n_sets, row_set, set_ids, n_set_ids, bad_off, n_words};
+  AKI_CLEAR_ERR();
+  hipLaunchKernelGGL(greedy_pick_rows_kernel, dim3(B), dim3(PICK_THREADS), 0, s, p, q, ps);
+  AKI_LAUNCH_CHECK();
+  return AKI_OK;
+}
+
+int sample_pick_rows_processed_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done,
+                                      int64_t* ids, int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance,
+                                      int* done_at, const void* emb_main, const void* emb_extra, int64_t max_original_id, int d, void* emb_out,
+                                      float* scores, int ld_scores, const int* sets, int n_sets, const int* row_set, const int64_t* set_ids,
+                                      int n_set_ids, const int* bad_off, int n_words, int step, const float* row_temperature,
+                                      const int* row_top_k, const float* row_top_p, const uint64_t* row_seed, float* probs, int ld_probs,
+                                      const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
+                                      const int* c_row_base, const int* c_row_states, hipStream_t s) {
+  PickParams p = {(const bf16_t*)logits, B, V, ld, eos, n_eos, pad, done, ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
+                  (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out, step};
+  ProcParams q = proc_params(logits, 0, ld, scores, ld_scores, V, tokens, tokens_ld, cache_len, start_len, step + (cache_len ? advance : 0),
+                             done, 1.f, 0, 0, eos, n_eos, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, 0);
+  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld, c_row_base, c_row_states};
+  const ProcSetParams ps = {sets, n_sets, row_set, set_ids, n_set_ids, bad_off, n_words};
+  // processed = 1: which rows have something to process is the device's to know; the neutral set's row is the plain f32 copy
+  const SampleRowParams sr = {row_temperature, row_top_k, row_top_p, (const unsigned long long*)row_seed, probs, ld_probs, 1};
+  AKI_CLEAR_ERR();
+  hipLaunchKernelGGL(sample_pick_rows_processed_kernel, dim3(B), dim3(PICK_THREADS), 0, s, p, q, ps, sr);
   AKI_LAUNCH_CHECK();
   return AKI_OK;
 }

@@ -7,6 +7,7 @@ CPU tensors or a missing library raise :class:`aki_amd._lib.AkiError`.
 from __future__ import annotations
 
 import ctypes as C
+import struct
 import threading
 from dataclasses import dataclass
 from typing import Optional, Tuple
@@ -914,6 +915,141 @@ class SlotConstraints:
         return (_ptr(t_), t_.stride(0), t_.shape[0], _ptr(st), st.shape[1], _ptr(self.row_base), _ptr(self.row_states))
 
 
+class ProcessorSets:
+    """One set of logits-processor settings per ROW, for rows that change hands (generate_many's slots): what the per-row picks take as
+    `processor_sets` (aki_logits_process_rows / aki_greedy_pick_rows / aki_sample_pick_rows_processed).  The distinct settings of a call
+    are a small pool, deduplicated by value and uploaded once:
+      keys     the pool on the host: (penalty, ngram, min_len, suppress ids, begin-suppress ids, bad words) per set
+               (slots.processor_set_key's values); keys[0] is always the neutral set
+      index    {key: its place in the pool}
+      sets     int32 [n_sets, 9]: word 0 the penalty's float bits, 1 ngram, 2 min_len, 3..4 / 5..6 the suppress / begin-suppress ranges
+               into `ids`, 7..8 the set's range of words in `bad_off`
+      ids      int64 [n_ids]: every set's suppress, begin-suppress and bad-word ids, one list behind the other
+      bad_off  int32 [n_words + 1]: ascending offsets into `ids`, one bad word between two neighbours
+      row_set  int32 [rows]: the set each row is processed with - allocated once, a captured step holds its address, and `admit`
+               rewrites a row's entry in place by a tensor fill
+    eos_ids: the ids the minimum length bans (the call's).  The object also owns the f32 scores scratch the picks scan."""
+    active = True
+    constraint = None
+
+    def __init__(self, V: int, device, eos_ids, keys, rows: int):
+        V = int(V)
+        if V <= 0 or V > L.AKI_LOGITS_PROCESS_MAX_V:
+            raise ValueError(f"logits processors: a vocabulary of {V} columns (1..{L.AKI_LOGITS_PROCESS_MAX_V} are served)")
+        from .slots import NEUTRAL_SET_KEY
+        pool = [NEUTRAL_SET_KEY]
+        for k in keys:
+            if k not in pool:
+                pool.append(k)
+        ids, offs, recs = [], [], []
+        for pen, ngram, min_len, sup, bsup, _ in pool:  # the plain id lists of every set first ...
+            rec = [struct.unpack("<i", struct.pack("<f", float(pen)))[0], int(ngram), int(min_len)]
+            for lst in (sup, bsup):
+                rec += [len(ids), len(ids) + len(lst)]
+                ids += [int(i) for i in lst]
+            recs.append(rec)
+        for rec, key in zip(recs, pool):                # ... then the words, back to back: a word ends where the next one begins
+            rec.append(len(offs))
+            for w in key[5]:
+                offs.append(len(ids))
+                ids += [int(i) for i in w]
+            rec.append(len(offs))
+        offs.append(len(ids))                           # the last word's end; a pool without words holds this one offset
+        if any(not 0 <= i < V for i in ids):
+            raise ValueError(f"logits processors: every id has to be in [0, {V})")
+        dev = torch.device(device)
+        self.V, self.keys, self.index = V, pool, {k: i for i, k in enumerate(pool)}
+        self.sets = torch.tensor(recs, dtype=torch.int32, device=dev)
+        self.ids = torch.tensor(ids, dtype=torch.int64, device=dev)
+        self.bad_off = torch.tensor(offs, dtype=torch.int32, device=dev)
+        self.row_set = torch.zeros(int(rows), dtype=torch.int32, device=dev)
+        eos = [int(e) for e in eos_ids]
+        self._eos = torch.tensor(eos, dtype=torch.int64, device=dev) if eos else None
+        self._scratch = {}
+
+    def admit(self, row: int, key) -> None:
+        """A new request in `row`: its set, by value.  A tensor fill - nothing is copied from the host or reallocated."""
+        self.row_set[int(row)] = self.index[key]
+
+    def row(self, slot: int) -> "ProcessorSets":
+        """The one-row view: what a B = 1 pick on the slot's row views takes.  The pool and the scratches are shared."""
+        s = int(slot)
+        view = ProcessorSets.__new__(ProcessorSets)
+        view.__dict__.update(self.__dict__)
+        view.row_set = self.row_set[s:s + 1]
+        return view
+
+    def scores(self, B: int, device) -> torch.Tensor:
+        """The f32 [B, >= V] scratch the per-row picks write the processed scores to, one per batch size (kept: a captured graph holds
+        its address; the admit's B = 1 picks use another than the step's)."""
+        key = (int(B), str(torch.device(device)))
+        if key not in self._scratch:
+            self._scratch[key] = torch.empty((int(B), (self.V + 3) // 4 * 4), dtype=torch.float32, device=device)
+        return self._scratch[key]
+
+    def _args(self, name: str, B: int, V: int, device):
+        """(sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words) of the per-row C entry points, checked."""
+        if V != self.V:
+            raise AkiError(f"{name}: the processor sets were built for V = {self.V}, the logits have {V} columns")
+        for nm, x, dt in (("sets", self.sets, torch.int32), ("ids", self.ids, torch.int64), ("bad_off", self.bad_off, torch.int32),
+                          ("row_set", self.row_set, torch.int32)):
+            if not torch.is_tensor(x) or x.dtype != dt or not x.is_contiguous() or x.device != device:
+                raise AkiError(f"{name}: processor_sets.{nm} is a contiguous {dt} tensor on {device}")
+        if self.sets.dim() != 2 or self.sets.shape[0] < 1 or self.sets.shape[1] != L.AKI_PROCESSOR_SET_WORDS:
+            raise AkiError(f"{name}: processor_sets.sets is [n_sets >= 1, {L.AKI_PROCESSOR_SET_WORDS}]")
+        if tuple(self.row_set.shape) != (B,) or self.bad_off.numel() < 1:
+            raise AkiError(f"{name}: processor_sets.row_set is [{B}] and bad_off holds at least one offset")
+        return (_ptr(self.sets), self.sets.shape[0], _ptr(self.row_set), _ptr(self.ids) if self.ids.numel() else None, self.ids.numel(),
+                _ptr(self.bad_off), self.bad_off.numel() - 1)
+
+    def apply(self, logits: torch.Tensor, out: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, step: int = 0,
+              cache_len: Optional[torch.Tensor] = None, start_len: Optional[torch.Tensor] = None, done: Optional[torch.Tensor] = None,
+              slot_constraints: Optional["SlotConstraints"] = None) -> torch.Tensor:
+        """LogitsProcessors.apply with row b processed by set row_set[b] (aki_logits_process_rows, one launch): f32 scores [B, V] of bf16
+        / f32 logits.  out=None: a view of the pool's own scratch for this batch size - kept, so a per-step caller allocates nothing, and
+        overwritten by the next call of that batch size.  slot_constraints: the rows' automata as the last stage (the state history is
+        read, not advanced)."""
+        if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[1] != self.V:
+            raise AkiError(f"logits processors: logits [B, {self.V}] with unit column stride are expected, got {tuple(logits.shape)}")
+        B = logits.shape[0]
+        dev = _dev(logits, out, tokens, cache_len, start_len, done)
+        if out is None:
+            out = self.scores(B, dev)[:, :self.V]
+        if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.stride(1) != 1 or out.shape[1] != self.V:
+            raise AkiError("logits processors: out is f32 [B, V] with unit column stride")
+        for t_, dt in ((tokens, torch.int64), (cache_len, torch.int32), (start_len, torch.int32), (done, torch.uint8)):
+            if t_ is not None and (t_.dtype != dt or not t_.is_contiguous()):
+                raise AkiError(f"logits processors: a contiguous {dt} tensor is expected, got {t_.dtype}")
+        if tokens is not None and (tokens.dim() != 2 or tokens.shape[0] != B):
+            raise AkiError("logits processors: tokens is [B, *]")
+        if tokens is not None and tokens.shape[1] == 0:
+            tokens = None
+        con = (None, 0, 0, None, 0, None, None)
+        if slot_constraints is not None:
+            con = slot_constraints._args("logits processors", B, self.V, dev)
+        L.check(L.load().aki_logits_process_rows(
+            _ptr(logits), _dt(logits), B, self.V, logits.stride(0), _ptr(out), out.stride(0), _ptr(tokens),
+            0 if tokens is None else tokens.shape[1], _ptr(cache_len), _ptr(start_len), int(step), _ptr(done), _ptr(self._eos),
+            0 if self._eos is None else self._eos.numel(), *self._args("logits processors", B, self.V, dev), *con, _stream()),
+            "aki_logits_process_rows")
+        return out
+
+
+def _processor_set_args(name: str, processor_sets, processors, slot_constraints, B: int, V: int, device):
+    """(the pool's seven C arguments, the per-row constraint's seven) for a pick with processor_sets=, or None without one.  The sets
+    stand in the place of `processors` (they own the scores scratch), so the two exclude each other."""
+    if processor_sets is None:
+        return None
+    if not isinstance(processor_sets, ProcessorSets):
+        raise AkiError(f"{name}: processor_sets is an ops.ProcessorSets")
+    if processors is not None:
+        raise AkiError(f"{name}: processor_sets together with processors: the sets hold every row's settings")
+    if slot_constraints is not None and not isinstance(slot_constraints, SlotConstraints):
+        raise AkiError(f"{name}: slot_constraints is an ops.SlotConstraints")
+    con = (None, 0, 0, None, 0, None, None) if slot_constraints is None else slot_constraints._args(name, B, V, device)
+    return processor_sets._args(name, B, V, device), con
+
+
 def _slot_constraint_args(name: str, slot_constraints, processors, B: int, V: int, device):
     """The per-row constraint's seven C arguments, or None without one.  The pick scans the processors' f32 scratch, so an active
     LogitsProcessors is needed (LogitsProcessors(..., slot_constraints=True) is one); it cannot carry a BoundConstraint of its own."""
@@ -932,7 +1068,7 @@ def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
                 done: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, cache_len: Optional[torch.Tensor] = None,
                 start_len: Optional[torch.Tensor] = None, advance: bool = False, done_at: Optional[torch.Tensor] = None,
                 embed=None, next_embeds: Optional[torch.Tensor] = None, processors: Optional[LogitsProcessors] = None,
-                slot_constraints: Optional[SlotConstraints] = None) -> torch.Tensor:
+                slot_constraints: Optional[SlotConstraints] = None, processor_sets: Optional[ProcessorSets] = None) -> torch.Tensor:
     """The step between two decode steps of a greedy `generate` as one launch (aki_greedy_pick; HF GenerationMixin's greedy branch):
     next_ids[b] = pad if done[b] else argmax(logits[b]); tokens[b, t] = next with t = cache_len[b] + advance - start_len[b]; rows whose
     next is an eos id become done (done_at[b] = t); advance: cache_len += 1.  logits: bf16 [B, V] (row stride >= V); next_ids / tokens /
@@ -944,7 +1080,9 @@ def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
     (aki_greedy_pick_processed); the history is tokens[b, :t] and the minimum length bans eos_ids.
     slot_constraints (an ops.SlotConstraints, with an active `processors` that carries no constraint of its own): one automaton per row as
     the last processor stage (aki_greedy_pick_constrained_rows) - row b in state s = states[b, t] is masked by pool row row_base[b] + s
-    and states[b, t + 1] receives the table entry, a state local to the row's automaton; a row in state -1 is picked unmasked."""
+    and states[b, t + 1] receives the table entry, a state local to the row's automaton; a row in state -1 is picked unmasked.
+    processor_sets (an ops.ProcessorSets, in the place of `processors`): one set of processor settings per row (aki_greedy_pick_rows) - row
+    b is processed with the pool's set row_set[b]; slot_constraints composes with it and needs no LogitsProcessors then."""
     if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
         raise AkiError("greedy_pick takes bf16 logits [B, V] with unit column stride")
     B, V = logits.shape
@@ -967,6 +1105,13 @@ def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
             raise AkiError("greedy_pick: next_embeds is [B, d]")
         if w.shape[0] <= max_orig:
             raise AkiError("greedy_pick: the embedding table has fewer than max_original_id + 1 rows")
+    sets = _processor_set_args("greedy_pick", processor_sets, processors, slot_constraints, B, V, logits.device)
+    if sets is not None:
+        sc = processor_sets.scores(B, logits.device)
+        emb = (None, None, 0, 0, 0, None) if embed is None else \
+            (_ptr(w), _ptr(extra), int(max_orig), 0 if extra is None else extra.shape[0], d, _ptr(next_embeds))
+        L.check(L.load().aki_greedy_pick_rows(*common, *emb, _ptr(sc), sc.stride(0), *sets[0], *sets[1], _stream()), "aki_greedy_pick_rows")
+        return next_ids
     rows_con = _slot_constraint_args("greedy_pick", slot_constraints, processors, B, V, logits.device)
     if processors is not None and processors.active:
         if processors.V != V:
@@ -1013,9 +1158,10 @@ class DeviceGenerator:
 
 
 def _sample_pick_front(name: str, logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len, advance, done_at, embed,
-                       next_embeds, processors, step, probs_out, scores, extra=()):
+                       next_embeds, processors, step, probs_out, scores, extra=(), processor_sets=None):
     """What ops.sample_pick and ops.sample_pick_rows share: the checks of the pick's tensors, the scratch rule and the C arguments up to
-    `step` -> (those arguments, the probs_out pair, the constraint's five or None).  extra: further (tensor, dtype) pairs to check."""
+    `step` -> (those arguments, the probs_out pair, the constraint's five or None).  extra: further (tensor, dtype) pairs to check.
+    processor_sets: an ops.ProcessorSets whose seven arguments take the place of the eleven scalar processor arguments."""
     if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
         raise AkiError(f"{name} takes bf16 logits [B, V] with unit column stride")
     B, V = logits.shape
@@ -1048,10 +1194,14 @@ def _sample_pick_front(name: str, logits, next_ids, pad_token_id, eos_ids, done,
     if V > L.AKI_LOGITS_PROCESS_MAX_V:
         raise AkiError(f"{name}: a vocabulary of {V} is above {L.AKI_LOGITS_PROCESS_MAX_V}")
     if scores is None:
-        scores = processors.scores(B, logits.device) if active else _sample_scratch(B, V, logits.device)
+        scores = processor_sets.scores(B, logits.device) if processor_sets is not None else \
+            processors.scores(B, logits.device) if active else _sample_scratch(B, V, logits.device)
     if scores.dim() != 2 or scores.shape[0] != B or scores.shape[1] < V:
         raise AkiError(f"{name}: scores is f32 [B, >= V]")
-    head, tail = processors._tail() if active else ((1.0, 0, 0), (None, 0, None, 0, None, None, 0, 0))
+    if processor_sets is not None:
+        head, tail = processor_sets._args(name, B, V, logits.device), ()
+    else:
+        head, tail = processors._tail() if active else ((1.0, 0, 0), (None, 0, None, 0, None, None, 0, 0))
     con = processors._constraint_args(B, tokens.shape[1] if tokens is not None else (int(step) + 1 if cache_len is None else None)) if active else None
     return ((*common, *emb, _ptr(scores), scores.stride(0), *head, *tail, int(step)),
             (_ptr(probs_out), 0 if probs_out is None else probs_out.stride(0)), con)
@@ -1086,7 +1236,8 @@ def sample_pick_rows(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id:
                      embed=None, next_embeds: Optional[torch.Tensor] = None, processors: Optional[LogitsProcessors] = None, step: int = 0,
                      temperature: Optional[torch.Tensor] = None, top_k: Optional[torch.Tensor] = None, top_p: Optional[torch.Tensor] = None,
                      seed: Optional[torch.Tensor] = None, probs_out: Optional[torch.Tensor] = None,
-                     scores: Optional[torch.Tensor] = None, slot_constraints: Optional[SlotConstraints] = None) -> torch.Tensor:
+                     scores: Optional[torch.Tensor] = None, slot_constraints: Optional[SlotConstraints] = None,
+                     processor_sets: Optional[ProcessorSets] = None) -> torch.Tensor:
     """ops.sample_pick with the sampling parameters per row, one launch (aki_sample_pick_rows): `temperature` f32, `top_k` int32, `top_p`
     f32 and `seed` int64 (its bits are the 64-bit Philox key) are contiguous device tensors [B], read by the launch - a captured step
     serves rows whose parameters are rewritten in place.  Row b draws u = Philox4x32-10(key = seed[b], counter = (n, 0, 0, 0))[0], n as
@@ -1095,7 +1246,9 @@ def sample_pick_rows(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id:
     (its row_start is fixed for its life); slot_constraints (an ops.SlotConstraints, as in ops.greedy_pick) gives every row its own
     automaton instead (aki_sample_pick_rows_constrained): the draw is made among the tokens the row's state allows.  The VALUES in the four arrays are not checked here (no host value is read: capturable); whoever writes them validates them
     (temperature > 0, top_k >= 0, 0 < top_p <= 1) - in the kernel a temperature that is not > 0 falls to the greedy token, top_k <= 0 or
-    >= V and top_p >= 1 switch their filter off."""
+    >= V and top_p >= 1 switch their filter off.
+    processor_sets (an ops.ProcessorSets, in the place of `processors`): one set of processor settings per row
+    (aki_sample_pick_rows_processed); slot_constraints composes with it and needs no LogitsProcessors then."""
     if int(step) < 0:
         raise ValueError(f"sample_pick_rows: step >= 0 is expected, got {step}")
     rows = ((temperature, torch.float32), (top_k, torch.int32), (top_p, torch.float32), (seed, torch.int64))
@@ -1104,12 +1257,22 @@ def sample_pick_rows(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id:
     if processors is not None and processors.active and processors.constraint is not None:
         raise AkiError("sample_pick_rows: a LogitsProcessors with a constraint of its own is not taken (no constrained form of that kind); "
                        "pass slot_constraints, or use ops.sample_pick")
-    if logits.dim() == 2:
+    sets = None
+    if logits.dim() == 2 and processor_sets is not None:
+        sets = _processor_set_args("sample_pick_rows", processor_sets, processors, slot_constraints, logits.shape[0], logits.shape[1],
+                                   logits.device)
+        rows_con = None
+    elif logits.dim() == 2:
         rows_con = _slot_constraint_args("sample_pick_rows", slot_constraints, processors, logits.shape[0], logits.shape[1], logits.device)
     else:
         rows_con = None
     front, probs, _ = _sample_pick_front("sample_pick_rows", logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len,
-                                         advance, done_at, embed, next_embeds, processors, step, probs_out, scores, extra=rows)
+                                         advance, done_at, embed, next_embeds, processors, step, probs_out, scores, extra=rows,
+                                         processor_sets=processor_sets if sets is not None else None)
+    if sets is not None:
+        L.check(L.load().aki_sample_pick_rows_processed(*front, _ptr(temperature), _ptr(top_k), _ptr(top_p), _ptr(seed), *probs, *sets[1],
+                                                        _stream()), "aki_sample_pick_rows_processed")
+        return next_ids
     if rows_con is not None:
         L.check(L.load().aki_sample_pick_rows_constrained(*front, _ptr(temperature), _ptr(top_k), _ptr(top_p), _ptr(seed), *probs, *rows_con,
                                                           _stream()), "aki_sample_pick_rows_constrained")

@@ -224,6 +224,8 @@ class DecodeGraph:
         they may be rewritten in place between replays (generate_many's admit).
         A "slot_constraints" key (an ops.SlotConstraints, with "processors") is handed to either pick unchanged: one token automaton per row,
         whose place in the pool and state history are device tensors rewritten in place at admit as well.
+        A "processor_sets" key (an ops.ProcessorSets, in the place of "processors") is handed on likewise: one set of logits-processor
+        settings per row, the row's set index a device int rewritten in place at admit.
         With a "logprob" key (the in-loop arguments of ops.token_logprob) that launch is captured right behind the pick.
         With a "tick" key (ops.slot_tick's done / done_at / start_len / limit) the rows' token budgets are ticked behind the pick too."""
         self.lm, self.cache = lm, cache

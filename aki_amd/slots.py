@@ -6,12 +6,76 @@ into it (a batch-1 prefill + ops.kv_slot_admit) while the other rows stay mid-se
 scheduler is driven through three callbacks, so a fake token source exercises the very loop generate_many runs."""
 from __future__ import annotations
 
+import struct
 from collections import deque
 from dataclasses import dataclass
 from typing import TYPE_CHECKING, Callable, List, Optional, Sequence, Tuple
 
 if TYPE_CHECKING:
     from .constraint import TokenConstraint
+
+
+# The logits-processor settings a request may own (HF GenerationMixin._get_logits_processor's keywords), with their neutral values
+PROCESSOR_FIELDS = {"repetition_penalty": 1.0, "no_repeat_ngram_size": 0, "bad_words_ids": (), "min_length": 0, "min_new_tokens": 0,
+                    "suppress_tokens": (), "begin_suppress_tokens": ()}
+
+
+MAX_PENALTY = 3.0e38                # what the C entry points accept (below FLT_MAX)
+
+
+def _is_int(x) -> bool:
+    """An integer, or a float / a one-element array or tensor whose value is a whole number (nothing is truncated silently)."""
+    if isinstance(x, bool):
+        return False
+    if isinstance(x, int):
+        return True
+    try:
+        return float(x) == int(x)
+    except (TypeError, ValueError, OverflowError):
+        return False
+
+
+def check_processor_value(who: str, name: str, value, V: Optional[int] = None):
+    """One processor setting, checked by the rules of ops.LogitsProcessors -> its normal form (float, int, tuple of ints, tuple of tuples).
+    ValueError beginning with `who`.  V (the logits' width) bounds the ids when it is known."""
+    def ids(x, what):
+        if isinstance(x, (str, bytes)) or not hasattr(x, "__iter__"):
+            raise ValueError(f"{who}: {what} is a list of token ids, got {x!r}")
+        out = []
+        for i in x:
+            if not _is_int(i):
+                raise ValueError(f"{who}: {what}: a token id is an integer, got {i!r}")
+            i = int(i)
+            if i < 0 or (V is not None and i >= int(V)):
+                raise ValueError(f"{who}: {what}: every id has to be in [0, {'V' if V is None else int(V)}), got {i}")
+            out.append(i)
+        return tuple(out)
+
+    if name == "repetition_penalty":
+        try:
+            pen = float(value)
+        except (TypeError, ValueError):
+            pen = float("nan")
+        if not (pen > 0.0 and pen <= MAX_PENALTY):
+            raise ValueError(f"{who}: repetition_penalty has to be a strictly positive float (at most {MAX_PENALTY:g}: it is a float32 on "
+                             f"the device), got {value}")
+        return struct.unpack("<f", struct.pack("<f", pen))[0]          # the float32 the device reads: 1.2 and np.float32(1.2) are one set
+    if name in ("no_repeat_ngram_size", "min_length", "min_new_tokens"):
+        if not _is_int(value) or not 0 <= int(value) < 1 << 31:
+            raise ValueError(f"{who}: {name} is a non-negative integer, got {value!r}")
+        return int(value)
+    if name in ("suppress_tokens", "begin_suppress_tokens"):
+        return ids(value, name)
+    if name == "bad_words_ids":
+        if isinstance(value, (str, bytes)) or not hasattr(value, "__iter__"):
+            raise ValueError(f"{who}: bad_words_ids has to be a list of non-empty lists of token ids, got {value!r}")
+        words = []
+        for w in value:
+            if isinstance(w, (str, bytes)) or not hasattr(w, "__iter__") or len(w) == 0:
+                raise ValueError(f"{who}: bad_words_ids has to be a list of non-empty lists of token ids, got {value!r}")
+            words.append(ids(w, "bad_words_ids"))
+        return tuple(words)
+    raise KeyError(name)
 
 
 @dataclass(frozen=True)
@@ -21,7 +85,10 @@ class RequestParams:
     request_seed) - its draws depend on (seed, generated-token index) only, never on the slot or the neighbours.  logprobs: return the
     log-probability of every returned token under the raw model distribution, with the top_logprobs most likely alternatives.
     constraint: an aki_amd.TokenConstraint with one start state, or None - the request's tokens walk that automaton (the same object may
-    serve several requests: its table is stored once); it composes with sampling and log-probabilities."""
+    serve several requests: its table is stored once); it composes with sampling and log-probabilities.
+    The logits processors (PROCESSOR_FIELDS: repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens,
+    suppress_tokens, begin_suppress_tokens): None = the request takes the call's value (params=, else the call-wide keyword); any other
+    value, the neutral ones 1.0 / 0 / () included, belongs to the request alone (resolve_processors)."""
     do_sample: bool = False
     temperature: float = 1.0
     top_k: int = 0
@@ -30,6 +97,13 @@ class RequestParams:
     logprobs: bool = False
     top_logprobs: int = 0
     constraint: Optional["TokenConstraint"] = None
+    repetition_penalty: Optional[float] = None
+    no_repeat_ngram_size: Optional[int] = None
+    bad_words_ids: Optional[Sequence[Sequence[int]]] = None
+    min_length: Optional[int] = None
+    min_new_tokens: Optional[int] = None
+    suppress_tokens: Optional[Sequence[int]] = None
+    begin_suppress_tokens: Optional[Sequence[int]] = None
 
     def check(self, index, max_top: int) -> "RequestParams":
         """ValueError naming request `index` (a number, or a word such as "default") for a value the device sampler or ops.token_logprob
@@ -54,7 +128,51 @@ class RequestParams:
             if len(self.constraint.starts) != 1:
                 raise ValueError(f"{who}: a constraint with {len(self.constraint.starts)} start states; a request is one row, so exactly one "
                                  "start state is expected")
+        for name in PROCESSOR_FIELDS:                   # the ids' upper bound needs the logits' width: processor_set_key
+            if getattr(self, name) is not None:
+                check_processor_value(who, name, getattr(self, name))
         return self
+
+
+def resolve_processors(own: Optional[RequestParams], default: Optional[RequestParams], call: dict) -> dict:
+    """One request's processor settings {field: value}: its own RequestParams' value, else that of `default` (generate_many's params=),
+    else the call-wide keyword's (`call`: every field of PROCESSOR_FIELDS, None read as neutral).  Only None passes a level on: an explicit
+    neutral value overrides."""
+    out = {}
+    for name, neutral in PROCESSOR_FIELDS.items():
+        v = None if own is None else getattr(own, name)
+        if v is None and default is not None:
+            v = getattr(default, name)
+        if v is None:
+            v = call.get(name)
+        out[name] = neutral if v is None else v
+    return out
+
+
+def processor_set_key(who: str, resolved: dict, eos_ids: Sequence[int], V: int) -> tuple:
+    """A request's resolved settings as one hashable value, equal for equal behaviour: (penalty, ngram, min_len, suppress ids, begin-suppress
+    ids, bad words) with min_len = max(min_length, min_new_tokens) (no prompt counts here), every id checked against [0, V) and a one-token
+    bad word that is an eos id dropped, as HF's NoBadWordsLogitsProcessor does.  ValueError beginning with `who`."""
+    v = {name: check_processor_value(who, name, resolved[name], V) for name in PROCESSOR_FIELDS}
+    eos = {int(e) for e in eos_ids}
+    words = tuple(w for w in v["bad_words_ids"] if not (len(w) == 1 and w[0] in eos))
+    min_len = max(v["min_length"], v["min_new_tokens"]) if eos else 0          # without an eos id there is nothing to ban
+    return (v["repetition_penalty"], v["no_repeat_ngram_size"], min_len, v["suppress_tokens"], v["begin_suppress_tokens"], words)
+
+
+NEUTRAL_SET_KEY = (1.0, 0, 0, (), (), ())
+
+
+def banning_keywords(who: str, resolved: dict, eos_ids: Sequence[int], V: int) -> List[str]:
+    """The keywords among a request's resolved settings that ban a token, judged on the NORMAL form processor_set_key builds: a minimum
+    length without an eos id and a bad word that is dropped ban nothing; lists may be arrays or tensors."""
+    v = {name: check_processor_value(who, name, resolved[name], V) for name in PROCESSOR_FIELDS}
+    eos = {int(e) for e in eos_ids}
+    on = {"no_repeat_ngram_size": v["no_repeat_ngram_size"] > 0,
+          "bad_words_ids": any(not (len(w) == 1 and w[0] in eos) for w in v["bad_words_ids"]),
+          "min_length": bool(eos) and v["min_length"] > 0, "min_new_tokens": bool(eos) and v["min_new_tokens"] > 0,
+          "suppress_tokens": len(v["suppress_tokens"]) > 0, "begin_suppress_tokens": len(v["begin_suppress_tokens"]) > 0}
+    return [k for k in PROCESSOR_FIELDS if on.get(k)]
 
 
 def philox4x32_10(counter: Sequence[int], key: Sequence[int]) -> Tuple[int, int, int, int]:

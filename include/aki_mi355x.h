@@ -950,6 +950,55 @@ int aki_sample_pick_rows_constrained(const void* logits, int32_t B, int32_t V, i
                                      const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld,
                                      const int32_t* row_base, const int32_t* row_states, void* stream);
 
+/* ---- logits processors, one SET of settings per ROW (generate_many: a slot's request, and so its settings, changes at admit under a
+ * captured step).  Purely additive: AKI_ABI_VERSION was not bumped (it stays 17).  aki_logits_process_rows is
+ * aki_logits_process_constrained, aki_greedy_pick_rows is aki_greedy_pick_constrained_rows and aki_sample_pick_rows_processed is
+ * aki_sample_pick_rows_constrained, each with the eleven scalar processor arguments (repetition_penalty ... n_bad_ids) replaced by a
+ * pool of settings and one set index per row, all device arrays read by the launch itself (no host value is read: capturable):
+ *   sets        int32 [n_sets, AKI_PROCESSOR_SET_WORDS], n_sets >= 1: one record per distinct setting -
+ *               word 0 the repetition penalty (the bits of a float), 1 no_repeat_ngram_size, 2 min_length,
+ *               3, 4 the suppress ids set_ids[w3, w4), 5, 6 the begin-suppress ids set_ids[w5, w6), 7, 8 the bad words [w7, w8).
+ *   row_set     int32 [B]: row b is processed with record row_set[b].
+ *   set_ids     int64 [n_set_ids]: every record's suppress, begin-suppress and bad-word ids, one list behind the other.
+ *   bad_offsets int32 [n_words + 1], ascending: bad word w is set_ids[bad_offsets[w], bad_offsets[w + 1]).
+ * The stages, their order and their arithmetic are those of aki_logits_process; the minimum length bans the call's eos_ids.  Nothing
+ * validates the arrays on the device, and bad bits stay inside their row: a set index outside [0, n_sets) processes the row with the
+ * neutral set (the plain f32 copy), every range is cut at its pool's end (an empty or reversed one holds nothing), a penalty that is
+ * not a finite positive float is read as 1, a negative n-gram size as 0, ids outside [0, V) are skipped.  The caller rewrites
+ * row_set[b] in place when the row changes hands.
+ * The token constraint is the per-row form of aki_greedy_pick_constrained_rows and stays the last stage; table == NULL means no
+ * constraint, and the six arguments behind it are then ignored.  aki_logits_process_rows takes row_base / row_states too (its
+ * constrained sibling has no per-row form) and AKI_DT_BF16 or AKI_DT_F32 logits; the two picks take bf16 logits.  In
+ * aki_sample_pick_rows_processed every row runs through the processors (a neutral row is the plain copy), so rows with top_k[b] == 1
+ * take aki_greedy_pick_rows' token.  Everything else is as documented for the entry points these extend. */
+#define AKI_PROCESSOR_SET_WORDS 9
+
+int aki_logits_process_rows(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
+                            const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step,
+                            const uint8_t* done, const int64_t* eos_ids, int32_t n_eos, const int32_t* sets, int32_t n_sets,
+                            const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets, int32_t n_words,
+                            const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld,
+                            const int32_t* row_base, const int32_t* row_states, void* stream);
+
+int aki_greedy_pick_rows(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                         uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                         int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                         int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, const int32_t* sets,
+                         int32_t n_sets, const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets,
+                         int32_t n_words, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld,
+                         const int32_t* row_base, const int32_t* row_states, void* stream);
+
+int aki_sample_pick_rows_processed(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos,
+                                   int64_t pad_token_id, uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld,
+                                   int32_t* cache_len, const int32_t* start_len, int32_t advance, int32_t* done_at, const void* embed_weight,
+                                   const void* additional_weight, int64_t max_original_id, int64_t num_additional, int32_t d,
+                                   void* next_embeds, float* scores, int64_t ld_scores, const int32_t* sets, int32_t n_sets,
+                                   const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets,
+                                   int32_t n_words, int32_t step, const float* temperature, const int32_t* top_k, const float* top_p,
+                                   const uint64_t* seed, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld,
+                                   int32_t n_states, int32_t* states, int32_t states_ld, const int32_t* row_base, const int32_t* row_states,
+                                   void* stream);
+
 /* ---- beam search on the device (beam.hip).  HF `GenerationMixin` beam search with a `BeamSearchScorer`, the algorithm AKI._beam_search
  * runs on the host: 2K candidates per step, hypotheses normalised by generated_length ** length_penalty, at most K per sample.
  * Purely additive: AKI_ABI_VERSION was not bumped (it stays 17). */

@@ -29,7 +29,13 @@ over the greedy leg of the same round (the admits are the same work in every leg
 16-state cycle object (state s allows the ids v with v % 16 == s: a pool of 64 x 16 states, one table row read per row and step), against
 the greedy queue, alternating in one process at 8 and 16 slots.  Writes profiles/many_constraint_bench.json: tokens/s and ms per decode
 step of both legs, the microseconds per step the constrained leg adds (median and spread over the rounds).
+--many --request-processors: the queue with per-request logits processors (many_processors_bench below): the same 64 requests, their
+settings cycling over four distinct sets (the neutral one, --repetition-penalty 1.2 with --no-repeat-ngram 3, and two with id lists), against
+the call-wide processors leg (those two keywords for every row) and the plain greedy queue, alternating in one process at 8 and 16 slots.
+Writes profiles/many_processors_bench.json: tokens/s and ms per decode step of the three legs, and the per-request leg's difference per
+step from the call-wide leg next to that leg's own spread over the rounds.
     python tools/generate_bench.py [--many] [--many --sample --temperature 0.8 --top-k 50 --top-p 0.9 --logprobs 8] [--many --constraint]
+                                   [--many --request-processors]
     python tools/generate_bench.py [--new 256] [--fp8] [--txt 64] [--repetition-penalty 1.2] [--no-repeat-ngram 3]
                                    [--sample --temperature 0.8 --top-k 50 --top-p 0.9] [--batch 8] [--logprobs 8 --rounds 4] [--constraint]"""
 import argparse, json, os, sys, time
@@ -276,6 +282,82 @@ def many_constraint_bench(a, model, dev):
     print(json.dumps({k: v for k, v in res.items() if k != "budgets"}))
 
 
+def many_processors_bench(a, model, dev):
+    """--many --request-processors: generate_many with per-request logits processors (the settings cycling over four distinct sets) against
+    the call-wide processors leg and the plain greedy queue, many_bench's requests.  Writes profiles/many_processors_bench.json."""
+    import aki_amd
+    import bench
+    n_req = a.many_requests
+    g = torch.Generator(device="cpu").manual_seed(4242)
+    budgets = torch.randint(16, 257, (n_req,), generator=g).tolist()
+    reqs = []
+    for i in range(n_req):
+        vx, ids, _ = bench.synth_batch(1, dev, torch.bfloat16, model.media_token_id, seed=1000 + i)
+        reqs.append((vx, ids, budgets[i]))
+    wide = dict(repetition_penalty=a.repetition_penalty if a.repetition_penalty != 1.0 else 1.2,
+                no_repeat_ngram_size=a.no_repeat_ngram if a.no_repeat_ngram > 0 else 3)
+    cycle = [{}, dict(wide), dict(repetition_penalty=1.05, suppress_tokens=[11, 12, 13], bad_words_ids=[[21, 22], [23]]),
+             dict(no_repeat_ngram_size=2, begin_suppress_tokens=[31, 32])]
+    plain = [aki_amd.RequestParams()] * n_req
+    legs = {"greedy": (plain, {}), "call_wide": (plain, wide),
+            "per_request": ([aki_amd.RequestParams(**cycle[i % len(cycle)]) for i in range(n_req)], {})}
+
+    def leg(name, slots):
+        params, kw = legs[name]
+        batch = [(vx, ids, b, rp) for (vx, ids, b), rp in zip(reqs, params)]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        outs = model.generate_many(batch, slots=slots, eos_token_id=[], **kw)
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        assert [o.numel() for o in outs] == budgets
+        if name == "per_request":                                    # the 3-gram ban holds on the requests that carry it, and only there is it asked
+            for i, o in enumerate(outs):
+                if cycle[i % len(cycle)].get("no_repeat_ngram_size") == 3:
+                    row = o.tolist()
+                    grams = list(zip(row, row[1:], row[2:]))
+                    assert len(grams) == len(set(grams)), f"request {i} repeats a 3-gram"
+        return wall, dict(model.last_many_stats)
+
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    res = {"requests": n_req, "prompt_tokens_lm_stream": bench.N_TXT - 1 + bench.NV, "budgets": budgets, "budget_seed": 4242,
+           "call_wide": wide, "per_request_cycle": cycle,
+           "method": "the three legs alternate in one process, wall clock around each generate_many call with a device synchronisation on "
+                     "both sides; tokens/s = returned tokens / wall time, prefills included; ms_per_step = wall time / decode steps replayed. "
+                     "All legs admit the same 64 prompts with the same budgets (EOS off), so they replay the same number of steps.  The "
+                     "per-request leg is compared with the call-wide leg of the same round (the per-row pick against the processed pick); "
+                     "the call-wide leg's own spread over the rounds is the yardstick", "slots": {}}
+    for slots in (8, 16):
+        for name in legs:
+            leg(name, slots)                                          # warm-up: allocator, folds, capture path
+        rounds = []
+        for _ in range(max(3, a.rounds)):
+            r = {}
+            for name in legs:
+                wall, stats = leg(name, slots)
+                r[name] = {"tokens_per_s": round(sum(budgets) / wall, 1), "wall_s": round(wall, 3), "steps": stats["steps"],
+                           "ms_per_step": round(wall * 1e3 / stats["steps"], 4)}
+            rounds.append(r)
+        summary = {}
+        for name in legs:
+            ms = [r[name]["ms_per_step"] for r in rounds]
+            summary[name] = {"tokens_per_s_median": med([r[name]["tokens_per_s"] for r in rounds]),
+                             "tokens_per_s_min_max": [min(r[name]["tokens_per_s"] for r in rounds), max(r[name]["tokens_per_s"] for r in rounds)],
+                             "ms_per_step_median": med(ms), "ms_per_step_min_max": [min(ms), max(ms)]}
+        ex = [(r["per_request"]["ms_per_step"] - r["call_wide"]["ms_per_step"]) * 1e3 for r in rounds]
+        cw = summary["call_wide"]["ms_per_step_min_max"]
+        summary["per_request"]["us_per_step_over_call_wide_median"] = round(med(ex), 1)
+        summary["per_request"]["us_per_step_over_call_wide_min_max"] = [round(min(ex), 1), round(max(ex), 1)]
+        summary["call_wide"]["us_per_step_spread_over_rounds"] = round((cw[1] - cw[0]) * 1e3, 1)
+        summary["per_request"]["inside_the_call_wide_legs_spread"] = bool(abs(med(ex)) <= (cw[1] - cw[0]) * 1e3)
+        res["slots"][str(slots)] = {"rounds": rounds, "summary": summary}
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "many_processors_bench.json")
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps({k: v for k, v in res.items() if k != "budgets"}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--new", type=int, default=256)
@@ -301,6 +383,8 @@ def main():
                     "queue against the queue with per-request sampling (and --logprobs K) -> profiles/many_sample_bench.json; with "
                     "--constraint: against the queue with one 16-state constraint per request -> profiles/many_constraint_bench.json")
     ap.add_argument("--many-requests", type=int, default=64)
+    ap.add_argument("--request-processors", action="store_true", help="with --many: per-request logits processors against the call-wide "
+                    "processors leg and the greedy queue -> profiles/many_processors_bench.json")
     a = ap.parse_args()
     lp_kw =dict(output_logprobs=True, top_logprobs=a.logprobs) if a.logprobs >= 0 else None
     proc_kw = {}
@@ -319,6 +403,8 @@ def main():
         model.lang_model.enable_mxfp4()
     model.lang_model.model.decode_chain_w4 = bool(a.w4_chain)
     if a.many:
+        if a.request_processors:
+            return many_processors_bench(a, model, dev)
         if a.constraint:
             return many_constraint_bench(a, model, dev)
         return many_sample_bench(a, model, dev) if a.sample else many_bench(a, model, dev)

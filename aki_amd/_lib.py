@@ -22,6 +22,7 @@ AKI_PROCESSOR_SET_WORDS = 9
 AKI_BEAM_MAX_K, AKI_BEAM_MAX_EOS, AKI_KV_BEAM_REORDER_CHUNK = 16, 8, 16
 AKI_LOGPROB_MAX_TOP, AKI_LOGPROB_MAX_V = 8, 262144
 AKI_SLOT_MAX_ROWS = 16
+AKI_STOP_MAX_SEQS, AKI_STOP_MAX_LEN = 64, 32
 
 
 class AkiError(RuntimeError):
@@ -299,6 +300,10 @@ SIGNATURES = {
                                     C.c_int32, C.c_void_p]),
     "aki_kv_slot_admit": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p]),
     "aki_slot_tick": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p]),
+    "aki_stop_check": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                                                           C.c_void_p, C.c_int32, C.c_void_p]),
+    "aki_slot_tick_stops": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                                         C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "aki_sft_collate_pad": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 4),
     "aki_mma_mask_to_table_workspace_bytes": (C.c_size_t, [C.c_int32] * 2),
     "aki_mma_mask_to_table": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),

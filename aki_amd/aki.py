@@ -22,6 +22,7 @@ from . import ops
 from .helpers import PerceiverResampler
 from .phi3 import AkiKVCache, DecodeGraph
 from .slots import RequestParams, SlotScheduler, banning_keywords, processor_set_key, request_seed, resolve_processors, slot_capacity
+from .stops import check_stop_sequences, first_finish, resolve_stop_sequences
 from .vlm import VLMWithLanguageStream
 
 
@@ -59,7 +60,8 @@ def _reject_unused_kwargs(kwargs: dict) -> None:
     """What HF's `_validate_model_kwargs` does with keywords generate() does not use: a ValueError naming them, never a silent drop."""
     if kwargs:
         raise ValueError(f"generate() cannot honour the keyword argument(s) {sorted(kwargs)}: the supported ones are the greedy / sampling / "
-                         f"beam-search controls and the logits processors {sorted(PROCESSOR_KWARGS)}")
+                         f"beam-search controls, the logits processors {sorted(PROCESSOR_KWARGS)} and stop_sequences (lists of token ids, "
+                         "matched on the device: what stopping_criteria / stop_strings would be asked for)")
 
 
 def _embedding_tables(emb: nn.Module, logits: torch.Tensor):
@@ -86,9 +88,10 @@ def _embedding_tables(emb: nn.Module, logits: torch.Tensor):
 # the logits-processor keywords (PROCESSOR_KWARGS) with None read as the neutral value; output_logprobs / top_logprobs: the per-token
 # log-probabilities of the returned tokens and that many alternatives (ops.token_logprob).
 # constraint: None, a constraint.TokenConstraint or a list of one per sample (constrained decoding; bound to the device in generate).
+# stops: the call's stop set in its normal form (stops.check_stop_sequences; () = none), one set for every row.
 GenerateOptions = namedtuple("GenerateOptions", "num_beams do_sample temperature top_k top_p rng device_rng length_penalty early_stopping "
                                                 "n_ret max_new_tokens eos_ids pad_id use_graph processors output_logprobs top_logprobs "
-                                                "constraint")
+                                                "constraint stops")
 
 # the processors that ban tokens outright: together with a constraint they could leave a row with nothing allowed
 BANNING_KWARGS = ("no_repeat_ngram_size", "bad_words_ids", "min_length", "min_new_tokens", "suppress_tokens", "begin_suppress_tokens")
@@ -220,16 +223,21 @@ def _parse_generate_kwargs(kwargs: dict, default_pad_id, default_eos_ids, from_c
                 raise ValueError("constraint is an aki_amd.TokenConstraint or a list of one per sample")
             if batch is not None and len(constraint) != batch:
                 raise ValueError(f"constraint lists {len(constraint)} constraints for a batch of {batch} samples")
+    stops = kwargs.pop("stop_sequences", None)
+    stops = () if stops is None else check_stop_sequences("generate", stops)       # the ids' upper bound needs the logits' width: generate
+    if stops and num_beams > 1:
+        raise NotImplementedError("stop_sequences with num_beams > 1: beam search under stop sequences")
     _reject_unused_kwargs(kwargs)
     return GenerateOptions(num_beams=num_beams, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, rng=rng,
                            device_rng=device_rng, length_penalty=length_penalty, early_stopping=early_stopping, n_ret=n_ret,
                            max_new_tokens=max_new_tokens, eos_ids=eos_ids, pad_id=pad_id, use_graph=use_graph, processors=processors,
-                           output_logprobs=output_logprobs, top_logprobs=top_logprobs, constraint=constraint)
+                           output_logprobs=output_logprobs, top_logprobs=top_logprobs, constraint=constraint, stops=stops)
 
 
 # The keyword arguments of `generate_many`, resolved by _parse_many_kwargs: max_new_tokens is the default budget of a request, params the
-# RequestParams of a request that brings none, generator None or the ops.DeviceGenerator the sampled requests' seeds are derived from.
-ManyOptions = namedtuple("ManyOptions", "max_new_tokens eos_ids pad_id use_graph processors params generator")
+# RequestParams of a request that brings none, generator None or the ops.DeviceGenerator the sampled requests' seeds are derived from,
+# stops the call-wide stop_sequences= keyword in its normal form or None: the default of every request whose RequestParams leave it None.
+ManyOptions = namedtuple("ManyOptions", "max_new_tokens eos_ids pad_id use_graph processors params generator stops")
 
 # what generate_many refuses, with the reason: (keyword, the test that it is in force, why)
 MANY_REFUSED = (
@@ -272,9 +280,12 @@ def _parse_many_kwargs(kwargs: dict, default_pad_id, default_eos_ids) -> ManyOpt
     if generator is not None and not isinstance(generator, ops.DeviceGenerator):
         raise ValueError("generate_many: generator is an aki_amd.DeviceGenerator (the sampled requests' seeds are derived from it on the "
                          "host) or None; a torch.Generator cannot seed the device sampler")
+    stops = kwargs.pop("stop_sequences", None)
+    if stops is not None:
+        stops = check_stop_sequences("generate_many: the call-wide keyword", stops)
     _reject_unused_kwargs(kwargs)
     return ManyOptions(max_new_tokens=max_new_tokens, eos_ids=eos_ids, pad_id=pad_id, use_graph=True if use_graph is None else bool(use_graph),
-                       processors=processors, params=params, generator=generator)
+                       processors=processors, params=params, generator=generator, stops=stops)
 
 
 def _many_requests(requests, default_budget: int, default_params: Optional[RequestParams] = None):
@@ -348,10 +359,21 @@ def _device_sampler_args(opt: GenerateOptions):
     return None if g is None else dict(temperature=opt.temperature, top_k=opt.top_k, top_p=opt.top_p, seed=g.seed, offset=g.next_offset())
 
 
-def _first_eos(tokens: torch.Tensor, eos_t: torch.Tensor):
-    """tokens [B, n], eos_t [E] -> (finished [B] bool: the row holds an EOS; index [B] int64 of its first one, 0 where it holds none)."""
-    hit = (tokens[:, :, None] == eos_t[None, None, :]).any(-1)
-    return hit.any(1), hit.to(torch.int32).argmax(1)
+def _first_end(tokens: torch.Tensor, eos_t, stops=()):
+    """tokens [B, n], eos_t [E] or None, the call's stop set `stops` (normal form, one set for every row) -> stops.first_finish's
+    (finished [B] bool: an EOS or a stop sequence ends the row; index [B] int64 of the token that ends it, 0 where nothing does;
+    stop_hit [B] int32)."""
+    return first_finish(tokens, eos_t, [stops], [0] * tokens.shape[0])
+
+
+def _many_stop_sets(reqs, opt: "ManyOptions", V: Optional[int] = None):
+    """Every request's resolved stop set in its normal form (stops.resolve_stop_sequences: its own, else params=, else the call-wide
+    keyword; none of them: ()), the ids checked against V where it is known.  ValueError naming the request."""
+    out = []
+    for i, (*_, rp) in enumerate(reqs):
+        v = resolve_stop_sequences(rp.stop_sequences, opt.params.stop_sequences, opt.stops)
+        out.append(() if v is None else check_stop_sequences(f"request {i}", v, V))
+    return out
 
 
 def _pad_rows(rows, pad_id: int, device) -> torch.Tensor:
@@ -586,17 +608,18 @@ class AkiMethods:
         return cache, last, (cache.cache_len.clone(), cache.host_len)           # the caller's cache: the state behind the new ids
 
     @staticmethod
-    def _trim_cache_to_returned(cache, start_len, host_len0, out, eos_t):
+    def _trim_cache_to_returned(cache, start_len, host_len0, out, eos_t, stops=()):
         """The end of generate(past_key_values=...): every row's cache ends right before its last returned token.  start_len / host_len0:
-        the cache's lengths behind the new ids; out [B, steps]: the returned tokens; a row's last token is its first EOS, or column
-        steps - 1.  The decode loops themselves run past that point: the graph / device loop looks at the finished flags only every 8th token,
+        the cache's lengths behind the new ids; out [B, steps]: the returned tokens; a row's last token is its first finish (its first EOS
+        or the end of its first stop sequence of `stops`), or column steps - 1.
+        The decode loops themselves run past that point: the graph / device loop looks at the finished flags only every 8th token,
         and until then ops.greedy_pick / ops.sample_pick feed a finished row pad tokens and advance its cache_len like any other (the host
         loop does the same to the finished rows of a batch), so pad-token rows land behind the EOS.  They are cut off here by rewinding
         cache_len, at B = 1 and per row in a batch: the rows behind are dead and the next append overwrites them."""
         steps = out.shape[1]
         kept = torch.full_like(start_len, steps - 1)
-        if eos_t is not None:
-            finished, first = _first_eos(out, eos_t)
+        if eos_t is not None or stops:
+            finished, first, _ = _first_end(out, eos_t, stops)
             kept = torch.where(finished, first.to(kept.dtype), kept)
         cache.cache_len.copy_(start_len + kept)
         cache.host_len = host_len0 + steps - 1
@@ -642,7 +665,10 @@ class AkiMethods:
         behind the EOS in the cache (_trim_cache_to_returned cuts them off for a caller who keeps the cache).
         logits [B, V'] bf16 on the GPU: the prompt stage's; proc: the active ops.LogitsProcessors or None; eos_t: the eos ids as an int64
         tensor or None.  Returns (the new tokens [B, <= max_new_tokens], cut behind the last row's EOS where every row hit one; the
-        _LogprobBuffers of opt.output_logprobs, uncut, else None)."""
+        _LogprobBuffers of opt.output_logprobs, uncut, else None).
+        opt.stops: one ops.stop_check behind the pick (and the log-probability launch) of token 0, of every eager step and inside the
+        graph; a row it ends is a done row like one the pick's EOS check ended, so the host looks every 8th token whenever there are
+        stops, also without an EOS id.  last_stop_hits is the StopSets' stop_hit afterwards."""
         lm, dev, B, max_new_tokens, pad_id = self.lang_model, logits.device, logits.shape[0], opt.max_new_tokens, opt.pad_id
         tokens = torch.full((B, max_new_tokens), pad_id, dtype=torch.long, device=dev)
         chained = lambda: getattr(cache, "chain", None) is not None
@@ -666,21 +692,29 @@ class AkiMethods:
         # output_logprobs: one ops.token_logprob behind each pick (in-loop form: it reads the index the pick just wrote from cache_len)
         lpb = _LogprobBuffers(B, max_new_tokens, opt.top_logprobs, dev) if opt.output_logprobs else None
         lp = None if lpb is None or max_new_tokens < 1 else dict(lpb.args(), tokens=tokens, cache_len=cache.cache_len, start_len=start_len, done_at=done_at)
+        stops = None
+        if opt.stops and max_new_tokens >= 1:           # one set for every row; row_set / stop_hit allocated ahead of any capture
+            stops = ops.StopSets(dev, [opt.stops], B)
+            stops.row_set.fill_(stops.index[opt.stops])
+            self.last_stop_hits = stops.stop_hit
+        check = (lambda: None) if stops is None else (lambda: ops.stop_check(tokens, cache.cache_len, start_len, done8, done_at, stops))
+        ends = eos_t is not None or stops is not None   # a row can finish ahead of its budget
         logits = logits.contiguous()
         pick_op(logits, ids, cache_len=cache.cache_len, advance=False, **pick_e)      # token 0, from the prefill
         if lp is not None:
             ops.token_logprob(logits, **lp)
+        check()
         t, t_ok = 1, 1                                  # tokens[:, :t_ok] are verified (token 0 comes from the prefill, not from the chain)
-        period = 8 if eos_t is not None else 32         # host synchronisations: the EOS check needs them often, the chain's verification alone does not
+        period = 8 if ends else 32                      # host synchronisations: the finished flags need them often, the chain's verification alone does not
         while True:
             ok = True
             while t < max_new_tokens:
-                if t % period == 0 and (eos_t is not None or chained()):
+                if t % period == 0 and (ends or chained()):
                     if chained() and not lm.decode_verified(cache):
                         ok = False
                         break
                     t_ok = t
-                    if eos_t is not None and bool(done8.all()):
+                    if ends and bool(done8.all()):
                         break
                 if stepper is not None:
                     stepper.step_greedy()
@@ -696,8 +730,10 @@ class AkiMethods:
                     pick_op(lg, ids, cache_len=cache.cache_len, advance=True, **pick_e)
                     if lp is not None:
                         ops.token_logprob(lg, **lp)
+                    check()
                     if not chained():
-                        stepper = DecodeGraph(lm, cache, greedy=pick if lp is None else dict(pick, logprob=lp))
+                        captured = pick if lp is None else dict(pick, logprob=lp)
+                        stepper = DecodeGraph(lm, cache, greedy=captured if stops is None else dict(captured, stops=stops))
                         stepper.ids.copy_(ids)
                 t += 1
             if ok and chained() and not lm.decode_verified(cache):
@@ -714,14 +750,16 @@ class AkiMethods:
                 lpb.reset_from(t_ok)
             done8.zero_()
             done_at.fill_(-1)
-            if eos_t is not None:
-                finished, first = _first_eos(tokens[:, :t_ok], eos_t)
+            if ends:
+                finished, first, hit = _first_end(tokens[:, :t_ok], eos_t, opt.stops)
                 done8.copy_(finished.to(torch.uint8))
                 done_at.copy_(torch.where(finished, first.to(torch.int32), torch.full_like(done_at, -1)))
+                if stops is not None:
+                    stops.stop_hit.copy_(hit)
             ids.copy_(tokens[:, t_ok - 1])
             if nxt_emb is not None:
                 nxt_emb.copy_(emb_mod(ids))
-        if eos_t is not None and bool(done8.all()):
+        if ends and bool(done8.all()):
             return tokens[:, :int(done_at.max()) + 1], lpb
         return tokens[:, :t], lpb
 
@@ -729,7 +767,8 @@ class AkiMethods:
         """The loop that picks on the host, one synchronisation per token where there is an EOS id: `sample_next` sampling (generator None or
         a torch.Generator), the device sampler outside a graph, and greedy where the device loop does not apply (f32, use_graph=False).  The
         decode step is replayed from a DecodeGraph with use_graph.  A finished row of a batch is stepped on with pad tokens until every row
-        has finished.  Arguments and return value as _decode_on_device; the tokens [B, <= max_new_tokens] are cut where every row has finished."""
+        has finished.  Arguments and return value as _decode_on_device; the tokens [B, <= max_new_tokens] are cut where every row has finished.
+        opt.stops: a row is also finished when stops.first_finish over tokens[:, :t] says so - the same synchronisation per token."""
         lm, B, max_new_tokens, pad_id = self.lang_model, logits.shape[0], opt.max_new_tokens, opt.pad_id
         do_sample, temperature, top_k, top_p, rng = opt.do_sample, opt.temperature, opt.top_k, opt.top_p, opt.rng
         tokens = torch.full((B, max_new_tokens), pad_id, dtype=torch.long, device=logits.device)
@@ -761,8 +800,11 @@ class AkiMethods:
                 if lpb is not None:                 # the raw logits of this step, at the token returned; rows finished before it are skipped
                     ops.token_logprob(logits, ids=nxt, skip=done.to(torch.uint8), step=t, **lpb.args())
                 t += 1
-                if eos_t is not None:
-                    done = done | (nxt[:, None] == eos_t[None, :]).any(-1)
+                if eos_t is not None or opt.stops:
+                    if opt.stops:
+                        done = done | _first_end(tokens[:, :t], eos_t, opt.stops)[0]
+                    else:
+                        done = done | (nxt[:, None] == eos_t[None, :]).any(-1)
                     if bool(done.all()):
                         n_out = t
                         break
@@ -780,6 +822,8 @@ class AkiMethods:
             n_out, stepper = max_new_tokens, None           # a graph captured around the chain is gone with it
             if opt.use_graph:
                 stepper = DecodeGraph(lm, cache)
+        if opt.stops:
+            self.last_stop_hits = _first_end(tokens[:, :n_out], eos_t, opt.stops)[2]
         return tokens[:, :n_out], lpb
 
     @torch.no_grad()
@@ -848,6 +892,16 @@ class AkiMethods:
                               top_token_ids=shape(buf.top_ids), top_logprobs=shape(buf.top_lp))
 
     last_many_stats = None      # after generate_many: the SlotScheduler's counters (slots.SlotScheduler.stats) as a dict
+    # after a generate() with stop_sequences: int32 device tensor [rows], rows = B * num_return_sequences - per row the index within the stop
+    # set of the sequence that ended it, -1 for a row that ended otherwise; after generate_many with stops: a list of ints in request
+    # order; after a call without stops: None
+    last_stop_hits = None
+
+    def _logits_width(self) -> int:
+        """V', the columns of the logits: DecoupledLinear's output is the original ids followed by the added ones (helpers.py), a plain
+        head's its rows."""
+        head = self.lang_model.get_output_embeddings()
+        return int(head.max_original_id) + 1 + int(head.additional_out_features) if hasattr(head, "max_original_id") else int(head.out_features)
 
     def _prefill_request(self, vision_x, lang_x):
         """One request of generate_many, prefilled at batch 1 into a cache of exactly its length: (cache, logits [1, V']).  Without an image
@@ -878,11 +932,11 @@ class AkiMethods:
         return row0(self.generate(None, lang_x[:, -1:], past_key_values=cache, **kwargs))
 
     @staticmethod
-    def _cut_behind_eos(row: torch.Tensor, eos_t):
-        """A 1-D token row cut behind its first EOS (EOS included)."""
-        if eos_t is None or row.numel() == 0:
+    def _cut_behind_eos(row: torch.Tensor, eos_t, stops=()):
+        """A 1-D token row cut behind its first finish: its first EOS or the end of its first stop sequence (both included)."""
+        if (eos_t is None and not stops) or row.numel() == 0:
             return row
-        finished, first = _first_eos(row[None], eos_t)
+        finished, first, _ = _first_end(row[None], eos_t, stops)
         return row[: int(first[0]) + 1] if bool(finished[0]) else row
 
     @torch.no_grad()
@@ -933,6 +987,16 @@ class AkiMethods:
             index, filled at admit ahead of the pick of token 0 and read by the captured pick (aki_greedy_pick_rows /
             aki_sample_pick_rows_processed; an f32 model's torch pick takes aki_logits_process_rows' scores).  A call whose requests all
             resolve to ONE set launches exactly what it launched before.  Log-probabilities stay the raw distribution's.
+          * stop_sequences (the rule and the limits: generate's docstring, aki_amd/stops.py), None by default: None takes the call's
+            value - params=, else the call-wide `stop_sequences=` keyword, which is every request's default; () means this request has
+            none.  The ids are checked against the logits' width; a bad value is a ValueError naming the request, before any device
+            work.  The distinct resolved sets of a call form one pool, deduplicated by value and uploaded once (ops.StopSets); each slot
+            holds the place of its request's set and its hit, filled at admit.  The admit checks the row behind the pick of token 0 and
+            ahead of the tick (a one-token stop can end a request at its prefill); the captured step takes the tick that checks the
+            stops in the same launch (ops.slot_tick(stops=...)), so a queue with stops costs no launch more than one without, and the
+            hits ride in the look's one copy.  A request is cut behind its matched sequence.  `last_stop_hits` is a list of ints in
+            request order afterwards (None after a call without stops).  A call in which no request resolves to a non-empty set
+            launches exactly what it launched before.
           Bad values (temperature <= 0, top_p outside (0, 1], top_k < 0, top_logprobs outside the limit or without logprobs, a seed outside
           [0, 2^64)): ValueError naming the request, before any device work.
         Refused with NotImplementedError (MANY_REFUSED): num_beams > 1, num_return_sequences > 1, past_key_values, and the
@@ -957,6 +1021,7 @@ class AkiMethods:
         reqs = _many_requests(requests, opt.max_new_tokens, opt.params)
         seeds = _many_seeds(reqs, opt.generator)
         self.last_many_stats = None
+        self.last_stop_hits = None
         if not reqs:
             self.last_many_stats = SlotScheduler(0, slots).stats()
             return []
@@ -974,6 +1039,9 @@ class AkiMethods:
             raise ValueError("generate_many: a sampled request needs the device sampler, which needs bf16 logits on the GPU")
         head = lm.get_output_embeddings()
         width = int(head.max_original_id) + 1 + int(head.additional_out_features) if hasattr(head, "max_original_id") else int(head.out_features)
+        # every request's stop set: its own, else params=, else the call-wide keyword, its ids checked against the logits' width
+        stop_keys = _many_stop_sets(reqs, opt, width)
+        any_stops = any(stop_keys)
         # every request's processor settings: its own, else params=, else the call-wide keyword - checked on the host against the logits'
         # width and reduced to one value per distinct behaviour.  A call whose requests all resolve to one set runs the call-wide path.
         resolved = [resolve_processors(rp, opt.params, pk) for *_, rp in reqs]
@@ -1009,9 +1077,11 @@ class AkiMethods:
                                     top_logprobs=top_lp[:, :k].clone() if k else None)
 
         if slots == 1 or len(reqs) == 1:
-            outs, sched = [], SlotScheduler(len(reqs), 1)
-            for (vx, lx, budget, rp), seed, own in zip(reqs, seeds, resolved):
+            outs, sched, hits = [], SlotScheduler(len(reqs), 1), []
+            for (vx, lx, budget, rp), seed, own, stop_key in zip(reqs, seeds, resolved, stop_keys):
                 kw_r = dict(own, eos_token_id=eos_list, pad_token_id=opt.pad_id, max_new_tokens=budget)
+                if stop_key:
+                    kw_r.update(stop_sequences=stop_key)
                 if rp.do_sample:                        # the same stream: key seed, counter (token index, row 0, offset 0)
                     kw_r.update(do_sample=True, temperature=float(rp.temperature), top_k=int(rp.top_k), top_p=float(rp.top_p),
                                 generator=ops.DeviceGenerator(seed))
@@ -1022,7 +1092,8 @@ class AkiMethods:
                 out = self._generate_one(vx, lx, **kw_r)
                 row = out.sequences if rp.logprobs else out
                 eos_t = torch.tensor(eos_list, dtype=torch.long, device=row.device) if eos_list else None
-                tok = self._cut_behind_eos(row, eos_t).clone()
+                tok = self._cut_behind_eos(row, eos_t, stop_key).clone()
+                hits.append(int(self.last_stop_hits[0]) if stop_key else -1)
                 n = tok.numel()
                 if rp.logprobs:
                     cut = lambda x: None if x is None else x[:n].clone()
@@ -1031,6 +1102,7 @@ class AkiMethods:
                 else:
                     outs.append(result(tok, rp))
             self.last_many_stats = dict(sched.stats(), per_request_generate=True)
+            self.last_stop_hits = hits if any_stops else None
             return outs
         slots = min(slots, len(reqs))
         flat = torch.cat([r[1][0] for r in reqs]).tolist()       # one copy for all prompts, ahead of any launch
@@ -1079,6 +1151,10 @@ class AkiMethods:
         if constrained:
             slot_con = ops.SlotConstraints(pool.bind(dev), slots, max_budget)
             pick["slot_constraints"] = slot_con
+        # a call with stops: the pool of distinct stop sets (uploaded once), and per slot the place of its request's set and its hit,
+        # allocated ahead of the capture and rewritten in place at admit.  The check rides in the tick's launch (ops.slot_tick(stops=...)).
+        stop_sets = ops.StopSets(dev, stop_keys, slots) if any_stops else None
+        tick_stops = {} if stop_sets is None else dict(stops=stop_sets, tokens=tokens)
         # a call with a sampled request: every row's sampler parameters and Philox key live in device arrays the captured pick reads
         # (ops.sample_pick_rows).  A parked row and a greedy request are top_k = 1 rows, the greedy pick's token.
         rows = None
@@ -1095,6 +1171,8 @@ class AkiMethods:
                     captured.update(temperature=rows["temperature"], top_k=rows["top_k"], top_p=rows["top_p"], row_seed=rows["seed"])
                 if lp is not None:
                     captured["logprob"] = lp
+                if stop_sets is not None:
+                    captured["stops"] = stop_sets
                 stepper = DecodeGraph(lm, cache, greedy=captured)
             else:
                 stepper = DecodeGraph(lm, cache)
@@ -1102,7 +1180,7 @@ class AkiMethods:
         else:
             stepper, ids = None, torch.zeros(slots, dtype=torch.long, device=dev)
         sched = SlotScheduler(len(reqs), slots, period=8)
-        results = {}
+        results, hits, seen = {}, {}, {}
         row = lambda x, s: x[s:s + 1]
 
         def admit(req, slot):
@@ -1126,6 +1204,8 @@ class AkiMethods:
                 slot_con.admit(slot, pool.base[req], pool.n_states[req], pool.start[req])
             if psets is not None:                       # the slot's processor set, ahead of the pick of token 0
                 psets.admit(slot, set_keys[req])
+            if stop_sets is not None:                   # the slot's stop set, its hit back to -1
+                stop_sets.admit(slot, stop_keys[req])
             args = dict(pad_token_id=opt.pad_id, eos_ids=eos_t, done=row(done, slot), tokens=row(tokens, slot), start_len=row(start_len, slot),
                         done_at=row(done_at, slot))
             if on_device:                               # token 0, from the prefill: the existing pick at B = 1 on row views
@@ -1145,6 +1225,9 @@ class AkiMethods:
                                  proc=proc1 if psets is None else psets.row(slot), **args)
             if lp is not None:
                 ops.token_logprob(logits.contiguous(), **{k: (row(v, slot) if torch.is_tensor(v) else v) for k, v in lp.items()})
+            if stop_sets is not None:                   # behind the pick of token 0, ahead of the tick: a one-token stop ends a request here
+                ops.stop_check(row(tokens, slot), row(cache.cache_len, slot), row(start_len, slot), row(done, slot), row(done_at, slot),
+                               stop_sets.row(slot))
             ops.slot_tick(row(done, slot), row(done_at, slot), row(cache.cache_len, slot), row(start_len, slot), row(limit, slot))
             return budget == 1
 
@@ -1168,11 +1251,13 @@ class AkiMethods:
                                      proc if psets is None else psets)
                 if lp is not None:
                     ops.token_logprob(lg, **lp)
-                ops.slot_tick(cache_len=cache.cache_len, **tick)
+                ops.slot_tick(cache_len=cache.cache_len, **tick, **tick_stops)
 
         def look():
-            state = torch.stack([done.to(torch.int32), done_at, cache.cache_len]).tolist()       # the one synchronisation
-            d, at, ln = state
+            state = [done.to(torch.int32), done_at, cache.cache_len] + ([] if stop_sets is None else [stop_sets.stop_hit])
+            state = torch.stack(state).tolist()         # the one synchronisation
+            d, at, ln = state[:3]
+            seen["hit"] = state[3] if stop_sets is not None else None
             # host_len bounds the row the next step appends at.  A parked row stays on its one dead cache row (ops.slot_tick), so under the
             # captured step, whose grid is sized by the capacity, only the live rows count; eager steps size their grid by host_len and
             # need every row's keys inside it.
@@ -1182,6 +1267,7 @@ class AkiMethods:
 
         def retire(req, slot, n):
             rp = reqs[req][3]
+            hits[req] = -1 if stop_sets is None else int(seen["hit"][slot])
             tok = tokens[slot, :n].clone()
             if rp.logprobs:                             # the columns behind n may hold what the slot's previous request left: never returned
                 results[req] = result(tok, rp, lpb.lp[slot, :n].clone(), None if lpb.top_ids is None else lpb.top_ids[slot, :n],
@@ -1191,6 +1277,7 @@ class AkiMethods:
 
         sched.run(admit, step, look, retire, room=lambda: capacity - cache.host_len)
         self.last_many_stats = sched.stats()
+        self.last_stop_hits = sched.in_request_order(hits) if stop_sets is not None else None
         self._post_forward_hook()
         return sched.in_request_order(results)
 
@@ -1242,9 +1329,26 @@ class AkiMethods:
             Greedy, sampling, N continuations and from a cache; with num_beams > 1 NotImplementedError (beam search keeps
             last_beam_scores).  `top_logprobs` without `output_logprobs`, or above the limit: ValueError.  `score` is the counterpart
             for continuations the caller supplies.
+          * `stop_sequences=[[id, ...], ...]`: one stop set for every row of the call - at most ops.STOP_MAX_SEQS = 64 token-id sequences
+            of 1 to ops.STOP_MAX_LEN = 32 ids in [0, V') (ValueError otherwise, before any device work); None, [] and () mean none, and
+            the call launches exactly what it launches without the keyword.  A live row finishes at the first generated-token index t
+            at which a sequence s of the set matches: with n = len(s), n <= t + 1 and tokens[t - n + 1 .. t] == s.  Only generated tokens
+            count, never the prompt.  The matched sequence STAYS in the returned tokens, as an EOS does and as HF's `stop_strings`
+            does; what follows it is pad.  `last_stop_hits` (int32 device tensor [rows], rows = B * num_return_sequences; None after a
+            call without stops) holds per row the index within the set of the LOWEST-numbered sequence that matched at that t, -1
+            for a row that ended otherwise; a row its EOS ended at the same t keeps -1 (EOS wins a tie), a stop at the last token of the
+            budget is a stop.  Stops change WHEN a row ends, never WHAT it picks: they apply behind the pick, so they ignore
+            `min_length` / `min_new_tokens`, as HF's stopping criteria do.  Matched on the device: one ops.stop_check launch behind
+            each pick (inside the replayed graph where there is one), and the host looks at the finished flags every 8th token as it
+            does for an EOS, also with `eos_token_id=[]`; the host loops (f32, `torch.Generator` sampling, `use_graph=False`) apply
+            the same rule in torch (stops.first_finish).  Composes with the processors, both samplers, `output_logprobs`,
+            `num_return_sequences`, `past_key_values` and `constraint` (a constrained row may end outside an accepting state, as it may
+            at its budget).  With `num_beams > 1`: NotImplementedError.  HF's `stopping_criteria` and `stop_strings` stay refused
+            (ValueError): pass the tokenised strings as `stop_sequences`.
         Returns, like HF `generate` called with `inputs_embeds` only, just the NEW tokens [B, <= max_new_tokens]; finished rows are padded
         with pad_token_id.
-        After a call from a cache the LAST returned token of a row - its EOS where it hit one, else the last column - is not in the cache,
+        After a call from a cache the LAST returned token of a row - its EOS or the end of its stop sequence where it hit one, else the
+        last column - is not in the cache,
         so the next turn's `lang_x` must begin with it: on return cache_len[b] = its value before the call + n_new[b] + (tokens returned
         for row b) - 1, at B = 1 and per row in a batch - there the next turn's chunk is ragged (chunked_continue).  The cache must have
         room for T + max_new_tokens - 1 more rows (AkiError before any launch otherwise).
@@ -1252,15 +1356,16 @@ class AkiMethods:
         prompt batch is right-padded and every sample continues from its own length."""
         opt = _parse_generate_kwargs(kwargs, self.pad_token_id, self.default_eos_token_ids, past_key_values is not None,
                                      batch=None if lang_x is None else lang_x.shape[0])
+        self.last_stop_hits = None
+        if opt.stops:                              # the ids against the logits' width, before any device work
+            check_stop_sequences("generate", opt.stops, self._logits_width())
         con = None
         if opt.constraint is not None:             # the host half of binding: the table with its eos columns, checked before any launch
             from .constraint import constraint_for_rows
             if lang_x is None:
                 raise ValueError("generate(constraint=...) needs lang_x")
             con, rows_start = constraint_for_rows(opt.constraint, lang_x.shape[0], opt.n_ret)
-            head = self.lang_model.get_output_embeddings()
-            # V': DecoupledLinear's output is the original ids followed by the added ones (helpers.py), a plain head's its rows
-            width = int(head.max_original_id) + 1 + int(head.additional_out_features) if hasattr(head, "max_original_id") else int(head.out_features)
+            width = self._logits_width()
             if con.V != width:
                 raise ValueError(f"the constraint was built for V = {con.V}, the logits have {width} columns")
             con.with_eos(sorted(opt.eos_ids))
@@ -1294,7 +1399,9 @@ class AkiMethods:
             else:
                 tokens, lpb = self._decode_on_host(opt, cache, logits, proc, eos_t)
             if appended is not None:               # the caller's cache: every row ends right before its last returned token
-                self._trim_cache_to_returned(cache, *appended, tokens, eos_t)
+                self._trim_cache_to_returned(cache, *appended, tokens, eos_t, opt.stops)
+            if opt.stops and self.last_stop_hits is None:          # nothing was generated
+                self.last_stop_hits = torch.full((tokens.shape[0],), -1, dtype=torch.int32, device=tokens.device)
         self._post_forward_hook()
         if opt.output_logprobs:                    # never with beams (_parse_generate_kwargs)
             lp, top_ids, top_lp = lpb.cut(tokens.shape[1])

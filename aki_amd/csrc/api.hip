@@ -110,6 +110,12 @@ int token_logprob_launch(const void* logits, int in_f32, int rows, int V, int ld
 int kv_slot_admit_launch(void* const* table, int n_tensors, const int* src_len, int H, int cap_src, int cap_dst, int slot, int row_bytes,
                          int vec_bytes, int host_len, hipStream_t s);
 int slot_tick_launch(unsigned char* done, int* done_at, int* cache_len, const int* start_len, const int* limit, int B, hipStream_t s);
+int stop_check_launch(const int64_t* tokens, int tokens_ld, const int* cache_len, const int* start_len, unsigned char* done, int* done_at,
+                      int* stop_hit, const int* ids, int n_ids, const int* seq_off, int n_seqs, const int* set_first, int n_sets,
+                      const int* row_set, int B, hipStream_t s);
+int slot_tick_stops_launch(unsigned char* done, int* done_at, int* cache_len, const int* start_len, const int* limit, const int64_t* tokens,
+                           int tokens_ld, int* stop_hit, const int* ids, int n_ids, const int* seq_off, int n_seqs, const int* set_first,
+                           int n_sets, const int* row_set, int B, hipStream_t s);
 int sft_collate_launch(const int64_t* ids, const int64_t* labels, const int64_t* mask, const int* offsets, int B, int T_out,
                        int64_t pad_id, int64_t ignore_index, int left, int64_t* out_ids, int64_t* out_labels, int64_t* out_mask,
                        hipStream_t s);
@@ -1225,6 +1231,34 @@ int aki_slot_tick(uint8_t* done, int32_t* done_at, int32_t* cache_len, const int
   AKI_CHECK_ARG(done && done_at && cache_len && start_len && limit && B > 0);
   if (B > AKI_SLOT_MAX_ROWS) return AKI_ERR_UNSUPPORTED;
   return slot_tick_launch(done, done_at, cache_len, start_len, limit, B, (hipStream_t)stream);
+}
+
+// the pool of stop sequences: ids may be null only when it is empty; the device checks every offset against these counts
+static bool stop_pool_ok(const int32_t* ids, int32_t n_ids, const int32_t* seq_off, int32_t n_seqs, const int32_t* set_first, int32_t n_sets,
+                         const int32_t* row_set) {
+  return n_ids >= 0 && n_seqs >= 0 && n_sets >= 0 && (ids || n_ids == 0) && seq_off && set_first && row_set;
+}
+
+int aki_stop_check(const int64_t* tokens, int64_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, uint8_t* done,
+                   int32_t* done_at, int32_t* stop_hit, const int32_t* ids, int32_t n_ids, const int32_t* seq_off, int32_t n_seqs,
+                   const int32_t* set_first, int32_t n_sets, const int32_t* row_set, int32_t B, void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(tokens && cache_len && start_len && done && done_at && stop_hit && B > 0 && tokens_ld > 0 && tokens_ld < (1ll << 31));
+  AKI_CHECK_ARG(stop_pool_ok(ids, n_ids, seq_off, n_seqs, set_first, n_sets, row_set));
+  return stop_check_launch(tokens, (int)tokens_ld, cache_len, start_len, done, done_at, stop_hit, ids, n_ids, seq_off, n_seqs, set_first,
+                           n_sets, row_set, B, (hipStream_t)stream);
+}
+
+int aki_slot_tick_stops(uint8_t* done, int32_t* done_at, int32_t* cache_len, const int32_t* start_len, const int32_t* limit,
+                        const int64_t* tokens, int64_t tokens_ld, int32_t* stop_hit, const int32_t* ids, int32_t n_ids,
+                        const int32_t* seq_off, int32_t n_seqs, const int32_t* set_first, int32_t n_sets, const int32_t* row_set, int32_t B,
+                        void* stream) {
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(done && done_at && cache_len && start_len && limit && tokens && stop_hit && B > 0 && tokens_ld > 0 && tokens_ld < (1ll << 31));
+  AKI_CHECK_ARG(stop_pool_ok(ids, n_ids, seq_off, n_seqs, set_first, n_sets, row_set));
+  if (B > AKI_SLOT_MAX_ROWS) return AKI_ERR_UNSUPPORTED;
+  return slot_tick_stops_launch(done, done_at, cache_len, start_len, limit, tokens, (int)tokens_ld, stop_hit, ids, n_ids, seq_off, n_seqs,
+                                set_first, n_sets, row_set, B, (hipStream_t)stream);
 }
 
 size_t aki_mma_mask_to_table_workspace_bytes(int32_t B, int32_t L) {

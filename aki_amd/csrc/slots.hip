@@ -1,6 +1,7 @@
 // slots.hip - in-flight batching for generate (include/aki_mi355x.h: aki_kv_slot_admit, aki_slot_tick): a prefilled request is copied into
 // one row ("slot") of a larger KV cache, and a per-row token budget retires a row on the device.  aki_amd/slots.py and
-// AkiMethods.generate_many (aki_amd/aki.py) are the host side.
+// AkiMethods.generate_many (aki_amd/aki.py) are the host side.  Stop sequences (aki_stop_check, aki_slot_tick_stops; aki_amd/stops.py): a
+// row also ends when its generated tokens end with one of its set's token sequences.
 #include "aki_device.h"
 
 namespace aki {
@@ -62,6 +63,95 @@ __global__ __launch_bounds__(64) void slot_tick_kernel(unsigned char* done, int*
   if (d && at >= 0) cache_len[b] = start + at;
 }
 
+// ---- stop sequences: a row ends when its generated tokens end with one of its set's sequences ---------------------------------------------
+// The pool: ids holds every sequence one behind the other, sequence s is ids[seq_off[s] .. seq_off[s + 1]), set k is the sequences
+// set_first[k] .. set_first[k + 1], row b is checked against set row_set[b].  One wave per row, lane l owns sequence l of the row's set
+// (a set holds at most 64).  Every index read from the pool is range-checked against the pool's counts before it is used, so a bad pool
+// or a row_set outside it reads nothing: such a row has no stops.
+struct StopPool {
+  const int* ids;
+  const int* seq_off;
+  const int* set_first;
+  const int* row_set;
+  int n_ids, n_seqs, n_sets;
+};
+
+// The index within row b's set of the lowest-numbered sequence that ends at row[t], or -1.  The whole wave calls it with the same b and t
+// (0 <= t < the row's length); the result is the same in every lane.  A lane walks backwards from row[t] and leaves at the first mismatch;
+// n <= t + 1 keeps the walk inside the row: only generated tokens count.
+__device__ __forceinline__ int stop_match(const long long* row, int t, const StopPool& p, int b, int lane) {
+  bool hit = false;
+  const int set = p.row_set[b];
+  if (set >= 0 && set < p.n_sets) {
+    const int first = p.set_first[set], last = p.set_first[set + 1];
+    if (first >= 0 && first <= last && last <= p.n_seqs && lane < last - first) {
+      const int s = first + lane;
+      const int o0 = p.seq_off[s], o1 = p.seq_off[s + 1];
+      const int n = o1 - o0;
+      if (o0 >= 0 && o1 <= p.n_ids && n >= 1 && n <= AKI_STOP_MAX_LEN && n <= t + 1) {
+        hit = true;
+        for (int i = 0; i < n; ++i) {
+          if (row[t - i] != (long long)p.ids[o1 - 1 - i]) {
+            hit = false;
+            break;
+          }
+        }
+      }
+    }
+  }
+  const unsigned long long lanes = __ballot(hit);
+  return lanes ? __ffsll(lanes) - 1 : -1;
+}
+
+// One wave per row, right behind the pick (and the log-probability): t = cache_len - start_len is the index the pick just wrote.  A done row
+// and a row whose t is outside the token buffer are skipped.  Lane 0 alone writes.
+__global__ __launch_bounds__(64) void stop_check_kernel(const long long* tokens, int tokens_ld, const int* cache_len, const int* start_len,
+                                                        unsigned char* done, int* done_at, int* stop_hit, const StopPool p, int B) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (b >= B || done[b] != 0) return;
+  const int t = cache_len[b] - start_len[b];
+  if (t < 0 || t >= tokens_ld) return;
+  const int hit = stop_match(tokens + (size_t)b * tokens_ld, t, p, b, lane);
+  if (hit >= 0 && lane == 0) {
+    done[b] = 1;
+    done_at[b] = t;
+    stop_hit[b] = hit;
+  }
+}
+
+// stop_check_kernel followed by slot_tick_kernel for row b = blockIdx.x, in one launch: the wave checks the row's stops, lane 0 then runs the
+// tick on the state it holds in registers (a stop and the budget at one token is a stop).
+__global__ __launch_bounds__(64) void slot_tick_stops_kernel(unsigned char* done, int* done_at, int* cache_len, const int* start_len,
+                                                             const int* limit, const long long* tokens, int tokens_ld, int* stop_hit,
+                                                             const StopPool p, int B) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (b >= B) return;
+  const int start = start_len[b], len = cache_len[b];
+  bool d = done[b] != 0;
+  int at = done_at[b];
+  const int t = len - start;
+  int hit = -1;
+  if (!d && t >= 0 && t < tokens_ld) hit = stop_match(tokens + (size_t)b * tokens_ld, t, p, b, lane);
+  if (lane != 0) return;
+  if (hit >= 0) {
+    at = t;
+    done[b] = 1;
+    done_at[b] = at;
+    stop_hit[b] = hit;
+    d = true;
+  }
+  if (!d) {
+    const int generated = t + 1;
+    if (generated >= limit[b]) {
+      at = generated - 1;
+      done[b] = 1;
+      done_at[b] = at;
+      d = true;
+    }
+  }
+  if (d && at >= 0) cache_len[b] = start + at;
+}
+
 // ---- launches ----------------------------------------------------------------------------------------------------------------------------
 int kv_slot_admit_launch(void* const* table, int n_tensors, const int* src_len, int H, int cap_src, int cap_dst, int slot, int row_bytes,
                          int vec_bytes, int host_len, hipStream_t s) {
@@ -80,6 +170,26 @@ int kv_slot_admit_launch(void* const* table, int n_tensors, const int* src_len, 
 
 int slot_tick_launch(unsigned char* done, int* done_at, int* cache_len, const int* start_len, const int* limit, int B, hipStream_t s) {
   hipLaunchKernelGGL(slot_tick_kernel, dim3(1), dim3(64), 0, s, done, done_at, cache_len, start_len, limit, B);
+  AKI_LAUNCH_CHECK();
+  return AKI_OK;
+}
+
+int stop_check_launch(const int64_t* tokens, int tokens_ld, const int* cache_len, const int* start_len, unsigned char* done, int* done_at,
+                      int* stop_hit, const int* ids, int n_ids, const int* seq_off, int n_seqs, const int* set_first, int n_sets,
+                      const int* row_set, int B, hipStream_t s) {
+  const StopPool p{ids, seq_off, set_first, row_set, n_ids, n_seqs, n_sets};
+  hipLaunchKernelGGL(stop_check_kernel, dim3(B), dim3(64), 0, s, (const long long*)tokens, tokens_ld, cache_len, start_len, done, done_at,
+                     stop_hit, p, B);
+  AKI_LAUNCH_CHECK();
+  return AKI_OK;
+}
+
+int slot_tick_stops_launch(unsigned char* done, int* done_at, int* cache_len, const int* start_len, const int* limit, const int64_t* tokens,
+                           int tokens_ld, int* stop_hit, const int* ids, int n_ids, const int* seq_off, int n_seqs, const int* set_first,
+                           int n_sets, const int* row_set, int B, hipStream_t s) {
+  const StopPool p{ids, seq_off, set_first, row_set, n_ids, n_seqs, n_sets};
+  hipLaunchKernelGGL(slot_tick_stops_kernel, dim3(B), dim3(64), 0, s, done, done_at, cache_len, start_len, limit, (const long long*)tokens,
+                     tokens_ld, stop_hit, p, B);
   AKI_LAUNCH_CHECK();
   return AKI_OK;
 }

@@ -1526,11 +1526,91 @@ def kv_slot_admit(src_cache, dst_cache, slot: int) -> None:
         launch(ss, ds)
 
 
-def slot_tick(done: torch.Tensor, done_at: torch.Tensor, cache_len: torch.Tensor, start_len: torch.Tensor, limit: torch.Tensor) -> None:
+STOP_MAX_SEQS, STOP_MAX_LEN = L.AKI_STOP_MAX_SEQS, L.AKI_STOP_MAX_LEN
+
+
+class StopSets:
+    """One stop set per ROW (aki_amd/stops.py states the rule): what ops.stop_check and ops.slot_tick(stops=...) take.  The distinct sets of
+    a call are a small pool, deduplicated by value and uploaded once (stops.StopPool; set 0 is the empty set):
+      ids        int32 [n_ids]: every sequence one behind the other
+      seq_off    int32 [n_seqs + 1], set_first int32 [n_sets + 1]: the pool's offsets
+      row_set    int32 [rows]: the set each row is checked against; a value outside the pool is the empty set
+      stop_hit   int32 [rows]: the index within its set of the sequence that ended the row, -1 for a row that ended otherwise
+    row_set and stop_hit are allocated once - a captured step holds their addresses - and `admit` rewrites a row's entries in place."""
+
+    def __init__(self, device, keys, rows: int, _view=None):
+        if _view is not None:
+            self.__dict__.update(_view)
+            return
+        from .stops import StopPool
+        pool = StopPool(keys)
+        dev = torch.device(device)
+        self.keys, self.index = pool.keys, pool.index
+        self.n_ids, self.n_seqs, self.n_sets = len(pool.ids), pool.n_seqs, pool.n_sets
+        self.ids = torch.tensor(pool.ids, dtype=torch.int32, device=dev)
+        self.seq_off = torch.tensor(pool.seq_off, dtype=torch.int32, device=dev)
+        self.set_first = torch.tensor(pool.set_first, dtype=torch.int32, device=dev)
+        self.row_set = torch.zeros(int(rows), dtype=torch.int32, device=dev)
+        self.stop_hit = torch.full((int(rows),), -1, dtype=torch.int32, device=dev)
+
+    def admit(self, slot: int, key) -> None:
+        """A new request in `slot`: its set, by value, and its hit back to -1.  Tensor fills - nothing is copied from the host or
+        reallocated."""
+        self.row_set[int(slot)] = self.index[key]
+        self.stop_hit[int(slot)] = -1
+
+    def row(self, slot: int) -> "StopSets":
+        """One-row views of row_set and stop_hit over the shared pool: what a B = 1 check on the slot's row views takes."""
+        s = int(slot)
+        return StopSets(None, None, 1, _view=dict(self.__dict__, row_set=self.row_set[s:s + 1], stop_hit=self.stop_hit[s:s + 1]))
+
+    def _args(self, name: str, B: int, device):
+        """(stop_hit | ids, n_ids, seq_off, n_seqs, set_first, n_sets, row_set) of the C entry points, checked."""
+        for nm, x, n in (("ids", self.ids, self.n_ids), ("seq_off", self.seq_off, self.n_seqs + 1), ("set_first", self.set_first, self.n_sets + 1),
+                         ("row_set", self.row_set, B), ("stop_hit", self.stop_hit, B)):
+            if not torch.is_tensor(x) or x.dtype != torch.int32 or tuple(x.shape) != (n,) or not x.is_contiguous() or not x.is_cuda \
+                    or x.device != device:
+                raise AkiError(f"{name}: stops.{nm} is a contiguous int32 GPU tensor [{n}] on {device}")
+        return _ptr(self.stop_hit), (_ptr(self.ids) if self.n_ids else None, self.n_ids, _ptr(self.seq_off), self.n_seqs, _ptr(self.set_first),
+                                     self.n_sets, _ptr(self.row_set))
+
+
+def _stop_tokens(name: str, tokens, B: int, device):
+    if not torch.is_tensor(tokens) or tokens.dtype != torch.int64 or tokens.dim() != 2 or tokens.shape[0] != B or tokens.shape[1] < 1 \
+            or not tokens.is_contiguous() or not tokens.is_cuda or tokens.device != device:
+        raise AkiError(f"{name}: tokens is a contiguous int64 GPU tensor [{B}, >= 1] on the rows' device")
+
+
+def stop_check(tokens: torch.Tensor, cache_len: torch.Tensor, start_len: torch.Tensor, done: torch.Tensor, done_at: torch.Tensor,
+               stops: StopSets) -> None:
+    """The rows' stop sequences, one launch right behind the pick - and behind ops.token_logprob where there is one (aki_stop_check; one wave
+    per row; capturable: no host value is read).  t = cache_len[b] - start_len[b] is the index the pick just wrote.  A live row whose
+    generated tokens tokens[b, :t + 1] end with a sequence of its set stops.row_set[b] gets done[b] = 1, done_at[b] = t and
+    stops.stop_hit[b] = the lowest-numbered such sequence; a done row, a row with t outside the buffer and a row without a match are not
+    touched.  tokens int64 [B, *], done uint8 [B], the others int32 [B]."""
+    if not isinstance(stops, StopSets):
+        raise AkiError("stop_check: stops is an ops.StopSets")
+    B = done.numel() if torch.is_tensor(done) else 0
+    for t_, dt in ((done, torch.uint8), (done_at, torch.int32), (cache_len, torch.int32), (start_len, torch.int32)):
+        if not torch.is_tensor(t_) or t_.dtype != dt or t_.dim() != 1 or t_.numel() != B or not t_.is_contiguous() or not t_.is_cuda \
+                or t_.device != done.device:
+            raise AkiError("stop_check: contiguous GPU tensors [B] are expected - done uint8, done_at / cache_len / start_len int32")
+    if B < 1:
+        raise AkiError("stop_check: at least one row is expected")
+    _stop_tokens("stop_check", tokens, B, done.device)
+    hit, pool = stops._args("stop_check", B, done.device)
+    L.check(L.load().aki_stop_check(_ptr(tokens), tokens.shape[1], _ptr(cache_len), _ptr(start_len), _ptr(done), _ptr(done_at), hit, *pool, B,
+                                    _stream()), "aki_stop_check")
+
+
+def slot_tick(done: torch.Tensor, done_at: torch.Tensor, cache_len: torch.Tensor, start_len: torch.Tensor, limit: torch.Tensor,
+              stops: Optional[StopSets] = None, tokens: Optional[torch.Tensor] = None) -> None:
     """The per-row token budget, one launch right behind the pick (aki_slot_tick; capturable: no host value is read).  With generated =
     cache_len[b] - start_len[b] + 1 tokens picked by row b: a live row with generated >= limit[b] gets done[b] = 1 and done_at[b] =
     generated - 1; a done row (done_at >= 0) is parked at cache_len[b] = start_len[b] + done_at[b], so the pad-token steps it is still fed
-    overwrite one dead cache row; a live row under its budget is not touched.  done uint8 [B], the others int32 [B], B <= SLOT_MAX_ROWS."""
+    overwrite one dead cache row; a live row under its budget is not touched.  done uint8 [B], the others int32 [B], B <= SLOT_MAX_ROWS.
+    stops (an ops.StopSets, with the rows' tokens int64 [B, *]): ops.stop_check and this tick in ONE launch (aki_slot_tick_stops), with
+    the effect of the two calls one behind the other; without it exactly the call above."""
     B = done.numel()
     for t_, dt in ((done, torch.uint8), (done_at, torch.int32), (cache_len, torch.int32), (start_len, torch.int32), (limit, torch.int32)):
         if t_.dtype != dt or t_.dim() != 1 or t_.numel() != B or not t_.is_contiguous() or not t_.is_cuda or t_.device != done.device:
@@ -1538,7 +1618,17 @@ def slot_tick(done: torch.Tensor, done_at: torch.Tensor, cache_len: torch.Tensor
                            f"got {t_.dtype} {tuple(t_.shape)}")
     if not 1 <= B <= SLOT_MAX_ROWS:
         raise AkiError(f"slot_tick: 1 <= B <= {SLOT_MAX_ROWS} rows are expected, got {B}")
-    L.check(L.load().aki_slot_tick(_ptr(done), _ptr(done_at), _ptr(cache_len), _ptr(start_len), _ptr(limit), B, _stream()), "aki_slot_tick")
+    if stops is None:
+        if tokens is not None:
+            raise AkiError("slot_tick: tokens goes with stops")
+        L.check(L.load().aki_slot_tick(_ptr(done), _ptr(done_at), _ptr(cache_len), _ptr(start_len), _ptr(limit), B, _stream()), "aki_slot_tick")
+        return
+    if not isinstance(stops, StopSets):
+        raise AkiError("slot_tick: stops is an ops.StopSets")
+    _stop_tokens("slot_tick", tokens, B, done.device)
+    hit, pool = stops._args("slot_tick", B, done.device)
+    L.check(L.load().aki_slot_tick_stops(_ptr(done), _ptr(done_at), _ptr(cache_len), _ptr(start_len), _ptr(limit), _ptr(tokens), tokens.shape[1],
+                                         hit, *pool, B, _stream()), "aki_slot_tick_stops")
 
 
 SKINNY_NORM_FUSED = True       # tools (decode_bench.py --norm-launch): False = the RMSNorm of 2-8 row decode GEMMs as a launch of its own

@@ -227,7 +227,9 @@ class DecodeGraph:
         A "processor_sets" key (an ops.ProcessorSets, in the place of "processors") is handed on likewise: one set of logits-processor
         settings per row, the row's set index a device int rewritten in place at admit.
         With a "logprob" key (the in-loop arguments of ops.token_logprob) that launch is captured right behind the pick.
-        With a "tick" key (ops.slot_tick's done / done_at / start_len / limit) the rows' token budgets are ticked behind the pick too."""
+        With a "tick" key (ops.slot_tick's done / done_at / start_len / limit) the rows' token budgets are ticked behind the pick too.
+        With a "stops" key (an ops.StopSets) the rows' stop sequences are checked behind the pick and the log-probability launch:
+        ops.stop_check on its own, or - with a "tick" key - inside the tick's launch (ops.slot_tick(stops=...)): no launch more."""
         self.lm, self.cache = lm, cache
         B = cache.cache_len.shape[0]
         self.ids = torch.zeros((B,), dtype=torch.long, device=cache.cache_len.device)
@@ -254,7 +256,7 @@ class DecodeGraph:
             else:                                   # the pick advances cache_len itself: one launch less per token
                 self.logits = lm.decode_step(input_ids=self.ids, past_key_values=cache, advance=False)
                 args = dict(self.greedy)
-                logprob, tick = args.pop("logprob", None), args.pop("tick", None)
+                logprob, tick, stops = args.pop("logprob", None), args.pop("tick", None), args.pop("stops", None)
                 if "row_seed" in args:
                     args["seed"] = args.pop("row_seed")
                     pick = ops.sample_pick_rows
@@ -263,8 +265,13 @@ class DecodeGraph:
                 pick(self.logits, self.ids, cache_len=cache.cache_len, advance=True, **args)
                 if logprob is not None:             # right behind the pick: it scores the token at the index the pick just wrote
                     ops.token_logprob(self.logits, **logprob)
+                if stops is not None and tick is None:
+                    ops.stop_check(args["tokens"], cache.cache_len, args["start_len"], args["done"], args["done_at"], stops)
                 if tick is not None:                # the rows' token budgets: retires and parks rows on the device (generate_many)
-                    ops.slot_tick(cache_len=cache.cache_len, **tick)
+                    if stops is not None:
+                        ops.slot_tick(cache_len=cache.cache_len, **tick, stops=stops, tokens=args["tokens"])
+                    else:
+                        ops.slot_tick(cache_len=cache.cache_len, **tick)
         cache.host_len = saved_host
 
     def step_greedy(self) -> torch.Tensor:

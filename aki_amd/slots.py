@@ -88,7 +88,9 @@ class RequestParams:
     serve several requests: its table is stored once); it composes with sampling and log-probabilities.
     The logits processors (PROCESSOR_FIELDS: repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length, min_new_tokens,
     suppress_tokens, begin_suppress_tokens): None = the request takes the call's value (params=, else the call-wide keyword); any other
-    value, the neutral ones 1.0 / 0 / () included, belongs to the request alone (resolve_processors)."""
+    value, the neutral ones 1.0 / 0 / () included, belongs to the request alone (resolve_processors).
+    stop_sequences: None = the request takes the call's stop set (params=, else the call-wide stop_sequences= keyword); a list of token-id
+    sequences is the request's own set (aki_amd/stops.py states the rule), () means this request has none."""
     do_sample: bool = False
     temperature: float = 1.0
     top_k: int = 0
@@ -104,6 +106,7 @@ class RequestParams:
     min_new_tokens: Optional[int] = None
     suppress_tokens: Optional[Sequence[int]] = None
     begin_suppress_tokens: Optional[Sequence[int]] = None
+    stop_sequences: Optional[Sequence[Sequence[int]]] = None
 
     def check(self, index, max_top: int) -> "RequestParams":
         """ValueError naming request `index` (a number, or a word such as "default") for a value the device sampler or ops.token_logprob
@@ -131,6 +134,9 @@ class RequestParams:
         for name in PROCESSOR_FIELDS:                   # the ids' upper bound needs the logits' width: processor_set_key
             if getattr(self, name) is not None:
                 check_processor_value(who, name, getattr(self, name))
+        if self.stop_sequences is not None:             # likewise: stops.check_stop_sequences again with the width
+            from .stops import check_stop_sequences
+            check_stop_sequences(who, self.stop_sequences)
         return self
 
 

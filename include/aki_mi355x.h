@@ -1096,6 +1096,36 @@ int aki_kv_slot_admit(void* const* table, int32_t n_tensors, const int32_t* src_
  * row under its budget is not touched.  done uint8, the others int32, all [B]. */
 int aki_slot_tick(uint8_t* done, int32_t* done_at, int32_t* cache_len, const int32_t* start_len, const int32_t* limit, int32_t B, void* stream);
 
+/* ---- stop sequences (slots.hip): a row ends when its generated tokens end with one of the token-id sequences of its stop set.
+ * Purely additive: AKI_ABI_VERSION was not bumped (it stays 17). */
+#define AKI_STOP_MAX_SEQS 64         /* sequences of one stop set: one lane of a wave each */
+#define AKI_STOP_MAX_LEN 32          /* ids of one stop sequence */
+
+/* The pool (DEVICE memory, all int32): ids[n_ids] holds every sequence one behind the other; sequence s is ids[seq_off[s] .. seq_off[s + 1]),
+ * seq_off[n_seqs + 1]; set k is the sequences set_first[k] .. set_first[k + 1], set_first[n_sets + 1], at most AKI_STOP_MAX_SEQS of 1 to
+ * AKI_STOP_MAX_LEN ids each, order significant; row b is checked against set row_set[b].  The device range-checks every index it reads
+ * against the counts: a row_set outside [0, n_sets) and a set or sequence whose offsets leave the pool are an empty set, never a read
+ * outside the arrays.
+ *
+ * aki_stop_check - launched right behind aki_greedy_pick / the sampling picks (and behind aki_token_logprob where there is one), inside the
+ * captured step.  One wave per row.  t = cache_len[b] - start_len[b] is the index the pick just wrote (with advance 0 or 1).  A done row
+ * and a row with t outside [0, tokens_ld) are skipped.  A live row whose tokens[b, t - n + 1 .. t] equal a sequence of n <= t + 1 ids of
+ * its set gets done[b] = 1, done_at[b] = t and stop_hit[b] = the index within the set of the LOWEST-numbered sequence that matches at t;
+ * nothing else is written (stop_hit of a row that does not match keeps its value: the caller presets -1).  Only the t + 1 generated
+ * tokens of the row are read.  tokens int64 [B, tokens_ld], done uint8 [B], the others int32 [B].  No host value is read.
+ * AKI_ERR_INVALID_ARG: a null pointer (ids may be null when n_ids == 0), B < 1, tokens_ld outside [1, 2^31), a count below zero. */
+int aki_stop_check(const int64_t* tokens, int64_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, uint8_t* done,
+                   int32_t* done_at, int32_t* stop_hit, const int32_t* ids, int32_t n_ids, const int32_t* seq_off, int32_t n_seqs,
+                   const int32_t* set_first, int32_t n_sets, const int32_t* row_set, int32_t B, void* stream);
+
+/* aki_slot_tick_stops - aki_stop_check followed by aki_slot_tick in ONE launch, for B <= AKI_SLOT_MAX_ROWS rows: on every input its effect on
+ * done, done_at, cache_len and stop_hit is that of the two calls one behind the other (a stop and the budget at one token is a stop).
+ * AKI_ERR_INVALID_ARG as for both; AKI_ERR_UNSUPPORTED: B above AKI_SLOT_MAX_ROWS. */
+int aki_slot_tick_stops(uint8_t* done, int32_t* done_at, int32_t* cache_len, const int32_t* start_len, const int32_t* limit,
+                        const int64_t* tokens, int64_t tokens_ld, int32_t* stop_hit, const int32_t* ids, int32_t n_ids,
+                        const int32_t* seq_off, int32_t n_seqs, const int32_t* set_first, int32_t n_sets, const int32_t* row_set, int32_t B,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

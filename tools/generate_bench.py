@@ -34,10 +34,17 @@ settings cycling over four distinct sets (the neutral one, --repetition-penalty 
 the call-wide processors leg (those two keywords for every row) and the plain greedy queue, alternating in one process at 8 and 16 slots.
 Writes profiles/many_processors_bench.json: tokens/s and ms per decode step of the three legs, and the per-request leg's difference per
 step from the call-wide leg next to that leg's own spread over the rounds.
+--many --stop: the queue with per-request stop sequences (many_stop_bench below): the same 64 requests, each with its OWN set of 8 token
+sequences of 1 to 4 ids built from ids the greedy queue never emits, so nothing ever matches and the schedules are identical; against the
+plain greedy queue, alternating in one process at 8 and 16 slots for at least 3 rounds.  Writes profiles/many_stop_bench.json: tokens/s
+and ms per decode step of both legs, and the stop leg's difference per step from the plain leg of the same round next to the plain leg's
+own spread between the rounds.
+--stop (without --many): every round also runs with stop_sequences= such a set of 8 (one ops.stop_check launch behind each pick),
+alternating with the plain leg; reports the per-token cost it adds and merges the result into profiles/stop_bench.json under "batch<B>".
     python tools/generate_bench.py [--many] [--many --sample --temperature 0.8 --top-k 50 --top-p 0.9 --logprobs 8] [--many --constraint]
-                                   [--many --request-processors]
+                                   [--many --request-processors] [--many --stop]
     python tools/generate_bench.py [--new 256] [--fp8] [--txt 64] [--repetition-penalty 1.2] [--no-repeat-ngram 3]
-                                   [--sample --temperature 0.8 --top-k 50 --top-p 0.9] [--batch 8] [--logprobs 8 --rounds 4] [--constraint]"""
+                                   [--sample --temperature 0.8 --top-k 50 --top-p 0.9] [--batch 8] [--logprobs 8 --rounds 4] [--constraint] [--stop]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -282,6 +289,99 @@ def many_constraint_bench(a, model, dev):
     print(json.dumps({k: v for k, v in res.items() if k != "budgets"}))
 
 
+def never_matching_stops(emitted, V, n_sets):
+    """n_sets stop sets of 8 sequences of 1 to 4 ids each (lengths 1, 2, 3, 4, 1, 2, 3, 4), built from the lowest ids >= 3 that are not in
+    `emitted`: a run whose tokens all lie in `emitted` never matches one.  Set r starts 20 ids behind set r - 1: the sets are distinct."""
+    unused = [i for i in range(3, V) if i not in emitted][:20 * n_sets + 64]
+    assert len(unused) >= 20 * n_sets + 20, "too few ids the run never emits"
+    sets = []
+    for r in range(n_sets):
+        ids, seqs = iter(unused[20 * r:20 * r + 20]), []
+        for n in (1, 2, 3, 4, 1, 2, 3, 4):
+            seqs.append([next(ids) for _ in range(n)])
+        sets.append(seqs)
+    return sets
+
+
+def many_stop_bench(a, model, dev):
+    """--many --stop: generate_many with a stop set per request that never matches against the plain greedy queue, many_bench's requests.
+    Writes profiles/many_stop_bench.json."""
+    import aki_amd
+    import bench
+    n_req = a.many_requests
+    g = torch.Generator(device="cpu").manual_seed(4242)
+    budgets = torch.randint(16, 257, (n_req,), generator=g).tolist()
+    reqs = []
+    for i in range(n_req):
+        vx, ids, _ = bench.synth_batch(1, dev, torch.bfloat16, model.media_token_id, seed=1000 + i)
+        reqs.append((vx, ids, budgets[i]))
+    legs = {"greedy": [aki_amd.RequestParams()] * n_req}
+    ref = {}
+
+    def leg(name, slots):
+        batch = [(vx, ids, b, rp) for (vx, ids, b), rp in zip(reqs, legs[name])]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        outs = model.generate_many(batch, slots=slots, eos_token_id=[])
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        if name == "stops":                                           # nothing matched: the same tokens, the same schedule
+            for r, (o, want, hit) in enumerate(zip(outs, ref[slots], model.last_stop_hits)):
+                if hit != -1 or not torch.equal(o, want):
+                    n = o.numel()
+                    raise AssertionError(f"request {r}: {n} of {budgets[r]} tokens, stop_hit {hit}, its set {legs[name][r].stop_sequences}, "
+                                         f"last tokens {o[-6:].tolist()}; equal to the plain queue's first {n}: {torch.equal(o, want[:n])}")
+        else:
+            assert model.last_stop_hits is None
+            ref[slots] = outs
+        assert [o.numel() for o in outs] == budgets
+        return wall, dict(model.last_many_stats)
+
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    res = {"requests": n_req, "prompt_tokens_lm_stream": bench.N_TXT - 1 + bench.NV, "budgets": budgets, "budget_seed": 4242,
+           "stops": "one set per request, 8 sequences of 1, 2, 3, 4, 1, 2, 3, 4 ids, from ids the greedy queue never emits: a pool of 64 "
+                    "sets that never match",
+           "method": "the two legs alternate in one process, wall clock around each generate_many call with a device synchronisation on "
+                     "both sides; tokens/s = returned tokens / wall time, prefills and the pool's one upload included; ms_per_step = wall "
+                     "time / decode steps replayed - both legs admit the same 64 prompts and replay the same number of steps, so the "
+                     "difference from the greedy leg of the same round is what the stops cost per step (the check inside the tick's "
+                     "launch, plus the admit's one check launch and the pool's upload spread over the steps); it is to be read next to "
+                     "greedy_ms_per_step_spread, the plain leg's own max - min between the rounds", "slots": {}}
+    emitted = set()
+    for slots in (8, 16):                                             # warm-up: allocator, folds, capture path - and the ids the queue emits
+        for _ in range(2):                                            # (another slot count is another batch size: other roundings, other tokens)
+            leg("greedy", slots)
+            emitted |= set(torch.cat(ref[slots]).tolist())
+    legs["stops"] = [aki_amd.RequestParams(stop_sequences=s) for s in never_matching_stops(emitted, model._logits_width(), n_req)]
+    for slots in (8, 16):
+        leg("greedy", slots), leg("stops", slots)
+        rounds = []
+        for _ in range(max(3, a.rounds)):
+            r = {}
+            for name in legs:
+                wall, stats = leg(name, slots)
+                r[name] = {"tokens_per_s": round(sum(budgets) / wall, 1), "wall_s": round(wall, 3), "steps": stats["steps"],
+                           "ms_per_step": round(wall * 1e3 / stats["steps"], 4)}
+            assert r["stops"]["steps"] == r["greedy"]["steps"]
+            rounds.append(r)
+        summary = {}
+        for name in legs:
+            summary[name] = {"tokens_per_s_median": med([r[name]["tokens_per_s"] for r in rounds]),
+                             "tokens_per_s_min_max": [min(r[name]["tokens_per_s"] for r in rounds), max(r[name]["tokens_per_s"] for r in rounds)],
+                             "ms_per_step_median": med([r[name]["ms_per_step"] for r in rounds])}
+        ex = [(r["stops"]["ms_per_step"] - r["greedy"]["ms_per_step"]) * 1e3 for r in rounds]
+        plain = [r["greedy"]["ms_per_step"] * 1e3 for r in rounds]
+        summary["stops"]["added_us_per_step_median"] = round(med(ex), 1)
+        summary["stops"]["added_us_per_step_min_max"] = [round(min(ex), 1), round(max(ex), 1)]
+        summary["greedy"]["us_per_step_spread_between_rounds"] = round(max(plain) - min(plain), 1)
+        res["slots"][str(slots)] = {"rounds": rounds, "summary": summary}
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "many_stop_bench.json")
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps({k: v for k, v in res.items() if k != "budgets"}))
+
+
 def many_processors_bench(a, model, dev):
     """--many --request-processors: generate_many with per-request logits processors (the settings cycling over four distinct sets) against
     the call-wide processors leg and the plain greedy queue, many_bench's requests.  Writes profiles/many_processors_bench.json."""
@@ -382,6 +482,9 @@ def main():
                     "budgets 16..256 at 8 and 16 slots -> profiles/many_bench.json (the other legs are skipped); with --sample: the greedy "
                     "queue against the queue with per-request sampling (and --logprobs K) -> profiles/many_sample_bench.json; with "
                     "--constraint: against the queue with one 16-state constraint per request -> profiles/many_constraint_bench.json")
+    ap.add_argument("--stop", action="store_true", help="one more leg per round: greedy with a stop set of 8 sequences that never match -> "
+                    "profiles/stop_bench.json; with --many: the greedy queue against the queue with one such set per request -> "
+                    "profiles/many_stop_bench.json")
     ap.add_argument("--many-requests", type=int, default=64)
     ap.add_argument("--request-processors", action="store_true", help="with --many: per-request logits processors against the call-wide "
                     "processors leg and the greedy queue -> profiles/many_processors_bench.json")
@@ -407,6 +510,8 @@ def main():
             return many_processors_bench(a, model, dev)
         if a.constraint:
             return many_constraint_bench(a, model, dev)
+        if a.stop:
+            return many_stop_bench(a, model, dev)
         return many_sample_bench(a, model, dev) if a.sample else many_bench(a, model, dev)
     vx, ids, am =bench.synth_batch(1, dev, torch.bfloat16, model.media_token_id, seed=1000)
     if a.batch > 1:
@@ -444,6 +549,11 @@ def main():
         cyc = TokenConstraint.from_table(nxt, np.ones(16, dtype=bool))
         con_kw = dict(proc_kw, constraint=cyc if a.batch == 1 else [cyc] * a.batch)
         run(16, **con_kw)
+    stop_kw = None
+    if a.stop:                                # ids the plain run never emits: nothing matches, all a.new tokens are returned
+        emitted = set(run(a.new)[1].flatten().tolist())
+        stop_kw = dict(stop_sequences=never_matching_stops(emitted, model._logits_width(), 1)[0])
+        run(16, **stop_kw)
     res = {"prompt_tokens_lm_stream": bench.N_TXT - 1 + bench.NV, "new_tokens": a.new, "fp8": bool(a.fp8), "mxfp4": bool(a.mxfp4), "w4_chain": bool(a.w4_chain), "rounds": []}
     if proc_kw:
         res["processors"] = proc_kw
@@ -472,6 +582,15 @@ def main():
             r = res["rounds"][-1]
             r["logprobs_ms_per_new_token_after_the_first"] = round(per_l, 4)
             r["logprobs_added_us_per_token"] = round((per_l - r["ms_per_new_token_after_the_first"]) * 1e3, 2)
+        if stop_kw:
+            t1s, _ = run(1, **stop_kw)
+            tns, toks_s = run(a.new, **stop_kw)
+            assert torch.equal(toks_s, ref), "generate with stops that never match returns other tokens than without"
+            assert model.last_stop_hits.tolist() == [-1] * a.batch
+            per_s = (tns - t1s) * 1e3 / (a.new - 1)
+            r = res["rounds"][-1]
+            r["stops_ms_per_new_token_after_the_first"] = round(per_s, 4)
+            r["stops_added_us_per_token"] = round((per_s - r["ms_per_new_token_after_the_first"]) * 1e3, 2)
         if proc_kw:
             t1p, _ = run(1, **proc_kw)
             tnp, toks_p = run(a.new, **proc_kw)
@@ -532,6 +651,19 @@ def main():
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "logprob_bench.json")
         book = json.load(open(path)) if os.path.exists(path) else {}
         book[f"batch{a.batch}_k{a.logprobs}"] = res
+        with open(path, "w") as f:
+            json.dump(book, f, indent=1, sort_keys=True)
+            f.write("\n")
+    if stop_kw:
+        med = lambda k: sorted(r[k] for r in res["rounds"])[len(res["rounds"]) // 2]
+        spread = lambda k: [min(r[k] for r in res["rounds"]), max(r[k] for r in res["rounds"])]
+        res["stops"] = {"sequences": 8, "added_us_per_token_median": med("stops_added_us_per_token"),
+                        "added_us_per_token_min_max": spread("stops_added_us_per_token"),
+                        "plain_ms_per_token_median": med("ms_per_new_token_after_the_first"),
+                        "plain_ms_per_token_min_max": spread("ms_per_new_token_after_the_first")}
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "stop_bench.json")
+        book = json.load(open(path)) if os.path.exists(path) else {}
+        book[f"batch{a.batch}"] = res
         with open(path, "w") as f:
             json.dump(book, f, indent=1, sort_keys=True)
             f.write("\n")

@@ -21,6 +21,7 @@ except Exception:  # pragma: no cover - transformers is present in this image
 from . import ops
 from .helpers import PerceiverResampler
 from .phi3 import AkiKVCache, DecodeGraph
+from .pick_stage import PickStage
 from .slots import RequestParams, SlotScheduler, banning_keywords, processor_set_key, request_seed, resolve_processors, slot_capacity
 from .stops import check_stop_sequences, first_finish, resolve_stop_sequences
 from .vlm import VLMWithLanguageStream
@@ -239,6 +240,60 @@ def _parse_generate_kwargs(kwargs: dict, default_pad_id, default_eos_ids, from_c
 # stops the call-wide stop_sequences= keyword in its normal form or None: the default of every request whose RequestParams leave it None.
 ManyOptions = namedtuple("ManyOptions", "max_new_tokens eos_ids pad_id use_graph processors params generator stops")
 
+
+@dataclass
+class _ManyPlan:
+    """What AkiMethods._plan_many hands to generate_many's two paths.  reqs: _many_requests' (vision_x, lang_x, budget, RequestParams);
+    seeds: _many_seeds' value per request; eos_list: the call's eos ids, sorted.  For a queue that is not empty also, per request:
+    resolved (its processor keywords), set_keys (their slots.processor_set_key), stop_keys (its stop set, normal form); mixed: the
+    requests resolve to more than one processor set, else pk is the one they share; pool: the constraint.ConstraintPool of a call with a
+    constrained request; dev / dtype / on_device (bf16 on the GPU: the device picks) and width, the logits' columns."""
+    opt: ManyOptions
+    slots: int
+    reqs: list
+    seeds: list
+    eos_list: list
+    resolved: Optional[list] = None
+    set_keys: Optional[list] = None
+    stop_keys: Optional[list] = None
+    mixed: bool = False
+    pk: Optional[dict] = None
+    pool: object = None
+    dev: Optional[torch.device] = None
+    dtype: Optional[torch.dtype] = None
+    on_device: bool = False
+    width: int = 0
+
+    @property
+    def sampled(self) -> bool:
+        return any(rp.do_sample for *_, rp in self.reqs)
+
+    @property
+    def constrained(self) -> bool:
+        return any(rp.constraint is not None for *_, rp in self.reqs)
+
+    @property
+    def want_lp(self) -> bool:
+        return any(rp.logprobs for *_, rp in self.reqs)
+
+    @property
+    def top(self) -> int:
+        return max(int(rp.top_logprobs) for *_, rp in self.reqs)
+
+    @property
+    def any_stops(self) -> bool:
+        return any(self.stop_keys)
+
+    def result(self, tok, rp, lp=None, top_ids=None, top_lp=None):
+        """One request's return value: the tokens, or an AkiRequestOutput when any request of the call asked for log-probabilities."""
+        if not self.want_lp:
+            return tok
+        if not rp.logprobs:
+            return AkiRequestOutput(tokens=tok)
+        k = int(rp.top_logprobs)
+        return AkiRequestOutput(tokens=tok, logprobs=lp, top_token_ids=top_ids[:, :k].clone() if k else None,
+                                top_logprobs=top_lp[:, :k].clone() if k else None)
+
 # what generate_many refuses, with the reason: (keyword, the test that it is in force, why)
 MANY_REFUSED = (
     ("do_sample", lambda v: bool(v), "sampling belongs to a request, not to the call: pass RequestParams(do_sample=True, ...) in the request "
@@ -335,22 +390,12 @@ def _many_seeds(reqs, generator) -> List[Optional[int]]:
     return seeds
 
 
-def _pick_rows_torch(logits, ids, pad_token_id: int, eos_ids, done, tokens, cache_len, start_len, done_at, proc=None):
-    """What ops.greedy_pick does with advance = 0, in torch, for logits that are not bf16 (an f32 model: generate() picks those on the host
-    loop too): next = pad for done rows, else the argmax of the (processed) row; tokens[b, cache_len[b] - start_len[b]] = next; a row whose
-    next is an eos id becomes done at that index.  In place, on the device, no synchronisation."""
-    x = logits if proc is None else proc.apply(logits, tokens=tokens, cache_len=cache_len, start_len=start_len, done=done)
-    was_done = done.bool()
-    nxt = torch.where(was_done, torch.full_like(ids, pad_token_id), x.float().argmax(dim=-1))
-    t = (cache_len - start_len).long()
-    ok = (t >= 0) & (t < tokens.shape[1])
-    col = t.clamp(0, tokens.shape[1] - 1)[:, None]
-    tokens.scatter_(1, col, torch.where(ok, nxt, tokens.gather(1, col)[:, 0])[:, None])
-    ids.copy_(nxt)
-    if eos_ids is not None:
-        hit = (nxt[:, None] == eos_ids[None, :]).any(-1) & ~was_done
-        done_at.copy_(torch.where(hit, t.to(torch.int32), done_at))
-        done.copy_(torch.where(hit, torch.ones_like(done), done))
+def _logits_processors(V: int, device, pk: dict, eos_ids, **kw):
+    """The ops.LogitsProcessors of a processor-keyword dict (PROCESSOR_KWARGS' keys; kw: constraint= or slot_constraints=), or None when
+    nothing in it is active: the picks then launch exactly what they launch without processors."""
+    p = ops.LogitsProcessors(V, device, pk["repetition_penalty"], pk["no_repeat_ngram_size"], max(int(pk["min_length"]), int(pk["min_new_tokens"])),
+                             eos_ids, pk["suppress_tokens"], pk["begin_suppress_tokens"], pk["bad_words_ids"], **kw)
+    return p if p.active else None
 
 
 def _device_sampler_args(opt: GenerateOptions):
@@ -382,6 +427,223 @@ def _pad_rows(rows, pad_id: int, device) -> torch.Tensor:
     for b, x in enumerate(rows):
         out[b, : x.numel()] = x
     return out.to(device)
+
+
+def _logits_width(lm) -> int:
+    """V', the columns of a language model's logits: DecoupledLinear's output is the original ids followed by the added ones (helpers.py),
+    a plain head's its rows."""
+    head = lm.get_output_embeddings()
+    return int(head.max_original_id) + 1 + int(head.additional_out_features) if hasattr(head, "max_original_id") else int(head.out_features)
+
+
+def _plan_many(model, requests, slots, kwargs) -> "_ManyPlan":
+    """generate_many's host half (model: the AkiMethods object, of which it reads pad_token_id, default_eos_token_ids and lang_model): the
+    keywords, the requests, their seeds, and every request's resolved processor settings, stop set and
+    constraint, checked against the logits' width.  Every ValueError / NotImplementedError the arguments can cause is raised here,
+    before any device work.  An empty queue: the plan holds no more than the (checked) slots."""
+    opt = _parse_many_kwargs(kwargs, model.pad_token_id, model.default_eos_token_ids)
+    slots = int(slots)
+    if slots < 1 or slots > ops.SLOT_MAX_ROWS:
+        raise ValueError(f"generate_many: 1 <= slots <= {ops.SLOT_MAX_ROWS} (the rows the skinny decode GEMMs take) is expected, got {slots}")
+    reqs = _many_requests(requests, opt.max_new_tokens, opt.params)
+    plan = _ManyPlan(opt, slots, reqs, _many_seeds(reqs, opt.generator), sorted(opt.eos_ids))
+    model.last_many_stats = None
+    model.last_stop_hits = None
+    if not reqs:
+        return plan
+    plan.dev = reqs[0][1].device
+    plan.dtype = model.lang_model.get_input_embeddings().weight.dtype
+    plan.on_device = plan.dev.type == "cuda" and plan.dtype == torch.bfloat16
+    if plan.sampled and not plan.on_device:
+        raise ValueError("generate_many: a sampled request needs the device sampler, which needs bf16 logits on the GPU")
+    eos_list, width = plan.eos_list, _logits_width(model.lang_model)
+    plan.width = width
+    # every request's stop set: its own, else params=, else the call-wide keyword, its ids checked against the logits' width
+    plan.stop_keys = _many_stop_sets(reqs, opt, width)
+    # every request's processor settings: its own, else params=, else the call-wide keyword - checked on the host against the logits'
+    # width and reduced to one value per distinct behaviour.  A call whose requests all resolve to one set runs the call-wide path.
+    plan.resolved = [resolve_processors(rp, opt.params, opt.processors) for *_, rp in reqs]
+    plan.set_keys = [processor_set_key(f"request {i}", r, eos_list, width) for i, r in enumerate(plan.resolved)]
+    plan.mixed = len(set(plan.set_keys)) > 1
+    plan.pk = opt.processors if plan.mixed else plan.resolved[0]
+    if plan.constrained:                            # the host half: every table with its eos columns, checked before any device work
+        from .constraint import ConstraintPool
+        plan.pool = ConstraintPool(eos_list, [rp.constraint for *_, rp in reqs], width)
+        for i, ((*_, rp), r) in enumerate(zip(reqs, plan.resolved)):
+            banning = banning_keywords(f"request {i}", r, eos_list, width) if rp.constraint is not None else []
+            for k in PROCESSOR_KWARGS:              # what bans nothing after normalisation goes to generate() as the neutral value
+                if rp.constraint is not None and k in BANNING_KWARGS and k not in banning:
+                    r[k] = PROCESSOR_KWARGS[k]
+            if banning:
+                raise ValueError(f"request {i}: a constraint together with {banning}: a processor that bans tokens can leave a constrained "
+                                 "row with nothing allowed; only repetition_penalty composes with a constraint (a request overrides a "
+                                 "call-wide keyword with the neutral value in its RequestParams)")
+        if not plan.on_device:
+            first = next(i for i, (*_, rp) in enumerate(reqs) if rp.constraint is not None)
+            raise ValueError(f"request {first}: a constrained request needs the device pick, which needs bf16 logits on the GPU")
+    return plan
+
+def _many_one_by_one(model, plan: "_ManyPlan"):
+    """generate_many with one slot or one request: generate() per request, in order."""
+    opt, eos_list = plan.opt, plan.eos_list
+    outs, sched, hits = [], SlotScheduler(len(plan.reqs), 1), []
+    for (vx, lx, budget, rp), seed, own, stop_key in zip(plan.reqs, plan.seeds, plan.resolved, plan.stop_keys):
+        kw_r = dict(own, eos_token_id=eos_list, pad_token_id=opt.pad_id, max_new_tokens=budget)
+        if stop_key:
+            kw_r.update(stop_sequences=stop_key)
+        if rp.do_sample:                        # the same stream: key seed, counter (token index, row 0, offset 0)
+            kw_r.update(do_sample=True, temperature=float(rp.temperature), top_k=int(rp.top_k), top_p=float(rp.top_p),
+                        generator=ops.DeviceGenerator(seed))
+        if rp.logprobs:
+            kw_r.update(output_logprobs=True, top_logprobs=int(rp.top_logprobs))
+        if rp.constraint is not None:
+            kw_r.update(constraint=rp.constraint)
+        out = model._generate_one(vx, lx, **kw_r)
+        row = out.sequences if rp.logprobs else out
+        eos_t = torch.tensor(eos_list, dtype=torch.long, device=row.device) if eos_list else None
+        tok = model._cut_behind_eos(row, eos_t, stop_key).clone()
+        hits.append(int(model.last_stop_hits[0]) if stop_key else -1)
+        n = tok.numel()
+        if rp.logprobs:
+            cut = lambda x: None if x is None else x[:n].clone()
+            outs.append(AkiRequestOutput(tokens=tok, logprobs=cut(out.logprobs), top_token_ids=cut(out.top_token_ids),
+                                         top_logprobs=cut(out.top_logprobs)))
+        else:
+            outs.append(plan.result(tok, rp))
+    model.last_many_stats = dict(sched.stats(), per_request_generate=True)
+    model.last_stop_hits = hits if plan.any_stops else None
+    return outs
+
+def _many_on_slots(model, plan: "_ManyPlan"):
+    """generate_many's loop over slots: the slot cache and the per-row buffers allocated once, ONE PickStage over them (what the
+    captured step, the eager step and - on one-row views - the admit all run), and the scheduler's four callbacks."""
+    opt, reqs, lm, dev, on_device = plan.opt, plan.reqs, model.lang_model, plan.dev, plan.on_device
+    eos_list, width = plan.eos_list, plan.width
+    slots = min(plan.slots, len(reqs))
+    flat = torch.cat([r[1][0] for r in reqs]).tolist()       # one copy for all prompts, ahead of any launch
+    ends = list(itertools.accumulate(r[1].shape[1] for r in reqs))
+    ids_host = [flat[e - r[1].shape[1]:e] for e, r in zip(ends, reqs)]
+    capacity = slot_capacity(ids_host, [r[2] for r in reqs], model.media_token_id, model.num_tokens_per_vis)
+    rot = lm.model.rotary_emb
+    if rot.short is not None and capacity > rot.orig_max:
+        raise NotImplementedError(f"generate_many on a LongRoPE model with a slot capacity of {capacity} rows above "
+                                  f"original_max_position_embeddings = {rot.orig_max}: HF picks the factor set per batch, not per row")
+    cfg = lm.config
+    H = cfg.num_attention_heads
+    Dh = getattr(cfg, "head_dim", None) or cfg.hidden_size // H
+    cache = AkiKVCache(len(lm.model.layers), slots, H, Dh, capacity, plan.dtype, dev, lm.kv_cache_dtype)    # valid_bits None: a lone prompt has no padding
+    max_budget = max(r[2] for r in reqs)
+    tokens = torch.full((slots, max_budget), opt.pad_id, dtype=torch.long, device=dev)
+    done = torch.ones(slots, dtype=torch.uint8, device=dev)
+    done_at = torch.zeros(slots, dtype=torch.int32, device=dev)
+    start_len = torch.zeros(slots, dtype=torch.int32, device=dev)
+    limit = torch.ones(slots, dtype=torch.int32, device=dev)
+    eos_t = torch.tensor(eos_list, dtype=torch.long, device=dev) if eos_list else None
+    pick = dict(pad_token_id=opt.pad_id, eos_ids=eos_t, done=done, tokens=tokens, start_len=start_len, done_at=done_at)
+    # the processed pick keeps a score scratch per batch size, whose address the captured step holds: the admit's one-row pick gets its own.
+    # Requests with different settings: the pool of distinct sets (uploaded once) and one set index per slot, allocated ahead of the
+    # capture and rewritten in place at admit (ops.ProcessorSets) - it stands in the place of the one LogitsProcessors.
+    processors = lambda: None if plan.mixed else _logits_processors(width, dev, plan.pk, eos_list, slot_constraints=plan.constrained)
+    proc, proc1 = processors(), processors()
+    psets = ops.ProcessorSets(width, dev, eos_list, plan.set_keys, slots) if plan.mixed else None
+    if proc is not None:
+        pick["processors"] = proc
+    if psets is not None:
+        pick["processor_sets"] = psets
+    owner = proc if proc is not None else psets
+    if on_device and owner is not None:
+        owner.scores(slots, dev)                    # allocated ahead of the capture
+    # a call with a constrained request: the pool of tables (uploaded once), and per slot the place of its request's table and its state
+    # history, allocated ahead of the capture and rewritten in place at admit.  An unconstrained request is a state -1 row.
+    slot_con = None
+    if plan.constrained:
+        slot_con = pick["slot_constraints"] = ops.SlotConstraints(plan.pool.bind(dev), slots, max_budget)
+    # a call with stops: the pool of distinct stop sets (uploaded once), and per slot the place of its request's set and its hit,
+    # allocated ahead of the capture and rewritten in place at admit.  The check rides in the tick's launch (ops.slot_tick(stops=...)).
+    stop_sets = ops.StopSets(dev, plan.stop_keys, slots) if plan.any_stops else None
+    # a call with a sampled request: every row's sampler parameters and Philox key live in device arrays the captured pick reads
+    # (ops.sample_pick_rows).  A parked row and a greedy request are top_k = 1 rows, the greedy pick's token.
+    rows = None
+    if plan.sampled:
+        rows = dict(temperature=torch.ones(slots, dtype=torch.float32, device=dev), top_k=torch.ones(slots, dtype=torch.int32, device=dev),
+                    top_p=torch.ones(slots, dtype=torch.float32, device=dev), seed=torch.zeros(slots, dtype=torch.int64, device=dev))
+    # log-probabilities: one ops.token_logprob behind each pick, per slot; a request's columns are [0, its tokens)
+    lpb = _LogprobBuffers(slots, max_budget, plan.top, dev) if plan.want_lp else None
+    stage = PickStage(pick, rows=rows, processors_row=proc1, logprob=None if lpb is None else lpb.args(), stops=stop_sets, limit=limit,
+                      torch_pick=not on_device)
+    stepper = None if not opt.use_graph else DecodeGraph(lm, cache, greedy=stage) if on_device else DecodeGraph(lm, cache)
+    ids = stepper.ids if stepper is not None else torch.zeros(slots, dtype=torch.long, device=dev)
+    sched = SlotScheduler(len(reqs), slots, period=8)
+    results, hits, seen = {}, {}, {}
+
+    def admit(req, slot):
+        vx, lx, budget, rp = reqs[req]
+        src, logits = model._prefill_request(vx, lx)
+        ops.kv_slot_admit(src, cache, slot)
+        cache.host_len = max(cache.host_len, src.host_len)
+        cache.cache_len[slot:slot + 1].copy_(src.cache_len)
+        start_len[slot:slot + 1].copy_(src.cache_len)
+        done[slot] = 0
+        done_at[slot] = -1
+        limit[slot] = budget
+        tokens[slot] = opt.pad_id
+        if rows is not None:                        # the slot's sampler parameters, in place: tensor fills, nothing copied from the host
+            seed = plan.seeds[req]
+            rows["temperature"][slot] = float(rp.temperature) if rp.do_sample else 1.0
+            rows["top_k"][slot] = int(rp.top_k) if rp.do_sample else 1
+            rows["top_p"][slot] = float(rp.top_p) if rp.do_sample else 1.0
+            rows["seed"][slot] = 0 if seed is None else (seed - (1 << 64) if seed >= 1 << 63 else seed)     # the key's bits as int64
+        if slot_con is not None:                    # the slot's automaton: where its table begins, its start state in column 0
+            slot_con.admit(slot, plan.pool.base[req], plan.pool.n_states[req], plan.pool.start[req])
+        if psets is not None:                       # the slot's processor set, ahead of the pick of token 0
+            psets.admit(slot, plan.set_keys[req])
+        if stop_sets is not None:                   # the slot's stop set, its hit back to -1
+            stop_sets.admit(slot, plan.stop_keys[req])
+        # token 0, from the prefill: the stage at B = 1 on row views.  The stops are checked behind the pick and AHEAD of the tick: a
+        # one-token stop ends a request here
+        stage.row(slot).run(logits.contiguous(), ids[slot:slot + 1], cache.cache_len[slot:slot + 1], advance=False, fuse_stops=False)
+        return budget == 1
+
+    def step(n):
+        for _ in range(n):
+            if stepper is not None and on_device:
+                stepper.step_greedy()
+                continue
+            if stepper is not None:
+                lg = stepper.step(ids)
+            elif on_device:                         # the pick advances cache_len; the torch pick leaves that to the decode step
+                lg = lm.decode_step(input_ids=ids, past_key_values=cache, advance=False)
+            else:
+                lg = lm.decode_step(input_ids=ids, past_key_values=cache)
+            stage.run(lg, ids, cache.cache_len, advance=True)
+
+    def look():
+        state = [done.to(torch.int32), done_at, cache.cache_len] + ([] if stop_sets is None else [stop_sets.stop_hit])
+        state = torch.stack(state).tolist()         # the one synchronisation
+        d, at, ln = state[:3]
+        seen["hit"] = state[3] if stop_sets is not None else None
+        # host_len bounds the row the next step appends at.  A parked row stays on its one dead cache row (ops.slot_tick), so under the
+        # captured step, whose grid is sized by the capacity, only the live rows count; eager steps size their grid by host_len and
+        # need every row's keys inside it.
+        live = [n for n, dd in zip(ln, d) if not dd]
+        cache.host_len = max(live, default=0) if stepper is not None else max(ln)
+        return d, at
+
+    def retire(req, slot, n):
+        rp = reqs[req][3]
+        hits[req] = -1 if stop_sets is None else int(seen["hit"][slot])
+        tok = tokens[slot, :n].clone()
+        if rp.logprobs:                             # the columns behind n may hold what the slot's previous request left: never returned
+            results[req] = plan.result(tok, rp, lpb.lp[slot, :n].clone(), None if lpb.top_ids is None else lpb.top_ids[slot, :n],
+                                       None if lpb.top_lp is None else lpb.top_lp[slot, :n])
+        else:
+            results[req] = plan.result(tok, rp)
+
+    sched.run(admit, step, look, retire, room=lambda: capacity - cache.host_len)
+    model.last_many_stats = sched.stats()
+    model.last_stop_hits = sched.in_request_order(hits) if stop_sets is not None else None
+    model._post_forward_hook()
+    return sched.in_request_order(results)
 
 
 class AkiMethods:
@@ -677,33 +939,24 @@ class AkiMethods:
         done_at = torch.full((B,), -1, dtype=torch.int32, device=dev)
         start_len, host_len0 = cache.cache_len.clone(), cache.host_len
         pick = dict(pad_token_id=pad_id, eos_ids=eos_t, done=done8, tokens=tokens, start_len=start_len, done_at=done_at)
-        pick_op = ops.greedy_pick
-        sampler = _device_sampler_args(opt)
-        if sampler is not None:
-            pick.update(sampler)
-            pick_op = ops.sample_pick
         if proc is not None:                    # the processors read tokens[:, :t] and t from cache_len: replays and rewinds stay right
             pick["processors"] = proc
         ids = torch.zeros(B, dtype=torch.long, device=dev)
         emb_mod = lm.get_input_embeddings()
         embed = _embedding_tables(emb_mod, logits)
         nxt_emb = None if embed is None else torch.empty((B, emb_mod.weight.shape[1]), dtype=torch.bfloat16, device=dev)
-        pick_e = pick if embed is None else dict(pick, embed=embed, next_embeds=nxt_emb)
         # output_logprobs: one ops.token_logprob behind each pick (in-loop form: it reads the index the pick just wrote from cache_len)
         lpb = _LogprobBuffers(B, max_new_tokens, opt.top_logprobs, dev) if opt.output_logprobs else None
-        lp = None if lpb is None or max_new_tokens < 1 else dict(lpb.args(), tokens=tokens, cache_len=cache.cache_len, start_len=start_len, done_at=done_at)
         stops = None
         if opt.stops and max_new_tokens >= 1:           # one set for every row; row_set / stop_hit allocated ahead of any capture
             stops = ops.StopSets(dev, [opt.stops], B)
             stops.row_set.fill_(stops.index[opt.stops])
             self.last_stop_hits = stops.stop_hit
-        check = (lambda: None) if stops is None else (lambda: ops.stop_check(tokens, cache.cache_len, start_len, done8, done_at, stops))
+        stage = PickStage(pick, embed=embed, next_embeds=nxt_emb, sampler=_device_sampler_args(opt),
+                          logprob=None if lpb is None or max_new_tokens < 1 else lpb.args(), stops=stops)
         ends = eos_t is not None or stops is not None   # a row can finish ahead of its budget
         logits = logits.contiguous()
-        pick_op(logits, ids, cache_len=cache.cache_len, advance=False, **pick_e)      # token 0, from the prefill
-        if lp is not None:
-            ops.token_logprob(logits, **lp)
-        check()
+        stage.run(logits, ids, cache.cache_len, advance=False)      # token 0, from the prefill
         t, t_ok = 1, 1                                  # tokens[:, :t_ok] are verified (token 0 comes from the prefill, not from the chain)
         period = 8 if ends else 32                      # host synchronisations: the finished flags need them often, the chain's verification alone does not
         while True:
@@ -727,13 +980,9 @@ class AkiMethods:
                         lg = lm.decode_step(inputs_embeds=nxt_emb, past_key_values=cache, advance=False)
                     else:
                         lg = lm.decode_step(input_ids=ids, past_key_values=cache, advance=False)
-                    pick_op(lg, ids, cache_len=cache.cache_len, advance=True, **pick_e)
-                    if lp is not None:
-                        ops.token_logprob(lg, **lp)
-                    check()
+                    stage.run(lg, ids, cache.cache_len, advance=True)
                     if not chained():
-                        captured = pick if lp is None else dict(pick, logprob=lp)
-                        stepper = DecodeGraph(lm, cache, greedy=captured if stops is None else dict(captured, stops=stops))
+                        stepper = DecodeGraph(lm, cache, greedy=stage)
                         stepper.ids.copy_(ids)
                 t += 1
             if ok and chained() and not lm.decode_verified(cache):
@@ -898,10 +1147,7 @@ class AkiMethods:
     last_stop_hits = None
 
     def _logits_width(self) -> int:
-        """V', the columns of the logits: DecoupledLinear's output is the original ids followed by the added ones (helpers.py), a plain
-        head's its rows."""
-        head = self.lang_model.get_output_embeddings()
-        return int(head.max_original_id) + 1 + int(head.additional_out_features) if hasattr(head, "max_original_id") else int(head.out_features)
+        return _logits_width(self.lang_model)
 
     def _prefill_request(self, vision_x, lang_x):
         """One request of generate_many, prefilled at batch 1 into a cache of exactly its length: (cache, logits [1, V']).  Without an image
@@ -1014,272 +1260,13 @@ class AkiMethods:
             nothing pending stays done and parked (slot_tick keeps it on one dead cache row).
         f32 models (logits the pick kernel does not take) replay the plain step and pick with torch operations on the device, still without
         a synchronisation per token.  slots == 1 or a single request: generate() per request (the one-launch chain is the batch-1 path)."""
-        opt = _parse_many_kwargs(kwargs, self.pad_token_id, self.default_eos_token_ids)
-        slots = int(slots)
-        if slots < 1 or slots > ops.SLOT_MAX_ROWS:
-            raise ValueError(f"generate_many: 1 <= slots <= {ops.SLOT_MAX_ROWS} (the rows the skinny decode GEMMs take) is expected, got {slots}")
-        reqs = _many_requests(requests, opt.max_new_tokens, opt.params)
-        seeds = _many_seeds(reqs, opt.generator)
-        self.last_many_stats = None
-        self.last_stop_hits = None
-        if not reqs:
-            self.last_many_stats = SlotScheduler(0, slots).stats()
+        plan = _plan_many(self, requests, slots, kwargs)
+        if not plan.reqs:
+            self.last_many_stats = SlotScheduler(0, plan.slots).stats()
             return []
-        eos_list = sorted(opt.eos_ids)
-        pk = opt.processors
-        sampled = any(rp.do_sample for *_, rp in reqs)
-        constrained = any(rp.constraint is not None for *_, rp in reqs)
-        want_lp = any(rp.logprobs for *_, rp in reqs)
-        top = max(int(rp.top_logprobs) for *_, rp in reqs)
-        lm = self.lang_model
-        dev = reqs[0][1].device
-        dtype = lm.get_input_embeddings().weight.dtype
-        on_device = dev.type == "cuda" and dtype == torch.bfloat16
-        if sampled and not on_device:
-            raise ValueError("generate_many: a sampled request needs the device sampler, which needs bf16 logits on the GPU")
-        head = lm.get_output_embeddings()
-        width = int(head.max_original_id) + 1 + int(head.additional_out_features) if hasattr(head, "max_original_id") else int(head.out_features)
-        # every request's stop set: its own, else params=, else the call-wide keyword, its ids checked against the logits' width
-        stop_keys = _many_stop_sets(reqs, opt, width)
-        any_stops = any(stop_keys)
-        # every request's processor settings: its own, else params=, else the call-wide keyword - checked on the host against the logits'
-        # width and reduced to one value per distinct behaviour.  A call whose requests all resolve to one set runs the call-wide path.
-        resolved = [resolve_processors(rp, opt.params, pk) for *_, rp in reqs]
-        set_keys = [processor_set_key(f"request {i}", r, eos_list, width) for i, r in enumerate(resolved)]
-        mixed = len(set(set_keys)) > 1
-        if not mixed:
-            pk = resolved[0]
-        pool = None
-        if constrained:                                 # the host half: every table with its eos columns, checked before any device work
-            from .constraint import ConstraintPool
-            pool = ConstraintPool(eos_list, [rp.constraint for *_, rp in reqs], width)
-            for i, ((*_, rp), r) in enumerate(zip(reqs, resolved)):
-                banning = banning_keywords(f"request {i}", r, eos_list, width) if rp.constraint is not None else []
-                for k in PROCESSOR_KWARGS:              # what bans nothing after normalisation goes to generate() as the neutral value
-                    if rp.constraint is not None and k in BANNING_KWARGS and k not in banning:
-                        r[k] = PROCESSOR_KWARGS[k]
-                if banning:
-                    raise ValueError(f"request {i}: a constraint together with {banning}: a processor that bans tokens can leave a constrained "
-                                     "row with nothing allowed; only repetition_penalty composes with a constraint (a request overrides a "
-                                     "call-wide keyword with the neutral value in its RequestParams)")
-            if not on_device:
-                first = next(i for i, (*_, rp) in enumerate(reqs) if rp.constraint is not None)
-                raise ValueError(f"request {first}: a constrained request needs the device pick, which needs bf16 logits on the GPU")
-
-        def result(tok, rp, lp=None, top_ids=None, top_lp=None):
-            """One request's return value: the tokens, or an AkiRequestOutput when any request of the call asked for log-probabilities."""
-            if not want_lp:
-                return tok
-            if not rp.logprobs:
-                return AkiRequestOutput(tokens=tok)
-            k = int(rp.top_logprobs)
-            return AkiRequestOutput(tokens=tok, logprobs=lp, top_token_ids=top_ids[:, :k].clone() if k else None,
-                                    top_logprobs=top_lp[:, :k].clone() if k else None)
-
-        if slots == 1 or len(reqs) == 1:
-            outs, sched, hits = [], SlotScheduler(len(reqs), 1), []
-            for (vx, lx, budget, rp), seed, own, stop_key in zip(reqs, seeds, resolved, stop_keys):
-                kw_r = dict(own, eos_token_id=eos_list, pad_token_id=opt.pad_id, max_new_tokens=budget)
-                if stop_key:
-                    kw_r.update(stop_sequences=stop_key)
-                if rp.do_sample:                        # the same stream: key seed, counter (token index, row 0, offset 0)
-                    kw_r.update(do_sample=True, temperature=float(rp.temperature), top_k=int(rp.top_k), top_p=float(rp.top_p),
-                                generator=ops.DeviceGenerator(seed))
-                if rp.logprobs:
-                    kw_r.update(output_logprobs=True, top_logprobs=int(rp.top_logprobs))
-                if rp.constraint is not None:
-                    kw_r.update(constraint=rp.constraint)
-                out = self._generate_one(vx, lx, **kw_r)
-                row = out.sequences if rp.logprobs else out
-                eos_t = torch.tensor(eos_list, dtype=torch.long, device=row.device) if eos_list else None
-                tok = self._cut_behind_eos(row, eos_t, stop_key).clone()
-                hits.append(int(self.last_stop_hits[0]) if stop_key else -1)
-                n = tok.numel()
-                if rp.logprobs:
-                    cut = lambda x: None if x is None else x[:n].clone()
-                    outs.append(AkiRequestOutput(tokens=tok, logprobs=cut(out.logprobs), top_token_ids=cut(out.top_token_ids),
-                                                 top_logprobs=cut(out.top_logprobs)))
-                else:
-                    outs.append(result(tok, rp))
-            self.last_many_stats = dict(sched.stats(), per_request_generate=True)
-            self.last_stop_hits = hits if any_stops else None
-            return outs
-        slots = min(slots, len(reqs))
-        flat = torch.cat([r[1][0] for r in reqs]).tolist()       # one copy for all prompts, ahead of any launch
-        ends = list(itertools.accumulate(r[1].shape[1] for r in reqs))
-        ids_host = [flat[e - r[1].shape[1]:e] for e, r in zip(ends, reqs)]
-        capacity = slot_capacity(ids_host, [r[2] for r in reqs], self.media_token_id, self.num_tokens_per_vis)
-        rot = lm.model.rotary_emb
-        if rot.short is not None and capacity > rot.orig_max:
-            raise NotImplementedError(f"generate_many on a LongRoPE model with a slot capacity of {capacity} rows above "
-                                      f"original_max_position_embeddings = {rot.orig_max}: HF picks the factor set per batch, not per row")
-        cfg = lm.config
-        H = cfg.num_attention_heads
-        Dh = getattr(cfg, "head_dim", None) or cfg.hidden_size // H
-        cache = AkiKVCache(len(lm.model.layers), slots, H, Dh, capacity, dtype, dev, lm.kv_cache_dtype)    # valid_bits None: a lone prompt has no padding
-        max_budget = max(r[2] for r in reqs)
-        tokens = torch.full((slots, max_budget), opt.pad_id, dtype=torch.long, device=dev)
-        done = torch.ones(slots, dtype=torch.uint8, device=dev)
-        done_at = torch.zeros(slots, dtype=torch.int32, device=dev)
-        start_len = torch.zeros(slots, dtype=torch.int32, device=dev)
-        limit = torch.ones(slots, dtype=torch.int32, device=dev)
-        eos_t = torch.tensor(eos_list, dtype=torch.long, device=dev) if eos_list else None
-
-        def processors():
-            p = ops.LogitsProcessors(width, dev, pk["repetition_penalty"], pk["no_repeat_ngram_size"],
-                                     max(int(pk["min_length"]), int(pk["min_new_tokens"])), eos_list, pk["suppress_tokens"],
-                                     pk["begin_suppress_tokens"], pk["bad_words_ids"], slot_constraints=constrained)
-            return p if p.active else None
-
-        # the processed pick keeps a score scratch per batch size, whose address the captured step holds: the admit's one-row pick gets its own.
-        # Requests with different settings: the pool of distinct sets (uploaded once) and one set index per slot, allocated ahead of the
-        # capture and rewritten in place at admit (ops.ProcessorSets) - it stands in the place of the one LogitsProcessors.
-        psets = ops.ProcessorSets(width, dev, eos_list, set_keys, slots) if mixed else None
-        proc, proc1 = (None, None) if mixed else (processors(), processors())
-        tick = dict(done=done, done_at=done_at, start_len=start_len, limit=limit)
-        pick = dict(pad_token_id=opt.pad_id, eos_ids=eos_t, done=done, tokens=tokens, start_len=start_len, done_at=done_at)
-        if proc is not None:
-            pick["processors"] = proc
-            if on_device:
-                proc.scores(slots, dev)                 # allocated ahead of the capture
-        if psets is not None and on_device:
-            pick["processor_sets"] = psets
-            psets.scores(slots, dev)
-        # a call with a constrained request: the pool of tables (uploaded once), and per slot the place of its request's table and its state
-        # history, allocated ahead of the capture and rewritten in place at admit.  An unconstrained request is a state -1 row.
-        slot_con = None
-        if constrained:
-            slot_con = ops.SlotConstraints(pool.bind(dev), slots, max_budget)
-            pick["slot_constraints"] = slot_con
-        # a call with stops: the pool of distinct stop sets (uploaded once), and per slot the place of its request's set and its hit,
-        # allocated ahead of the capture and rewritten in place at admit.  The check rides in the tick's launch (ops.slot_tick(stops=...)).
-        stop_sets = ops.StopSets(dev, stop_keys, slots) if any_stops else None
-        tick_stops = {} if stop_sets is None else dict(stops=stop_sets, tokens=tokens)
-        # a call with a sampled request: every row's sampler parameters and Philox key live in device arrays the captured pick reads
-        # (ops.sample_pick_rows).  A parked row and a greedy request are top_k = 1 rows, the greedy pick's token.
-        rows = None
-        if sampled:
-            rows = dict(temperature=torch.ones(slots, dtype=torch.float32, device=dev), top_k=torch.ones(slots, dtype=torch.int32, device=dev),
-                        top_p=torch.ones(slots, dtype=torch.float32, device=dev), seed=torch.zeros(slots, dtype=torch.int64, device=dev))
-        # log-probabilities: one ops.token_logprob behind each pick, per slot; a request's columns are [0, its tokens)
-        lpb = _LogprobBuffers(slots, max_budget, top, dev) if want_lp else None
-        lp = None if lpb is None else dict(lpb.args(), tokens=tokens, cache_len=cache.cache_len, start_len=start_len, done_at=done_at)
-        if opt.use_graph:
-            if on_device:
-                captured = dict(pick, tick=tick)
-                if rows is not None:
-                    captured.update(temperature=rows["temperature"], top_k=rows["top_k"], top_p=rows["top_p"], row_seed=rows["seed"])
-                if lp is not None:
-                    captured["logprob"] = lp
-                if stop_sets is not None:
-                    captured["stops"] = stop_sets
-                stepper = DecodeGraph(lm, cache, greedy=captured)
-            else:
-                stepper = DecodeGraph(lm, cache)
-            ids = stepper.ids
-        else:
-            stepper, ids = None, torch.zeros(slots, dtype=torch.long, device=dev)
-        sched = SlotScheduler(len(reqs), slots, period=8)
-        results, hits, seen = {}, {}, {}
-        row = lambda x, s: x[s:s + 1]
-
-        def admit(req, slot):
-            vx, lx, budget, rp = reqs[req]
-            src, logits = self._prefill_request(vx, lx)
-            ops.kv_slot_admit(src, cache, slot)
-            cache.host_len = max(cache.host_len, src.host_len)
-            cache.cache_len[slot:slot + 1].copy_(src.cache_len)
-            start_len[slot:slot + 1].copy_(src.cache_len)
-            done[slot] = 0
-            done_at[slot] = -1
-            limit[slot] = budget
-            tokens[slot] = opt.pad_id
-            if rows is not None:                        # the slot's sampler parameters, in place: tensor fills, nothing copied from the host
-                seed = seeds[req]
-                rows["temperature"][slot] = float(rp.temperature) if rp.do_sample else 1.0
-                rows["top_k"][slot] = int(rp.top_k) if rp.do_sample else 1
-                rows["top_p"][slot] = float(rp.top_p) if rp.do_sample else 1.0
-                rows["seed"][slot] = 0 if seed is None else (seed - (1 << 64) if seed >= 1 << 63 else seed)     # the key's bits as int64
-            if slot_con is not None:                    # the slot's automaton: where its table begins, its start state in column 0
-                slot_con.admit(slot, pool.base[req], pool.n_states[req], pool.start[req])
-            if psets is not None:                       # the slot's processor set, ahead of the pick of token 0
-                psets.admit(slot, set_keys[req])
-            if stop_sets is not None:                   # the slot's stop set, its hit back to -1
-                stop_sets.admit(slot, stop_keys[req])
-            args = dict(pad_token_id=opt.pad_id, eos_ids=eos_t, done=row(done, slot), tokens=row(tokens, slot), start_len=row(start_len, slot),
-                        done_at=row(done_at, slot))
-            if on_device:                               # token 0, from the prefill: the existing pick at B = 1 on row views
-                logits = logits.contiguous()
-                args = args if proc1 is None else dict(args, processors=proc1)
-                if psets is not None:
-                    args = dict(args, processor_sets=psets.row(slot))
-                if slot_con is not None:
-                    args = dict(args, slot_constraints=slot_con.row(slot))
-                if rows is not None:
-                    ops.sample_pick_rows(logits, row(ids, slot), cache_len=row(cache.cache_len, slot), advance=False,
-                                         **{k: row(v, slot) for k, v in rows.items()}, **args)
-                else:
-                    ops.greedy_pick(logits, row(ids, slot), cache_len=row(cache.cache_len, slot), advance=False, **args)
-            else:
-                _pick_rows_torch(logits, row(ids, slot), cache_len=row(cache.cache_len, slot),
-                                 proc=proc1 if psets is None else psets.row(slot), **args)
-            if lp is not None:
-                ops.token_logprob(logits.contiguous(), **{k: (row(v, slot) if torch.is_tensor(v) else v) for k, v in lp.items()})
-            if stop_sets is not None:                   # behind the pick of token 0, ahead of the tick: a one-token stop ends a request here
-                ops.stop_check(row(tokens, slot), row(cache.cache_len, slot), row(start_len, slot), row(done, slot), row(done_at, slot),
-                               stop_sets.row(slot))
-            ops.slot_tick(row(done, slot), row(done_at, slot), row(cache.cache_len, slot), row(start_len, slot), row(limit, slot))
-            return budget == 1
-
-        def step(n):
-            for _ in range(n):
-                if stepper is not None and on_device:
-                    stepper.step_greedy()
-                    continue
-                if stepper is not None:
-                    lg = stepper.step(ids)
-                elif on_device:
-                    lg = lm.decode_step(input_ids=ids, past_key_values=cache, advance=False)
-                    if rows is not None:
-                        ops.sample_pick_rows(lg, ids, cache_len=cache.cache_len, advance=True, **rows, **pick)
-                    else:
-                        ops.greedy_pick(lg, ids, cache_len=cache.cache_len, advance=True, **pick)
-                else:
-                    lg = lm.decode_step(input_ids=ids, past_key_values=cache)
-                if not on_device:
-                    _pick_rows_torch(lg, ids, opt.pad_id, eos_t, done, tokens, cache.cache_len, start_len, done_at,
-                                     proc if psets is None else psets)
-                if lp is not None:
-                    ops.token_logprob(lg, **lp)
-                ops.slot_tick(cache_len=cache.cache_len, **tick, **tick_stops)
-
-        def look():
-            state = [done.to(torch.int32), done_at, cache.cache_len] + ([] if stop_sets is None else [stop_sets.stop_hit])
-            state = torch.stack(state).tolist()         # the one synchronisation
-            d, at, ln = state[:3]
-            seen["hit"] = state[3] if stop_sets is not None else None
-            # host_len bounds the row the next step appends at.  A parked row stays on its one dead cache row (ops.slot_tick), so under the
-            # captured step, whose grid is sized by the capacity, only the live rows count; eager steps size their grid by host_len and
-            # need every row's keys inside it.
-            live = [n for n, dd in zip(ln, d) if not dd]
-            cache.host_len = max(live, default=0) if stepper is not None else max(ln)
-            return d, at
-
-        def retire(req, slot, n):
-            rp = reqs[req][3]
-            hits[req] = -1 if stop_sets is None else int(seen["hit"][slot])
-            tok = tokens[slot, :n].clone()
-            if rp.logprobs:                             # the columns behind n may hold what the slot's previous request left: never returned
-                results[req] = result(tok, rp, lpb.lp[slot, :n].clone(), None if lpb.top_ids is None else lpb.top_ids[slot, :n],
-                                      None if lpb.top_lp is None else lpb.top_lp[slot, :n])
-            else:
-                results[req] = result(tok, rp)
-
-        sched.run(admit, step, look, retire, room=lambda: capacity - cache.host_len)
-        self.last_many_stats = sched.stats()
-        self.last_stop_hits = sched.in_request_order(hits) if stop_sets is not None else None
-        self._post_forward_hook()
-        return sched.in_request_order(results)
+        if plan.slots == 1 or len(plan.reqs) == 1:
+            return _many_one_by_one(self, plan)
+        return _many_on_slots(self, plan)
 
     @torch.no_grad()
     def generate(self, vision_x, lang_x, image_size=None, attention_mask=None, past_key_values=None,
@@ -1375,12 +1362,8 @@ class AkiMethods:
             raise NotImplementedError("text-only generation is outside the AKI hot path")
         else:
             cache, logits, appended = self._prefill_prompt(vision_x, lang_x, attention_mask, opt.max_new_tokens)
-        pk = opt.processors
         bound = None if con is None else con.bind(sorted(opt.eos_ids), logits.device, rows_start)
-        proc = ops.LogitsProcessors(logits.shape[-1], logits.device, pk["repetition_penalty"], pk["no_repeat_ngram_size"],
-                                    max(int(pk["min_length"]), int(pk["min_new_tokens"])), sorted(opt.eos_ids), pk["suppress_tokens"],
-                                    pk["begin_suppress_tokens"], pk["bad_words_ids"], constraint=bound)
-        proc = proc if proc.active else None       # no processor: exactly the launches of a plain generate
+        proc = _logits_processors(logits.shape[-1], logits.device, opt.processors, sorted(opt.eos_ids), constraint=bound)
         if opt.num_beams > 1:
             beam = (opt.num_beams, opt.max_new_tokens, opt.eos_ids, opt.pad_id, opt.length_penalty, opt.early_stopping, proc)
             if self._device_beam_search_ok(cache, logits, opt.num_beams, opt.eos_ids):

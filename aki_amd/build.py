@@ -62,7 +62,7 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = True, l
     objdir = os.path.join(LIBDIR, "obj")
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, "aki_device.h"), os.path.join(CSRC, "attn_mma_common.h"), os.path.join(CSRC, "decode_attn_common.h"),
-               os.path.join(CSRC, "weight_dot.h"), os.path.join(ROOT, "include", "aki_mi355x.h")]
+               os.path.join(CSRC, "weight_dot.h"), os.path.join(CSRC, "pick_params.h"), os.path.join(ROOT, "include", "aki_mi355x.h")]
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     lab_only = [os.path.join(CSRC, s_) for s_ in LAB_ONLY_SOURCES]
     if not force and _newer(LIB, srcs + headers) and (not lab or _newer(LAB_LIB, srcs + lab_only + headers)):

@@ -1,6 +1,7 @@
 // api.hip - extern "C" entry points of libaki_mi355x.so (include/aki_mi355x.h).
 // Host-side validation only; every launch goes to the stream the caller passes.
 #include "aki_device.h"
+#include "pick_params.h"
 
 namespace aki {
 int linear_bf16(const aki_linear_args* a, hipStream_t stream);
@@ -55,48 +56,8 @@ int splice_launch(const aki_splice_args* a, hipStream_t s);
 int mask_dense_launch(const aki_mma_rect* rects, int max_rects, const uint64_t* vbits, const int* seq_lens, int B, int L,
                       int64_t* out, hipStream_t s);
 int im2col_launch(const void* pix, void* out, int N, int S, int P, int Kp, int dtype, hipStream_t s);
-int greedy_pick_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done, int64_t* ids,
-                       int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at, const void* emb_main,
-                       const void* emb_extra, int64_t max_original_id, int d, void* emb_out, hipStream_t s);
-int logits_process_launch(const void* logits, int in_f32, int B, int V, int ld, float* out, int ld_out, const int64_t* tokens, int tokens_ld,
-                          const int* cache_len, const int* start_len, int step, const unsigned char* done, float penalty, int ngram,
-                          int min_len, const int64_t* eos, int n_eos, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress,
-                          int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad, int n_bad_ids,
-                          const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s);
-int greedy_pick_processed_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done,
-                                 int64_t* ids, int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at,
-                                 const void* emb_main, const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores,
-                                 int ld_scores, float penalty, int ngram, int min_len, const int64_t* suppress, int n_suppress,
-                                 const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad,
-                                 int n_bad_ids, const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
-                                 const int* c_row_base, const int* c_row_states, hipStream_t s);
-int sample_pick_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done, int64_t* ids,
-                       int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at, const void* emb_main,
-                       const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores, int ld_scores, float penalty, int ngram,
-                       int min_len, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids,
-                       const int* bad_off, int n_bad, int n_bad_ids, int step, float temperature, int top_k, float top_p, uint64_t seed,
-                       uint64_t offset, const float* row_temperature, const int* row_top_k, const float* row_top_p, const uint64_t* row_seed,
-                       float* probs, int ld_probs, const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
-                       const int* c_row_base, const int* c_row_states, hipStream_t s);
-int logits_process_rows_launch(const void* logits, int in_f32, int B, int V, int ld, float* out, int ld_out, const int64_t* tokens, int tokens_ld,
-                               const int* cache_len, const int* start_len, int step, const unsigned char* done, const int64_t* eos, int n_eos,
-                               const int* sets, int n_sets, const int* row_set, const int64_t* set_ids, int n_set_ids, const int* bad_off,
-                               int n_words, const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
-                               const int* c_row_base, const int* c_row_states, hipStream_t s);
-int greedy_pick_rows_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done, int64_t* ids,
-                            int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at, const void* emb_main,
-                            const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores, int ld_scores, const int* sets,
-                            int n_sets, const int* row_set, const int64_t* set_ids, int n_set_ids, const int* bad_off, int n_words,
-                            const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, const int* c_row_base,
-                            const int* c_row_states, hipStream_t s);
-int sample_pick_rows_processed_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done,
-                                      int64_t* ids, int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance,
-                                      int* done_at, const void* emb_main, const void* emb_extra, int64_t max_original_id, int d, void* emb_out,
-                                      float* scores, int ld_scores, const int* sets, int n_sets, const int* row_set, const int64_t* set_ids,
-                                      int n_set_ids, const int* bad_off, int n_words, int step, const float* row_temperature,
-                                      const int* row_top_k, const float* row_top_p, const uint64_t* row_seed, float* probs, int ld_probs,
-                                      const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
-                                      const int* c_row_base, const int* c_row_states, hipStream_t s);
+int pick_call_launch(const PickCall& c, hipStream_t s);
+int logits_process_call_launch(const ProcParams& q, const ProcSetParams* ps, int B, hipStream_t s);
 int beam_logprob_launch(const void* logits, int in_f32, int rows, int V, int ld, float* out, int ld_out, hipStream_t s);
 int beam_step_launch(const float* logp, int ld, int B, int K, int V, int t, int max_new, float* beam_scores, const int64_t* seqs_in,
                      int64_t* seqs_out, float* hyp_score, int* hyp_len, int64_t* hyp_tokens, int* hyp_count, unsigned char* done,
@@ -800,123 +761,210 @@ int aki_sft_collate_pad(const int64_t* ids, const int64_t* labels, const int64_t
                             out_mask, (hipStream_t)stream);
 }
 
+// ---- the picks and the logits processors (include/aki_mi355x.h) -------------------------------------------------------------------------
+// Every entry point fills a PickCall (pick_params.h) from its argument groups, then pick_call_check and pick_call_launch (decode.hip) do
+// the rest: each argument rule is written once, below.
+
+// the processor arguments of the call-wide forms
+static bool processors_ok(const ProcParams& q) {
+  return q.V <= AKI_LOGITS_PROCESS_MAX_V && q.penalty > 0.f && q.penalty <= 3.0e38f && q.ngram >= 0 && q.min_len >= 0 && q.n_suppress >= 0 &&
+         (q.n_suppress == 0 || q.suppress) && q.n_begin >= 0 && (q.n_begin == 0 || q.begin_suppress) && q.n_bad >= 0 &&
+         q.n_bad_ids >= q.n_bad && (q.n_bad == 0 || (q.bad_ids && q.bad_off));
+}
+
+// The per-row processor forms: the pool's arrays and the rows' set indices.  Their VALUES are the caller's: the kernel reads a set index
+// outside the pool as the neutral set and cuts every range at the pools' ends.
+static bool processor_sets_ok(int32_t V, const ProcSetParams& ps) {
+  return V <= AKI_LOGITS_PROCESS_MAX_V && ps.sets && ps.n_sets > 0 && ps.row_set && ps.n_ids >= 0 && (ps.n_ids == 0 || ps.ids) &&
+         ps.n_words >= 0 && (ps.n_words == 0 || (ps.bad_off && ps.ids));
+}
+
+// The constrained forms: a device table with a row for every state and a state history with at least its start column.  CON_WIDE: one
+// automaton, below 32768 states.  The per-row kinds: the table is a pool of n_states rows (any positive count: a row's own automaton stays
+// below 32768 states, the pool need not), and every row names its slice; the arrays' values are the caller's: the kernel cuts a slice at
+// the pool's end.
+static bool constraint_ok(int kind, int32_t V, const ConstraintParams& c, int64_t table_ld) {
+  if (kind == CON_NONE || (kind == CON_ROWS_OR_NONE && !c.table)) return true;
+  if (!(c.table && c.states && c.n_states > 0 && table_ld >= V && table_ld < (1ll << 31) && c.states_ld >= 1)) return false;
+  return kind == CON_WIDE ? c.n_states <= 32767 : (c.row_base && c.row_states);
+}
+
+// the sampler's own arguments (the greedy forms have none: step is 0)
+static bool sampler_ok(const PickCall& c) {
+  if (c.p.step < 0) return false;
+  if (c.sampler == SAMPLER_ROWS) {                // device arrays: their values are the caller's to check
+    return c.sr.temperature && c.sr.top_k && c.sr.top_p && c.sr.seed && (!c.sr.probs || (c.ld_probs >= c.p.V && c.ld_probs < (1ll << 31)));
+  }
+  if (c.sampler == SAMPLER_SCALAR) {
+    return c.sp.temperature > 0.f && c.sp.temperature <= 3.0e38f && c.sp.top_p > 0.f && c.sp.top_p <= 1.f && c.sp.top_k >= 0 &&
+           (!c.sp.probs || (c.ld_probs >= c.p.V && c.ld_probs < (1ll << 31)));
+  }
+  return true;
+}
+
+static int pick_call_check(const PickCall& c) {
+  const PickParams& p = c.p;
+  const ProcParams& q = c.q;
+  AKI_CLEAR_ERR();
+  AKI_CHECK_ARG(p.logits && p.ids && p.B > 0 && p.V > 0 && c.ld >= p.V && c.ld < (1ll << 31) && p.n_eos >= 0 && (p.n_eos == 0 || p.eos));
+  AKI_CHECK_ARG((!p.tokens || p.tokens_ld > 0) && (!p.advance || p.cache_len) && (p.advance == 0 || p.advance == 1));
+  if (c.processed) {
+    AKI_CHECK_ARG(q.out && c.ld_scores >= p.V && c.ld_scores < (1ll << 31));
+    AKI_CHECK_ARG(c.sets ? processor_sets_ok(p.V, c.ps) : processors_ok(q));
+  }
+  AKI_CHECK_ARG(constraint_ok(c.constraint, p.V, q.c, c.table_ld));
+  // aki_sample_pick_rows_processed has always looked at its sampler arguments last: a misaligned scratch outranks them there, and only there
+  if (!c.sets) AKI_CHECK_ARG(sampler_ok(c));
+  if (c.processed && ((((uintptr_t)q.out) & 15) != 0 || (c.ld_scores & 3) != 0)) return AKI_ERR_ALIGNMENT;
+  if (p.emb_main || c.embed_required) {
+    AKI_CHECK_ARG(p.emb_main && p.emb_out && p.d > 0 && p.d % 8 == 0 && p.max_original_id >= 0 && c.num_additional >= 0);
+    AKI_CHECK_ARG((((uintptr_t)p.emb_main | (uintptr_t)p.emb_extra | (uintptr_t)p.emb_out) & 15) == 0);
+    // every id the pick can produce has a row: V' = original rows + additional rows (DecoupledLinear's output width), pad included
+    AKI_CHECK_ARG((int64_t)p.V <= p.max_original_id + 1 + (p.emb_extra ? c.num_additional : 0) && p.pad >= 0 &&
+                  p.pad <= p.max_original_id + (p.emb_extra ? c.num_additional : 0));
+  } else {
+    AKI_CHECK_ARG(!p.emb_extra && !p.emb_out);
+  }
+  if (c.sets) AKI_CHECK_ARG(sampler_ok(c));
+  return AKI_OK;
+}
+
+static int pick_call(const PickCall& c, void* stream) {
+  const int rc = pick_call_check(c);
+  return rc != AKI_OK ? rc : pick_call_launch(c, (hipStream_t)stream);
+}
+
+// -- the argument groups, in the order the entry points take them
+// the 15 every pick begins with
+static PickCall pick_common(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                            uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                            int32_t advance, int32_t* done_at) {
+  PickCall c{};
+  c.p = PickParams{(const bf16_t*)logits, B, V, (int)ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len,
+                   advance, done_at};
+  c.ld = ld;
+  return c;
+}
+
+// the embedding gather's 6
+static void pick_embed(PickCall& c, const void* embed_weight, const void* additional_weight, int64_t max_original_id, int64_t num_additional,
+                       int32_t d, void* next_embeds) {
+  c.p.emb_main = (const bf16_t*)embed_weight; c.p.emb_extra = (const bf16_t*)additional_weight; c.p.max_original_id = max_original_id;
+  c.p.d = d; c.p.emb_out = (bf16_t*)next_embeds;
+  c.num_additional = num_additional;
+}
+
+// what a logits-process launch reads of the call, with neutral processor values
+static ProcParams proc_common(const void* in, int in_f32, int64_t ld_in, float* out, int64_t ld_out, int32_t V, const int64_t* tokens,
+                              int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step, const uint8_t* done,
+                              const int64_t* eos_ids, int32_t n_eos) {
+  ProcParams q{};
+  q.in = in; q.in_f32 = in_f32; q.ld_in = (int)ld_in; q.out = out; q.ld_out = (int)ld_out; q.V = V; q.tokens = tokens; q.tokens_ld = tokens_ld;
+  q.cache_len = cache_len; q.start_len = start_len; q.step = step; q.done = done; q.penalty = 1.f; q.eos = eos_ids; q.n_eos = n_eos;
+  return q;
+}
+
+// the f32 scratch of the processed picks: the processors read what the pick reads
+static void pick_scratch(PickCall& c, float* scores, int64_t ld_scores) {
+  const PickParams& p = c.p;
+  c.q = proc_common(p.logits, 0, c.ld, scores, ld_scores, p.V, p.tokens, p.tokens_ld, p.cache_len, p.start_len, 0, p.done, p.eos, p.n_eos);
+  c.ld_scores = ld_scores;
+  c.processed = true;
+}
+
+// the call-wide processors' 11
+static void proc_values(ProcParams& q, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids,
+                        int32_t n_suppress, const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids,
+                        const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids) {
+  q.penalty = repetition_penalty; q.ngram = no_repeat_ngram_size; q.min_len = min_length;
+  q.suppress = suppress_ids; q.n_suppress = n_suppress; q.begin_suppress = begin_suppress_ids; q.n_begin = n_begin_suppress;
+  q.bad_ids = bad_ids; q.bad_off = bad_offsets; q.n_bad = n_bad; q.n_bad_ids = n_bad_ids;
+}
+
+// the per-row processor sets' 7
+static ProcSetParams proc_sets(const int32_t* sets, int32_t n_sets, const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids,
+                               const int32_t* bad_offsets, int32_t n_words) {
+  return ProcSetParams{sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words};
+}
+
+// the constraint's 5 (row_base and row_states null) or 7
+static ConstraintParams constraint(const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld,
+                                   const int32_t* row_base = nullptr, const int32_t* row_states = nullptr) {
+  return ConstraintParams{table, (int)table_ld, n_states, states, states_ld, row_base, row_states};
+}
+
+static void pick_constraint(PickCall& c, int kind, const ConstraintParams& con, int64_t table_ld) {
+  c.q.c = con; c.constraint = kind; c.table_ld = table_ld;
+}
+
+// the scalar sampler's 8
+static void pick_sampler(PickCall& c, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed, uint64_t offset,
+                         float* probs_out, int64_t ld_probs) {
+  c.p.step = step;
+  c.sp = SampleParams{temperature, top_k, top_p, (unsigned)seed, (unsigned)(seed >> 32), (unsigned)offset, (unsigned)(offset >> 32),
+                      probs_out, (int)ld_probs, 0};
+  c.sampler = SAMPLER_SCALAR; c.ld_probs = ld_probs;
+}
+
+// the per-row sampler's 7: four device arrays of B entries in the scalars' place
+static void pick_sampler_rows(PickCall& c, int32_t step, const float* temperature, const int32_t* top_k, const float* top_p,
+                              const uint64_t* seed, float* probs_out, int64_t ld_probs) {
+  c.p.step = step;
+  c.sr = SampleRowParams{temperature, top_k, top_p, (const unsigned long long*)seed, probs_out, (int)ld_probs, 0};
+  c.sampler = SAMPLER_ROWS; c.ld_probs = ld_probs;
+}
+
 int aki_greedy_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
                     uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
                     int32_t advance, int32_t* done_at, void* stream) {
-  AKI_CLEAR_ERR();
-  AKI_CHECK_ARG(logits && next_ids && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && n_eos >= 0 && (n_eos == 0 || eos_ids));
-  AKI_CHECK_ARG((!tokens || tokens_ld > 0) && (!advance || cache_len) && (advance == 0 || advance == 1));
-  return greedy_pick_launch(logits, B, V, (int)ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
-                            done_at, nullptr, nullptr, 0, 0, nullptr, (hipStream_t)stream);
+  const PickCall c = pick_common(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
+                                 done_at);
+  return pick_call(c, stream);
 }
 
 int aki_greedy_pick_embed(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
                           uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
                           int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
                           int64_t num_additional, int32_t d, void* next_embeds, void* stream) {
-  AKI_CLEAR_ERR();
-  AKI_CHECK_ARG(logits && next_ids && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && n_eos >= 0 && (n_eos == 0 || eos_ids));
-  AKI_CHECK_ARG((!tokens || tokens_ld > 0) && (!advance || cache_len) && (advance == 0 || advance == 1));
-  AKI_CHECK_ARG(embed_weight && next_embeds && d > 0 && d % 8 == 0 && max_original_id >= 0 && num_additional >= 0);
-  AKI_CHECK_ARG((((uintptr_t)embed_weight | (uintptr_t)additional_weight | (uintptr_t)next_embeds) & 15) == 0);
-  // every id the pick can produce has a row: V' = original rows + additional rows (DecoupledLinear's output width), pad included
-  AKI_CHECK_ARG((int64_t)V <= max_original_id + 1 + (additional_weight ? num_additional : 0) && pad_token_id >= 0 &&
-                pad_token_id <= max_original_id + (additional_weight ? num_additional : 0));
-  return greedy_pick_launch(logits, B, V, (int)ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
-                            done_at, embed_weight, additional_weight, max_original_id, d, next_embeds, (hipStream_t)stream);
+  PickCall c = pick_common(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
+                           done_at);
+  pick_embed(c, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds);
+  c.embed_required = true;
+  return pick_call(c, stream);
 }
 
-// the processor arguments shared by aki_logits_process and aki_greedy_pick_processed (include/aki_mi355x.h)
-static bool processors_ok(int32_t V, float penalty, int32_t ngram, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
-                          const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
-                          int32_t n_bad, int32_t n_bad_ids) {
-  return V <= AKI_LOGITS_PROCESS_MAX_V && penalty > 0.f && penalty <= 3.0e38f && ngram >= 0 && min_length >= 0 && n_suppress >= 0 &&
-         (n_suppress == 0 || suppress_ids) && n_begin_suppress >= 0 && (n_begin_suppress == 0 || begin_suppress_ids) && n_bad >= 0 &&
-         n_bad_ids >= n_bad && (n_bad == 0 || (bad_ids && bad_offsets));
+// the 15 + 6 + 2 + 11 arguments aki_greedy_pick_processed, its constrained forms and the scalar-processor samplers begin with
+static PickCall pick_processed(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                               uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                               int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight,
+                               int64_t max_original_id, int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores,
+                               float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids,
+                               int32_t n_suppress, const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids,
+                               const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids) {
+  PickCall c = pick_common(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
+                           done_at);
+  pick_embed(c, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds);
+  pick_scratch(c, scores, ld_scores);
+  proc_values(c.q, repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids,
+              bad_offsets, n_bad, n_bad_ids);
+  return c;
 }
 
-// The constrained forms (include/aki_mi355x.h): a device table with a row for every state and a state history with at least its start column.
-static bool constraint_ok(int32_t V, const int16_t* table, int64_t table_ld, int32_t n_states, const int32_t* states, int32_t states_ld) {
-  return table && states && n_states > 0 && n_states <= 32767 && table_ld >= V && table_ld < (1ll << 31) && states_ld >= 1;
-}
-
-// The per-row forms: the table is a pool of n_states rows (any positive count: a row's own automaton stays below 32768 states, the pool
-// need not), and every row names its slice.  The arrays' values are the caller's: the kernel cuts a slice at the pool's end.
-static bool constraint_rows_ok(int32_t V, const int16_t* table, int64_t table_ld, int32_t n_states, const int32_t* states, int32_t states_ld,
-                               const int32_t* row_base, const int32_t* row_states) {
-  return table && states && row_base && row_states && n_states > 0 && table_ld >= V && table_ld < (1ll << 31) && states_ld >= 1;
-}
-
-// the shared bodies: the plain entry points hand over a null constraint and launch exactly what they launched before
-static int logits_process_checked(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
-                                  const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step,
-                                  const uint8_t* done, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length,
-                                  const int64_t* eos_ids, int32_t n_eos, const int64_t* suppress_ids, int32_t n_suppress,
-                                  const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids,
-                                  const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
-  AKI_CLEAR_ERR();
-  AKI_CHECK_ARG(logits && out && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && ld_out >= V && ld_out < (1ll << 31) && step >= 0);
-  AKI_CHECK_ARG((!tokens || tokens_ld > 0) && n_eos >= 0 && (n_eos == 0 || eos_ids));
-  AKI_CHECK_ARG(processors_ok(V, repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
-                              n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids));
-  if (dtype != AKI_DT_BF16 && dtype != AKI_DT_F32) return AKI_ERR_UNSUPPORTED;
-  return logits_process_launch(logits, dtype == AKI_DT_F32, B, V, (int)ld, out, (int)ld_out, tokens, tokens_ld, cache_len, start_len, step, done,
-                               repetition_penalty, no_repeat_ngram_size, min_length, eos_ids, n_eos, suppress_ids, n_suppress,
-                               begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids, table, (int)table_ld, n_states, states, states_ld, (hipStream_t)stream);
-}
-
-int aki_logits_process(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out, const int64_t* tokens,
-                       int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step, const uint8_t* done,
-                       float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* eos_ids, int32_t n_eos,
-                       const int64_t* suppress_ids, int32_t n_suppress, const int64_t* begin_suppress_ids, int32_t n_begin_suppress,
-                       const int64_t* bad_ids, const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, void* stream) {
-  return logits_process_checked(logits, dtype, B, V, ld, out, ld_out, tokens, tokens_ld, cache_len, start_len, step, done, repetition_penalty,
-                                no_repeat_ngram_size, min_length, eos_ids, n_eos, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress,
-                                bad_ids, bad_offsets, n_bad, n_bad_ids, nullptr, 0, 0, nullptr, 0, stream);
-}
-
-int aki_logits_process_constrained(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
-                                   const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step,
-                                   const uint8_t* done, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length,
-                                   const int64_t* eos_ids, int32_t n_eos, const int64_t* suppress_ids, int32_t n_suppress,
-                                   const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids,
-                                   const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld,
-                                   int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
-  AKI_CLEAR_ERR();
-  AKI_CHECK_ARG(V > 0 && constraint_ok(V, table, table_ld, n_states, states, states_ld));
-  return logits_process_checked(logits, dtype, B, V, ld, out, ld_out, tokens, tokens_ld, cache_len, start_len, step, done, repetition_penalty,
-                                no_repeat_ngram_size, min_length, eos_ids, n_eos, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress,
-                                bad_ids, bad_offsets, n_bad, n_bad_ids, table, table_ld, n_states, states, states_ld, stream);
-}
-
-static int greedy_pick_processed_checked(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
-                                         uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
-                                         int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
-                                         int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
-                                         int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
-                                         const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
-                                         int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld,
-                                         const int32_t* row_base, const int32_t* row_states, void* stream) {
-  AKI_CLEAR_ERR();
-  AKI_CHECK_ARG(logits && next_ids && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && n_eos >= 0 && (n_eos == 0 || eos_ids));
-  AKI_CHECK_ARG((!tokens || tokens_ld > 0) && (!advance || cache_len) && (advance == 0 || advance == 1));
-  AKI_CHECK_ARG(scores && ld_scores >= V && ld_scores < (1ll << 31));
-  AKI_CHECK_ARG(processors_ok(V, repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
-                              n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids));
-  if ((((uintptr_t)scores) & 15) != 0 || (ld_scores & 3) != 0) return AKI_ERR_ALIGNMENT;
-  if (embed_weight) {
-    AKI_CHECK_ARG(next_embeds && d > 0 && d % 8 == 0 && max_original_id >= 0 && num_additional >= 0);
-    AKI_CHECK_ARG((((uintptr_t)embed_weight | (uintptr_t)additional_weight | (uintptr_t)next_embeds) & 15) == 0);
-    AKI_CHECK_ARG((int64_t)V <= max_original_id + 1 + (additional_weight ? num_additional : 0) && pad_token_id >= 0 &&
-                  pad_token_id <= max_original_id + (additional_weight ? num_additional : 0));
-  } else {
-    AKI_CHECK_ARG(!additional_weight && !next_embeds);
-  }
-  return greedy_pick_processed_launch(logits, B, V, (int)ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len,
-                                      advance, done_at, embed_weight, additional_weight, max_original_id, d, next_embeds, scores, (int)ld_scores,
-                                      repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
-                                      n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids, table, (int)table_ld, n_states, states, states_ld, row_base,
-                                      row_states, (hipStream_t)stream);
+// the 15 + 6 + 2 + 7 arguments the per-row processor picks begin with; their constraint is per row, and optional
+static PickCall pick_processed_rows(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos,
+                                    int64_t pad_token_id, uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld,
+                                    int32_t* cache_len, const int32_t* start_len, int32_t advance, int32_t* done_at, const void* embed_weight,
+                                    const void* additional_weight, int64_t max_original_id, int64_t num_additional, int32_t d,
+                                    void* next_embeds, float* scores, int64_t ld_scores, const int32_t* sets, int32_t n_sets,
+                                    const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets,
+                                    int32_t n_words) {
+  PickCall c = pick_common(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
+                           done_at);
+  pick_embed(c, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds);
+  pick_scratch(c, scores, ld_scores);
+  c.ps = proc_sets(sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words);
+  c.sets = true;
+  return c;
 }
 
 int aki_greedy_pick_processed(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -926,10 +974,11 @@ int aki_greedy_pick_processed(const void* logits, int32_t B, int32_t V, int64_t 
                               int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
                               const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
                               int32_t n_bad, int32_t n_bad_ids, void* stream) {
-  return greedy_pick_processed_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
-                                       embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
-                                       no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
-                                       n_bad_ids, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, stream);
+  const PickCall c = pick_processed(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
+                                    done_at, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores,
+                                    repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
+                                    n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids);
+  return pick_call(c, stream);
 }
 
 int aki_greedy_pick_constrained(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -939,12 +988,12 @@ int aki_greedy_pick_constrained(const void* logits, int32_t B, int32_t V, int64_
                                 int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
                                 const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
                                 int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
-  AKI_CLEAR_ERR();
-  AKI_CHECK_ARG(V > 0 && constraint_ok(V, table, table_ld, n_states, states, states_ld));
-  return greedy_pick_processed_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
-                                       embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
-                                       no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
-                                       n_bad_ids, table, table_ld, n_states, states, states_ld, nullptr, nullptr, stream);
+  PickCall c = pick_processed(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
+                              done_at, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores,
+                              repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
+                              n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids);
+  pick_constraint(c, CON_WIDE, constraint(table, table_ld, n_states, states, states_ld), table_ld);
+  return pick_call(c, stream);
 }
 
 int aki_greedy_pick_constrained_rows(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -955,50 +1004,12 @@ int aki_greedy_pick_constrained_rows(const void* logits, int32_t B, int32_t V, i
                                      const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
                                      int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states,
                                      int32_t states_ld, const int32_t* row_base, const int32_t* row_states, void* stream) {
-  AKI_CLEAR_ERR();
-  AKI_CHECK_ARG(V > 0 && constraint_rows_ok(V, table, table_ld, n_states, states, states_ld, row_base, row_states));
-  return greedy_pick_processed_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
-                                       embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
-                                       no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
-                                       n_bad_ids, table, table_ld, n_states, states, states_ld, row_base, row_states, stream);
-}
-
-// aki_sample_pick_rows' four device arrays of B entries, in the scalars' place (nullptr: the scalar form)
-struct SampleRowArrays { const float* temperature; const int32_t* top_k; const float* top_p; const uint64_t* seed; };
-
-static int sample_pick_checked(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
-                               uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
-                               int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
-                               int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
-                               int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
-                               const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
-                               int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
-                               uint64_t offset, const SampleRowArrays* rows, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld,
-                               const int32_t* row_base, const int32_t* row_states, void* stream) {
-  AKI_CLEAR_ERR();
-  AKI_CHECK_ARG(logits && next_ids && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && n_eos >= 0 && (n_eos == 0 || eos_ids));
-  AKI_CHECK_ARG((!tokens || tokens_ld > 0) && (!advance || cache_len) && (advance == 0 || advance == 1) && step >= 0);
-  AKI_CHECK_ARG(scores && ld_scores >= V && ld_scores < (1ll << 31));
-  AKI_CHECK_ARG(processors_ok(V, repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
-                              n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids));
-  if (rows) AKI_CHECK_ARG(rows->temperature && rows->top_k && rows->top_p && rows->seed);     // device arrays: their values are the caller's to check
-  else AKI_CHECK_ARG(temperature > 0.f && temperature <= 3.0e38f && top_p > 0.f && top_p <= 1.f && top_k >= 0);
-  AKI_CHECK_ARG(!probs_out || (ld_probs >= V && ld_probs < (1ll << 31)));
-  if ((((uintptr_t)scores) & 15) != 0 || (ld_scores & 3) != 0) return AKI_ERR_ALIGNMENT;
-  if (embed_weight) {
-    AKI_CHECK_ARG(next_embeds && d > 0 && d % 8 == 0 && max_original_id >= 0 && num_additional >= 0);
-    AKI_CHECK_ARG((((uintptr_t)embed_weight | (uintptr_t)additional_weight | (uintptr_t)next_embeds) & 15) == 0);
-    AKI_CHECK_ARG((int64_t)V <= max_original_id + 1 + (additional_weight ? num_additional : 0) && pad_token_id >= 0 &&
-                  pad_token_id <= max_original_id + (additional_weight ? num_additional : 0));
-  } else {
-    AKI_CHECK_ARG(!additional_weight && !next_embeds);
-  }
-  return sample_pick_launch(logits, B, V, (int)ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
-                            done_at, embed_weight, additional_weight, max_original_id, d, next_embeds, scores, (int)ld_scores, repetition_penalty,
-                            no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets,
-                            n_bad, n_bad_ids, step, temperature, top_k, top_p, seed, offset, rows ? rows->temperature : nullptr, rows ? rows->top_k : nullptr,
-                            rows ? rows->top_p : nullptr, rows ? rows->seed : nullptr, probs_out, (int)ld_probs, table, (int)table_ld, n_states, states, states_ld,
-                            row_base, row_states, (hipStream_t)stream);
+  PickCall c = pick_processed(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
+                              done_at, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores,
+                              repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
+                              n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids);
+  pick_constraint(c, CON_ROWS, constraint(table, table_ld, n_states, states, states_ld, row_base, row_states), table_ld);
+  return pick_call(c, stream);
 }
 
 int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -1009,10 +1020,12 @@ int aki_sample_pick(const void* logits, int32_t B, int32_t V, int64_t ld, const 
                     const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
                     int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
                     uint64_t offset, float* probs_out, int64_t ld_probs, void* stream) {
-  return sample_pick_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
-                             embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
-                             no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
-                             n_bad_ids, step, temperature, top_k, top_p, seed, offset, nullptr, probs_out, ld_probs, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, stream);
+  PickCall c = pick_processed(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
+                              done_at, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores,
+                              repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
+                              n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids);
+  pick_sampler(c, step, temperature, top_k, top_p, seed, offset, probs_out, ld_probs);
+  return pick_call(c, stream);
 }
 
 int aki_sample_pick_rows(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -1023,11 +1036,12 @@ int aki_sample_pick_rows(const void* logits, int32_t B, int32_t V, int64_t ld, c
                          const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
                          int32_t n_bad, int32_t n_bad_ids, int32_t step, const float* temperature, const int32_t* top_k, const float* top_p,
                          const uint64_t* seed, float* probs_out, int64_t ld_probs, void* stream) {
-  const SampleRowArrays rows = {temperature, top_k, top_p, seed};
-  return sample_pick_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
-                             embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
-                             no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
-                             n_bad_ids, step, 1.f, 0, 1.f, 0ull, 0ull, &rows, probs_out, ld_probs, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, stream);
+  PickCall c = pick_processed(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
+                              done_at, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores,
+                              repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
+                              n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids);
+  pick_sampler_rows(c, step, temperature, top_k, top_p, seed, probs_out, ld_probs);
+  return pick_call(c, stream);
 }
 
 int aki_sample_pick_rows_constrained(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -1040,14 +1054,13 @@ int aki_sample_pick_rows_constrained(const void* logits, int32_t B, int32_t V, i
                                      const float* top_p, const uint64_t* seed, float* probs_out, int64_t ld_probs, const int16_t* table,
                                      int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld, const int32_t* row_base,
                                      const int32_t* row_states, void* stream) {
-  AKI_CLEAR_ERR();
-  AKI_CHECK_ARG(V > 0 && constraint_rows_ok(V, table, table_ld, n_states, states, states_ld, row_base, row_states));
-  const SampleRowArrays rows = {temperature, top_k, top_p, seed};
-  return sample_pick_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
-                             embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
-                             no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
-                             n_bad_ids, step, 1.f, 0, 1.f, 0ull, 0ull, &rows, probs_out, ld_probs, table, table_ld, n_states, states, states_ld,
-                             row_base, row_states, stream);
+  PickCall c = pick_processed(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
+                              done_at, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores,
+                              repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
+                              n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids);
+  pick_sampler_rows(c, step, temperature, top_k, top_p, seed, probs_out, ld_probs);
+  pick_constraint(c, CON_ROWS, constraint(table, table_ld, n_states, states, states_ld, row_base, row_states), table_ld);
+  return pick_call(c, stream);
 }
 
 int aki_sample_pick_constrained(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -1058,70 +1071,13 @@ int aki_sample_pick_constrained(const void* logits, int32_t B, int32_t V, int64_
                                 const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
                                 int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
                                 uint64_t offset, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
-  AKI_CLEAR_ERR();
-  AKI_CHECK_ARG(V > 0 && constraint_ok(V, table, table_ld, n_states, states, states_ld));
-  return sample_pick_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
-                             embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, repetition_penalty,
-                             no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids, bad_offsets, n_bad,
-                             n_bad_ids, step, temperature, top_k, top_p, seed, offset, nullptr, probs_out, ld_probs, table, table_ld, n_states, states, states_ld, nullptr, nullptr, stream);
-}
-
-// The per-row processor forms (include/aki_mi355x.h): the pool's arrays and the rows' set indices.  Their VALUES are the caller's: the
-// kernel reads a set index outside the pool as the neutral set and cuts every range at the pools' ends.
-static bool processor_sets_ok(int32_t V, const int32_t* sets, int32_t n_sets, const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids,
-                              const int32_t* bad_offsets, int32_t n_words) {
-  return V <= AKI_LOGITS_PROCESS_MAX_V && sets && n_sets > 0 && row_set && n_set_ids >= 0 && (n_set_ids == 0 || set_ids) && n_words >= 0 &&
-         (n_words == 0 || (bad_offsets && set_ids));
-}
-
-// a NULL table: no constraint, the other six are not looked at
-static bool constraint_rows_or_none_ok(int32_t V, const int16_t* table, int64_t table_ld, int32_t n_states, const int32_t* states,
-                                       int32_t states_ld, const int32_t* row_base, const int32_t* row_states) {
-  return !table || constraint_rows_ok(V, table, table_ld, n_states, states, states_ld, row_base, row_states);
-}
-
-int aki_logits_process_rows(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
-                            const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step,
-                            const uint8_t* done, const int64_t* eos_ids, int32_t n_eos, const int32_t* sets, int32_t n_sets,
-                            const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets, int32_t n_words,
-                            const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld,
-                            const int32_t* row_base, const int32_t* row_states, void* stream) {
-  AKI_CLEAR_ERR();
-  AKI_CHECK_ARG(logits && out && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && ld_out >= V && ld_out < (1ll << 31) && step >= 0);
-  AKI_CHECK_ARG((!tokens || tokens_ld > 0) && n_eos >= 0 && (n_eos == 0 || eos_ids));
-  AKI_CHECK_ARG(processor_sets_ok(V, sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words));
-  AKI_CHECK_ARG(constraint_rows_or_none_ok(V, table, table_ld, n_states, states, states_ld, row_base, row_states));
-  if (dtype != AKI_DT_BF16 && dtype != AKI_DT_F32) return AKI_ERR_UNSUPPORTED;
-  const bool con = table != nullptr;
-  return logits_process_rows_launch(logits, dtype == AKI_DT_F32, B, V, (int)ld, out, (int)ld_out, tokens, tokens_ld, cache_len, start_len, step,
-                                    done, eos_ids, n_eos, sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words, table,
-                                    con ? (int)table_ld : 0, con ? n_states : 0, con ? states : nullptr, con ? states_ld : 0,
-                                    con ? row_base : nullptr, con ? row_states : nullptr, (hipStream_t)stream);
-}
-
-// what aki_greedy_pick_rows and aki_sample_pick_rows_processed check alike
-static int pick_rows_checked(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
-                             const int64_t* next_ids, const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, int32_t advance,
-                             const void* embed_weight, const void* additional_weight, int64_t max_original_id, int64_t num_additional, int32_t d,
-                             const void* next_embeds, const float* scores, int64_t ld_scores, const int32_t* sets, int32_t n_sets,
-                             const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets, int32_t n_words,
-                             const int16_t* table, int64_t table_ld, int32_t n_states, const int32_t* states, int32_t states_ld,
-                             const int32_t* row_base, const int32_t* row_states) {
-  AKI_CHECK_ARG(logits && next_ids && B > 0 && V > 0 && ld >= V && ld < (1ll << 31) && n_eos >= 0 && (n_eos == 0 || eos_ids));
-  AKI_CHECK_ARG((!tokens || tokens_ld > 0) && (!advance || cache_len) && (advance == 0 || advance == 1));
-  AKI_CHECK_ARG(scores && ld_scores >= V && ld_scores < (1ll << 31));
-  AKI_CHECK_ARG(processor_sets_ok(V, sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words));
-  AKI_CHECK_ARG(constraint_rows_or_none_ok(V, table, table_ld, n_states, states, states_ld, row_base, row_states));
-  if ((((uintptr_t)scores) & 15) != 0 || (ld_scores & 3) != 0) return AKI_ERR_ALIGNMENT;
-  if (embed_weight) {
-    AKI_CHECK_ARG(next_embeds && d > 0 && d % 8 == 0 && max_original_id >= 0 && num_additional >= 0);
-    AKI_CHECK_ARG((((uintptr_t)embed_weight | (uintptr_t)additional_weight | (uintptr_t)next_embeds) & 15) == 0);
-    AKI_CHECK_ARG((int64_t)V <= max_original_id + 1 + (additional_weight ? num_additional : 0) && pad_token_id >= 0 &&
-                  pad_token_id <= max_original_id + (additional_weight ? num_additional : 0));
-  } else {
-    AKI_CHECK_ARG(!additional_weight && !next_embeds);
-  }
-  return AKI_OK;
+  PickCall c = pick_processed(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
+                              done_at, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores,
+                              repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
+                              n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids);
+  pick_sampler(c, step, temperature, top_k, top_p, seed, offset, probs_out, ld_probs);
+  pick_constraint(c, CON_WIDE, constraint(table, table_ld, n_states, states, states_ld), table_ld);
+  return pick_call(c, stream);
 }
 
 int aki_greedy_pick_rows(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
@@ -1131,17 +1087,11 @@ int aki_greedy_pick_rows(const void* logits, int32_t B, int32_t V, int64_t ld, c
                          int32_t n_sets, const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets,
                          int32_t n_words, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld,
                          const int32_t* row_base, const int32_t* row_states, void* stream) {
-  AKI_CLEAR_ERR();
-  const int rc = pick_rows_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, next_ids, tokens, tokens_ld, cache_len, advance, embed_weight,
-                                   additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, sets, n_sets, row_set,
-                                   set_ids, n_set_ids, bad_offsets, n_words, table, table_ld, n_states, states, states_ld, row_base, row_states);
-  if (rc != AKI_OK) return rc;
-  const bool con = table != nullptr;
-  return greedy_pick_rows_launch(logits, B, V, (int)ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len,
-                                 advance, done_at, embed_weight, additional_weight, max_original_id, d, next_embeds, scores, (int)ld_scores, sets,
-                                 n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words, table, con ? (int)table_ld : 0, con ? n_states : 0,
-                                 con ? states : nullptr, con ? states_ld : 0, con ? row_base : nullptr, con ? row_states : nullptr,
-                                 (hipStream_t)stream);
+  PickCall c = pick_processed_rows(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len,
+                                   advance, done_at, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores,
+                                   ld_scores, sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words);
+  pick_constraint(c, CON_ROWS_OR_NONE, constraint(table, table_ld, n_states, states, states_ld, row_base, row_states), table_ld);
+  return pick_call(c, stream);
 }
 
 int aki_sample_pick_rows_processed(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos,
@@ -1154,20 +1104,61 @@ int aki_sample_pick_rows_processed(const void* logits, int32_t B, int32_t V, int
                                    const uint64_t* seed, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld,
                                    int32_t n_states, int32_t* states, int32_t states_ld, const int32_t* row_base, const int32_t* row_states,
                                    void* stream) {
+  PickCall c = pick_processed_rows(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len,
+                                   advance, done_at, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores,
+                                   ld_scores, sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words);
+  pick_sampler_rows(c, step, temperature, top_k, top_p, seed, probs_out, ld_probs);
+  pick_constraint(c, CON_ROWS_OR_NONE, constraint(table, table_ld, n_states, states, states_ld, row_base, row_states), table_ld);
+  return pick_call(c, stream);
+}
+
+// aki_logits_process*: q as proc_common / proc_values filled it, ps the per-row sets or nullptr; ld / ld_out / table_ld as the caller passed them
+static int logits_process_call(const ProcParams& q, const ProcSetParams* ps, int32_t B, int64_t ld, int64_t ld_out, int32_t dtype, int kind,
+                               int64_t table_ld, void* stream) {
   AKI_CLEAR_ERR();
-  const int rc = pick_rows_checked(logits, B, V, ld, eos_ids, n_eos, pad_token_id, next_ids, tokens, tokens_ld, cache_len, advance, embed_weight,
-                                   additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores, sets, n_sets, row_set,
-                                   set_ids, n_set_ids, bad_offsets, n_words, table, table_ld, n_states, states, states_ld, row_base, row_states);
-  if (rc != AKI_OK) return rc;
-  AKI_CHECK_ARG(step >= 0 && temperature && top_k && top_p && seed);
-  AKI_CHECK_ARG(!probs_out || (ld_probs >= V && ld_probs < (1ll << 31)));
-  const bool con = table != nullptr;
-  return sample_pick_rows_processed_launch(logits, B, V, (int)ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len,
-                                           start_len, advance, done_at, embed_weight, additional_weight, max_original_id, d, next_embeds, scores,
-                                           (int)ld_scores, sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words, step, temperature,
-                                           top_k, top_p, seed, probs_out, (int)ld_probs, table, con ? (int)table_ld : 0, con ? n_states : 0,
-                                           con ? states : nullptr, con ? states_ld : 0, con ? row_base : nullptr, con ? row_states : nullptr,
-                                           (hipStream_t)stream);
+  AKI_CHECK_ARG(q.in && q.out && B > 0 && q.V > 0 && ld >= q.V && ld < (1ll << 31) && ld_out >= q.V && ld_out < (1ll << 31) && q.step >= 0);
+  AKI_CHECK_ARG((!q.tokens || q.tokens_ld > 0) && q.n_eos >= 0 && (q.n_eos == 0 || q.eos));
+  AKI_CHECK_ARG(ps ? processor_sets_ok(q.V, *ps) : processors_ok(q));
+  AKI_CHECK_ARG(constraint_ok(kind, q.V, q.c, table_ld));
+  if (dtype != AKI_DT_BF16 && dtype != AKI_DT_F32) return AKI_ERR_UNSUPPORTED;
+  return logits_process_call_launch(q, ps, B, (hipStream_t)stream);
+}
+
+int aki_logits_process(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out, const int64_t* tokens,
+                       int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step, const uint8_t* done,
+                       float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* eos_ids, int32_t n_eos,
+                       const int64_t* suppress_ids, int32_t n_suppress, const int64_t* begin_suppress_ids, int32_t n_begin_suppress,
+                       const int64_t* bad_ids, const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, void* stream) {
+  ProcParams q = proc_common(logits, dtype == AKI_DT_F32, ld, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, eos_ids, n_eos);
+  proc_values(q, repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids,
+              bad_offsets, n_bad, n_bad_ids);
+  return logits_process_call(q, nullptr, B, ld, ld_out, dtype, CON_NONE, 0, stream);
+}
+
+int aki_logits_process_constrained(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
+                                   const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step,
+                                   const uint8_t* done, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length,
+                                   const int64_t* eos_ids, int32_t n_eos, const int64_t* suppress_ids, int32_t n_suppress,
+                                   const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids,
+                                   const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld,
+                                   int32_t n_states, int32_t* states, int32_t states_ld, void* stream) {
+  ProcParams q = proc_common(logits, dtype == AKI_DT_F32, ld, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, eos_ids, n_eos);
+  proc_values(q, repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids,
+              bad_offsets, n_bad, n_bad_ids);
+  q.c = constraint(table, table_ld, n_states, states, states_ld);
+  return logits_process_call(q, nullptr, B, ld, ld_out, dtype, CON_WIDE, table_ld, stream);
+}
+
+int aki_logits_process_rows(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
+                            const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step,
+                            const uint8_t* done, const int64_t* eos_ids, int32_t n_eos, const int32_t* sets, int32_t n_sets,
+                            const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets, int32_t n_words,
+                            const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states, int32_t states_ld,
+                            const int32_t* row_base, const int32_t* row_states, void* stream) {
+  ProcParams q = proc_common(logits, dtype == AKI_DT_F32, ld, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, eos_ids, n_eos);
+  q.c = constraint(table, table_ld, n_states, states, states_ld, row_base, row_states);
+  const ProcSetParams ps = proc_sets(sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words);
+  return logits_process_call(q, &ps, B, ld, ld_out, dtype, CON_ROWS_OR_NONE, table_ld, stream);
 }
 
 int aki_beam_logprob(const void* logits, int32_t dtype, int32_t rows, int32_t V, int64_t ld, float* out, int64_t ld_out, void* stream) {

@@ -19,6 +19,7 @@
 
 #include "aki_device.h"
 #include "decode_attn_common.h"
+#include "pick_params.h"
 
 namespace aki {
 
@@ -1481,18 +1482,8 @@ int decode_attn_launch(const void* q, const void* kc, const void* vc, void* o, c
 // ---- greedy token pick: what the reference's generate loop does between two decode steps (HF GenerationMixin greedy branch:
 // argmax over the vocabulary, finished rows take pad_token_id, append, eos check; src/aki.py:136-209 hands its kwargs to it) as
 // ONE launch that can sit inside the replayed step - the loop's five small launches and its per-token host sync were 4 % of a token.
-// Ties go to the lower index and a NaN outranks every number (torch.argmax's ordering).
-struct PickParams {
-  const bf16_t* logits; int B, V, ld;
-  const int64_t* eos; int n_eos; int64_t pad;
-  unsigned char* done; int64_t* ids; int64_t* tokens; int tokens_ld;
-  int* cache_len; const int* start_len; int advance; int* done_at;
-  // optional: the NEXT decode step's input row, gathered here (DecoupledEmbedding, src/helpers.py:350-492: ids above max_original_id index the
-  // additional table) so that a greedy token needs no embedding launch
-  const bf16_t* emb_main; const bf16_t* emb_extra; int64_t max_original_id; int d; bf16_t* emb_out;
-  int step;   // added to t (the sampler's eager loop passes the token index here when it has no cache_len); 0 for the greedy picks
-};
-
+// Ties go to the lower index and a NaN outranks every number (torch.argmax's ordering).  PickParams and the other parameter structs of
+// this section: pick_params.h.
 __device__ __forceinline__ bool pick_better(float a, int ia, float b, int ib) {
   const bool na = a != a, nb = b != b;
   if (na != nb) return na;
@@ -1500,20 +1491,7 @@ __device__ __forceinline__ bool pick_better(float a, int ia, float b, int ib) {
   return a > b || (a == b && ia < ib);
 }
 
-// Constrained decoding (aki_amd/constraint.py): a deterministic automaton over token ids.  table[s, v] is the state behind token v in state
-// s, negative = v is not allowed in s; states[b, n] is the state in which row b picks its generated token n (column 0: the start state).
-// The state is addressed by the token index, like the processors' history, never carried in a counter: a replayed graph, a rewind of
-// cache_len after a chain give-up and a repeated step then read and write the right column with nothing to reset.
-// The per-row form (row_base and row_states set, both or neither): `table` is a POOL of n_states rows holding several automata one behind
-// the other, each with its own state numbers from 0; row b's automaton is the row_states[b] pool rows from row_base[b] on.  Both arrays
-// are read by the launch, so a captured step serves a row whose automaton is replaced in place between replays (generate_many's admit).
-struct ConstraintParams {
-  const int16_t* table; int table_ld, n_states;
-  int* states; int states_ld;
-  const int* row_base; const int* row_states;
-};
-
-// The table rows row b's states index: [base, base + count).  Without the per-row arrays that is the whole table; with them the row's own
+// Constrained decoding (ConstraintParams, pick_params.h).  The table rows row b's states index: [base, base + count).  Without the per-row arrays that is the whole table; with them the row's own
 // slice, cut at the pool's end (a negative base: no rows at all, the row is left untouched).
 struct ConstraintRow { int base, count; };
 __device__ __forceinline__ ConstraintRow constraint_row(const ConstraintParams* c, int b) {
@@ -1669,17 +1647,6 @@ __device__ __forceinline__ void greedy_pick_row(const PickParams& p, const float
 
 __global__ __launch_bounds__(PICK_THREADS) void greedy_pick_kernel(const PickParams p) { greedy_pick_row<false>(p, nullptr); }
 
-int greedy_pick_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done, int64_t* ids,
-                       int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at, const void* emb_main,
-                       const void* emb_extra, int64_t max_original_id, int d, void* emb_out, hipStream_t s) {
-  PickParams p = {(const bf16_t*)logits, B, V, ld, eos, n_eos, pad, done, ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
-                  (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out};
-  AKI_CLEAR_ERR();
-  hipLaunchKernelGGL(greedy_pick_kernel, dim3(B), dim3(PICK_THREADS), 0, s, p);
-  AKI_LAUNCH_CHECK();
-  return AKI_OK;
-}
-
 
 // ---- logits processors: what HF `generate` applies to a step's f32 scores before it picks (GenerationMixin._get_logits_processor, in its
 // order), for the case the reference runs - a decoder-only model called with inputs_embeds only, so the processors' input_ids are the row's
@@ -1692,22 +1659,7 @@ int greedy_pick_launch(const void* logits, int B, int V, int ld, const int64_t* 
 //   5 suppress tokens     -inf always; begin-suppress tokens -inf at n == 0
 //   6 token constraint    (not HF's: ConstraintParams above) -inf for every token the row's state states[b, n] does not allow, n unclamped
 // n = step + (cache_len ? cache_len[b] - start_len[b] : 0), so that one captured graph serves every replay.  Rows with done[b] set get the
-// plain f32 copy.  One workgroup per row, O(V + n * ngram + bad-word ids); ids outside [0, V) are skipped.
-struct ProcParams {
-  const void* in; int in_f32, ld_in;
-  float* out; int ld_out;
-  int V;
-  const int64_t* tokens; int tokens_ld;
-  const int* cache_len; const int* start_len; int step;
-  const unsigned char* done;
-  float penalty; int ngram, min_len;
-  const int64_t* eos; int n_eos;
-  const int64_t* suppress; int n_suppress;
-  const int64_t* begin_suppress; int n_begin;
-  const int64_t* bad_ids; const int* bad_off; int n_bad, n_bad_ids;
-  ConstraintParams c;                 // c.table == nullptr: no constraint
-};
-
+// plain f32 copy.  One workgroup per row, O(V + n * ngram + bad-word ids); ids outside [0, V) are skipped.  (ProcParams: pick_params.h)
 constexpr int PROC_MAX_V = 131072;   // the repetition penalty's LDS bitmap: 16 KB
 
 __device__ __forceinline__ void ban(float* out, int V, int64_t g) {
@@ -1830,24 +1782,7 @@ __global__ __launch_bounds__(PICK_THREADS) void greedy_pick_processed_kernel(con
 // The histograms are 64-bit INTEGERS (the mass as 2^-40 fixed point) filled with integer atomics, so the result does not depend on the
 // order the atomics land in: run-to-run deterministic without a float atomic.  The draw is a counter-based Philox4x32-10 word per
 // (token index, row, call), inverted through the cumulative sum in index order: per-thread chunk sums and a fixed-order block scan.
-struct SampleParams {
-  float temperature; int top_k; float top_p;
-  unsigned seed_lo, seed_hi, off_lo, off_hi;
-  float* probs; int ld_probs;
-  int processed;                                            // the processors ran: x is the f32 scratch row, not the bf16 logits
-};
-
-// The per-row form (aki_sample_pick_rows): row b reads its own temperature[b], top_k[b], top_p[b] and Philox key seed[b] from device
-// arrays of B entries, and draws with the counter (n, 0, 0, 0) - the stream belongs to the row's seed, not to the row index, so it is the
-// draw row 0 of a batch-1 scalar call with that seed and offset 0 makes.  One workgroup per row: the values are workgroup-uniform.
-// Nothing validates the arrays on the device; bad bits stay inside the row: a temperature that is not > 0 (zero, negative, NaN) takes
-// the greedy pick, top_k[b] <= 0 or >= V is no top-k filter, top_p[b] >= 1 is no top-p filter (and a top_p that is not > 0 keeps the
-// maximum only).  top_k[b] == 1 is the greedy branch, as in the scalar form.
-struct SampleRowParams {
-  const float* temperature; const int* top_k; const float* top_p; const unsigned long long* seed;
-  float* probs; int ld_probs;
-  int processed;
-};
+// SampleParams and SampleRowParams (the per-row form, aki_sample_pick_rows): pick_params.h.
 template <bool ROWS> struct SampleArgs { using type = SampleParams; };
 template <> struct SampleArgs<true> { using type = SampleRowParams; };
 
@@ -2133,11 +2068,7 @@ __global__ __launch_bounds__(PICK_THREADS) void sample_pick_kernel(const PickPar
 // outside [0, n_sets) is the neutral set, ranges are cut at the pools' ends, a penalty that is not finite and positive is 1, and
 // process_row skips ids outside [0, V) and cuts bad_off itself.  One workgroup serves one row and every thread reads the same words, so
 // what process_row branches on around its barriers stays workgroup-uniform; the words are moved to scalar registers to say so.
-constexpr int PROC_SET_WORDS = 9;
-struct ProcSetParams {
-  const int* sets; int n_sets; const int* row_set;
-  const int64_t* ids; int n_ids; const int* bad_off; int n_words;
-};
+// (PROC_SET_WORDS and ProcSetParams: pick_params.h)
 
 // q with row b's record in the place of the call-wide processor values (q's own are ignored)
 __device__ __forceinline__ ProcParams proc_row_params(const ProcParams& q, const ProcSetParams& ps, int b) {
@@ -2185,130 +2116,55 @@ __global__ __launch_bounds__(PICK_THREADS) void sample_pick_rows_processed_kerne
 }
 
 
-static ProcParams proc_params(const void* in, int in_f32, int ld_in, float* out, int ld_out, int V, const int64_t* tokens, int tokens_ld,
-                              const int* cache_len, const int* start_len, int step, const unsigned char* done, float penalty, int ngram,
-                              int min_len, const int64_t* eos, int n_eos, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress,
-                              int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad, int n_bad_ids) {
-  return ProcParams{in, in_f32, ld_in, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, penalty, ngram, min_len,
-                    eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off, n_bad, n_bad_ids, ConstraintParams{}};
-}
-
-int logits_process_launch(const void* logits, int in_f32, int B, int V, int ld, float* out, int ld_out, const int64_t* tokens, int tokens_ld,
-                          const int* cache_len, const int* start_len, int step, const unsigned char* done, float penalty, int ngram,
-                          int min_len, const int64_t* eos, int n_eos, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress,
-                          int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad, int n_bad_ids,
-                          const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, hipStream_t s) {
-  ProcParams q = proc_params(logits, in_f32, ld, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, penalty, ngram,
-                             min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off, n_bad, n_bad_ids);
-  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld, nullptr, nullptr};
+// ---- the two launchers (api.hip has checked the arguments) ----------------------------------------------------------------------------
+// aki_logits_process*: ps == nullptr is the call-wide form; with ps the processor values of q are placeholders, proc_row_params fills them
+// per row, and a NULL table is "no constraint"
+int logits_process_call_launch(const ProcParams& q_in, const ProcSetParams* ps, int B, hipStream_t s) {
+  ProcParams q = q_in;
+  if (ps != nullptr && q.c.table == nullptr) q.c = ConstraintParams{};
   AKI_CLEAR_ERR();
-  hipLaunchKernelGGL(logits_process_kernel, dim3(B), dim3(PROC_THREADS), 0, s, q);
+  if (ps != nullptr) hipLaunchKernelGGL(logits_process_rows_kernel, dim3(B), dim3(PROC_THREADS), 0, s, q, *ps);
+  else hipLaunchKernelGGL(logits_process_kernel, dim3(B), dim3(PROC_THREADS), 0, s, q);
   AKI_LAUNCH_CHECK();
   return AKI_OK;
 }
 
-int greedy_pick_processed_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done,
-                                 int64_t* ids, int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at,
-                                 const void* emb_main, const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores,
-                                 int ld_scores, float penalty, int ngram, int min_len, const int64_t* suppress, int n_suppress,
-                                 const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids, const int* bad_off, int n_bad,
-                                 int n_bad_ids, const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
-                                 const int* c_row_base, const int* c_row_states, hipStream_t s) {
-  PickParams p = {(const bf16_t*)logits, B, V, ld, eos, n_eos, pad, done, ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
-                  (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out};
-  // the processors see the tokens generated BEFORE this pick: n = cache_len + advance - start_len, the index the pick writes
-  ProcParams q = proc_params(logits, 0, ld, scores, ld_scores, V, tokens, tokens_ld, cache_len, start_len, cache_len ? advance : 0, done,
-                             penalty, ngram, min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off, n_bad,
-                             n_bad_ids);
-  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld, c_row_base, c_row_states};
+// every aki_greedy_pick* / aki_sample_pick*: one of the six pick kernels, chosen by what the descriptor holds
+int pick_call_launch(const PickCall& c, hipStream_t s) {
+  const PickParams& p = c.p;
+  ProcParams q = c.q;
+  // the processors see the tokens generated BEFORE this pick: n = step + cache_len + advance - start_len, the index the pick writes
+  q.step = p.step + (p.cache_len ? p.advance : 0);
+  if (c.sets && q.c.table == nullptr) q.c = ConstraintParams{};
+  const dim3 grid(p.B), block(PICK_THREADS);
   AKI_CLEAR_ERR();
-  hipLaunchKernelGGL(greedy_pick_processed_kernel, dim3(B), dim3(PICK_THREADS), 0, s, p, q);
-  AKI_LAUNCH_CHECK();
-  return AKI_OK;
-}
-
-int sample_pick_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done, int64_t* ids,
-                       int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at, const void* emb_main,
-                       const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores, int ld_scores, float penalty, int ngram,
-                       int min_len, const int64_t* suppress, int n_suppress, const int64_t* begin_suppress, int n_begin, const int64_t* bad_ids,
-                       const int* bad_off, int n_bad, int n_bad_ids, int step, float temperature, int top_k, float top_p, uint64_t seed,
-                       uint64_t offset, const float* row_temperature, const int* row_top_k, const float* row_top_p, const uint64_t* row_seed,
-                       float* probs, int ld_probs, const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
-                       const int* c_row_base, const int* c_row_states, hipStream_t s) {
-  PickParams p = {(const bf16_t*)logits, B, V, ld, eos, n_eos, pad, done, ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
-                  (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out, step};
-  ProcParams q = proc_params(logits, 0, ld, scores, ld_scores, V, tokens, tokens_ld, cache_len, start_len, step + (cache_len ? advance : 0),
-                             done, penalty, ngram, min_len, eos, n_eos, suppress, n_suppress, begin_suppress, n_begin, bad_ids, bad_off,
-                             n_bad, n_bad_ids);
-  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld, c_row_base, c_row_states};
-  const bool processed = penalty != 1.f || ngram > 0 || n_bad > 0 || (min_len > 0 && n_eos > 0) || n_suppress > 0 || n_begin > 0 || c_table != nullptr;
-  const SampleParams sp = {temperature, top_k, top_p, (unsigned)seed, (unsigned)(seed >> 32), (unsigned)offset, (unsigned)(offset >> 32),
-                           probs, ld_probs, processed ? 1 : 0};
-  AKI_CLEAR_ERR();
-  if (row_seed != nullptr) {                                // the per-row form: the four arrays stand in for the scalars
-    const SampleRowParams sr = {row_temperature, row_top_k, row_top_p, (const unsigned long long*)row_seed, probs, ld_probs, processed ? 1 : 0};
-    hipLaunchKernelGGL(sample_pick_kernel<true>, dim3(B), dim3(PICK_THREADS), 0, s, p, q, sr);
+  if (!c.processed) {
+    hipLaunchKernelGGL(greedy_pick_kernel, grid, block, 0, s, p);
+  } else if (c.sampler == SAMPLER_NONE) {
+    if (c.sets) hipLaunchKernelGGL(greedy_pick_rows_kernel, grid, block, 0, s, p, q, c.ps);
+    else hipLaunchKernelGGL(greedy_pick_processed_kernel, grid, block, 0, s, p, q);
+  } else if (c.sets) {
+    // processed = 1: which rows have something to process is the device's to know; the neutral set's row is the plain f32 copy
+    SampleRowParams sr = c.sr;
+    sr.processed = 1;
+    hipLaunchKernelGGL(sample_pick_rows_processed_kernel, grid, block, 0, s, p, q, c.ps, sr);
   } else {
-    hipLaunchKernelGGL(sample_pick_kernel<false>, dim3(B), dim3(PICK_THREADS), 0, s, p, q, sp);
+    const bool processed = q.penalty != 1.f || q.ngram > 0 || q.n_bad > 0 || (q.min_len > 0 && q.n_eos > 0) || q.n_suppress > 0 ||
+                           q.n_begin > 0 || q.c.table != nullptr;
+    if (c.sampler == SAMPLER_ROWS) {                        // the per-row form: the four arrays stand in for the scalars
+      SampleRowParams sr = c.sr;
+      sr.processed = processed ? 1 : 0;
+      hipLaunchKernelGGL(sample_pick_kernel<true>, grid, block, 0, s, p, q, sr);
+    } else {
+      SampleParams sp = c.sp;
+      sp.processed = processed ? 1 : 0;
+      hipLaunchKernelGGL(sample_pick_kernel<false>, grid, block, 0, s, p, q, sp);
+    }
   }
   AKI_LAUNCH_CHECK();
   return AKI_OK;
 }
 
-// the per-row forms: the processor values of proc_params are placeholders, proc_row_params fills them per row
-int logits_process_rows_launch(const void* logits, int in_f32, int B, int V, int ld, float* out, int ld_out, const int64_t* tokens, int tokens_ld,
-                               const int* cache_len, const int* start_len, int step, const unsigned char* done, const int64_t* eos, int n_eos,
-                               const int* sets, int n_sets, const int* row_set, const int64_t* set_ids, int n_set_ids, const int* bad_off,
-                               int n_words, const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
-                               const int* c_row_base, const int* c_row_states, hipStream_t s) {
-  ProcParams q = proc_params(logits, in_f32, ld, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, 1.f, 0, 0, eos, n_eos,
-                             nullptr, 0, nullptr, 0, nullptr, nullptr, 0, 0);
-  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld, c_row_base, c_row_states};
-  const ProcSetParams ps = {sets, n_sets, row_set, set_ids, n_set_ids, bad_off, n_words};
-  AKI_CLEAR_ERR();
-  hipLaunchKernelGGL(logits_process_rows_kernel, dim3(B), dim3(PROC_THREADS), 0, s, q, ps);
-  AKI_LAUNCH_CHECK();
-  return AKI_OK;
-}
-
-int greedy_pick_rows_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done, int64_t* ids,
-                            int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance, int* done_at, const void* emb_main,
-                            const void* emb_extra, int64_t max_original_id, int d, void* emb_out, float* scores, int ld_scores, const int* sets,
-                            int n_sets, const int* row_set, const int64_t* set_ids, int n_set_ids, const int* bad_off, int n_words,
-                            const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld, const int* c_row_base,
-                            const int* c_row_states, hipStream_t s) {
-  PickParams p = {(const bf16_t*)logits, B, V, ld, eos, n_eos, pad, done, ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
-                  (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out};
-  ProcParams q = proc_params(logits, 0, ld, scores, ld_scores, V, tokens, tokens_ld, cache_len, start_len, cache_len ? advance : 0, done,
-                             1.f, 0, 0, eos, n_eos, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, 0);
-  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld, c_row_base, c_row_states};
-  const ProcSetParams ps = {sets, n_sets, row_set, set_ids, n_set_ids, bad_off, n_words};
-  AKI_CLEAR_ERR();
-  hipLaunchKernelGGL(greedy_pick_rows_kernel, dim3(B), dim3(PICK_THREADS), 0, s, p, q, ps);
-  AKI_LAUNCH_CHECK();
-  return AKI_OK;
-}
-
-int sample_pick_rows_processed_launch(const void* logits, int B, int V, int ld, const int64_t* eos, int n_eos, int64_t pad, unsigned char* done,
-                                      int64_t* ids, int64_t* tokens, int tokens_ld, int* cache_len, const int* start_len, int advance,
-                                      int* done_at, const void* emb_main, const void* emb_extra, int64_t max_original_id, int d, void* emb_out,
-                                      float* scores, int ld_scores, const int* sets, int n_sets, const int* row_set, const int64_t* set_ids,
-                                      int n_set_ids, const int* bad_off, int n_words, int step, const float* row_temperature,
-                                      const int* row_top_k, const float* row_top_p, const uint64_t* row_seed, float* probs, int ld_probs,
-                                      const int16_t* c_table, int c_table_ld, int c_n_states, int* c_states, int c_states_ld,
-                                      const int* c_row_base, const int* c_row_states, hipStream_t s) {
-  PickParams p = {(const bf16_t*)logits, B, V, ld, eos, n_eos, pad, done, ids, tokens, tokens_ld, cache_len, start_len, advance, done_at,
-                  (const bf16_t*)emb_main, (const bf16_t*)emb_extra, max_original_id, d, (bf16_t*)emb_out, step};
-  ProcParams q = proc_params(logits, 0, ld, scores, ld_scores, V, tokens, tokens_ld, cache_len, start_len, step + (cache_len ? advance : 0),
-                             done, 1.f, 0, 0, eos, n_eos, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, 0);
-  q.c = ConstraintParams{c_table, c_table_ld, c_n_states, c_states, c_states_ld, c_row_base, c_row_states};
-  const ProcSetParams ps = {sets, n_sets, row_set, set_ids, n_set_ids, bad_off, n_words};
-  // processed = 1: which rows have something to process is the device's to know; the neutral set's row is the plain f32 copy
-  const SampleRowParams sr = {row_temperature, row_top_k, row_top_p, (const unsigned long long*)row_seed, probs, ld_probs, 1};
-  AKI_CLEAR_ERR();
-  hipLaunchKernelGGL(sample_pick_rows_processed_kernel, dim3(B), dim3(PICK_THREADS), 0, s, p, q, ps, sr);
-  AKI_LAUNCH_CHECK();
-  return AKI_OK;
-}
-
 }  // namespace aki
+
+

@@ -1083,59 +1083,15 @@ def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
     and states[b, t + 1] receives the table entry, a state local to the row's automaton; a row in state -1 is picked unmasked.
     processor_sets (an ops.ProcessorSets, in the place of `processors`): one set of processor settings per row (aki_greedy_pick_rows) - row
     b is processed with the pool's set row_set[b]; slot_constraints composes with it and needs no LogitsProcessors then."""
-    if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
-        raise AkiError("greedy_pick takes bf16 logits [B, V] with unit column stride")
-    B, V = logits.shape
-    for t_, dt in ((next_ids, torch.int64), (tokens, torch.int64), (eos_ids, torch.int64), (done, torch.uint8), (cache_len, torch.int32),
-                   (start_len, torch.int32), (done_at, torch.int32)):
-        if t_ is not None and (t_.dtype != dt or not t_.is_contiguous() or t_.device != logits.device):
-            raise AkiError(f"greedy_pick: a {dt} contiguous tensor on {logits.device} is expected, got {t_.dtype} {tuple(t_.shape)}")
-    if tokens is not None and (tokens.dim() != 2 or tokens.shape[0] != B):
-        raise AkiError("greedy_pick: tokens is [B, max_new_tokens]")
-    common = (_ptr(logits), B, V, logits.stride(0), _ptr(eos_ids), 0 if eos_ids is None else eos_ids.numel(), int(pad_token_id), _ptr(done),
-              _ptr(next_ids), _ptr(tokens), 0 if tokens is None else tokens.shape[1], _ptr(cache_len), _ptr(start_len), 1 if advance else 0,
-              _ptr(done_at))
-    if embed is not None:
-        w, extra, max_orig = embed
-        d = w.shape[1]
-        for t_ in (w, extra, next_embeds):
-            if t_ is not None and (t_.dtype != torch.bfloat16 or not t_.is_contiguous() or t_.device != logits.device or t_.shape[-1] != d):
-                raise AkiError("greedy_pick: embedding tables and next_embeds are contiguous bf16 [*, d] on the logits' device")
-        if next_embeds is None or next_embeds.numel() != B * d:
-            raise AkiError("greedy_pick: next_embeds is [B, d]")
-        if w.shape[0] <= max_orig:
-            raise AkiError("greedy_pick: the embedding table has fewer than max_original_id + 1 rows")
-    sets = _processor_set_args("greedy_pick", processor_sets, processors, slot_constraints, B, V, logits.device)
-    if sets is not None:
-        sc = processor_sets.scores(B, logits.device)
-        emb = (None, None, 0, 0, 0, None) if embed is None else \
-            (_ptr(w), _ptr(extra), int(max_orig), 0 if extra is None else extra.shape[0], d, _ptr(next_embeds))
-        L.check(L.load().aki_greedy_pick_rows(*common, *emb, _ptr(sc), sc.stride(0), *sets[0], *sets[1], _stream()), "aki_greedy_pick_rows")
-        return next_ids
-    rows_con = _slot_constraint_args("greedy_pick", slot_constraints, processors, B, V, logits.device)
-    if processors is not None and processors.active:
-        if processors.V != V:
-            raise AkiError(f"greedy_pick: the processors were built for V = {processors.V}, the logits have {V} columns")
-        sc = processors.scores(B, logits.device)
-        head, tail = processors._tail()
-        emb = (None, None, 0, 0, 0, None) if embed is None else \
-            (_ptr(w), _ptr(extra), int(max_orig), 0 if extra is None else extra.shape[0], d, _ptr(next_embeds))
-        if rows_con is not None:
-            L.check(L.load().aki_greedy_pick_constrained_rows(*common, *emb, _ptr(sc), sc.stride(0), *head, *tail, *rows_con, _stream()),
-                    "aki_greedy_pick_constrained_rows")
-            return next_ids
-        con = processors._constraint_args(B, tokens.shape[1] if tokens is not None else (1 if cache_len is None else None))
-        if con is not None:
-            L.check(L.load().aki_greedy_pick_constrained(*common, *emb, _ptr(sc), sc.stride(0), *head, *tail, *con, _stream()),
-                    "aki_greedy_pick_constrained")
-            return next_ids
-        L.check(L.load().aki_greedy_pick_processed(*common, *emb, _ptr(sc), sc.stride(0), *head, *tail, _stream()), "aki_greedy_pick_processed")
-        return next_ids
-    if embed is None:
-        L.check(L.load().aki_greedy_pick(*common, _stream()), "aki_greedy_pick")
-        return next_ids
-    L.check(L.load().aki_greedy_pick_embed(*common, _ptr(w), _ptr(extra), int(max_orig), 0 if extra is None else extra.shape[0], d,
-                                           _ptr(next_embeds), _stream()), "aki_greedy_pick_embed")
+    common, emb, processed, con = _pick_front("greedy_pick", logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len, advance,
+                                              done_at, embed, next_embeds, processors, slot_constraints, processor_sets, scratch=False)
+    if processed is None:                   # no processors: the plain forms take no scratch (and no V limit)
+        fn, args = ("aki_greedy_pick", common) if embed is None else ("aki_greedy_pick_embed", (*common, *emb))
+    else:
+        fn = "aki_greedy_pick_rows" if processor_sets is not None else "aki_greedy_pick_constrained_rows" if slot_constraints is not None \
+            else "aki_greedy_pick_processed" if con is None else "aki_greedy_pick_constrained"
+        args = (*common, *emb, *processed, *(con or ()))
+    L.check(getattr(L.load(), fn)(*args, _stream()), fn)
     return next_ids
 
 
@@ -1157,11 +1113,15 @@ class DeviceGenerator:
         return o
 
 
-def _sample_pick_front(name: str, logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len, advance, done_at, embed,
-                       next_embeds, processors, step, probs_out, scores, extra=(), processor_sets=None):
-    """What ops.sample_pick and ops.sample_pick_rows share: the checks of the pick's tensors, the scratch rule and the C arguments up to
-    `step` -> (those arguments, the probs_out pair, the constraint's five or None).  extra: further (tensor, dtype) pairs to check.
-    processor_sets: an ops.ProcessorSets whose seven arguments take the place of the eleven scalar processor arguments."""
+def _pick_front(name: str, logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len, advance, done_at, embed, next_embeds,
+                processors, slot_constraints=None, processor_sets=None, step=0, probs_out=None, scores=None, extra=(), scratch=True):
+    """What ops.greedy_pick, ops.sample_pick and ops.sample_pick_rows share: the checks of the pick's tensors and embedding tables, the
+    scratch rule and the C arguments in their groups -> (the common 15, the embedding 6, the processed part or None, the constraint's
+    arguments or None).  The processed part is the scratch pair followed by the processors' eleven arguments - or, with processor_sets (an
+    ops.ProcessorSets, in their place), the pool's seven; the constraint's arguments are then always the per-row seven (NULLs without
+    slot_constraints), else slot_constraints' seven, else the five of a constraint the processors carry.
+    scratch=False (ops.greedy_pick): without active processors or sets there is no processed part - the plain forms take no scratch and no
+    V limit.  extra: further (tensor, dtype) pairs to check."""
     if logits.dtype != torch.bfloat16 or logits.dim() != 2 or logits.stride(1) != 1:
         raise AkiError(f"{name} takes bf16 logits [B, V] with unit column stride")
     B, V = logits.shape
@@ -1188,23 +1148,28 @@ def _sample_pick_front(name: str, logits, next_ids, pad_token_id, eos_ids, done,
         if w.shape[0] <= max_orig:
             raise AkiError(f"{name}: the embedding table has fewer than max_original_id + 1 rows")
         emb = (_ptr(w), _ptr(extra_w), int(max_orig), 0 if extra_w is None else extra_w.shape[0], d, _ptr(next_embeds))
+    sets = _processor_set_args(name, processor_sets, processors, slot_constraints, B, V, logits.device)
+    con = None if sets is not None else _slot_constraint_args(name, slot_constraints, processors, B, V, logits.device)
     active = processors is not None and processors.active
     if active and processors.V != V:
         raise AkiError(f"{name}: the processors were built for V = {processors.V}, the logits have {V} columns")
+    if not (scratch or active or sets is not None):
+        return common, emb, None, None
     if V > L.AKI_LOGITS_PROCESS_MAX_V:
         raise AkiError(f"{name}: a vocabulary of {V} is above {L.AKI_LOGITS_PROCESS_MAX_V}")
     if scores is None:
-        scores = processor_sets.scores(B, logits.device) if processor_sets is not None else \
+        scores = processor_sets.scores(B, logits.device) if sets is not None else \
             processors.scores(B, logits.device) if active else _sample_scratch(B, V, logits.device)
     if scores.dim() != 2 or scores.shape[0] != B or scores.shape[1] < V:
         raise AkiError(f"{name}: scores is f32 [B, >= V]")
-    if processor_sets is not None:
-        head, tail = processor_sets._args(name, B, V, logits.device), ()
+    if sets is not None:
+        proc, con = sets
     else:
         head, tail = processors._tail() if active else ((1.0, 0, 0), (None, 0, None, 0, None, None, 0, 0))
-    con = processors._constraint_args(B, tokens.shape[1] if tokens is not None else (int(step) + 1 if cache_len is None else None)) if active else None
-    return ((*common, *emb, _ptr(scores), scores.stride(0), *head, *tail, int(step)),
-            (_ptr(probs_out), 0 if probs_out is None else probs_out.stride(0)), con)
+        proc = (*head, *tail)
+        if con is None and active:
+            con = processors._constraint_args(B, tokens.shape[1] if tokens is not None else (int(step) + 1 if cache_len is None else None))
+    return common, emb, (_ptr(scores), scores.stride(0), *proc), con
 
 
 def sample_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int = 0, eos_ids: Optional[torch.Tensor] = None,
@@ -1220,13 +1185,12 @@ def sample_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
     (default: the processors' own, or one kept per shape).  Capturable: no host value is read."""
     if not (float(temperature) > 0.0) or not (0.0 < float(top_p) <= 1.0) or int(top_k) < 0 or int(step) < 0:
         raise ValueError(f"sample_pick: temperature > 0, 0 < top_p <= 1, top_k >= 0 and step >= 0 are expected, got {temperature}, {top_p}, {top_k}, {step}")
-    front, probs, con = _sample_pick_front("sample_pick", logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len, advance,
-                                           done_at, embed, next_embeds, processors, step, probs_out, scores)
-    args = (*front, float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, *probs)
-    if con is not None:
-        L.check(L.load().aki_sample_pick_constrained(*args, *con, _stream()), "aki_sample_pick_constrained")
-        return next_ids
-    L.check(L.load().aki_sample_pick(*args, _stream()), "aki_sample_pick")
+    common, emb, processed, con = _pick_front("sample_pick", logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len, advance,
+                                              done_at, embed, next_embeds, processors, step=step, probs_out=probs_out, scores=scores)
+    fn = "aki_sample_pick" if con is None else "aki_sample_pick_constrained"
+    L.check(getattr(L.load(), fn)(*common, *emb, *processed, int(step), float(temperature), int(top_k), float(top_p),
+                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _ptr(probs_out),
+                                  0 if probs_out is None else probs_out.stride(0), *(con or ()), _stream()), fn)
     return next_ids
 
 
@@ -1257,28 +1221,13 @@ def sample_pick_rows(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id:
     if processors is not None and processors.active and processors.constraint is not None:
         raise AkiError("sample_pick_rows: a LogitsProcessors with a constraint of its own is not taken (no constrained form of that kind); "
                        "pass slot_constraints, or use ops.sample_pick")
-    sets = None
-    if logits.dim() == 2 and processor_sets is not None:
-        sets = _processor_set_args("sample_pick_rows", processor_sets, processors, slot_constraints, logits.shape[0], logits.shape[1],
-                                   logits.device)
-        rows_con = None
-    elif logits.dim() == 2:
-        rows_con = _slot_constraint_args("sample_pick_rows", slot_constraints, processors, logits.shape[0], logits.shape[1], logits.device)
-    else:
-        rows_con = None
-    front, probs, _ = _sample_pick_front("sample_pick_rows", logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len,
-                                         advance, done_at, embed, next_embeds, processors, step, probs_out, scores, extra=rows,
-                                         processor_sets=processor_sets if sets is not None else None)
-    if sets is not None:
-        L.check(L.load().aki_sample_pick_rows_processed(*front, _ptr(temperature), _ptr(top_k), _ptr(top_p), _ptr(seed), *probs, *sets[1],
-                                                        _stream()), "aki_sample_pick_rows_processed")
-        return next_ids
-    if rows_con is not None:
-        L.check(L.load().aki_sample_pick_rows_constrained(*front, _ptr(temperature), _ptr(top_k), _ptr(top_p), _ptr(seed), *probs, *rows_con,
-                                                          _stream()), "aki_sample_pick_rows_constrained")
-        return next_ids
-    L.check(L.load().aki_sample_pick_rows(*front, _ptr(temperature), _ptr(top_k), _ptr(top_p), _ptr(seed), *probs, _stream()),
-            "aki_sample_pick_rows")
+    common, emb, processed, con = _pick_front("sample_pick_rows", logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len,
+                                              advance, done_at, embed, next_embeds, processors, slot_constraints, processor_sets, step=step,
+                                              probs_out=probs_out, scores=scores, extra=rows)
+    fn = "aki_sample_pick_rows_processed" if processor_sets is not None else \
+        "aki_sample_pick_rows" if con is None else "aki_sample_pick_rows_constrained"
+    L.check(getattr(L.load(), fn)(*common, *emb, *processed, int(step), _ptr(temperature), _ptr(top_k), _ptr(top_p), _ptr(seed), _ptr(probs_out),
+                                  0 if probs_out is None else probs_out.stride(0), *(con or ()), _stream()), fn)
     return next_ids
 
 

@@ -21,6 +21,7 @@ from torch import nn
 from . import ops
 from . import train_ops as T
 from .helpers import CausalLMOutputWithPast
+from .pick_stage import PickStage
 
 
 def make_phi3_config(**kw):
@@ -214,29 +215,20 @@ class DecodeGraph:
     `decode_verified(cache)` (or `cache.chain.check()`) before trusting a run of steps, as generate does - a wait that gave up leaves
     garbage logits and a sticky error word, nothing is raised by the step itself."""
 
-    def __init__(self, lm: "Phi3ForCausalLM", cache: AkiKVCache, greedy: Optional[dict] = None):
-        """greedy (optional): the arguments of ops.greedy_pick except logits / next_ids / cache_len / advance - the pick then sits INSIDE the
-        replayed step and writes the next step's input ids itself: one replay per token (`step_greedy`), nothing else on the stream.
-        With a "seed" key the dict holds ops.sample_pick's arguments instead (temperature, top_k, top_p, seed, offset): the captured pick
-        is the device sampler, whose draw depends on the device-side token index, so one capture serves every replay.
-        With a "row_seed" key it holds ops.sample_pick_rows' arguments (temperature, top_k, top_p and row_seed: device arrays of one entry per
-        row, the last one passed on as `seed`): the captured pick reads every row's parameters and key from those arrays at each replay, so
-        they may be rewritten in place between replays (generate_many's admit).
-        A "slot_constraints" key (an ops.SlotConstraints, with "processors") is handed to either pick unchanged: one token automaton per row,
-        whose place in the pool and state history are device tensors rewritten in place at admit as well.
-        A "processor_sets" key (an ops.ProcessorSets, in the place of "processors") is handed on likewise: one set of logits-processor
-        settings per row, the row's set index a device int rewritten in place at admit.
-        With a "logprob" key (the in-loop arguments of ops.token_logprob) that launch is captured right behind the pick.
-        With a "tick" key (ops.slot_tick's done / done_at / start_len / limit) the rows' token budgets are ticked behind the pick too.
-        With a "stops" key (an ops.StopSets) the rows' stop sequences are checked behind the pick and the log-probability launch:
-        ops.stop_check on its own, or - with a "tick" key - inside the tick's launch (ops.slot_tick(stops=...)): no launch more."""
+    def __init__(self, lm: "Phi3ForCausalLM", cache: AkiKVCache, greedy=None):
+        """greedy (optional): a pick_stage.PickStage, or a plain dict of ops.greedy_pick's arguments except logits / next_ids / cache_len /
+        advance (wrapped into a greedy-only stage).  The stage's launches then sit INSIDE the replayed step - the pick (greedy or one of the
+        device samplers, whose draws depend on the device-side token index and whose per-row arrays are read at every replay, so one
+        capture serves every replay and an admit may rewrite a row in place), then the log-probability launch, the stop check and the
+        slots' tick where the stage holds them - and the pick writes the next step's input ids itself: one replay per token
+        (`step_greedy`), nothing else on the stream.  The embedding gather is left out: the captured step feeds ids."""
         self.lm, self.cache = lm, cache
         B = cache.cache_len.shape[0]
         self.ids = torch.zeros((B,), dtype=torch.long, device=cache.cache_len.device)
         self.graph = None
         self.logits = None
         self._long = None
-        self.greedy = greedy
+        self.greedy = PickStage(greedy) if isinstance(greedy, dict) else greedy
 
     def _capture(self):
         lm, cache = self.lm, self.cache
@@ -255,28 +247,12 @@ class DecodeGraph:
                 self.logits = lm.decode_step(input_ids=self.ids, past_key_values=cache)
             else:                                   # the pick advances cache_len itself: one launch less per token
                 self.logits = lm.decode_step(input_ids=self.ids, past_key_values=cache, advance=False)
-                args = dict(self.greedy)
-                logprob, tick, stops = args.pop("logprob", None), args.pop("tick", None), args.pop("stops", None)
-                if "row_seed" in args:
-                    args["seed"] = args.pop("row_seed")
-                    pick = ops.sample_pick_rows
-                else:
-                    pick = ops.sample_pick if "seed" in args else ops.greedy_pick
-                pick(self.logits, self.ids, cache_len=cache.cache_len, advance=True, **args)
-                if logprob is not None:             # right behind the pick: it scores the token at the index the pick just wrote
-                    ops.token_logprob(self.logits, **logprob)
-                if stops is not None and tick is None:
-                    ops.stop_check(args["tokens"], cache.cache_len, args["start_len"], args["done"], args["done_at"], stops)
-                if tick is not None:                # the rows' token budgets: retires and parks rows on the device (generate_many)
-                    if stops is not None:
-                        ops.slot_tick(cache_len=cache.cache_len, **tick, stops=stops, tokens=args["tokens"])
-                    else:
-                        ops.slot_tick(cache_len=cache.cache_len, **tick)
+                self.greedy.run(self.logits, self.ids, cache.cache_len, advance=True, embed=False)
         cache.host_len = saved_host
 
     def step_greedy(self) -> torch.Tensor:
         """One token of a greedy generation: replay; the ids picked by the previous replay (or placed in `self.ids` by the caller) go in,
-        the ids picked from this step's logits are left in `self.ids` (and in greedy['tokens'])."""
+        the ids picked from this step's logits are left in `self.ids` (and in the stage's tokens)."""
         if self.greedy is None:
             raise ops.AkiError("DecodeGraph was built without a greedy pick")
         self._ready()

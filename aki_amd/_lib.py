@@ -309,6 +309,16 @@ SIGNATURES = {
     "aki_mma_mask_to_table": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
 }
 
+# min_p and the frequency / presence penalties: the named entry point's arguments with two (frequency_penalty, presence_penalty) or, for
+# the two sample forms, three (then min_p) nullable device arrays of B floats in front of the stream
+for _name, _base, _more in (("aki_logits_process_penalized", "aki_logits_process_constrained", 2),
+                            ("aki_greedy_pick_penalized", "aki_greedy_pick_constrained", 2),
+                            ("aki_sample_pick_penalized", "aki_sample_pick_constrained", 3),
+                            ("aki_logits_process_rows_penalized", "aki_logits_process_rows", 2),
+                            ("aki_greedy_pick_rows_penalized", "aki_greedy_pick_rows", 2),
+                            ("aki_sample_pick_rows_penalized", "aki_sample_pick_rows_processed", 3)):
+    SIGNATURES[_name] = (C.c_int, SIGNATURES[_base][1][:-1] + [C.c_void_p] * (_more + 1))
+
 _lib: Optional[C.CDLL] = None
 
 

@@ -22,13 +22,15 @@ from . import ops
 from .helpers import PerceiverResampler
 from .phi3 import AkiKVCache, DecodeGraph
 from .pick_stage import PickStage
-from .slots import RequestParams, SlotScheduler, banning_keywords, processor_set_key, request_seed, resolve_processors, slot_capacity
+from .slots import (PENALTY_FIELDS, RequestParams, SlotScheduler, banning_keywords, check_additive_penalty, check_min_p, processor_set_key,
+                    request_seed, resolve_penalties, resolve_processors, slot_capacity)
 from .stops import check_stop_sequences, first_finish, resolve_stop_sequences
 from .vlm import VLMWithLanguageStream
 
 
-def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, generator=None) -> torch.Tensor:
-    """One sampling step on [B, V] logits, in HF's processor order: temperature, top-k, top-p (nucleus), multinomial."""
+def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, generator=None,
+                min_p: float = 0.0) -> torch.Tensor:
+    """One sampling step on [B, V] logits, in HF's processor order: temperature, top-k, top-p (nucleus), min-p, multinomial."""
     x = logits.float() / temperature
     V = x.shape[-1]
     if 0 < top_k < V:
@@ -40,6 +42,9 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 0, 
         drop = cum - sx.softmax(dim=-1) >= top_p            # keep the smallest prefix whose mass reaches top_p (always >= 1 token)
         sx = sx.masked_fill(drop, float("-inf"))
         x = torch.full_like(x, float("-inf")).scatter(-1, si, sx)
+    if min_p > 0.0:                                         # HF MinPLogitsWarper: drop what lies below min_p times the largest probability
+        probs = x.softmax(dim=-1)
+        x = x.masked_fill(probs < min_p * probs.amax(dim=-1, keepdim=True), float("-inf"))
     return torch.multinomial(x.softmax(dim=-1), 1, generator=generator).squeeze(-1)
 
 
@@ -57,11 +62,20 @@ def _pop_processor_kwargs(kwargs: dict) -> dict:
     return out
 
 
+def _pop_penalty_kwargs(who: str, kwargs: dict) -> dict:
+    """frequency_penalty= / presence_penalty= (popped, None read as 0), checked: finite floats in [-2, 2], as the float32 the device reads."""
+    out = {}
+    for k, neutral in PENALTY_FIELDS.items():
+        v = kwargs.pop(k, None)
+        out[k] = check_additive_penalty(who, k, neutral if v is None else v)
+    return out
+
+
 def _reject_unused_kwargs(kwargs: dict) -> None:
     """What HF's `_validate_model_kwargs` does with keywords generate() does not use: a ValueError naming them, never a silent drop."""
     if kwargs:
         raise ValueError(f"generate() cannot honour the keyword argument(s) {sorted(kwargs)}: the supported ones are the greedy / sampling / "
-                         f"beam-search controls, the logits processors {sorted(PROCESSOR_KWARGS)} and stop_sequences (lists of token ids, "
+                         f"beam-search controls, the logits processors {sorted(PROCESSOR_KWARGS)}, min_p, {sorted(PENALTY_FIELDS)} and stop_sequences (lists of token ids, "
                          "matched on the device: what stopping_criteria / stop_strings would be asked for)")
 
 
@@ -90,9 +104,11 @@ def _embedding_tables(emb: nn.Module, logits: torch.Tensor):
 # log-probabilities of the returned tokens and that many alternatives (ops.token_logprob).
 # constraint: None, a constraint.TokenConstraint or a list of one per sample (constrained decoding; bound to the device in generate).
 # stops: the call's stop set in its normal form (stops.check_stop_sequences; () = none), one set for every row.
+# min_p: the sampler's min-p filter (0 = none; ignored without do_sample, as top_p is); penalties: {frequency_penalty, presence_penalty},
+# the additive penalties beside the processors (PENALTY_FIELDS; 0 = neutral).
 GenerateOptions = namedtuple("GenerateOptions", "num_beams do_sample temperature top_k top_p rng device_rng length_penalty early_stopping "
                                                 "n_ret max_new_tokens eos_ids pad_id use_graph processors output_logprobs top_logprobs "
-                                                "constraint stops")
+                                                "constraint stops min_p penalties", defaults=(0.0, None))
 
 # the processors that ban tokens outright: together with a constraint they could leave a row with nothing allowed
 BANNING_KWARGS = ("no_repeat_ngram_size", "bad_words_ids", "min_length", "min_new_tokens", "suppress_tokens", "begin_suppress_tokens")
@@ -166,6 +182,8 @@ def _parse_generate_kwargs(kwargs: dict, default_pad_id, default_eos_ids, from_c
     temperature = float(kwargs.pop("temperature", 1.0))
     top_k = int(kwargs.pop("top_k", 0) or 0)
     top_p = float(kwargs.pop("top_p", 1.0))
+    min_p = check_min_p("generate", kwargs.pop("min_p", None) or 0.0)
+    penalties = _pop_penalty_kwargs("generate", kwargs)
     rng = kwargs.pop("generator", None)
     length_penalty = float(kwargs.pop("length_penalty", 1.0))
     early_stopping = kwargs.pop("early_stopping", False)
@@ -182,6 +200,9 @@ def _parse_generate_kwargs(kwargs: dict, default_pad_id, default_eos_ids, from_c
         raise NotImplementedError("num_return_sequences > 1 with beam search")
     if num_beams < 1 or (num_beams > 1 and do_sample):
         raise NotImplementedError("beam-sample decoding (num_beams > 1 with do_sample=True)")
+    for name, v in (("min_p", min_p), *penalties.items()):
+        if num_beams > 1 and v != 0.0:
+            raise NotImplementedError(f"{name} with num_beams > 1: beam search under min_p or the frequency / presence penalties")
     if n_ret > 1 and not do_sample:
         raise ValueError("num_return_sequences > 1 needs do_sample=True: greedy decoding returns one sequence per sample")
     if do_sample and temperature <= 0:
@@ -232,13 +253,16 @@ def _parse_generate_kwargs(kwargs: dict, default_pad_id, default_eos_ids, from_c
     return GenerateOptions(num_beams=num_beams, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, rng=rng,
                            device_rng=device_rng, length_penalty=length_penalty, early_stopping=early_stopping, n_ret=n_ret,
                            max_new_tokens=max_new_tokens, eos_ids=eos_ids, pad_id=pad_id, use_graph=use_graph, processors=processors,
-                           output_logprobs=output_logprobs, top_logprobs=top_logprobs, constraint=constraint, stops=stops)
+                           output_logprobs=output_logprobs, top_logprobs=top_logprobs, constraint=constraint, stops=stops, min_p=min_p,
+                           penalties=penalties)
 
 
 # The keyword arguments of `generate_many`, resolved by _parse_many_kwargs: max_new_tokens is the default budget of a request, params the
 # RequestParams of a request that brings none, generator None or the ops.DeviceGenerator the sampled requests' seeds are derived from,
-# stops the call-wide stop_sequences= keyword in its normal form or None: the default of every request whose RequestParams leave it None.
-ManyOptions = namedtuple("ManyOptions", "max_new_tokens eos_ids pad_id use_graph processors params generator stops")
+# stops the call-wide stop_sequences= keyword in its normal form or None: the default of every request whose RequestParams leave it None;
+# penalties the call-wide frequency_penalty= / presence_penalty= keywords (PENALTY_FIELDS), the default of the same kind.
+ManyOptions = namedtuple("ManyOptions", "max_new_tokens eos_ids pad_id use_graph processors params generator stops penalties",
+                         defaults=(None,))
 
 
 @dataclass
@@ -247,7 +271,8 @@ class _ManyPlan:
     seeds: _many_seeds' value per request; eos_list: the call's eos ids, sorted.  For a queue that is not empty also, per request:
     resolved (its processor keywords), set_keys (their slots.processor_set_key), stop_keys (its stop set, normal form); mixed: the
     requests resolve to more than one processor set, else pk is the one they share; pool: the constraint.ConstraintPool of a call with a
-    constrained request; dev / dtype / on_device (bf16 on the GPU: the device picks) and width, the logits' columns."""
+    constrained request; dev / dtype / on_device (bf16 on the GPU: the device picks) and width, the logits' columns; extras: per request
+    {frequency_penalty, presence_penalty, min_p} (slots.resolve_penalties; min_p 0 for a greedy request, which ignores it)."""
     opt: ManyOptions
     slots: int
     reqs: list
@@ -256,6 +281,7 @@ class _ManyPlan:
     resolved: Optional[list] = None
     set_keys: Optional[list] = None
     stop_keys: Optional[list] = None
+    extras: Optional[list] = None
     mixed: bool = False
     pk: Optional[dict] = None
     pool: object = None
@@ -267,6 +293,14 @@ class _ManyPlan:
     @property
     def sampled(self) -> bool:
         return any(rp.do_sample for *_, rp in self.reqs)
+
+    def uses(self, name: str) -> bool:
+        """Some request of the call carries a value of `name` (frequency_penalty, presence_penalty, min_p) that is not neutral."""
+        return any(e[name] != 0.0 for e in self.extras or ())
+
+    @property
+    def penalized(self) -> bool:
+        return any(self.uses(k) for k in ("frequency_penalty", "presence_penalty", "min_p"))
 
     @property
     def constrained(self) -> bool:
@@ -325,6 +359,7 @@ def _parse_many_kwargs(kwargs: dict, default_pad_id, default_eos_ids) -> ManyOpt
     pad_id = kwargs.pop("pad_token_id", default_pad_id)
     use_graph = kwargs.pop("use_graph", None)
     processors = _pop_processor_kwargs(kwargs)
+    penalties = _pop_penalty_kwargs("generate_many: the call-wide keyword", kwargs)
     params = kwargs.pop("params", None)
     if params is None:
         params = RequestParams()
@@ -340,7 +375,7 @@ def _parse_many_kwargs(kwargs: dict, default_pad_id, default_eos_ids) -> ManyOpt
         stops = check_stop_sequences("generate_many: the call-wide keyword", stops)
     _reject_unused_kwargs(kwargs)
     return ManyOptions(max_new_tokens=max_new_tokens, eos_ids=eos_ids, pad_id=pad_id, use_graph=True if use_graph is None else bool(use_graph),
-                       processors=processors, params=params, generator=generator, stops=stops)
+                       processors=processors, params=params, generator=generator, stops=stops, penalties=penalties)
 
 
 def _many_requests(requests, default_budget: int, default_params: Optional[RequestParams] = None):
@@ -391,7 +426,8 @@ def _many_seeds(reqs, generator) -> List[Optional[int]]:
 
 
 def _logits_processors(V: int, device, pk: dict, eos_ids, **kw):
-    """The ops.LogitsProcessors of a processor-keyword dict (PROCESSOR_KWARGS' keys; kw: constraint= or slot_constraints=), or None when
+    """The ops.LogitsProcessors of a processor-keyword dict (PROCESSOR_KWARGS' keys; kw: constraint=, slot_constraints= or the additive
+    penalties frequency_penalty= / presence_penalty=), or None when
     nothing in it is active: the picks then launch exactly what they launch without processors."""
     p = ops.LogitsProcessors(V, device, pk["repetition_penalty"], pk["no_repeat_ngram_size"], max(int(pk["min_length"]), int(pk["min_new_tokens"])),
                              eos_ids, pk["suppress_tokens"], pk["begin_suppress_tokens"], pk["bad_words_ids"], **kw)
@@ -401,7 +437,12 @@ def _logits_processors(V: int, device, pk: dict, eos_ids, **kw):
 def _device_sampler_args(opt: GenerateOptions):
     """ops.sample_pick's own arguments when a DeviceGenerator selected the device sampler, else None: one offset per generate call."""
     g = opt.device_rng
-    return None if g is None else dict(temperature=opt.temperature, top_k=opt.top_k, top_p=opt.top_p, seed=g.seed, offset=g.next_offset())
+    if g is None:
+        return None
+    args = dict(temperature=opt.temperature, top_k=opt.top_k, top_p=opt.top_p, seed=g.seed, offset=g.next_offset())
+    if opt.min_p:                               # without it the pick takes the entry point it always took
+        args["min_p"] = opt.min_p
+    return args
 
 
 def _first_end(tokens: torch.Tensor, eos_t, stops=()):
@@ -464,6 +505,9 @@ def _plan_many(model, requests, slots, kwargs) -> "_ManyPlan":
     # width and reduced to one value per distinct behaviour.  A call whose requests all resolve to one set runs the call-wide path.
     plan.resolved = [resolve_processors(rp, opt.params, opt.processors) for *_, rp in reqs]
     plan.set_keys = [processor_set_key(f"request {i}", r, eos_list, width) for i, r in enumerate(plan.resolved)]
+    # the additive penalties resolve the same way; min_p is the request's own (a greedy request's is ignored, as its top_p is)
+    plan.extras = [dict(resolve_penalties(rp, opt.params, opt.penalties), min_p=check_min_p(f"request {i}", rp.min_p) if rp.do_sample else 0.0)
+                   for i, (*_, rp) in enumerate(reqs)]
     plan.mixed = len(set(plan.set_keys)) > 1
     plan.pk = opt.processors if plan.mixed else plan.resolved[0]
     if plan.constrained:                            # the host half: every table with its eos columns, checked before any device work
@@ -487,8 +531,9 @@ def _many_one_by_one(model, plan: "_ManyPlan"):
     """generate_many with one slot or one request: generate() per request, in order."""
     opt, eos_list = plan.opt, plan.eos_list
     outs, sched, hits = [], SlotScheduler(len(plan.reqs), 1), []
-    for (vx, lx, budget, rp), seed, own, stop_key in zip(plan.reqs, plan.seeds, plan.resolved, plan.stop_keys):
+    for (vx, lx, budget, rp), seed, own, stop_key, extra in zip(plan.reqs, plan.seeds, plan.resolved, plan.stop_keys, plan.extras):
         kw_r = dict(own, eos_token_id=eos_list, pad_token_id=opt.pad_id, max_new_tokens=budget)
+        kw_r.update({k: v for k, v in extra.items() if v != 0.0})
         if stop_key:
             kw_r.update(stop_sequences=stop_key)
         if rp.do_sample:                        # the same stream: key seed, counter (token index, row 0, offset 0)
@@ -543,9 +588,12 @@ def _many_on_slots(model, plan: "_ManyPlan"):
     # the processed pick keeps a score scratch per batch size, whose address the captured step holds: the admit's one-row pick gets its own.
     # Requests with different settings: the pool of distinct sets (uploaded once) and one set index per slot, allocated ahead of the
     # capture and rewritten in place at admit (ops.ProcessorSets) - it stands in the place of the one LogitsProcessors.
-    processors = lambda: None if plan.mixed else _logits_processors(width, dev, plan.pk, eos_list, slot_constraints=plan.constrained)
+    # A call in which a request carries min_p or a frequency / presence penalty takes the per-row form too (those values travel beside the
+    # sets, one float per slot), whether or not its processor settings differ.
+    by_sets = plan.mixed or plan.penalized
+    processors = lambda: None if by_sets else _logits_processors(width, dev, plan.pk, eos_list, slot_constraints=plan.constrained)
     proc, proc1 = processors(), processors()
-    psets = ops.ProcessorSets(width, dev, eos_list, plan.set_keys, slots) if plan.mixed else None
+    psets = ops.ProcessorSets(width, dev, eos_list, plan.set_keys, slots) if by_sets else None
     if proc is not None:
         pick["processors"] = proc
     if psets is not None:
@@ -567,6 +615,12 @@ def _many_on_slots(model, plan: "_ManyPlan"):
     if plan.sampled:
         rows = dict(temperature=torch.ones(slots, dtype=torch.float32, device=dev), top_k=torch.ones(slots, dtype=torch.int32, device=dev),
                     top_p=torch.ones(slots, dtype=torch.float32, device=dev), seed=torch.zeros(slots, dtype=torch.int64, device=dev))
+    # min_p and the two penalties: per-slot f32 arrays beside the sampler's four, allocated only when some request uses one, written in
+    # place at admit ahead of the pick of token 0, read by the one captured step.  (min_p belongs to the sampler: without a sampled
+    # request nothing uses it.)
+    extra = {k: torch.zeros(slots, dtype=torch.float32, device=dev) for k in ("frequency_penalty", "presence_penalty", "min_p") if plan.uses(k)}
+    for k, x in extra.items():
+        (rows if k == "min_p" else pick)[k] = x
     # log-probabilities: one ops.token_logprob behind each pick, per slot; a request's columns are [0, its tokens)
     lpb = _LogprobBuffers(slots, max_budget, plan.top, dev) if plan.want_lp else None
     stage = PickStage(pick, rows=rows, processors_row=proc1, logprob=None if lpb is None else lpb.args(), stops=stop_sets, limit=limit,
@@ -593,6 +647,8 @@ def _many_on_slots(model, plan: "_ManyPlan"):
             rows["top_k"][slot] = int(rp.top_k) if rp.do_sample else 1
             rows["top_p"][slot] = float(rp.top_p) if rp.do_sample else 1.0
             rows["seed"][slot] = 0 if seed is None else (seed - (1 << 64) if seed >= 1 << 63 else seed)     # the key's bits as int64
+        for k, x in extra.items():                  # the slot's min_p and penalties, in place
+            x[slot] = plan.extras[req][k]
         if slot_con is not None:                    # the slot's automaton: where its table begins, its start state in column 0
             slot_con.admit(slot, plan.pool.base[req], plan.pool.n_states[req], plan.pool.start[req])
         if psets is not None:                       # the slot's processor set, ahead of the pick of token 0
@@ -1024,6 +1080,7 @@ class AkiMethods:
         done = torch.zeros(B, dtype=torch.bool, device=logits.device)
         chained = lambda: getattr(cache, "chain", None) is not None
         sampler = _device_sampler_args(opt)
+        min_p = {"min_p": opt.min_p} if opt.min_p else {}       # sample_next's; without it the call is the one it always was
         stepper = DecodeGraph(lm, cache) if opt.use_graph else None
         lpb = _LogprobBuffers(B, max_new_tokens, opt.top_logprobs, logits.device) if opt.output_logprobs else None
         t, n_out = 0, max_new_tokens
@@ -1041,7 +1098,7 @@ class AkiMethods:
                                           tokens=tokens, step=t, **sampler)
                 else:
                     x = logits if proc is None else proc.apply(logits, tokens=tokens, step=t)
-                    nxt = sample_next(x, temperature, top_k, top_p, rng) if do_sample else x.float().argmax(dim=-1)
+                    nxt = sample_next(x, temperature, top_k, top_p, rng, **min_p) if do_sample else x.float().argmax(dim=-1)
                 nxt = torch.where(done, torch.full_like(nxt, pad_id), nxt)
                 tokens[:, t] = nxt
                 if proc is not None and sampler is None:        # a constraint's next state (ops.sample_pick stores it itself)
@@ -1243,7 +1300,15 @@ class AkiMethods:
             hits ride in the look's one copy.  A request is cut behind its matched sequence.  `last_stop_hits` is a list of ints in
             request order afterwards (None after a call without stops).  A call in which no request resolves to a non-empty set
             launches exactly what it launched before.
-          Bad values (temperature <= 0, top_p outside (0, 1], top_k < 0, top_logprobs outside the limit or without logprobs, a seed outside
+          * min_p (a float in [0, 1], 0 = no filter; generate's docstring states the rule): request-owned like temperature, ignored for a
+            greedy request as its top_p is; a call-wide `min_p=` keyword is a ValueError.  frequency_penalty / presence_penalty (finite
+            floats in [-2, 2]), None by default: None takes the call's value - params=, else the call-wide keyword; an explicit 0.0 is
+            the request's alone.  The three values are per-slot f32 device arrays beside the sampler's four, allocated only when some
+            request of the call uses one, written in place at admit ahead of the pick of token 0 and read by the captured pick
+            (aki_greedy_pick_rows_penalized / aki_sample_pick_rows_penalized; such a call takes the per-row processor form whether or
+            not its processor settings differ).  The counts are taken from the slot's own generated tokens on every step, so a refilled
+            slot starts from nothing.  A call in which no request uses them launches exactly what it launched before.
+          Bad values (temperature <= 0, min_p outside [0, 1], a penalty outside [-2, 2], top_p outside (0, 1], top_k < 0, top_logprobs outside the limit or without logprobs, a seed outside
           [0, 2^64)): ValueError naming the request, before any device work.
         Refused with NotImplementedError (MANY_REFUSED): num_beams > 1, num_return_sequences > 1, past_key_values, and the
         CALL-WIDE do_sample / output_logprobs / constraint keywords (use RequestParams); a LongRoPE model whose slot capacity exceeds
@@ -1291,6 +1356,15 @@ class AkiMethods:
             `no_repeat_ngram_size`, `bad_words_ids`, `min_length` / `min_new_tokens` (eos ids banned until that many tokens are generated),
             `suppress_tokens`, `begin_suppress_tokens`.  As in HF `generate` with inputs_embeds only, they see the generated tokens, never
             the prompt; beam search applies them to each beam's log-softmax scores.
+          * `frequency_penalty`, `presence_penalty` (the OpenAI definition in vLLM's order; finite floats in [-2, 2], 0 = neutral): stage
+            1b of the processors, directly behind the repetition penalty and before every ban.  For every distinct GENERATED token (never
+            the prompt's) with c occurrences: score - fl(frequency_penalty * c), then score - presence_penalty, each one rounded f32
+            operation; the counts are recomputed from the row's tokens on every step.  They ban nothing, so they compose with a
+            constraint.  In every mode but beam search (NotImplementedError).
+          * `min_p` (HF MinPLogitsWarper; a float in [0, 1], 0 = no filter) with sampling: behind temperature, top-k and top-p, a kept
+            token stays iff exp(y - max y) >= min_p, i.e. its probability is at least min_p times the largest.  The maximum always
+            stays; top-p's mass is decided before it.  Both samplers (the device sampler inside its one launch, `sample_next` in torch).
+            Without `do_sample` it is ignored, as `top_p` is (its range is still checked); with beams NotImplementedError.
           * `constraint=` an `aki_amd.TokenConstraint` (aki_amd/constraint.py), or a list of one per sample: constrained decoding.  The
             automaton's table lives on the device, the mask is the last stage of the logits processors and the pick stores each row's
             next state, so the launches per token and the host's look every 8th token stay as they are.  Every returned row is a walk of
@@ -1363,7 +1437,8 @@ class AkiMethods:
         else:
             cache, logits, appended = self._prefill_prompt(vision_x, lang_x, attention_mask, opt.max_new_tokens)
         bound = None if con is None else con.bind(sorted(opt.eos_ids), logits.device, rows_start)
-        proc = _logits_processors(logits.shape[-1], logits.device, opt.processors, sorted(opt.eos_ids), constraint=bound)
+        proc = _logits_processors(logits.shape[-1], logits.device, opt.processors, sorted(opt.eos_ids), constraint=bound,
+                                  **(opt.penalties or {}))
         if opt.num_beams > 1:
             beam = (opt.num_beams, opt.max_new_tokens, opt.eos_ids, opt.pad_id, opt.length_penalty, opt.early_stopping, proc)
             if self._device_beam_search_ok(cache, logits, opt.num_beams, opt.eos_ids):

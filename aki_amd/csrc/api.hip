@@ -784,9 +784,9 @@ static bool processor_sets_ok(int32_t V, const ProcSetParams& ps) {
 // below 32768 states, the pool need not), and every row names its slice; the arrays' values are the caller's: the kernel cuts a slice at
 // the pool's end.
 static bool constraint_ok(int kind, int32_t V, const ConstraintParams& c, int64_t table_ld) {
-  if (kind == CON_NONE || (kind == CON_ROWS_OR_NONE && !c.table)) return true;
+  if (kind == CON_NONE || ((kind == CON_ROWS_OR_NONE || kind == CON_WIDE_OR_NONE) && !c.table)) return true;
   if (!(c.table && c.states && c.n_states > 0 && table_ld >= V && table_ld < (1ll << 31) && c.states_ld >= 1)) return false;
-  return kind == CON_WIDE ? c.n_states <= 32767 : (c.row_base && c.row_states);
+  return (kind == CON_WIDE || kind == CON_WIDE_OR_NONE) ? c.n_states <= 32767 : (c.row_base && c.row_states);
 }
 
 // the sampler's own arguments (the greedy forms have none: step is 0)
@@ -1112,6 +1112,81 @@ int aki_sample_pick_rows_processed(const void* logits, int32_t B, int32_t V, int
   return pick_call(c, stream);
 }
 
+// ---- the penalised forms: min_p and the frequency / presence penalties as nullable per-row device arrays of B floats, beside the
+// arguments of the forms above.  A NULL table is "no constraint", so one entry point serves the constrained and the plain call.
+int aki_greedy_pick_penalized(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                              uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                              int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                              int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                              int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                              const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                              int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states,
+                              int32_t states_ld, const float* frequency_penalty, const float* presence_penalty, void* stream) {
+  PickCall c = pick_processed(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
+                              done_at, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores,
+                              repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
+                              n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids);
+  pick_constraint(c, CON_WIDE_OR_NONE, constraint(table, table_ld, n_states, states, states_ld), table_ld);
+  c.q.freq = frequency_penalty; c.q.pres = presence_penalty;
+  return pick_call(c, stream);
+}
+
+int aki_sample_pick_penalized(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                              uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                              int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                              int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                              int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                              const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                              int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                              uint64_t offset, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld, int32_t n_states,
+                              int32_t* states, int32_t states_ld, const float* frequency_penalty, const float* presence_penalty,
+                              const float* min_p, void* stream) {
+  PickCall c = pick_processed(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len, advance,
+                              done_at, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores, ld_scores,
+                              repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids,
+                              n_begin_suppress, bad_ids, bad_offsets, n_bad, n_bad_ids);
+  pick_sampler(c, step, temperature, top_k, top_p, seed, offset, probs_out, ld_probs);
+  pick_constraint(c, CON_WIDE_OR_NONE, constraint(table, table_ld, n_states, states, states_ld), table_ld);
+  c.q.freq = frequency_penalty; c.q.pres = presence_penalty; c.sp.min_p = min_p;
+  return pick_call(c, stream);
+}
+
+int aki_greedy_pick_rows_penalized(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos,
+                                   int64_t pad_token_id, uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld,
+                                   int32_t* cache_len, const int32_t* start_len, int32_t advance, int32_t* done_at, const void* embed_weight,
+                                   const void* additional_weight, int64_t max_original_id, int64_t num_additional, int32_t d,
+                                   void* next_embeds, float* scores, int64_t ld_scores, const int32_t* sets, int32_t n_sets,
+                                   const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets,
+                                   int32_t n_words, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states,
+                                   int32_t states_ld, const int32_t* row_base, const int32_t* row_states, const float* frequency_penalty,
+                                   const float* presence_penalty, void* stream) {
+  PickCall c = pick_processed_rows(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len,
+                                   advance, done_at, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores,
+                                   ld_scores, sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words);
+  pick_constraint(c, CON_ROWS_OR_NONE, constraint(table, table_ld, n_states, states, states_ld, row_base, row_states), table_ld);
+  c.q.freq = frequency_penalty; c.q.pres = presence_penalty;
+  return pick_call(c, stream);
+}
+
+int aki_sample_pick_rows_penalized(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos,
+                                   int64_t pad_token_id, uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld,
+                                   int32_t* cache_len, const int32_t* start_len, int32_t advance, int32_t* done_at, const void* embed_weight,
+                                   const void* additional_weight, int64_t max_original_id, int64_t num_additional, int32_t d,
+                                   void* next_embeds, float* scores, int64_t ld_scores, const int32_t* sets, int32_t n_sets,
+                                   const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets,
+                                   int32_t n_words, int32_t step, const float* temperature, const int32_t* top_k, const float* top_p,
+                                   const uint64_t* seed, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld,
+                                   int32_t n_states, int32_t* states, int32_t states_ld, const int32_t* row_base, const int32_t* row_states,
+                                   const float* frequency_penalty, const float* presence_penalty, const float* min_p, void* stream) {
+  PickCall c = pick_processed_rows(logits, B, V, ld, eos_ids, n_eos, pad_token_id, done, next_ids, tokens, tokens_ld, cache_len, start_len,
+                                   advance, done_at, embed_weight, additional_weight, max_original_id, num_additional, d, next_embeds, scores,
+                                   ld_scores, sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words);
+  pick_sampler_rows(c, step, temperature, top_k, top_p, seed, probs_out, ld_probs);
+  pick_constraint(c, CON_ROWS_OR_NONE, constraint(table, table_ld, n_states, states, states_ld, row_base, row_states), table_ld);
+  c.q.freq = frequency_penalty; c.q.pres = presence_penalty; c.sr.min_p = min_p;
+  return pick_call(c, stream);
+}
+
 // aki_logits_process*: q as proc_common / proc_values filled it, ps the per-row sets or nullptr; ld / ld_out / table_ld as the caller passed them
 static int logits_process_call(const ProcParams& q, const ProcSetParams* ps, int32_t B, int64_t ld, int64_t ld_out, int32_t dtype, int kind,
                                int64_t table_ld, void* stream) {
@@ -1157,6 +1232,36 @@ int aki_logits_process_rows(const void* logits, int32_t dtype, int32_t B, int32_
                             const int32_t* row_base, const int32_t* row_states, void* stream) {
   ProcParams q = proc_common(logits, dtype == AKI_DT_F32, ld, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, eos_ids, n_eos);
   q.c = constraint(table, table_ld, n_states, states, states_ld, row_base, row_states);
+  const ProcSetParams ps = proc_sets(sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words);
+  return logits_process_call(q, &ps, B, ld, ld_out, dtype, CON_ROWS_OR_NONE, table_ld, stream);
+}
+
+int aki_logits_process_penalized(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
+                                 const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step,
+                                 const uint8_t* done, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length,
+                                 const int64_t* eos_ids, int32_t n_eos, const int64_t* suppress_ids, int32_t n_suppress,
+                                 const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids,
+                                 const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld,
+                                 int32_t n_states, int32_t* states, int32_t states_ld, const float* frequency_penalty,
+                                 const float* presence_penalty, void* stream) {
+  ProcParams q = proc_common(logits, dtype == AKI_DT_F32, ld, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, eos_ids, n_eos);
+  proc_values(q, repetition_penalty, no_repeat_ngram_size, min_length, suppress_ids, n_suppress, begin_suppress_ids, n_begin_suppress, bad_ids,
+              bad_offsets, n_bad, n_bad_ids);
+  q.c = constraint(table, table_ld, n_states, states, states_ld);
+  q.freq = frequency_penalty; q.pres = presence_penalty;
+  return logits_process_call(q, nullptr, B, ld, ld_out, dtype, CON_WIDE_OR_NONE, table_ld, stream);
+}
+
+int aki_logits_process_rows_penalized(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
+                                      const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len,
+                                      int32_t step, const uint8_t* done, const int64_t* eos_ids, int32_t n_eos, const int32_t* sets,
+                                      int32_t n_sets, const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids,
+                                      const int32_t* bad_offsets, int32_t n_words, const int16_t* table, int64_t table_ld, int32_t n_states,
+                                      int32_t* states, int32_t states_ld, const int32_t* row_base, const int32_t* row_states,
+                                      const float* frequency_penalty, const float* presence_penalty, void* stream) {
+  ProcParams q = proc_common(logits, dtype == AKI_DT_F32, ld, out, ld_out, V, tokens, tokens_ld, cache_len, start_len, step, done, eos_ids, n_eos);
+  q.c = constraint(table, table_ld, n_states, states, states_ld, row_base, row_states);
+  q.freq = frequency_penalty; q.pres = presence_penalty;
   const ProcSetParams ps = proc_sets(sets, n_sets, row_set, set_ids, n_set_ids, bad_offsets, n_words);
   return logits_process_call(q, &ps, B, ld, ld_out, dtype, CON_ROWS_OR_NONE, table_ld, stream);
 }

@@ -1652,6 +1652,8 @@ __global__ __launch_bounds__(PICK_THREADS) void greedy_pick_kernel(const PickPar
 // order), for the case the reference runs - a decoder-only model called with inputs_embeds only, so the processors' input_ids are the row's
 // GENERATED tokens h[0, n) and never the prompt:
 //   1 repetition penalty  s = s < 0 ? s * penalty : s / penalty for every distinct token of h (RepetitionPenaltyLogitsProcessor)
+//   1b frequency / presence penalty  (not HF's: the OpenAI definition, in vLLM's place) for every distinct token of h with c occurrences:
+//                         s = s - fl(frequency * c) when frequency != 0, then s = s - presence when presence != 0; one value of each per row
 //   2 no-repeat n-gram    -inf for every token that would complete an n-gram already in h (NoRepeatNGramLogitsProcessor)
 //   3 bad words           -inf for a one-token word; for a longer word, -inf for its last token when h ends with the rest of it and h holds
 //                         at least the whole word's length (SequenceBiasLogitsProcessor's rule)
@@ -1666,7 +1668,17 @@ __device__ __forceinline__ void ban(float* out, int V, int64_t g) {
   if (g >= 0 && g < V) out[g] = -INFINITY;
 }
 
+constexpr int PROC_HIST_LDS = 4096;  // 1b counts from an LDS copy of a history up to this length (16 KB), from global memory above it
+
+// arr[b] of a nullable per-row float array, in a scalar register; nullptr and a value that is not finite read as 0
+__device__ __forceinline__ float row_penalty(const float* arr, int b) {
+  if (arr == nullptr) return 0.f;
+  const float v = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(arr[b])));
+  return (v >= -3.0e38f && v <= 3.0e38f) ? v : 0.f;
+}
+
 __device__ void process_row(const ProcParams& q, int b, float* out, unsigned* s_bits) {
+  __shared__ __attribute__((aligned(16))) int s_hist_ids[PROC_HIST_LDS];
   const int tid = threadIdx.x, nt = blockDim.x, V = q.V;
   int n = q.step;
   if (q.cache_len != nullptr) n += q.cache_len[b] - (q.start_len != nullptr ? q.start_len[b] : 0);
@@ -1693,19 +1705,48 @@ __device__ void process_row(const ProcParams& q, int b, float* out, unsigned* s_
     return;
   }
   const int64_t* h = q.tokens + (size_t)b * q.tokens_ld;
-  const bool pen = q.penalty != 1.f && n > 0;
+  // 1b's two values: one float per row, the same address for every thread of the row, so what they decide below is workgroup-uniform
+  // (moved to a scalar register to say so).  A value that is not finite reads as 0.
+  const float fq = row_penalty(q.freq, b), pr = row_penalty(q.pres, b);
+  const bool rep = q.penalty != 1.f;
+  const bool pen = (rep || fq != 0.f || pr != 0.f) && n > 0;
+  const bool hist_lds = pen && fq != 0.f && n <= PROC_HIST_LDS;
   if (pen)
     for (int i = tid; i < (V + 31) / 32; i += nt) s_bits[i] = 0u;
-  __syncthreads();                                           // the copy (and the bitmap) before any scattered write
+  if (hist_lds)                                              // the history as 32-bit ids (V < 2^31), what is outside [0, V) as -1
+    for (int i = tid; i < n; i += nt) {
+      const int64_t g = h[i];
+      s_hist_ids[i] = (g >= 0 && g < V) ? (int)g : -1;
+    }
+  __syncthreads();                                           // the copy (and the bitmap, the staged history) before any scattered write
   if (pen) {
-    // every distinct token once: the occurrence that sets its bit owns it, reads the copied score and writes the penalised one
+    // every distinct token once: the occurrence that sets its bit owns it, reads the copied score and writes the penalised one.
+    // 1 the repetition penalty; 1b then x - fl(frequency * count) and x - presence, each ONE rounded f32 operation (never an FMA).
+    // The owner counts its token's occurrences itself, over the whole history: no counter lives between steps and no atomic adds up.
     for (int i = tid; i < n; i += nt) {
       const int64_t g = h[i];
       if (g < 0 || g >= V) continue;
       const unsigned m = 1u << (g & 31);
       if (atomicOr(&s_bits[g >> 5], m) & m) continue;
-      const float x = out[g];
-      out[g] = x < 0.f ? x * q.penalty : x / q.penalty;
+      float x = out[g];
+      if (rep) x = x < 0.f ? x * q.penalty : x / q.penalty;
+      if (fq != 0.f) {
+        int c = 0;
+        if (hist_lds) {
+          const int gi = (int)g;
+          int j = 0;
+          for (; j + 4 <= n; j += 4) {                       // every lane reads the same words: one broadcast read per four tokens
+            const int4 v = *(const int4*)(s_hist_ids + j);
+            c += (v.x == gi) + (v.y == gi) + (v.z == gi) + (v.w == gi);
+          }
+          for (; j < n; ++j) c += s_hist_ids[j] == gi;
+        } else {
+          for (int j = 0; j < n; ++j) c += h[j] == g;
+        }
+        x = __fsub_rn(x, __fmul_rn(fq, (float)c));
+      }
+      if (pr != 0.f) x = __fsub_rn(x, pr);
+      out[g] = x;
     }
     __syncthreads();                                         // penalties before the bans: a banned token ends at -inf
   }
@@ -1926,6 +1967,10 @@ __device__ __forceinline__ void sample_pick_body(const PickParams& p, const Proc
     seed_lo = sp.seed_lo; seed_hi = sp.seed_hi;
     ctr1 = (unsigned)b; off_lo = sp.off_lo; off_hi = sp.off_hi;
   }
+  // min_p (HF MinPLogitsWarper, behind top-k and top-p): a kept token stays iff exp(y - ymax) >= min_p - the weight the draw computes
+  // anyway.  One float per row, every thread reads the same entry; a value outside (0, 1] (0, NaN, no array) is no filter: w >= 0 holds.
+  float min_p = sp.min_p != nullptr ? sp.min_p[b] : 0.f;
+  if (!(min_p > 0.f && min_p <= 1.f)) min_p = 0.f;
   // pass 0: argmax of x in the greedy pick's ordering, y = x / T (correctly rounded) into the scratch row
   float best = -INFINITY;
   int bi = 0x7fffffff;
@@ -2007,8 +2052,9 @@ __device__ __forceinline__ void sample_pick_body(const PickParams& p, const Proc
       float w[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const bool keep = g * 4 + e < V && sample_key(ve[e]) >= tau;
+        bool keep = g * 4 + e < V && sample_key(ve[e]) >= tau;
         w[e] = keep ? expf(ve[e] - ymax) : 0.f;
+        if (w[e] < min_p) { keep = false; w[e] = 0.f; }
         if (keep) last = g * 4 + e;
       }
       csum += (w[0] + w[1]) + (w[2] + w[3]);
@@ -2029,7 +2075,10 @@ __device__ __forceinline__ void sample_pick_body(const PickParams& p, const Proc
         const float ve[4] = {v.x, v.y, v.z, v.w};
         float w[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = (g * 4 + e < V && sample_key(ve[e]) >= tau) ? expf(ve[e] - ymax) : 0.f;
+        for (int e = 0; e < 4; ++e) {
+          w[e] = (g * 4 + e < V && sample_key(ve[e]) >= tau) ? expf(ve[e] - ymax) : 0.f;
+          if (w[e] < min_p) w[e] = 0.f;
+        }
         const float c[4] = {w[0], w[0] + w[1], (w[0] + w[1]) + w[2], (w[0] + w[1]) + (w[2] + w[3])};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -2046,7 +2095,8 @@ __device__ __forceinline__ void sample_pick_body(const PickParams& p, const Proc
     if (probs) {
       for (int i = tid; i < V; i += PICK_THREADS) {
         const float y = rowf[i];
-        probs[i] = sample_key(y) >= tau ? expf(y - ymax) / total : 0.f;
+        const float w = sample_key(y) >= tau ? expf(y - ymax) : 0.f;
+        probs[i] = (w > 0.f && w >= min_p) ? w / total : 0.f;
       }
     }
   }
@@ -2121,7 +2171,7 @@ __global__ __launch_bounds__(PICK_THREADS) void sample_pick_rows_processed_kerne
 // per row, and a NULL table is "no constraint"
 int logits_process_call_launch(const ProcParams& q_in, const ProcSetParams* ps, int B, hipStream_t s) {
   ProcParams q = q_in;
-  if (ps != nullptr && q.c.table == nullptr) q.c = ConstraintParams{};
+  if (q.c.table == nullptr) q.c = ConstraintParams{};
   AKI_CLEAR_ERR();
   if (ps != nullptr) hipLaunchKernelGGL(logits_process_rows_kernel, dim3(B), dim3(PROC_THREADS), 0, s, q, *ps);
   else hipLaunchKernelGGL(logits_process_kernel, dim3(B), dim3(PROC_THREADS), 0, s, q);
@@ -2135,7 +2185,7 @@ int pick_call_launch(const PickCall& c, hipStream_t s) {
   ProcParams q = c.q;
   // the processors see the tokens generated BEFORE this pick: n = step + cache_len + advance - start_len, the index the pick writes
   q.step = p.step + (p.cache_len ? p.advance : 0);
-  if (c.sets && q.c.table == nullptr) q.c = ConstraintParams{};
+  if (q.c.table == nullptr) q.c = ConstraintParams{};     // the "or none" kinds: a NULL table is no constraint, whatever stands behind it
   const dim3 grid(p.B), block(PICK_THREADS);
   AKI_CLEAR_ERR();
   if (!c.processed) {
@@ -2150,7 +2200,7 @@ int pick_call_launch(const PickCall& c, hipStream_t s) {
     hipLaunchKernelGGL(sample_pick_rows_processed_kernel, grid, block, 0, s, p, q, c.ps, sr);
   } else {
     const bool processed = q.penalty != 1.f || q.ngram > 0 || q.n_bad > 0 || (q.min_len > 0 && q.n_eos > 0) || q.n_suppress > 0 ||
-                           q.n_begin > 0 || q.c.table != nullptr;
+                           q.n_begin > 0 || q.c.table != nullptr || q.freq != nullptr || q.pres != nullptr;
     if (c.sampler == SAMPLER_ROWS) {                        // the per-row form: the four arrays stand in for the scalars
       SampleRowParams sr = c.sr;
       sr.processed = processed ? 1 : 0;

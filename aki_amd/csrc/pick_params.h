@@ -43,6 +43,9 @@ struct ProcParams {
   const int64_t* begin_suppress; int n_begin;
   const int64_t* bad_ids; const int* bad_off; int n_bad, n_bad_ids;
   ConstraintParams c;                 // c.table == nullptr: no constraint
+  // stage 1b, optional: the OpenAI frequency / presence penalties, one float per row (device arrays of B entries; nullptr = 0 for every
+  // row).  A value that is not finite reads as 0.  Every thread of row b reads the same entry: workgroup-uniform.
+  const float* freq; const float* pres;
 };
 
 struct SampleParams {
@@ -50,6 +53,7 @@ struct SampleParams {
   unsigned seed_lo, seed_hi, off_lo, off_hi;
   float* probs; int ld_probs;
   int processed;                                            // the processors ran: x is the f32 scratch row, not the bf16 logits
+  const float* min_p;                                       // optional, one float per row (B entries): keep iff exp(y - ymax) >= min_p[b]
 };
 
 // The per-row form (aki_sample_pick_rows): row b reads its own temperature[b], top_k[b], top_p[b] and Philox key seed[b] from device
@@ -57,11 +61,13 @@ struct SampleParams {
 // draw row 0 of a batch-1 scalar call with that seed and offset 0 makes.  One workgroup per row: the values are workgroup-uniform.
 // Nothing validates the arrays on the device; bad bits stay inside the row: a temperature that is not > 0 (zero, negative, NaN) takes
 // the greedy pick, top_k[b] <= 0 or >= V is no top-k filter, top_p[b] >= 1 is no top-p filter (and a top_p that is not > 0 keeps the
-// maximum only).  top_k[b] == 1 is the greedy branch, as in the scalar form.
+// maximum only).  top_k[b] == 1 is the greedy branch, as in the scalar form.  min_p (nullable, as in SampleParams): a value outside
+// (0, 1] is no filter.
 struct SampleRowParams {
   const float* temperature; const int* top_k; const float* top_p; const unsigned long long* seed;
   float* probs; int ld_probs;
   int processed;
+  const float* min_p;
 };
 
 constexpr int PROC_SET_WORDS = 9;
@@ -73,8 +79,8 @@ struct ProcSetParams {
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 // How an entry point takes its token constraint.  WIDE allows at most 32767 states (one automaton for every row); the two ROWS kinds take
 // a pool of any positive size with row_base / row_states, and ROWS_OR_NONE reads a NULL table as "no constraint" (the other six arguments
-// are then not looked at).
-enum ConstraintKind { CON_NONE = 0, CON_WIDE, CON_ROWS, CON_ROWS_OR_NONE };
+// are then not looked at); WIDE_OR_NONE is WIDE with the same reading of a NULL table.
+enum ConstraintKind { CON_NONE = 0, CON_WIDE, CON_ROWS, CON_ROWS_OR_NONE, CON_WIDE_OR_NONE };
 enum SamplerKind { SAMPLER_NONE = 0, SAMPLER_SCALAR, SAMPLER_ROWS };
 
 // One pick, as its entry point was called.  The kernel structs hold the narrowed values; the strides and counts the C ABI takes as 64-bit

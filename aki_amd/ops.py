@@ -719,6 +719,54 @@ def chain_replay_on_current_stream() -> None:
         _CHAIN_LAST[cur.device_index] = cur
 
 
+_NO_WIDE_CONSTRAINT = (None, 0, 0, None, 0)
+_NO_ROW_CONSTRAINT = (None, 0, 0, None, 0, None, None)
+
+
+def check_penalty(name: str, value) -> float:
+    """frequency_penalty / presence_penalty: a finite float in [-2, 2] -> the float32 the device reads (slots.check_additive_penalty)."""
+    from .slots import check_additive_penalty
+    return check_additive_penalty("logits processors", name, value)
+
+
+def check_min_p(value) -> float:
+    """min_p: a float in [0, 1] -> the float32 the device reads (slots.check_min_p)."""
+    from .slots import check_min_p as check
+    return check("sampler", value)
+
+
+def _penalty_rows(name: str, processors, frequency_penalty, presence_penalty, B: int, device, min_p=None):
+    """The nullable per-row arrays of the *_penalized entry points: (frequency_penalty, presence_penalty, min_p) as given (f32
+    contiguous tensors [B] on the logits' device), else a penalised LogitsProcessors' own; None when nothing is set - the call then takes
+    the entry point it took before these existed."""
+    for nm, x in (("frequency_penalty", frequency_penalty), ("presence_penalty", presence_penalty), ("min_p", min_p)):
+        if x is not None and (not torch.is_tensor(x) or x.dtype != torch.float32 or tuple(x.shape) != (B,) or not x.is_contiguous()
+                              or x.device != device):
+            raise AkiError(f"{name}: {nm} is a contiguous f32 tensor [{B}] on {device}")
+    if processors is not None and processors.active and getattr(processors, "penalized", False):
+        fq, pr = processors.penalty_rows(B, device)
+        frequency_penalty = fq if frequency_penalty is None else frequency_penalty
+        presence_penalty = pr if presence_penalty is None else presence_penalty
+    if frequency_penalty is None and presence_penalty is None and min_p is None:
+        return None
+    return frequency_penalty, presence_penalty, min_p
+
+
+_MIN_P_ROWS = {}
+
+
+def _min_p_rows(min_p: float, B: int, device) -> Optional[torch.Tensor]:
+    """A scalar min_p as the f32 [B] device array the sampler reads (kept per value and shape: a captured graph holds its address);
+    None for 0, no filter."""
+    v = check_min_p(min_p)
+    if v == 0.0:
+        return None
+    key = (v, int(B), str(device))
+    if key not in _MIN_P_ROWS:
+        _MIN_P_ROWS[key] = torch.full((int(B),), v, dtype=torch.float32, device=device)
+    return _MIN_P_ROWS[key]
+
+
 class LogitsProcessors:
     """HF `generate`'s logits processors for a decoder-only model called with inputs_embeds only (what src/aki.py:192-207 runs), on the
     device (aki_logits_process / aki_greedy_pick_processed; include/aki_mi355x.h): the processors' input_ids are the GENERATED tokens,
@@ -731,11 +779,20 @@ class LogitsProcessors:
     this object, one per generation: column 0 holds each row's start state, the picks store the state behind every token they pick, and
     all of them address it by the generated-token index, as they do the token history.
     slot_constraints=True: the picks will be handed a SlotConstraints (one automaton per row, generate_many) - the object is then active
-    even with every processor neutral, because the constrained pick scans the f32 scores scratch this object owns."""
+    even with every processor neutral, because the constrained pick scans the f32 scores scratch this object owns.
+    frequency_penalty / presence_penalty (the OpenAI definition, in vLLM's place: stage 1b, directly behind the repetition penalty and
+    before every ban): for every distinct generated token with c occurrences, score - fl(frequency_penalty * c), then score -
+    presence_penalty; finite floats in [-2, 2], 0 is neutral.  They ban nothing, so they compose with a constraint.  With either set the
+    object routes to the *_penalized entry points, which take the values as device arrays of one float per row, filled here."""
 
     def __init__(self, V: int, device, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_length: int = 0, eos_ids=(),
-                 suppress_tokens=None, begin_suppress_tokens=None, bad_words_ids=None, constraint=None, slot_constraints: bool = False):
+                 suppress_tokens=None, begin_suppress_tokens=None, bad_words_ids=None, constraint=None, slot_constraints: bool = False,
+                 frequency_penalty: float = 0.0, presence_penalty: float = 0.0):
         V = int(V)
+        self.frequency = check_penalty("frequency_penalty", frequency_penalty)
+        self.presence = check_penalty("presence_penalty", presence_penalty)
+        self.penalized = bool(self.frequency != 0.0 or self.presence != 0.0)
+        self._pen_rows = {}
         if V <= 0:
             raise ValueError(f"logits processors: a vocabulary of {V} columns")
         pen = float(repetition_penalty)
@@ -762,7 +819,7 @@ class LogitsProcessors:
         self.suppress, self.begin_suppress = ids("suppress_tokens", suppress_tokens), ids("begin_suppress_tokens", begin_suppress_tokens)
         self.words = words
         self.active = bool(pen != 1.0 or self.ngram > 0 or words or (self.min_length > 0 and eos) or self.suppress or self.begin_suppress
-                           or constraint is not None or slot_constraints)
+                           or constraint is not None or slot_constraints or self.penalized)
         if self.active and V > L.AKI_LOGITS_PROCESS_MAX_V:
             raise ValueError(f"logits processors: a vocabulary of {V} is above {L.AKI_LOGITS_PROCESS_MAX_V}")
         dev = torch.device(device)
@@ -787,6 +844,15 @@ class LogitsProcessors:
         n = lambda t: 0 if t is None else t.numel()
         return (self.penalty, self.ngram, self.min_length), (_ptr(self._sup), n(self._sup), _ptr(self._bsup), n(self._bsup), _ptr(self._bad),
                                                             _ptr(self._off), len(self.words), n(self._bad))
+
+    def penalty_rows(self, B: int, device):
+        """(frequency_penalty, presence_penalty) as f32 device tensors [B] filled with this object's values, None for a zero one; kept
+        per batch size (a captured graph holds their addresses)."""
+        key = (int(B), str(torch.device(device)))
+        if key not in self._pen_rows:
+            row = lambda v: torch.full((int(B),), v, dtype=torch.float32, device=device) if v != 0.0 else None
+            self._pen_rows[key] = (row(self.frequency), row(self.presence))
+        return self._pen_rows[key]
 
     def scores(self, B: int, device) -> torch.Tensor:
         """The f32 [B, >= V] scratch the processed greedy pick writes its scores to (kept: a captured graph holds its address)."""
@@ -858,6 +924,11 @@ class LogitsProcessors:
                 0 if tokens is None else tokens.shape[1], _ptr(cache_len), _ptr(start_len), int(step), _ptr(done),
                 *head, _ptr(self._eos), 0 if self._eos is None else self._eos.numel(), *tail)
         con = self._constraint_args(B, tokens.shape[1] if tokens is not None else (int(step) + 1 if cache_len is None else None))
+        if self.penalized:
+            fq, pr = self.penalty_rows(B, dev)
+            L.check(L.load().aki_logits_process_penalized(*args, *(con or _NO_WIDE_CONSTRAINT), _ptr(fq), _ptr(pr), _stream()),
+                    "aki_logits_process_penalized")
+            return out
         if con is not None:
             L.check(L.load().aki_logits_process_constrained(*args, *con, _stream()), "aki_logits_process_constrained")
             return out
@@ -1004,11 +1075,13 @@ class ProcessorSets:
 
     def apply(self, logits: torch.Tensor, out: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, step: int = 0,
               cache_len: Optional[torch.Tensor] = None, start_len: Optional[torch.Tensor] = None, done: Optional[torch.Tensor] = None,
-              slot_constraints: Optional["SlotConstraints"] = None) -> torch.Tensor:
+              slot_constraints: Optional["SlotConstraints"] = None, frequency_penalty: Optional[torch.Tensor] = None,
+              presence_penalty: Optional[torch.Tensor] = None) -> torch.Tensor:
         """LogitsProcessors.apply with row b processed by set row_set[b] (aki_logits_process_rows, one launch): f32 scores [B, V] of bf16
         / f32 logits.  out=None: a view of the pool's own scratch for this batch size - kept, so a per-step caller allocates nothing, and
         overwritten by the next call of that batch size.  slot_constraints: the rows' automata as the last stage (the state history is
-        read, not advanced)."""
+        read, not advanced).  frequency_penalty / presence_penalty: optional f32 tensors [B], one value per row (stage 1b;
+        aki_logits_process_rows_penalized)."""
         if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[1] != self.V:
             raise AkiError(f"logits processors: logits [B, {self.V}] with unit column stride are expected, got {tuple(logits.shape)}")
         B = logits.shape[0]
@@ -1024,14 +1097,16 @@ class ProcessorSets:
             raise AkiError("logits processors: tokens is [B, *]")
         if tokens is not None and tokens.shape[1] == 0:
             tokens = None
-        con = (None, 0, 0, None, 0, None, None)
+        con = _NO_ROW_CONSTRAINT
         if slot_constraints is not None:
             con = slot_constraints._args("logits processors", B, self.V, dev)
-        L.check(L.load().aki_logits_process_rows(
+        pen = _penalty_rows("logits processors", None, frequency_penalty, presence_penalty, B, dev)
+        fn = "aki_logits_process_rows" if pen is None else "aki_logits_process_rows_penalized"
+        L.check(getattr(L.load(), fn)(
             _ptr(logits), _dt(logits), B, self.V, logits.stride(0), _ptr(out), out.stride(0), _ptr(tokens),
             0 if tokens is None else tokens.shape[1], _ptr(cache_len), _ptr(start_len), int(step), _ptr(done), _ptr(self._eos),
-            0 if self._eos is None else self._eos.numel(), *self._args("logits processors", B, self.V, dev), *con, _stream()),
-            "aki_logits_process_rows")
+            0 if self._eos is None else self._eos.numel(), *self._args("logits processors", B, self.V, dev), *con,
+            *(() if pen is None else (_ptr(pen[0]), _ptr(pen[1]))), _stream()), fn)
         return out
 
 
@@ -1068,7 +1143,8 @@ def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
                 done: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None, cache_len: Optional[torch.Tensor] = None,
                 start_len: Optional[torch.Tensor] = None, advance: bool = False, done_at: Optional[torch.Tensor] = None,
                 embed=None, next_embeds: Optional[torch.Tensor] = None, processors: Optional[LogitsProcessors] = None,
-                slot_constraints: Optional[SlotConstraints] = None, processor_sets: Optional[ProcessorSets] = None) -> torch.Tensor:
+                slot_constraints: Optional[SlotConstraints] = None, processor_sets: Optional[ProcessorSets] = None,
+                frequency_penalty: Optional[torch.Tensor] = None, presence_penalty: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The step between two decode steps of a greedy `generate` as one launch (aki_greedy_pick; HF GenerationMixin's greedy branch):
     next_ids[b] = pad if done[b] else argmax(logits[b]); tokens[b, t] = next with t = cache_len[b] + advance - start_len[b]; rows whose
     next is an eos id become done (done_at[b] = t); advance: cache_len += 1.  logits: bf16 [B, V] (row stride >= V); next_ids / tokens /
@@ -1082,10 +1158,16 @@ def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
     the last processor stage (aki_greedy_pick_constrained_rows) - row b in state s = states[b, t] is masked by pool row row_base[b] + s
     and states[b, t + 1] receives the table entry, a state local to the row's automaton; a row in state -1 is picked unmasked.
     processor_sets (an ops.ProcessorSets, in the place of `processors`): one set of processor settings per row (aki_greedy_pick_rows) - row
-    b is processed with the pool's set row_set[b]; slot_constraints composes with it and needs no LogitsProcessors then."""
+    b is processed with the pool's set row_set[b]; slot_constraints composes with it and needs no LogitsProcessors then.
+    frequency_penalty / presence_penalty: optional f32 tensors [B], one value per row (stage 1b of the processors; a penalised
+    LogitsProcessors brings its own) - with processor_sets aki_greedy_pick_rows_penalized, with processors aki_greedy_pick_penalized."""
     common, emb, processed, con = _pick_front("greedy_pick", logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len, advance,
                                               done_at, embed, next_embeds, processors, slot_constraints, processor_sets, scratch=False)
-    if processed is None:                   # no processors: the plain forms take no scratch (and no V limit)
+    pen = _penalty_rows("greedy_pick", processors, frequency_penalty, presence_penalty, logits.shape[0], logits.device)
+    if pen is not None:
+        fn = _penalized_form("greedy_pick", processed, processors, slot_constraints, processor_sets)
+        args = (*common, *emb, *processed, *(con or _NO_WIDE_CONSTRAINT), _ptr(pen[0]), _ptr(pen[1]))
+    elif processed is None:                 # no processors: the plain forms take no scratch (and no V limit)
         fn, args = ("aki_greedy_pick", common) if embed is None else ("aki_greedy_pick_embed", (*common, *emb))
     else:
         fn = "aki_greedy_pick_rows" if processor_sets is not None else "aki_greedy_pick_constrained_rows" if slot_constraints is not None \
@@ -1093,6 +1175,19 @@ def greedy_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
         args = (*common, *emb, *processed, *(con or ()))
     L.check(getattr(L.load(), fn)(*args, _stream()), fn)
     return next_ids
+
+
+def _penalized_form(name: str, processed, processors, slot_constraints, processor_sets) -> str:
+    """The *_penalized entry point of a pick that carries min_p or a frequency / presence penalty: the per-row form with processor_sets,
+    else the call-wide one, which has no per-row constraint."""
+    if processed is None:
+        raise AkiError(f"{name}: frequency_penalty / presence_penalty need the f32 scores scratch of an active LogitsProcessors or of "
+                       "processor_sets")
+    if processor_sets is not None:
+        return f"aki_{name}_rows_penalized"
+    if slot_constraints is not None:
+        raise AkiError(f"{name}: min_p / frequency_penalty / presence_penalty with slot_constraints take processor_sets (the per-row form)")
+    return f"aki_{name}_penalized"
 
 
 class DeviceGenerator:
@@ -1177,20 +1272,29 @@ def sample_pick(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id: int 
                 start_len: Optional[torch.Tensor] = None, advance: bool = False, done_at: Optional[torch.Tensor] = None,
                 embed=None, next_embeds: Optional[torch.Tensor] = None, processors: Optional[LogitsProcessors] = None, step: int = 0,
                 temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, offset: int = 0,
-                probs_out: Optional[torch.Tensor] = None, scores: Optional[torch.Tensor] = None) -> torch.Tensor:
+                probs_out: Optional[torch.Tensor] = None, scores: Optional[torch.Tensor] = None, min_p: float = 0.0,
+                frequency_penalty: Optional[torch.Tensor] = None, presence_penalty: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ops.greedy_pick's sibling for `do_sample=True`, one launch (aki_sample_pick): processors, temperature, top-k, top-p and one
     counter-based draw per row, then the same bookkeeping and embedding gather.  The draw of row b is u = Philox4x32-10(key = seed,
     counter = (n, b, offset))[0], n = step + (cache_len[b] + advance - start_len[b] when cache_len is given) - the index tokens[b, n] is
     written at.  probs_out: optional f32 [B, V], the filtered distribution the draw was made from.  scores: the f32 [B, >= V] scratch
-    (default: the processors' own, or one kept per shape).  Capturable: no host value is read."""
+    (default: the processors' own, or one kept per shape).  Capturable: no host value is read.
+    min_p (HF MinPLogitsWarper, behind top-p): of the tokens top-k and top-p kept, those with exp(y - ymax) >= min_p stay; 0 = no filter.
+    frequency_penalty / presence_penalty: optional f32 tensors [B] (a penalised LogitsProcessors brings its own).  With any of the three
+    the launch is aki_sample_pick_penalized."""
     if not (float(temperature) > 0.0) or not (0.0 < float(top_p) <= 1.0) or int(top_k) < 0 or int(step) < 0:
         raise ValueError(f"sample_pick: temperature > 0, 0 < top_p <= 1, top_k >= 0 and step >= 0 are expected, got {temperature}, {top_p}, {top_k}, {step}")
     common, emb, processed, con = _pick_front("sample_pick", logits, next_ids, pad_token_id, eos_ids, done, tokens, cache_len, start_len, advance,
                                               done_at, embed, next_embeds, processors, step=step, probs_out=probs_out, scores=scores)
+    pen = _penalty_rows("sample_pick", processors, frequency_penalty, presence_penalty, logits.shape[0], logits.device,
+                        _min_p_rows(min_p, logits.shape[0], logits.device))
     fn = "aki_sample_pick" if con is None else "aki_sample_pick_constrained"
+    tail = ()
+    if pen is not None:
+        fn, con, tail = "aki_sample_pick_penalized", con or _NO_WIDE_CONSTRAINT, tuple(_ptr(x) for x in pen)
     L.check(getattr(L.load(), fn)(*common, *emb, *processed, int(step), float(temperature), int(top_k), float(top_p),
                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _ptr(probs_out),
-                                  0 if probs_out is None else probs_out.stride(0), *(con or ()), _stream()), fn)
+                                  0 if probs_out is None else probs_out.stride(0), *(con or ()), *tail, _stream()), fn)
     return next_ids
 
 
@@ -1201,7 +1305,8 @@ def sample_pick_rows(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id:
                      temperature: Optional[torch.Tensor] = None, top_k: Optional[torch.Tensor] = None, top_p: Optional[torch.Tensor] = None,
                      seed: Optional[torch.Tensor] = None, probs_out: Optional[torch.Tensor] = None,
                      scores: Optional[torch.Tensor] = None, slot_constraints: Optional[SlotConstraints] = None,
-                     processor_sets: Optional[ProcessorSets] = None) -> torch.Tensor:
+                     processor_sets: Optional[ProcessorSets] = None, min_p: Optional[torch.Tensor] = None,
+                     frequency_penalty: Optional[torch.Tensor] = None, presence_penalty: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ops.sample_pick with the sampling parameters per row, one launch (aki_sample_pick_rows): `temperature` f32, `top_k` int32, `top_p`
     f32 and `seed` int64 (its bits are the 64-bit Philox key) are contiguous device tensors [B], read by the launch - a captured step
     serves rows whose parameters are rewritten in place.  Row b draws u = Philox4x32-10(key = seed[b], counter = (n, 0, 0, 0))[0], n as
@@ -1212,7 +1317,10 @@ def sample_pick_rows(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id:
     (temperature > 0, top_k >= 0, 0 < top_p <= 1) - in the kernel a temperature that is not > 0 falls to the greedy token, top_k <= 0 or
     >= V and top_p >= 1 switch their filter off.
     processor_sets (an ops.ProcessorSets, in the place of `processors`): one set of processor settings per row
-    (aki_sample_pick_rows_processed); slot_constraints composes with it and needs no LogitsProcessors then."""
+    (aki_sample_pick_rows_processed); slot_constraints composes with it and needs no LogitsProcessors then.
+    min_p, frequency_penalty, presence_penalty: optional f32 tensors [B], one value per row, read by the launch like the four above
+    (aki_sample_pick_rows_penalized: the per-row form, so they come with processor_sets - a pool that holds the neutral set alone will
+    do).  A min_p[b] outside (0, 1] is no filter, a penalty that is not finite reads as 0."""
     if int(step) < 0:
         raise ValueError(f"sample_pick_rows: step >= 0 is expected, got {step}")
     rows = ((temperature, torch.float32), (top_k, torch.int32), (top_p, torch.float32), (seed, torch.int64))
@@ -1226,8 +1334,15 @@ def sample_pick_rows(logits: torch.Tensor, next_ids: torch.Tensor, pad_token_id:
                                               probs_out=probs_out, scores=scores, extra=rows)
     fn = "aki_sample_pick_rows_processed" if processor_sets is not None else \
         "aki_sample_pick_rows" if con is None else "aki_sample_pick_rows_constrained"
+    pen = _penalty_rows("sample_pick_rows", processors, frequency_penalty, presence_penalty, logits.shape[0], logits.device, min_p)
+    tail = ()
+    if pen is not None:
+        if processor_sets is None:
+            raise AkiError("sample_pick_rows: min_p / frequency_penalty / presence_penalty take processor_sets (the per-row form: "
+                           "aki_sample_pick_rows_penalized); a pool that holds the neutral set alone will do")
+        fn, tail = "aki_sample_pick_rows_penalized", tuple(_ptr(x) for x in pen)
     L.check(getattr(L.load(), fn)(*common, *emb, *processed, int(step), _ptr(temperature), _ptr(top_k), _ptr(top_p), _ptr(seed), _ptr(probs_out),
-                                  0 if probs_out is None else probs_out.stride(0), *(con or ()), _stream()), fn)
+                                  0 if probs_out is None else probs_out.stride(0), *(con or ()), *tail, _stream()), fn)
     return next_ids
 
 

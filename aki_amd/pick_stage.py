@@ -11,11 +11,12 @@ from . import ops
 from .ops import ProcessorSets, SlotConstraints, StopSets      # the classes, bound here: isinstance must not depend on a patched ops attribute
 
 
-def pick_rows_torch(logits, ids, pad_token_id: int, eos_ids, done, tokens, cache_len, start_len, done_at, proc=None):
+def pick_rows_torch(logits, ids, pad_token_id: int, eos_ids, done, tokens, cache_len, start_len, done_at, proc=None, penalties=None):
     """What ops.greedy_pick does with advance = 0, in torch, for logits that are not bf16 (an f32 model: generate() picks those on the host
     loop too): next = pad for done rows, else the argmax of the (processed) row; tokens[b, cache_len[b] - start_len[b]] = next; a row whose
-    next is an eos id becomes done at that index.  In place, on the device, no synchronisation."""
-    x = logits if proc is None else proc.apply(logits, tokens=tokens, cache_len=cache_len, start_len=start_len, done=done)
+    next is an eos id becomes done at that index.  In place, on the device, no synchronisation.  penalties: the per-row
+    frequency_penalty / presence_penalty tensors a ProcessorSets' apply takes, or None."""
+    x = logits if proc is None else proc.apply(logits, tokens=tokens, cache_len=cache_len, start_len=start_len, done=done, **(penalties or {}))
     was_done = done.bool()
     nxt = torch.where(was_done, torch.full_like(ids, pad_token_id), x.float().argmax(dim=-1))
     t = (cache_len - start_len).long()
@@ -39,11 +40,11 @@ def _row(x, slot: int):
 class PickStage:
     """The launches behind a decode step.
       pick            the keywords of ops.greedy_pick that stay the same from token to token: pad_token_id, eos_ids, done, tokens, start_len,
-                      done_at, and optionally processors, processor_sets or slot_constraints.  eos_ids is shared by every row; the others that
-                      are tensors hold one row per sequence
+                      done_at, and optionally processors, processor_sets or slot_constraints, and the per-row frequency_penalty /
+                      presence_penalty tensors.  eos_ids is shared by every row; the others that are tensors hold one row per sequence
       embed, next_embeds   the embedding gather of the pick (ops.greedy_pick's arguments of that name); run(embed=False) leaves it out
       sampler         ops.sample_pick's own keywords (temperature, top_k, top_p, seed, offset): the pick is the device sampler
-      rows            ops.sample_pick_rows' four per-row arrays (temperature, top_k, top_p, seed): the pick is the per-row sampler
+      rows            ops.sample_pick_rows' per-row arrays (temperature, top_k, top_p, seed, optionally min_p): the pick is the per-row sampler
       processors_row  the second ops.LogitsProcessors, which owns the B = 1 scores scratch: what row() swaps `processors` for (the call-wide
                       one's scratch address is held by the captured step)
       logprob         ops.token_logprob's output keywords (top_k, out_logprob, out_top_ids, out_top_logprobs): that launch right behind the
@@ -68,7 +69,9 @@ class PickStage:
         self._gather = self._plain if embed is None else dict(self._plain, embed=embed, next_embeds=next_embeds)
         if torch_pick:
             proc = self.pick.get("processor_sets") if self.pick.get("processor_sets") is not None else self.pick.get("processors")
-            self._torch = (self.pick.get("pad_token_id", 0), self.pick.get("eos_ids"), self.done, self.tokens), (self.start_len, self.done_at, proc)
+            pen = {k: self.pick[k] for k in ("frequency_penalty", "presence_penalty") if self.pick.get(k) is not None}
+            self._torch = (self.pick.get("pad_token_id", 0), self.pick.get("eos_ids"), self.done, self.tokens), \
+                (self.start_len, self.done_at, proc, pen or None)
         self._lp = None if logprob is None else dict(logprob, tokens=self.tokens, start_len=self.start_len, done_at=self.done_at)
         self._tick = None if limit is None else dict(done=self.done, done_at=self.done_at, start_len=self.start_len, limit=limit)
         self._tick_stops = None if limit is None or stops is None else dict(self._tick, stops=stops, tokens=self.tokens)

@@ -22,6 +22,33 @@ PROCESSOR_FIELDS = {"repetition_penalty": 1.0, "no_repeat_ngram_size": 0, "bad_w
 
 MAX_PENALTY = 3.0e38                # what the C entry points accept (below FLT_MAX)
 
+# The additive penalties a request may own (the OpenAI / vLLM definition; ops.LogitsProcessors states the arithmetic), with their neutral
+# values.  They travel BESIDE the processor sets, as one float per slot, never inside a set's record.
+PENALTY_FIELDS = {"frequency_penalty": 0.0, "presence_penalty": 0.0}
+MAX_ADDITIVE_PENALTY = 2.0
+
+
+def check_additive_penalty(who: str, name: str, value) -> float:
+    """frequency_penalty / presence_penalty: a finite float in [-2, 2] -> the float32 the device reads.  ValueError beginning with `who`."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not -MAX_ADDITIVE_PENALTY <= v <= MAX_ADDITIVE_PENALTY:
+        raise ValueError(f"{who}: {name} has to be a finite float in [-{MAX_ADDITIVE_PENALTY:g}, {MAX_ADDITIVE_PENALTY:g}], got {value}")
+    return struct.unpack("<f", struct.pack("<f", v))[0]
+
+
+def check_min_p(who: str, value) -> float:
+    """min_p: a float in [0, 1] -> the float32 the device reads.  ValueError beginning with `who`."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not 0.0 <= v <= 1.0:
+        raise ValueError(f"{who}: min_p has to be a float in [0, 1], got {value}")
+    return struct.unpack("<f", struct.pack("<f", v))[0]
+
 
 def _is_int(x) -> bool:
     """An integer, or a float / a one-element array or tensor whose value is a whole number (nothing is truncated silently)."""
@@ -90,7 +117,10 @@ class RequestParams:
     suppress_tokens, begin_suppress_tokens): None = the request takes the call's value (params=, else the call-wide keyword); any other
     value, the neutral ones 1.0 / 0 / () included, belongs to the request alone (resolve_processors).
     stop_sequences: None = the request takes the call's stop set (params=, else the call-wide stop_sequences= keyword); a list of token-id
-    sequences is the request's own set (aki_amd/stops.py states the rule), () means this request has none."""
+    sequences is the request's own set (aki_amd/stops.py states the rule), () means this request has none.
+    min_p (HF MinPLogitsWarper, behind top-p; a float in [0, 1], 0 = no filter) is request-owned like temperature, and like top_p it is
+    ignored for a greedy request.  frequency_penalty / presence_penalty (PENALTY_FIELDS; finite floats in [-2, 2]): None = the call's
+    value (params=, else the call-wide keyword); any other value, 0.0 included, belongs to the request alone (resolve_penalties)."""
     do_sample: bool = False
     temperature: float = 1.0
     top_k: int = 0
@@ -107,6 +137,9 @@ class RequestParams:
     suppress_tokens: Optional[Sequence[int]] = None
     begin_suppress_tokens: Optional[Sequence[int]] = None
     stop_sequences: Optional[Sequence[Sequence[int]]] = None
+    min_p: float = 0.0
+    frequency_penalty: Optional[float] = None
+    presence_penalty: Optional[float] = None
 
     def check(self, index, max_top: int) -> "RequestParams":
         """ValueError naming request `index` (a number, or a word such as "default") for a value the device sampler or ops.token_logprob
@@ -134,6 +167,10 @@ class RequestParams:
         for name in PROCESSOR_FIELDS:                   # the ids' upper bound needs the logits' width: processor_set_key
             if getattr(self, name) is not None:
                 check_processor_value(who, name, getattr(self, name))
+        check_min_p(who, self.min_p)
+        for name in PENALTY_FIELDS:
+            if getattr(self, name) is not None:
+                check_additive_penalty(who, name, getattr(self, name))
         if self.stop_sequences is not None:             # likewise: stops.check_stop_sequences again with the width
             from .stops import check_stop_sequences
             check_stop_sequences(who, self.stop_sequences)
@@ -152,6 +189,21 @@ def resolve_processors(own: Optional[RequestParams], default: Optional[RequestPa
         if v is None:
             v = call.get(name)
         out[name] = neutral if v is None else v
+    return out
+
+
+def resolve_penalties(own: Optional[RequestParams], default: Optional[RequestParams], call: Optional[dict]) -> dict:
+    """One request's {frequency_penalty, presence_penalty}, by resolve_processors' rule: its own RequestParams' value, else that of
+    `default` (generate_many's params=), else the call-wide keyword's (`call`), else 0.  Only None passes a level on: an explicit 0.0
+    overrides.  The values as the float32 the device reads."""
+    out = {}
+    for name, neutral in PENALTY_FIELDS.items():
+        v = None if own is None else getattr(own, name)
+        if v is None and default is not None:
+            v = getattr(default, name)
+        if v is None and call is not None:
+            v = call.get(name)
+        out[name] = struct.unpack("<f", struct.pack("<f", float(neutral if v is None else v)))[0]
     return out
 
 

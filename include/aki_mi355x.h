@@ -999,6 +999,81 @@ int aki_sample_pick_rows_processed(const void* logits, int32_t B, int32_t V, int
                                    int32_t n_states, int32_t* states, int32_t states_ld, const int32_t* row_base, const int32_t* row_states,
                                    void* stream);
 
+/* ---- min_p and the frequency / presence penalties (HF MinPLogitsWarper; the OpenAI penalties in vLLM's order).  Purely additive:
+ * AKI_ABI_VERSION was not bumped (it stays 17).  Six entry points: aki_logits_process_penalized, aki_greedy_pick_penalized and
+ * aki_sample_pick_penalized are aki_logits_process_constrained, aki_greedy_pick_constrained and aki_sample_pick_constrained, and the
+ * three *_rows_penalized are aki_logits_process_rows, aki_greedy_pick_rows and aki_sample_pick_rows_processed, each with two or three
+ * more arguments in front of the stream - device arrays of B floats, read by the launch itself (capturable), each of which may be NULL:
+ *   frequency_penalty, presence_penalty   stage 1b of the processors, directly behind the repetition penalty and before every ban: for
+ *               every distinct token g of the row's generated history h[0, n) with 0 <= g < V and c occurrences,
+ *               x = x - fl(frequency_penalty[b] * (float)c) when frequency_penalty[b] != 0, then x = x - presence_penalty[b] when
+ *               presence_penalty[b] != 0; each ONE correctly rounded f32 operation (no FMA).  The counts are recomputed from the
+ *               history in every launch: nothing is carried between steps, no float atomics, the same bits on every run.  Rows with
+ *               done[b] keep the plain copy; -inf stays -inf.  A value that is not finite reads as 0; NULL is 0 for every row.
+ *   min_p       (the two sample forms) behind temperature, top-k and top-p: a token those kept stays iff
+ *               expf(y - ymax) >= min_p[b], y = x / T.  The maximum always stays (and its ties at min_p = 1); top-p's mass is decided
+ *               before it; the draw and probs_out are made over what remains.  A value outside (0, 1] is no filter; NULL is none for
+ *               every row.  Rows that take the greedy branch take it as before.
+ * In the three call-wide forms table == NULL means no constraint (the four arguments behind it are then ignored), as in the per-row
+ * forms.  The hosts' checks are those of the entry points these extend; the arrays' values are the caller's to validate. */
+int aki_logits_process_penalized(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
+                                 const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len, int32_t step,
+                                 const uint8_t* done, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_length,
+                                 const int64_t* eos_ids, int32_t n_eos, const int64_t* suppress_ids, int32_t n_suppress,
+                                 const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids,
+                                 const int32_t* bad_offsets, int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld,
+                                 int32_t n_states, int32_t* states, int32_t states_ld, const float* frequency_penalty,
+                                 const float* presence_penalty, void* stream);
+
+int aki_greedy_pick_penalized(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                              uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                              int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                              int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                              int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                              const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                              int32_t n_bad, int32_t n_bad_ids, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states,
+                              int32_t states_ld, const float* frequency_penalty, const float* presence_penalty, void* stream);
+
+int aki_sample_pick_penalized(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos, int64_t pad_token_id,
+                              uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld, int32_t* cache_len, const int32_t* start_len,
+                              int32_t advance, int32_t* done_at, const void* embed_weight, const void* additional_weight, int64_t max_original_id,
+                              int64_t num_additional, int32_t d, void* next_embeds, float* scores, int64_t ld_scores, float repetition_penalty,
+                              int32_t no_repeat_ngram_size, int32_t min_length, const int64_t* suppress_ids, int32_t n_suppress,
+                              const int64_t* begin_suppress_ids, int32_t n_begin_suppress, const int64_t* bad_ids, const int32_t* bad_offsets,
+                              int32_t n_bad, int32_t n_bad_ids, int32_t step, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                              uint64_t offset, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld, int32_t n_states,
+                              int32_t* states, int32_t states_ld, const float* frequency_penalty, const float* presence_penalty,
+                              const float* min_p, void* stream);
+
+int aki_logits_process_rows_penalized(const void* logits, int32_t dtype, int32_t B, int32_t V, int64_t ld, float* out, int64_t ld_out,
+                                      const int64_t* tokens, int32_t tokens_ld, const int32_t* cache_len, const int32_t* start_len,
+                                      int32_t step, const uint8_t* done, const int64_t* eos_ids, int32_t n_eos, const int32_t* sets,
+                                      int32_t n_sets, const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids,
+                                      const int32_t* bad_offsets, int32_t n_words, const int16_t* table, int64_t table_ld, int32_t n_states,
+                                      int32_t* states, int32_t states_ld, const int32_t* row_base, const int32_t* row_states,
+                                      const float* frequency_penalty, const float* presence_penalty, void* stream);
+
+int aki_greedy_pick_rows_penalized(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos,
+                                   int64_t pad_token_id, uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld,
+                                   int32_t* cache_len, const int32_t* start_len, int32_t advance, int32_t* done_at, const void* embed_weight,
+                                   const void* additional_weight, int64_t max_original_id, int64_t num_additional, int32_t d,
+                                   void* next_embeds, float* scores, int64_t ld_scores, const int32_t* sets, int32_t n_sets,
+                                   const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets,
+                                   int32_t n_words, const int16_t* table, int64_t table_ld, int32_t n_states, int32_t* states,
+                                   int32_t states_ld, const int32_t* row_base, const int32_t* row_states, const float* frequency_penalty,
+                                   const float* presence_penalty, void* stream);
+
+int aki_sample_pick_rows_penalized(const void* logits, int32_t B, int32_t V, int64_t ld, const int64_t* eos_ids, int32_t n_eos,
+                                   int64_t pad_token_id, uint8_t* done, int64_t* next_ids, int64_t* tokens, int32_t tokens_ld,
+                                   int32_t* cache_len, const int32_t* start_len, int32_t advance, int32_t* done_at, const void* embed_weight,
+                                   const void* additional_weight, int64_t max_original_id, int64_t num_additional, int32_t d,
+                                   void* next_embeds, float* scores, int64_t ld_scores, const int32_t* sets, int32_t n_sets,
+                                   const int32_t* row_set, const int64_t* set_ids, int32_t n_set_ids, const int32_t* bad_offsets,
+                                   int32_t n_words, int32_t step, const float* temperature, const int32_t* top_k, const float* top_p,
+                                   const uint64_t* seed, float* probs_out, int64_t ld_probs, const int16_t* table, int64_t table_ld,
+                                   int32_t n_states, int32_t* states, int32_t states_ld, const int32_t* row_base, const int32_t* row_states,
+                                   const float* frequency_penalty, const float* presence_penalty, const float* min_p, void* stream);
+
 /* ---- beam search on the device (beam.hip).  HF `GenerationMixin` beam search with a `BeamSearchScorer`, the algorithm AKI._beam_search
  * runs on the host: 2K candidates per step, hypotheses normalised by generated_length ** length_penalty, at most K per sample.
  * Purely additive: AKI_ABI_VERSION was not bumped (it stays 17). */

@@ -43,6 +43,13 @@ own spread between the rounds.
 alternating with the plain leg; reports the per-token cost it adds and merges the result into profiles/stop_bench.json under "batch<B>".
     python tools/generate_bench.py [--many] [--many --sample --temperature 0.8 --top-k 50 --top-p 0.9 --logprobs 8] [--many --constraint]
                                    [--many --request-processors] [--many --stop]
+--min-p M / --frequency-penalty F / --presence-penalty P (any of them): the penalty bench instead of the legs above - plain greedy, the
+device sampler (--temperature / --top-k / --top-p) without and with min_p, and repetition_penalty (--repetition-penalty, default 1.2)
+without and with the two additive penalties, alternating in one process for at least 3 rounds; --long-history N runs the two
+repetition legs once more at N new tokens.  With --many the same five legs over generate_many's queue (the values in every request's
+RequestParams) at 8 and 16 slots.  Each new leg is reported against its neighbour leg of the same round, beside that neighbour's own
+spread over the rounds.  Merges the result into profiles/penalty_bench.json under "static" / "many".
+
     python tools/generate_bench.py [--new 256] [--fp8] [--txt 64] [--repetition-penalty 1.2] [--no-repeat-ngram 3]
                                    [--sample --temperature 0.8 --top-k 50 --top-p 0.9] [--batch 8] [--logprobs 8 --rounds 4] [--constraint] [--stop]"""
 import argparse, json, os, sys, time
@@ -458,6 +465,131 @@ def many_processors_bench(a, model, dev):
     print(json.dumps({k: v for k, v in res.items() if k != "budgets"}))
 
 
+def _leg_summary(rounds, names, key):
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    return {n: {"median": med([r[n][key] for r in rounds]), "min_max": [min(r[n][key] for r in rounds), max(r[n][key] for r in rounds)]}
+            for n in names}
+
+
+def _penalty_deltas(rounds, summary, key, scale):
+    """Each new leg against its neighbour leg of the same round, in microseconds, with the neighbour's own spread over the rounds."""
+    med = lambda xs: sorted(xs)[len(xs) // 2]
+    out = {}
+    for new, base in (("sampled_min_p", "sampled"), ("repetition_penalties", "repetition")):
+        d = [(r[new][key] - r[base][key]) * scale for r in rounds]
+        lo, hi = summary[base]["min_max"]
+        out[f"{new}_over_{base}_us"] = {"median": round(med(d), 2), "min_max": [round(min(d), 2), round(max(d), 2)],
+                                        f"{base}_spread_over_rounds_us": round((hi - lo) * scale, 2)}
+    return out
+
+
+def penalty_bench(a, model, dev):
+    """--min-p / --frequency-penalty / --presence-penalty: the sampled leg with and without min_p, and the repetition_penalty leg with and
+    without the two additive penalties, beside plain greedy, alternating in one process - generate() on one prompt (with --long-history N
+    also once at N new tokens: the history the penalties count), or with --many generate_many over many_bench's queue with the values in
+    every request's RequestParams.  Merges the result into profiles/penalty_bench.json under "static" / "many"."""
+    import aki_amd
+    import bench
+    pen = {k: v for k, v in (("frequency_penalty", a.frequency_penalty), ("presence_penalty", a.presence_penalty)) if v != 0.0}
+    rp = a.repetition_penalty if a.repetition_penalty != 1.0 else 1.2
+    samp = dict(do_sample=True, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
+    minp = {"min_p": a.min_p} if a.min_p > 0.0 else {}
+    names = ("greedy", "sampled", "sampled_min_p", "repetition", "repetition_penalties")
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "penalty_bench.json")
+    res = {"values": dict(pen, repetition_penalty=rp, **minp), "sampling": dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p),
+           "prompt_tokens_lm_stream": bench.N_TXT - 1 + bench.NV}
+    if a.many:
+        n_req = a.many_requests
+        g = torch.Generator(device="cpu").manual_seed(4242)
+        budgets = torch.randint(16, 257, (n_req,), generator=g).tolist()
+        reqs = []
+        for i in range(n_req):
+            vx, ids, _ = bench.synth_batch(1, dev, torch.bfloat16, model.media_token_id, seed=1000 + i)
+            reqs.append((vx, ids, budgets[i]))
+        P = aki_amd.RequestParams
+        legs = {"greedy": (lambda i: P(), {}), "sampled": (lambda i: P(seed=i, **samp), {}),
+                "sampled_min_p": (lambda i: P(seed=i, **samp, **minp), {}), "repetition": (lambda i: P(), dict(repetition_penalty=rp)),
+                "repetition_penalties": (lambda i: P(**pen), dict(repetition_penalty=rp))}
+
+        def leg(name, slots):
+            make, kw = legs[name]
+            batch = [(vx, ids, b, make(i)) for i, (vx, ids, b) in enumerate(reqs)]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            outs = model.generate_many(batch, slots=slots, eos_token_id=[], **kw)
+            torch.cuda.synchronize()
+            wall = time.perf_counter() - t0
+            assert [o.numel() for o in outs] == budgets
+            return wall, dict(model.last_many_stats)
+
+        res.update(requests=n_req, budget_seed=4242, slots={},
+                   method="the five legs alternate in one process, wall clock around each generate_many call with a device synchronisation on "
+                          "both sides; ms_per_step = wall time / decode steps replayed, prefills included.  All legs admit the same prompts "
+                          "with the same budgets (EOS off) and replay the same number of steps; a new leg is compared with its neighbour leg "
+                          "of the same round, whose spread over the rounds is the yardstick")
+        for slots in (8, 16):
+            for name in names:
+                leg(name, slots)
+            rounds = []
+            for _ in range(max(3, a.rounds)):
+                r = {}
+                for name in names:
+                    wall, stats = leg(name, slots)
+                    r[name] = {"tokens_per_s": round(sum(budgets) / wall, 1), "steps": stats["steps"], "ms_per_step": round(wall * 1e3 / stats["steps"], 4)}
+                rounds.append(r)
+            summary = _leg_summary(rounds, names, "ms_per_step")
+            res["slots"][str(slots)] = {"rounds": rounds, "ms_per_step": summary, "added_per_step": _penalty_deltas(rounds, summary, "ms_per_step", 1e3)}
+    else:
+        vx, ids, am = bench.synth_batch(1, dev, torch.bfloat16, model.media_token_id, seed=1000)
+        kws = {"greedy": {}, "sampled": samp, "sampled_min_p": dict(samp, **minp), "repetition": dict(repetition_penalty=rp),
+               "repetition_penalties": dict(pen, repetition_penalty=rp)}
+
+        def run(n_new, name):
+            kw = dict(kws[name])
+            if kw.get("do_sample"):
+                kw["generator"] = aki_amd.DeviceGenerator(0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            toks = model.generate(vx, ids, attention_mask=am, max_new_tokens=n_new, eos_token_id=[], **kw)
+            torch.cuda.synchronize()
+            assert toks.shape == (1, n_new)
+            return time.perf_counter() - t0
+
+        def measure(n_new, which, n_rounds):
+            rounds = []
+            for _ in range(n_rounds):
+                r = {}
+                for name in which:
+                    t1 = run(1, name)
+                    r[name] = {"ms_per_new_token_after_the_first": round((run(n_new, name) - t1) * 1e3 / (n_new - 1), 4)}
+                rounds.append(r)
+            return rounds
+
+        for name in names:
+            run(16, name)                                                 # warm-up: allocator, folds, the capture path
+        rounds = measure(a.new, names, max(3, a.rounds))
+        summary = _leg_summary(rounds, names, "ms_per_new_token_after_the_first")
+        res.update(new_tokens=a.new, rounds=rounds, ms_per_token=summary,
+                   added_per_token=_penalty_deltas(rounds, summary, "ms_per_new_token_after_the_first", 1e3),
+                   method="the five legs alternate in one process; ms per new token after the first = (wall time of a call with new_tokens "
+                          "- wall time of a call with one) / (new_tokens - 1), a device synchronisation on both sides of each call")
+        if a.long_history > 1:
+            two = ("repetition", "repetition_penalties")
+            long_rounds = measure(a.long_history, two, 2)
+            ls = _leg_summary(long_rounds, two, "ms_per_new_token_after_the_first")
+            d = [(r[two[1]][k] - r[two[0]][k]) * 1e3 for r in long_rounds for k in ("ms_per_new_token_after_the_first",)]
+            res["long_history"] = {"new_tokens": a.long_history, "rounds": long_rounds, "ms_per_token": ls,
+                                   "repetition_penalties_over_repetition_us_mean_over_the_history": [round(x, 2) for x in d],
+                                   "note": "the mean over histories of 1 .. new_tokens - 1 tokens; the count is taken over the whole "
+                                           "history on every step"}
+    book = json.load(open(path)) if os.path.exists(path) else {}
+    book["many" if a.many else "static"] = res
+    with open(path, "w") as f:
+        json.dump(book, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps({k: v for k, v in res.items() if k != "rounds"}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--new", type=int, default=256)
@@ -488,6 +620,12 @@ def main():
     ap.add_argument("--many-requests", type=int, default=64)
     ap.add_argument("--request-processors", action="store_true", help="with --many: per-request logits processors against the call-wide "
                     "processors leg and the greedy queue -> profiles/many_processors_bench.json")
+    ap.add_argument("--min-p", type=float, default=0.0, help="with --frequency-penalty / --presence-penalty: the penalty bench - sampled with and "
+                    "without min_p, repetition_penalty with and without the two penalties, alternating; with --many over generate_many's "
+                    "queue -> profiles/penalty_bench.json")
+    ap.add_argument("--frequency-penalty", type=float, default=0.0)
+    ap.add_argument("--presence-penalty", type=float, default=0.0)
+    ap.add_argument("--long-history", type=int, default=0, help="the penalty bench's static legs once more at this many new tokens (4096)")
     a = ap.parse_args()
     lp_kw =dict(output_logprobs=True, top_logprobs=a.logprobs) if a.logprobs >= 0 else None
     proc_kw = {}
@@ -505,6 +643,8 @@ def main():
     if a.mxfp4:
         model.lang_model.enable_mxfp4()
     model.lang_model.model.decode_chain_w4 = bool(a.w4_chain)
+    if a.min_p > 0.0 or a.frequency_penalty != 0.0 or a.presence_penalty != 0.0:
+        return penalty_bench(a, model, dev)
     if a.many:
         if a.request_processors:
             return many_processors_bench(a, model, dev)

@@ -205,7 +205,8 @@ int aki_attn_fwd(const aki_attn_args* a, void* ws, size_t ws_bytes, void* stream
   AKI_CHECK_ARG(a && a->q && a->k && a->v && a->o);
   AKI_CHECK_ARG(a->B > 0 && a->H > 0 && a->Lq > 0 && a->Lk > 0 && a->Dh > 0 && a->scale > 0.f && dtype_ok(a->dtype));
   if (a->dtype == AKI_DT_BF16) return attn_nc_bf16(a, (hipStream_t)stream);
-  // f32 parity path: the simple kernel wants contiguous head-major tensors and equal q/kv lengths are not required
+  // f32 parity path: the simple kernel wants contiguous head-major tensors and Lq == Lk (ops.attention pads shorter queries to Lk rows and
+  // refuses longer ones); anything else is UNSUPPORTED
   const int64_t Dh = a->Dh;
   if (a->q_stride_t != Dh || a->k_stride_t != Dh || a->v_stride_t != Dh || a->q_stride_h != (int64_t)a->Lq * Dh ||
       a->k_stride_h != (int64_t)a->Lk * Dh || a->v_stride_h != (int64_t)a->Lk * Dh || a->Lq != a->Lk)

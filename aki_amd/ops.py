@@ -338,6 +338,8 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, r
     o = torch.empty((B, Lq, H * Dh), dtype=q.dtype, device=dev)
     lib = L.load()
     if q.dtype == torch.float32:
+        if Lq > Lk:
+            raise AkiError(f"attention: the f32 parity path needs Lq <= Lk (its kernel is square and shorter queries are padded to Lk rows); got Lq = {Lq}, Lk = {Lk}")
         if Lq != Lk:  # the f32 parity kernel is square: pad the queries (extra rows are discarded)
             qp = torch.zeros((B, Lk, H, Dh), dtype=q.dtype, device=dev)
             qp[:, :Lq] = q

@@ -1,6 +1,7 @@
 """Case table, inputs, float64 reference, componentwise tolerance and reference mutations of the attention FORWARD at the lengths the
 64-row core exists for (aki_amd/csrc/mma_attn64_bf16.hip, routed to at L >= AKI_ATTN64_MIN_L; mma_attn_bf16.hip below it), of its dead
-rows under both conventions, and of the vision attention (attn_nc_bf16.hip, ops.attention) at head_dim 72 and 32.
+rows under both conventions, and of the vision attention (attn_nc_bf16.hip, ops.attention) at every head_dim it exports - 72 (SigLIP), 64
+(the Perceiver), 96 and 32 - in the memory layouts the product hands it ("layouts of the plain route" at the end of this file).
 
 numpy and CPU torch only.  tests/test_attn_fwd_cases_cpu.py checks the table itself and tests/test_attn_fwd_gpu.py runs it on the device.
 Case, visible(), bf16, hb, sentinel_pairs, FORBIDDEN_V, LIFT and MIN_RATIO are those of attn_bwd_cases.py; the reference is not: Sample
@@ -16,7 +17,8 @@ Why a bar of its own.  With N(0, 1) inputs a row that sees n keys has |o| ~ (e /
 Derivation, term by term (unit 2^-9; u = 2^-8 = 2 units is the unit roundoff of bf16).
   KAPPA   attn_bwd_cases.py derives it: one cast of p per term (u M_o = 2 units) and e_P = 0.5 units for the error of a recomputed p (f32
           dot product of 96 exact bf16 products while sum_d |q_d k_d| scale <= MAX_SCORE_TERMS = 64, exp2 / log of the hardware): 2.5 for
-          the 32-row core and ops.attention.  The 64-row core sums the bf16-ROUNDED p on the matrix pipe and divides by that sum: 2 more
+          the 32-row core and ops.attention (attn_nc_bf16 at every head_dim: it adds the unrounded f32 p into l_part on the VALU, casts
+          p to bf16 once as the PV operand and divides by the unrounded sum - head_dim changes KS, DT and the LDS pitches, not this).  The 64-row core sums the bf16-ROUNDED p on the matrix pipe and divides by that sum: 2 more
           units, 4.5 - in its shipped build (blind softmax), in its every-tile-exact build and through the product rule alike.  Against
           the reference maximum of a rank's first tile p = exp2(s c - m_ref) may be as large as 2^64: bf16 has f32's exponent, the cast
           stays a RELATIVE error u, and the bound does not move.
@@ -124,6 +126,7 @@ def _boundary(L):
               why="AKI_ATTN64_MIN_L - 1 / + 0 / + 1 through the product rule: a ragged two-sample batch, one rectangle each")
 
 
+PLAIN_DH = (72, 32, 64, 96)                    # every head_dim attn_nc_bf16 exports: SigLIP 72, the Perceiver 64
 _S32 = 32 * KC["SCHED32"]                      # the lengths aimed at a constant of the kernels move with it
 CASES = (
     _boundary(KC["MIN_L"] - 1), _boundary(KC["MIN_L"]), _boundary(KC["MIN_L"] + 1),
@@ -146,18 +149,24 @@ CASES = (
        why="left padding of more than 64 (137) and of 64 k + 3 (195) keys: rows that see nothing through the first tile(s); a hole later on"),
     _m("L2304-b1-h2-rising-blind", 1, 2, 2304, [[(6, 150, 150, 2200)]], [N], why="later tiles beat the first tile's maximum by 2^40: inside the 2^64 bound, the rank stays blind"),
     _m("L2304-b1-h2-rising-redo", 1, 2, 2304, [[(6, 150, 150, 2200)]], [N], why="later tiles beat it by 2^72: the row sums pass 2^64 and the rank is walked again"),
-) + tuple(_p(Dh, B, H, Lq, Lk, why) for Dh in (72, 32) for B, H, Lq, Lk, why in (
+) + tuple(_p(Dh, B, H, Lq, Lk, why) for Dh in PLAIN_DH for B, H, Lq, Lk, why in (
     (2, 1, 1, 1, "one row, one key"),
     (1, 3, 33, 31, "tails on both sides, Lq > Lk"),
     (2, 3, 129, 257, "one row / one key past a workgroup"),
     (1, 2, 576, 576, "SigLIP's token count"),
     (1, 2, 144, 873, "the Perceiver shape"),
+    (1, 2, 729, 729, "SigLIP at 384 px: 5 workgroups + 89 rows, 11 tiles + 25 keys"),
+    (1, 2, 144, 720, "the Perceiver at 336 px: 11 tiles + 16 keys"),
 ))
 CASE_BY_ID = {c.id: c for c in CASES}
 assert len(CASE_BY_ID) == len(CASES)
 RISING = {"L2304-b1-h2-rising-blind": 40.0, "L2304-b1-h2-rising-redo": 72.0}       # lift of the late keys, log2 units
 # aki_dead_rows values a case runs under (default: uniform); the boundary case below MIN_L also takes the 32-row route
 DEAD_ROWS = {"L2300-b2-h2-ragged-mid-tile-and-tile-edge": (1, 0), CASES[0].id: (1, 0)}
+# The sentinel keys are random directions.  With the plain seed the six keys of row 143, head 0 of this case lie so close to a common
+# subspace that the minimum-norm q is long and ordinary keys take 86 % of the row (share 0.137 against the 0.2 the CPU test asks for):
+# another draw, not another condition.  No other (case, family) is salted, so no other input moves.
+SEED_SALT = {("plain-d64-b1-h2-144x873", "sentinel"): "/draw-1"}
 KV_CACHE_CASE = "L4097-b1-h2-position-order-tile64-one-key"                         # two heads; the last tile holds one key
 
 
@@ -244,7 +253,7 @@ def properties(case: Case) -> set:
 
 
 REQUIRED = tuple(f"L={L}" for L in (KC["MIN_L"] - 1, KC["MIN_L"], KC["MIN_L"] + 1, _S32, _S32 + 1, 4096, 4097, 4160, 4161, 5000, 2300, 1856, 2304)) + tuple(
-    f"plain-d{d}:{a}x{b}" for d in (72, 32) for a, b in ((1, 1), (33, 31), (129, 257), (576, 576), (144, 873))) + (
+    f"plain-d{d}:{a}x{b}" for d in PLAIN_DH for a, b in ((1, 1), (33, 31), (129, 257), (576, 576), (144, 873), (729, 729), (144, 720))) + (
     "min_l-1", "min_l+0", "min_l+1", "sched32:ranked-at-limit", "sched32:position-order-first", "sched64:ranked-at-limit",
     "sched64:position-order-first", "two-mask-windows", "tile-64-holds-one-key", "B!=H", "rects=1", "rects=2", "rects=4",
     "col_hi%64=-1", "col_hi%64=+0", "col_hi%64=+1", "rect-across-seam:col_hi-in-tile-64", "rect-across-seam:col_hi-in-tile-65",
@@ -339,7 +348,7 @@ class Inputs:
 def make_inputs(case: Case, family: str) -> Inputs:
     assert family in families(case)
     B, H, Lq, Lk, D = case.B, case.H, case.Lq, case.Lk, case.Dh
-    rng = np.random.default_rng(zlib.crc32(f"fwd/{case.id}/{family}".encode()))
+    rng = np.random.default_rng(zlib.crc32(f"fwd/{case.id}/{family}{SEED_SALT.get((case.id, family), '')}".encode()))
     q = rng.standard_normal((B, H, Lq, D))
     k = rng.standard_normal((B, H, Lk, D))
     pairs, forbidden = [[] for _ in range(B)], [[] for _ in range(B)]
@@ -671,4 +680,159 @@ def mutation_ratios(inp, b: int, names=None, dead_rows: int = 1, core: str = "64
                 pattern = (np.isfinite(l2) | past[None]) != (np.isfinite(R.lse) | past[None])
                 rl = np.where(pattern, np.inf, np.where(live[None] & np.isfinite(l2), np.abs(l2 - R.lse) / t_l, 0.0))
             res[name][label] = float(max(np.where(o2 == o, 0.0, ro).max(), rl.max()))
+    return res
+
+
+# ---- layouts of the plain route ---------------------------------------------------------------------------------------------------
+# The same values and the same float64 result; only where the device finds them differs.  ops.attention reads q, k, v in place through a
+# batch, a head and a token stride each, and the product never hands it head-major tensors:
+#   heads        permuted contiguous [B, H, L, Dh] tensors (token stride Dh, head stride L Dh)
+#   heads+spare  the same with SPARE more key rows per head in the k and the v buffer that the call does not name
+#   qkv          one buffer [B, L + SPARE, 3, H, Dh], q / k / v = buf[:, :L, i]: SigLIP's call (token stride 3 H Dh, head stride Dh)
+#   q+kv         q [B, Lq, H, Dh] and one buffer [B, Lk + SPARE, 2, H, Dh], k / v = kv[:, :Lk, i]: the Perceiver's call (v sits H Dh behind k)
+# Every layout but "heads" takes its views from buffers with one more LEADING sample when B > 1 (the base is not the allocation's and,
+# with the spare rows, the batch stride is not the product of the view's sizes).  What the call does not name is adversarial, as the table
+# treats forbidden pairs: a spare key row scores LEVEL + LIFT against a sentinel row's q (row Lk against the last row's, the others in turn
+# against every row that has pairs; N(0, 1) in the diffuse family, where the value alone is enough) and carries v = FORBIDDEN_V; the
+# leading sample is sample 0 with v = FORBIDDEN_V throughout.  Spare rows of a q slot are zero: the kernel guards its stores by row < Lq.
+# attn_nc_bf16 loads the rows min(c, Lk - 1) and masks the last tile by a count: a kernel that keeps to that never touches a spare row;
+# one that rounds Lk up to a tile, or miscounts by one, reads row Lk.  Every stride is a multiple of 8 elements and every base of 16 bytes.
+LAYOUTS = ("heads", "heads+spare", "qkv", "q+kv")
+SPARE = 70                                     # more than one 64-key tile and no multiple of it
+
+
+def layouts(case: Case) -> tuple:
+    if case.masked:
+        return ()
+    return LAYOUTS if case.Lq == case.Lk else tuple(l for l in LAYOUTS if l != "qkv")
+
+
+@dataclass
+class Placed:
+    """The buffers of one (case, family, layout) on the host; views() cuts q, k, v out of them (or out of copies on a device)."""
+    case: Case
+    layout: str
+    bufs: dict                     # name -> bf16 tensor
+    lead: int                      # leading samples the views skip
+
+    def views(self, bufs=None):
+        """q [B, Lq, H, Dh], k, v [B, Lk, H, Dh] as ops.attention takes them."""
+        b_, c, s = self.bufs if bufs is None else bufs, self.case, self.lead
+        if self.layout in ("heads", "heads+spare"):
+            return tuple(b_[n_][s:, :, :L_].permute(0, 2, 1, 3) for n_, L_ in (("q", c.Lq), ("k", c.Lk), ("v", c.Lk)))
+        if self.layout == "qkv":
+            return tuple(b_["qkv"][s:, :c.Lq, i] for i in range(3))
+        return b_["q"][s:], b_["kv"][s:, :c.Lk, 0], b_["kv"][s:, :c.Lk, 1]
+
+
+def spare_rows(inp, b: int):
+    """(k, v) [H, SPARE, Dh] float64 of the rows behind key Lk - 1 of sample b (the comment above)."""
+    c = inp.case
+    rng = np.random.default_rng(zlib.crc32(f"fwd/{c.id}/{inp.family}/spare/{b}".encode()))
+    k = rng.standard_normal((c.H, SPARE, c.Dh))
+    if inp.family == "sentinel":
+        rows = sorted({r for r, _ in inp.pairs[b]}, reverse=True)              # the last row first: it is on every case's list
+        assert rows and rows[0] == c.Lq - 1
+        q = inp.q[b].double().numpy()
+        for j in range(SPARE):
+            qr = q[:, rows[j % len(rows)]]                                       # [H, Dh]
+            k[:, j] = qr * ((np.log(100.0 * c.Lk) + LIFT) / (c.scale * (qr * qr).sum(-1, keepdims=True)))
+    return k, np.full((c.H, SPARE, c.Dh), FORBIDDEN_V)
+
+
+def place(inp, layout: str) -> Placed:
+    c = inp.case
+    assert layout in layouts(c)
+    B, H, Lq, Lk, D = c.B, c.H, c.Lq, c.Lk, c.Dh
+    if layout == "heads":
+        return Placed(c, layout, dict(q=inp.q.contiguous(), k=inp.k.contiguous(), v=inp.v.contiguous()), 0)
+    lead = 1 if B > 1 else 0
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.bfloat16)
+    q = torch.cat([inp.q[:lead], inp.q])                                         # [lead + B, H, L, D]: the leading sample is sample 0 ...
+    k = torch.cat([inp.k[:lead], inp.k])
+    v = torch.cat([torch.full_like(inp.v[:lead], FORBIDDEN_V), inp.v])           # ... with the forbidden value on every key
+    sp = [spare_rows(inp, max(i - lead, 0)) for i in range(lead + B)]
+    k = torch.cat([k, t(np.stack([s[0] for s in sp]))], 2)                       # [lead + B, H, Lk + SPARE, D]
+    v = torch.cat([v, t(np.stack([s[1] for s in sp]))], 2)
+    if layout == "heads+spare":
+        bufs = dict(q=q.contiguous(), k=k.contiguous(), v=v.contiguous())
+    elif layout == "qkv":
+        qs = torch.cat([q, torch.zeros_like(k[:, :, Lk:])], 2)
+        bufs = dict(qkv=torch.stack([a.permute(0, 2, 1, 3) for a in (qs, k, v)], 2).contiguous())                   # [., L + SPARE, 3, H, D]
+    else:
+        bufs = dict(q=q.permute(0, 2, 1, 3).contiguous(), kv=torch.stack([a.permute(0, 2, 1, 3) for a in (k, v)], 2).contiguous())
+    return Placed(c, layout, bufs, lead)
+
+
+def check_views(placed: Placed, views):
+    """What attn_nc_bf16 refuses, asserted before a launch: channel stride 1, the other strides multiples of 8 elements, bases of 16 bytes;
+    and every element the strides can reach lies inside its buffer."""
+    for x in views:
+        assert x.stride(3) == 1 and all(x.stride(i) % 8 == 0 for i in range(3)) and x.data_ptr() % 16 == 0, (placed.layout, x.stride())
+        last = x.storage_offset() + sum((n_ - 1) * s for n_, s in zip(x.shape, x.stride()))
+        assert last < x.untyped_storage().nbytes() // 2
+
+
+def gather(placed: Placed, mutation: str = None):
+    """q, k, v [B, H, L, Dh] bf16 read back out of the buffers by the kernel's own address rule - element = base + b s_b + h s_h + t s_t + d
+    with the base and the strides of the views - or by a subtly wrong one: the layout mutations."""
+    c = placed.case
+    views = placed.views()
+    check_views(placed, views)
+    out = []
+    for name, x in zip("qkv", views):
+        flat = torch.as_strided(x, (x.untyped_storage().nbytes() // 2,), (1,), 0)                                  # the whole allocation
+        base, (sb, st, sh, _) = x.storage_offset(), x.stride()
+        L_ = x.shape[1]
+        if name != "q" and mutation == "keys-past-Lk-visible":
+            L_ += SPARE
+        if name != "q" and mutation == "one-key-past-Lk-visible":
+            L_ += 1
+        if name == "v" and mutation == "v-read-from-k-slot":
+            base = views[1].storage_offset()
+        bi = torch.arange(c.B)[:, None, None, None] * (0 if mutation == "batch-stride-ignored" else sb)
+        hi = torch.arange(c.H)[None, :, None, None]
+        if name == "v" and mutation == "head-h-reads-head-h+1":
+            hi = (hi + 1) % c.H
+        idx = base + bi + hi * sh + torch.arange(L_)[None, None, :, None] * st + torch.arange(c.Dh)[None, None, None, :]
+        out.append(flat[idx])
+    return tuple(out)
+
+
+def _fused(placed):
+    return placed.layout in ("qkv", "q+kv")
+
+
+def _spare(placed):
+    return placed.layout != "heads"
+
+
+# name -> (applies(placed), samples that show it)
+LAYOUT_MUTATIONS = {
+    "v-read-from-k-slot": (_fused, lambda c: range(c.B)),                        # the fused offset: v = k
+    "head-h-reads-head-h+1": (lambda p: p.case.H > 1, lambda c: range(c.B)),     # v of the next head (the last head reads the first)
+    "batch-stride-ignored": (lambda p: p.case.B > 1, lambda c: range(1, c.B)),   # every sample reads the first one the call names
+    "keys-past-Lk-visible": (_spare, lambda c: range(c.B)),                      # the whole spare region counted
+    "one-key-past-Lk-visible": (_spare, lambda c: range(c.B)),                   # a last-tile count that is one too large
+}
+
+
+def layout_mutation_ratios(inp, layout: str, core: str = "64") -> dict:
+    """{mutation: {sample: worst |mutated - reference| / tolerance over o and lse}} of the layout mutations that apply, under the widest
+    bar as in mutation_ratios().  The unmutated gather must give back the inputs bit for bit."""
+    c = inp.case
+    placed = place(inp, layout)
+    assert all(torch.equal(a, b_) for a, b_ in zip(gather(placed), (inp.q, inp.k, inp.v))), f"{c.id} [{layout}]: the gather does not return the inputs"
+    res = {}
+    for name, (applies, samples) in LAYOUT_MUTATIONS.items():
+        if not applies(placed):
+            continue
+        q, k, v = gather(placed, name)
+        got = Inputs(c, inp.family, q, k, v, inp.pairs, inp.forbidden)
+        res[name] = {}
+        for b in samples(c):
+            R = forward_rows(inp, b)
+            R2 = forward_rows(got, b, vis=np.ones((c.Lq, k.shape[2]), dtype=bool))
+            t_o, t_l = tol_of(c, core, R.o, R.M, R.n.astype(np.float64), R.lse, R.S_o, R.S_lse)
+            res[name][b] = float(max((np.abs(R2.o - R.o) / t_o).max(), (np.abs(R2.lse - R.lse) / t_l).max()))
     return res

@@ -1,10 +1,11 @@
 """The attention-forward case table (tests/attn_fwd_cases.py) is checked here, without a GPU: the row-blocked float64 reference agrees
 with a dense float64 softmax and with attn_bwd_cases.Sample, every named corner is reached by a case, the inputs meet the conditions the
-derivation of the bar assumes (score-term sums, the rising family's margins to 2^64 on both sides, sentinel shares), and every
+derivation of the bar assumes (score-term sums, the rising family's margins to 2^64 on both sides, sentinel shares), every
 mutation of the reference moves some compared element by MIN_RATIO = 8 times its tolerance, in some family, on every case it applies
-to.  A condition on the table, not a measurement of the kernels.  Run with -s to see the ratios."""
+to, and so does every mutation of the address rule in every layout of the plain route.  A condition on the table, not a measurement of the kernels.  Run with -s to see the ratios."""
 import numpy as np
 import pytest
+import torch
 
 import attn_bwd_cases as A
 import attn_fwd_cases as F
@@ -68,7 +69,7 @@ def test_every_named_corner_is_reached_by_a_case():
     for c in F.CASES:
         assert c.why
         assert c.H <= 2 or max(c.Lq, c.Lk) <= 2048
-        assert c.Dh == (96 if c.masked else c.Dh) and (c.masked or c.Dh in (72, 32))
+        assert c.Dh == (96 if c.masked else c.Dh) and (c.masked or c.Dh in (72, 32, 64, 96))
         for p in F.properties(c):
             reached.setdefault(p, c.id)
     missing = [p for p in F.REQUIRED if p not in reached]
@@ -163,6 +164,49 @@ def test_inputs_meet_the_conditions_of_the_derivation(case):
                     assert (np.exp(s - R.lse[:, at[r]]) > 0.3).all(), (r, c)     # a leak would take a quarter of the row's mass or more
 
 
+PLAIN = [c for c in F.CASES if not c.masked]
+
+
+@pytest.mark.parametrize("case", PLAIN, ids=lambda c: c.id)
+def test_layouts_hold_the_same_values_where_the_product_puts_them(case):
+    """Every layout of the plain route gives back the inputs bit for bit through the kernel's address rule; the strides are SigLIP's and
+    the Perceiver's; what the call does not name is adversarial; nothing is placed where attn_nc_bf16 would refuse it."""
+    B, H, Lq, Lk, D = case.B, case.H, case.Lq, case.Lk, case.Dh
+    assert F.layouts(case) == (F.LAYOUTS if Lq == Lk else ("heads", "heads+spare", "q+kv"))
+    for family in F.families(case):
+        inp = inputs(case, family)
+        for layout in F.layouts(case):
+            P = F.place(inp, layout)
+            q, k, v = P.views()
+            F.check_views(P, (q, k, v))
+            assert q.shape == (B, Lq, H, D) and k.shape == v.shape == (B, Lk, H, D)
+            assert all(torch.equal(a, b_) for a, b_ in zip(F.gather(P), (inp.q, inp.k, inp.v))), (case.id, family, layout)
+            assert all(torch.equal(a.permute(0, 2, 1, 3), b_) for a, b_ in zip((q, k, v), (inp.q, inp.k, inp.v)))
+            rows = Lk + (F.SPARE if layout != "heads" else 0)
+            if layout in ("heads", "heads+spare"):
+                assert k.stride() == v.stride() == (H * rows * D, D, rows * D, 1) and q.stride() == (H * Lq * D, D, Lq * D, 1)
+            elif layout == "qkv":
+                assert q.stride() == k.stride() == v.stride() == (rows * 3 * H * D, 3 * H * D, D, 1)
+                assert k.storage_offset() - q.storage_offset() == v.storage_offset() - k.storage_offset() == H * D
+            else:
+                assert q.stride() == (Lq * H * D, H * D, D, 1) and k.stride() == v.stride() == (rows * 2 * H * D, 2 * H * D, D, 1)
+                assert v.storage_offset() - k.storage_offset() == H * D
+            if layout == "heads":
+                assert P.lead == 0 and k.storage_offset() == 0
+                continue
+            assert P.lead == (B > 1) and (B == 1 or k.storage_offset() // k.stride(0) == 1)
+            assert B == 1 or k.stride(0) != Lk * k.stride(1)                     # the batch stride is not the product of the view's sizes
+            # behind key Lk - 1: SPARE rows with the forbidden value, row Lk at LEVEL + LIFT against the last row's q (sentinel family)
+            kf, vf = (F.gather(P, "keys-past-Lk-visible")[i] for i in (1, 2))
+            assert kf.shape[2] == Lk + F.SPARE > Lk + F.TILE and F.SPARE % F.TILE and (vf[:, :, Lk:].float() == F.FORBIDDEN_V).all()
+            if family == "sentinel":
+                s = (inp.q[:, :, Lq - 1].double() * kf[:, :, Lk].double()).sum(-1) * case.scale
+                assert (s - (np.log(100.0 * Lk) + F.LIFT)).abs().max() <= 0.1, (case.id, layout, s)
+            if B > 1:                                                            # the leading sample: sample 0's keys under the forbidden value
+                lead_v = P.bufs["v"][0, :, :Lk] if layout == "heads+spare" else P.bufs["qkv" if layout == "qkv" else "kv"][0, :Lk, -1]
+                assert (lead_v.float() == F.FORBIDDEN_V).all()
+
+
 @pytest.mark.parametrize("case", F.CASES, ids=lambda c: c.id)
 def test_every_mutation_is_visible_on_every_case_it_applies_to(case):
     assert len(F.CAPPED) <= 1 and not set(F.CAPPED) & set(F.PER_KEY)
@@ -175,11 +219,23 @@ def test_every_mutation_is_visible_on_every_case_it_applies_to(case):
                     for label, r in res.items():
                         key = (name, b, label.split(":")[0] if family == "rising" else label)
                         best[key] = max(best.get(key, 0.0), r)
+    got = {k[0] for k in best}                                                   # (the layout mutations below have a need-list of their own)
+    for layout in F.layouts(case):                                               # the plain route: a gather that misreads the buffers
+        seen = set()
+        for family in F.families(case):
+            for name, res in F.layout_mutation_ratios(inputs(case, family), layout).items():
+                seen.add(name)
+                for b, r in res.items():
+                    best[(name, b, layout)] = max(best.get((name, b, layout), 0.0), r)
+        want = {"head-h-reads-head-h+1"} if case.H > 1 else set()
+        want |= {"batch-stride-ignored"} if case.B > 1 else set()
+        want |= {"keys-past-Lk-visible", "one-key-past-Lk-visible"} if layout != "heads" else set()
+        want |= {"v-read-from-k-slot"} if layout in ("qkv", "q+kv") else set()
+        assert seen == want, f"{case.id} [{layout}]: layout mutations {sorted(seen)}, expected {sorted(want)}"
     for (name, b, label), r in sorted(best.items()):
         print(f"{case.id} sample {b}: {name}: {r:.1f}  ({label})")
     bad = {k: v for k, v in best.items() if not v >= F.CAPPED.get(k[0], F.MIN_RATIO)}
     assert not bad, f"{case.id}: mutations the inputs would let through: {bad}"
-    got = {k[0] for k in best}
     if case.id in F.RISING:
         assert got == set(F.RISING_MUTATIONS)
         return

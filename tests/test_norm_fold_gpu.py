@@ -3,7 +3,9 @@ aki_mma_attn_args.row_scale, aki_row_stats): a block's pre-norm rides on the GEM
 statistics of its output) and on the GEMM after it (gain folded into the weight, 1/rms - and the mean's share - applied to the
 accumulator).  Oracle: norm-then-linear in f32 numpy on the bf16-rounded inputs (oracle/aki_oracle.py rms_norm / layer_norm /
 linear), i.e. Phi3RMSNorm -> qkv_proj / gate_up_proj (HF:phi3/modeling_phi3.py:266-284) and nn.LayerNorm -> q/k/v / fc1
-(HF:siglip/modeling_siglip.py).  Tolerance as in test_kernels_gpu.py.
+(HF:siglip/modeling_siglip.py).  Tolerance as in test_kernels_gpu.py.  The derived bars of the statistics and of the folded epilogue - per
+tile configuration, against float64, with the reference mutations they exclude - are in tests/norm_fold_cases.py and run in
+tests/test_norm_fold_f64_gpu.py; the assertions here are the older, looser ones and stay as they are.
 """
 import numpy as np
 import pytest
